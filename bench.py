@@ -2,7 +2,7 @@
 """bench.py -- rendered frames/s, forward+backward, 300k dynamic Gaussians @ 854x480 (BASELINE.json
 configs[1]) through the MI355X-native rasterizer behind the dptr.gs operator surface.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: one rank per GPU over RCCL.  Started under torch.distributed.run the process is one of the N ranks; started
     plainly -- no RANK in the environment -- it launches the N ranks itself through torch.distributed.run on 127.0.0.1 and
     relays rank 0's JSON line.  Either way world size == --gpus is asserted and the line carries `ranks_seen`, an
@@ -14,7 +14,13 @@ A "step" is one SYNCHRONOUS gradient step of the frame-sharded data-parallel ren
 ONE all-reduce of that bucket (RCCL; skipped at N=1), then one Adam step on the flat parameter buffer
 (every rank applies the same update) -- only then does the next step's forward start.  Weak scaling:
 frames per rank fixed, so N ranks render N*frames frames per step (N=8, frames=25 -> the 200-frame
-configs[2]).  value = frames rendered by all ranks / wall time (max over ranks).
+configs[2]).  value = frames rendered by all ranks / wall time (max over ranks); ms_per_step = wall time / K.
+
+A plain run sets up, warms up, times the K steps and prints the line; at N > 1 it also times the other exact schedules
+(--overlap, --zero1) because `value` is the fastest of them.  --full adds everything else the line can carry: the
+collective's cost, per-kernel times and the roofline, forward-only and scene statistics, the extra lines (training frame,
+training step), the other configurations and the CPU baselines.  --dump-outputs DIR writes what the timed path computed in
+its last step (images, gradient, parameters after the optimiser) as DIR/<name>.npy.
 
 Paths (same images and gradients, tests/test_gpu_frames.py, test_gpu_fused.py):
   default      frame batch: every kernel takes the frame as a grid dimension (splatter_a_video_amd.frames),
@@ -34,6 +40,7 @@ import os
 import statistics
 import sys
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -168,6 +175,14 @@ def parse():
     ap.add_argument("--scene", choices=["uniform", "clustered"], default="uniform",
                     help="clustered: 70 %% of the Gaussians inside blobs that cover 10 %% of the image (foreground objects; "
                          "tile-list imbalance stress, SURVEY 7 hard part ii)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the collective's cost, per-kernel times and roofline, forward-only and scene "
+                         "statistics, the extra lines, the other configurations and the CPU baselines (the --no-* options below "
+                         "leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write what the timed path computed in its last step (images, gradient, "
+                         "parameters after the optimiser) as DIR/<name>.npy, float32, at most 64 MB in all (an array above its "
+                         "share is written as a fixed, seeded sample of its elements)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
@@ -186,7 +201,12 @@ def parse():
                     help="--train-step: the L1 losses as three splat_l1_loss_grad launches + gradient images (A/B of the loss-fused backward)")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous only: start / join the N ranks, all-reduce ones, print {n_gpus, ranks_seen} and exit")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and a.train_step:
+        ap.error("--dump-outputs writes the outputs of the frame renderer's step, not those of --train-step")
+    return a
 
 
 def self_launch(a) -> int:
@@ -306,6 +326,10 @@ class FrameRenderer:
             self.batch = self.parts[0].batch
         self.last = {}
         self._feat_in = None
+        self.images = {}          # name -> the images the current step rendered ([F,C,H,W] per batch or [C,H,W] per frame)
+
+    def _keep(self, name, img):
+        self.images.setdefault(name, []).append(img.detach())
 
     @property
     def flat_grad(self):
@@ -359,6 +383,7 @@ class FrameRenderer:
                                             scaling=p["scaling"], cubic_layout=SEGMENT_MAJOR, bg=self.sc.bg, nearest=0.01,
                                             grad_sink=sink)
             out.backward(part.dL_all)
+            self._keep("image", out)
             self.last = dict(M=self.last.get("M", 0), T=self.batch.T)
             return
         sink = {"xyz": g["xyz"], "scales": g["scale"], "uquats": g["rotate"], "opacity": g["opacity"]}
@@ -367,6 +392,7 @@ class FrameRenderer:
         out = part.batch.render(p["xyz"], p["scale"], p["rotate"], p["opacity"], feat, part.off_all, self.extr,
                                 bg=self.sc.bg, nearest=0.01, grad_sink=sink)
         out.backward(part.dL_all)
+        self._keep("image", out)
         self.last = dict(M=self.last.get("M", 0), T=self.batch.T)
 
     # ------------------------------------------------------------------ the reference's real frame (row a1), frame batch
@@ -391,11 +417,15 @@ class FrameRenderer:
                 scaling=p["scaling"], cubic_layout=SEGMENT_MAJOR, K=20, grad_sink=sink)
             torch.autograd.backward(list(out[:3]), part.dL_sets)
             positions_batch_backward(part.tab2, part.g_pos2, I, SEGMENT_MAJOR, None, g["pos_cubic_node"])
+            for name, img in zip(("rgb", "depth", "attributes"), out[:3]):
+                self._keep(name, img)
             self.last = dict(M=self.last.get("M", 0), T=self.batch.T)
             return
         out = part.batch.render_sets(p["xyz"], p["scale"], p["rotate"], p["opacity"], sets, part.off_all, self.extr, K=20,
                                      grad_sink={"xyz": g["xyz"], "scales": g["scale"], "uquats": g["rotate"], "opacity": g["opacity"]})
         torch.autograd.backward(list(out[:3]), part.dL_sets)
+        for name, img in zip(("rgb", "depth", "attributes"), out[:3]):
+            self._keep(name, img)
         self.last = dict(M=self.last.get("M", 0), T=self.batch.T)
 
     # ------------------------------------------------------------------ the reference's real frame (row a1), frame by frame
@@ -412,6 +442,8 @@ class FrameRenderer:
             f = r["rendered_features_split"]
             torch.autograd.backward([f["rgb"], f["depth"], f["mask_attribute"], f["dino_attribute"]],
                                     [self.dL_dout, self.dL_depth, self.dL_attr[:1], self.dL_attr[1:]])
+            for name in ("rgb", "depth", "mask_attribute", "dino_attribute"):
+                self._keep(name, f[name])
             self._radii = r["radii"]
         rgb.backward(rgb_in.grad)
         row.backward(row_in.grad)
@@ -443,6 +475,8 @@ class FrameRenderer:
             att = gs.alpha_blending(uv, conic, p["opacity"].detach(), p["attrs"], idx, tr, 0.0, W, H, ndc.detach())
             if backward:
                 torch.autograd.backward([img, dep, att], [self.dL_dout, self.dL_depth, self.dL_attr])
+                for name, x in (("rgb", img), ("depth", dep), ("attributes", att)):
+                    self._keep(name, x)
             self.last = dict(M=idx.numel(), T=tr.shape[0])
 
     def eager_steps_only(self):
@@ -604,6 +638,7 @@ class FrameRenderer:
     def step(self, collective=True):
         """one gradient step: local frames forward+backward, ONE all-reduce of the flat bucket (skipped when no process
         group exists, and in rank 0's private kernel-timing pass), one Adam step; returns when everything is enqueued"""
+        self.images = {}
         if self.halves:
             from splatter_a_video_amd.parallel import overlapped_halves_step
             run = self.frames_batched if self.mode == "batch" else self.frames_render_iter_batched
@@ -637,7 +672,7 @@ class FrameRenderer:
                 feat = gs.compute_sh_into(self.p["shs"], 3, self.dirs, None, self.bucket.grad("shs"))
                 self._feat_in = feat.detach().requires_grad_(True)
             for off in self.offs:
-                self.frame(off)
+                self._keep("image", self.frame(off))
             if feat is not None:
                 feat.backward(self._feat_in.grad)
                 self._feat_in = None
@@ -678,6 +713,28 @@ class FrameRenderer:
                 m = int(tiles.sum().item())
         if m:
             self.last["M"] = m
+
+
+DUMP_BYTES = 64 * 10**6
+
+
+def dump_outputs(R, out_dir):
+    """--dump-outputs: what the timed path computed in its last step -- the images it rendered, the (reduced) gradient and the
+    parameters after its optimiser step -- as out_dir/<name>.npy, float32.  The arrays share DUMP_BYTES equally; one above
+    its share is written as a sorted sample of its flattened elements, drawn without replacement by a generator seeded with
+    its name, so that every build samples the same elements."""
+    arrays = {k: torch.cat([t if t.dim() == 4 else t[None] for t in ts]) for k, ts in R.images.items()}
+    for k in R.p:
+        arrays["grad_" + k] = R.bucket.grad(k)
+        arrays["param_" + k] = R.p[k]
+    cap = (DUMP_BYTES // len(arrays) - 4096) // 4     # (4 KB per file for the .npy header)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, x in arrays.items():
+        x = x.detach()
+        if x.numel() > cap:
+            idx = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(x.numel(), cap, replace=False))
+            x = x.reshape(-1)[torch.from_numpy(idx).to(x.device)]
+        np.save(os.path.join(out_dir, k + ".npy"), x.float().cpu().numpy())
 
 
 def kernel_bytes(name, N, M, HW, C, T, use_sh, fpl=1.0, sets=False, nparam=None, sh_acc=True, dyn=False):
@@ -1087,39 +1144,43 @@ def main():
                       optimizer=not a.no_optimizer, halves=a.overlap, attr_channels=a.attr_channels, zero1=a.zero1)
     dt = timed(R.step, R.finish)
     R.check_sorts()   # the sync-free sorts of the timed steps all fitted their capacity (raises otherwise)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(R, a.dump_outputs)
 
     # N > 1: what the collective costs (every rank takes part; rank 0 reports).  The step is synchronous, so the all-reduce of
-    # the flat bucket is exposed by construction; these figures say how much of the step it is, and what the exact half-batch
-    # overlap (--overlap) makes of it.  Failures here must not cost the line its headline: they are reported in `comm.error`.
+    # the flat bucket is exposed by construction; these figures (--full) say how much of the step it is, and the other exact
+    # schedules (--overlap, --zero1) are timed beside it because `value` is the fastest of them.  Failures here must not cost
+    # the line its headline: they are reported in `comm.error`.
     def comm_analysis(R_, dt_, mode_, dynamic_, with_overlap=True):
         if not (launched and world > 1) or a.no_comm_analysis or a.stale_overlap:
             return None
         comm = {"bucket_MB": round(R_.flat_grad.numel() * 4 / 1e6, 1), "backend": backend}
-        try:
-            buf = torch.zeros_like(R_.flat_grad)
-            for _ in range(2):
-                dist.all_reduce(buf)
-            reps = 10
-            sync()
-            t0 = time.perf_counter()
-            for _ in range(reps):
-                dist.all_reduce(buf)
-            sync()
-            tt = torch.tensor([(time.perf_counter() - t0) / reps], device=dev, dtype=torch.float64)
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            ar = float(tt.item())
-            del buf
-            dt_nc = timed(lambda: R_.step(collective=False))
-            step_ms, nc_ms = dt_ / a.steps * 1e3, dt_nc / a.steps * 1e3
-            nbytes = R_.flat_grad.numel() * 4
-            comm.update({"allreduce_ms": round(ar * 1e3, 4), "allreduce_reps": reps,
-                         "allreduce_algbw_GBps": round(nbytes / ar / 1e9, 1),
-                         "allreduce_busbw_GBps": round(nbytes / ar / 1e9 * 2 * (world - 1) / world, 1),
-                         "step_ms": round(step_ms, 3), "step_ms_without_collective": round(nc_ms, 3),
-                         "exposed_comm_frac": round(max(0.0, step_ms - nc_ms) / step_ms, 4),
-                         "mode": "exact half-batch overlap" if R_.halves else "synchronous"})
-        except Exception as e:   # noqa: BLE001
-            comm["error"] = repr(e)[:300]
+        if a.full:
+            try:
+                buf = torch.zeros_like(R_.flat_grad)
+                for _ in range(2):
+                    dist.all_reduce(buf)
+                reps = 10
+                sync()
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    dist.all_reduce(buf)
+                sync()
+                tt = torch.tensor([(time.perf_counter() - t0) / reps], device=dev, dtype=torch.float64)
+                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+                ar = float(tt.item())
+                del buf
+                dt_nc = timed(lambda: R_.step(collective=False))
+                step_ms, nc_ms = dt_ / a.steps * 1e3, dt_nc / a.steps * 1e3
+                nbytes = R_.flat_grad.numel() * 4
+                comm.update({"allreduce_ms": round(ar * 1e3, 4), "allreduce_reps": reps,
+                             "allreduce_algbw_GBps": round(nbytes / ar / 1e9, 1),
+                             "allreduce_busbw_GBps": round(nbytes / ar / 1e9 * 2 * (world - 1) / world, 1),
+                             "step_ms": round(step_ms, 3), "step_ms_without_collective": round(nc_ms, 3),
+                             "exposed_comm_frac": round(max(0.0, step_ms - nc_ms) / step_ms, 4),
+                             "mode": "exact half-batch overlap" if R_.halves else "synchronous"})
+            except Exception as e:   # noqa: BLE001
+                comm["error"] = repr(e)[:300]
         if with_overlap and not a.overlap and mode_ in ("batch", "render_iter") and a.frames >= 2:
             try:
                 R3 = FrameRenderer(sc, dev, frames, a.channels if mode_ == mode else 0, mode=mode_, dynamic=dynamic_,
@@ -1180,7 +1241,7 @@ def main():
     roofline = None
     kernels = {}
     fwd_ms = bwd_ms = opt_ms = None
-    if rank == 0 and not a.no_kernel_timing:
+    if rank == 0 and a.full and not a.no_kernel_timing:
         # same step again with per-kernel HIP events recorded on the launch stream
         torch.cuda.synchronize()
         L.profile_reset()
@@ -1238,7 +1299,7 @@ def main():
 
     # forward only (the north star's render target: >= 149 frames/s at 480p / 300k), timed the same way
     forward_only = None
-    if mode in ("batch", "render_iter", "ref_flow"):
+    if a.full and mode in ("batch", "render_iter", "ref_flow"):
         dtf = timed(R.forward_only)
         R.check_sorts()
         forward_only = {"value": round(a.frames * a.steps * world / dtf, 2), "unit": "frames/s",
@@ -1247,9 +1308,9 @@ def main():
                                  "synchronising sort, three blends), frame by frame: the north star's >= 149 FPS check on the unchanged "
                                  "renderer flow" if mode == "ref_flow" else
                                  "forward pass alone (SH -> preprocess -> binning -> sort -> compositing), same frames, timed like `value`")}
-    stats = R.scene_stats() if rank == 0 else None
+    stats = R.scene_stats() if (rank == 0 and a.full) else None
     eager_only = None
-    if mode == "ref_flow":
+    if a.full and mode == "ref_flow":
         dte = timed(R.eager_steps_only)
         eager_only = {"ms_per_frame": round(dte / (a.frames * a.steps) * 1e3, 4),
                       "what": "the flow's two eager-torch steps alone (orthographic projection + EWA, with gs.compute_cov3d between "
@@ -1279,11 +1340,11 @@ def main():
                                                     "reference's flops per visit, per launch / launch duration, against the dense f32 "
                                                     "MFMA peak = packed-FP32 vector peak"}})
 
-    # second workload of the line (N = 1, default configuration only): the reference's REAL training frame -- its dynamic
+    # second workload of the line (--full, default configuration only): the reference's REAL training frame -- its dynamic
     # Gaussians (time-varying position and rotation) through render_iter's three blends (rgb enhanced K = 20 + depth + 19
     # attribute channels) -- forward + backward + Adam, timed exactly like `value`
     extra_lines = []
-    if mode == "batch" and not a.dynamic and a.channels == 0 and not a.no_extra_lines and not a.stale_overlap and not a.overlap:
+    if a.full and mode == "batch" and not a.dynamic and a.channels == 0 and not a.no_extra_lines and not a.stale_overlap and not a.overlap:
         # (every rank takes part at N > 1: the line carries its own bucket / all-reduce / exposed-communication figures)
         R2 = FrameRenderer(sc, dev, frames, 0, mode="render_iter", dynamic=True, optimizer=not a.no_optimizer)
         dt2 = timed(R2.step, R2.finish)
@@ -1314,10 +1375,10 @@ def main():
         except Exception as e:   # noqa: BLE001  (must not cost the line its headline; identical on every rank)
             extra_lines.append({"metric": "training step (train_step.py)", "error": repr(e)[:400]})
 
-    # the other configurations of BASELINE.json / BASELINE.md section 9 inside the SAME (driver-run) default line, N = 1: each timed
+    # the other configurations of BASELINE.json / BASELINE.md section 9 inside the SAME --full line, N = 1: each timed
     # exactly like `value` (W + K steps between synchronisations), compact -- their full lines are `profiles/r05_bench_*.json`
     other_configs = []
-    if (world == 1 and mode == "batch" and not a.dynamic and a.channels == 0 and not a.no_extra_lines and not a.stale_overlap
+    if (a.full and world == 1 and mode == "batch" and not a.dynamic and a.channels == 0 and not a.no_extra_lines and not a.stale_overlap
             and not a.overlap and not a.no_other_configs):
         specs = [("c5 (configs[4]): 32 feature channels", "--channels 32", dict(channels=32), "batch"),
                  ("render_iter, static Gaussians: the renderer's three blends, 23 channels", "--render-iter", {}, "render_iter"),
@@ -1362,7 +1423,7 @@ def main():
             other_configs.append({"what": "knn_points over all Gaussians", "equivalent_flags": "(knn_full)", "error": repr(e)[:300]})
 
     cpu = cpu_c = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and a.full and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline_torch(sc, a.channels)
         cpu_c = cpu_baseline_c(sc, a.channels)
 

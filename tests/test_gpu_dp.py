@@ -114,7 +114,7 @@ def test_bench_gpus_2_launches_and_reports_two_ranks():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     small = ["--gaussians", "6000", "--width", "128", "--height", "96", "--frames", "3", "--steps", "2", "--warmup", "1",
-             "--no-cpu-baseline", "--no-kernel-timing", "--no-extra-lines"]
+             "--no-cpu-baseline", "--no-kernel-timing", "--no-extra-lines", "--full"]
     lines = {}
     for n in (2, 1):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n)] + small, env=env, capture_output=True,
@@ -244,7 +244,7 @@ def test_bench_gpus_8_and_4_rehearsal_over_gloo(n):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     small = ["--gaussians", "4000", "--width", "128", "--height", "96", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-             "--no-kernel-timing"]
+             "--no-kernel-timing", "--full"]
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n)] + small, env=env, capture_output=True,
                        text=True, timeout=1400)
     assert r.returncode == 0, r.stderr[-3000:]

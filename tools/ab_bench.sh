@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT
 export PYTHONPATH=$GRAFT_REPO_ROOT
 K=$1; shift
-run() { timeout 300 python bench.py --no-cpu-baseline --no-extra-lines --steps 6 $BENCH_ARGS < /dev/null 2>/dev/null | tail -1 | python -c "
+run() { timeout 300 python bench.py --full --no-cpu-baseline --no-extra-lines --steps 6 $BENCH_ARGS < /dev/null 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); ks = '$K'.split(',')
 print(d['value'], {k: d['kernels'][k]['us_per_frame'] for k in ks if k in d['kernels']})"; }

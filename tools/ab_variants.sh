@@ -6,7 +6,7 @@ flags=$1; shift
 for r in $(seq 1 ${ROUNDS:-2}); do
   for v in "$@"; do
     if [ "$v" = default ]; then unset SPLAT_LIB_PATH; else export SPLAT_LIB_PATH=$GRAFT_REPO_ROOT/variants/libsplat_$v.so; fi
-    python bench.py $flags --no-cpu-baseline --no-extra-lines 2>/dev/null | tail -1 | python -c "
+    python bench.py --full $flags --no-cpu-baseline --no-extra-lines 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d.get('kernels') or {}
 g=lambda n: (k.get(n) or {}).get('us_per_frame')

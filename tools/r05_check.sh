@@ -11,7 +11,7 @@ for a in "$@"; do
     timeout 1500 python -m pytest tests -q -m gpu --deselect tests/test_gpu_train_step.py --deselect tests/test_gpu_dp.py < /dev/null > $O/pytest_gpu.log 2>&1; tail -15 $O/pytest_gpu.log
   fi
   if [ "$a" = "bench" ]; then
-    timeout 600 python bench.py < /dev/null 2> $O/bench.err | tail -1 > $O/bench.json; python - <<PY
+    timeout 600 python bench.py --full < /dev/null 2> $O/bench.err | tail -1 > $O/bench.json; python - <<PY
 import json
 d = json.load(open("$O/bench.json"))
 print("value", d["value"], "ms/frame", d["ms_per_frame"], "fwd_only", d["forward_only"]["value"])

@@ -13,7 +13,7 @@ from stamp import stamp
 print(json.dumps(stamp(), indent=1))
 PY
 cat $O/stamp.json
-run() { name=$1; shift; timeout 400 python bench.py "$@" < /dev/null 2> $O/$name.err | tail -1 > $O/$name.json; cut -c1-160 $O/$name.json; }
+run() { name=$1; shift; timeout 400 python bench.py --full "$@" < /dev/null 2> $O/$name.err | tail -1 > $O/$name.json; cut -c1-160 $O/$name.json; }
 timeout 900 python -m pytest tests -m gpu -q < /dev/null > $O/pytest_gpu.log 2>&1; tail -2 $O/pytest_gpu.log
 run bench_line                                   # default: frame batch, synchronous step with Adam, CPU baselines
 run bench_random_order --no-spatial-order --no-cpu-baseline
