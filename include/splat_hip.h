@@ -41,6 +41,7 @@ typedef void *splat_stream_t; /* hipStream_t */
 
 const char *splat_last_error(void);
 /* ABI version of this header; bumped on any signature change. */
+#define SPLAT_ABI_VERSION 22
 int splat_abi_version(void);
 /* Hash (16 hex digits) of the sources this binary was built from (csrc/Makefile); "unstamped" for a build outside the
    Makefile.  Measurement records under profiles/ carry it; bench.py only quotes PMC constants taken from the same build. */
@@ -730,6 +731,41 @@ int splat_dynamic_positions_batch_backward(int F, int P, int I, const void *tab,
  * image row), *loss_sum (zero-init, optional) += sum |pred - target| (float atomics: the sum is not bit-reproducible, the gradient is). */
 int splat_l1_loss_grad(int F, int64_t inner, const float *pred, int64_t pred_frame_stride, const float *target, float scale,
                        float *grad, float *loss_sum, splat_stream_t stream);
+
+/* ---- SSIM image loss (ABI 22): the reference's `ssim` / `_ssim` (src/pointrix/model/loss.py:58-112) and the RGB term of its
+ *      training step, loss_rgb = (1 - lambda) * l1 + lambda * (1 - ssim) (src/trainer_fragGS.py:575-578).
+ *      Window: `window` taps (odd, 1 .. 15; even -> SPLAT_E_ARG), Gaussian of sigma 1.5 normalised to sum 1, separable; zero
+ *      padding of window / 2 (no renormalisation at the borders); C1 = 0.01^2, C2 = 0.03^2; sigma^2 = E[x^2] - mu^2,
+ *      sigma_xy = E[xy] - mu_x mu_y; s = (2 mu_x mu_y + C1)(2 sigma_xy + C2) / ((mu_x^2 + mu_y^2 + C1)(sigma_x^2 + sigma_y^2 + C2)).
+ *      Planes: an image is [N, Cp, Hp, Wp] with four ELEMENT strides (host int64[4], each >= 0) of its own, read in place; the
+ *      window slides over the (Hp, Wp) plane of every (n, c).  So the RGB slice of a composited row [F, C, H, W] is
+ *      strides {C*H*W, H*W, W, 1} (the usual per-colour SSIM) and the reference's literal call ssim(pred.reshape(-1, h, w, 3))
+ *      -- channel = dim -3 = the image row, planes of W x 3 -- is the HWC view of the same row, strides {C*H*W, W, 1, H*W}.
+ *      Sums are per-workgroup partials (scratch: splat_ssim_scratch_bytes(...) bytes) added up by one more launch in a fixed
+ *      order: no float atomics, bit-reproducible.  No host synchronisation (capturable).  Every argument is validated before
+ *      any HIP call.  Sizes must be >= 1. ---- */
+/* bytes of scratch of splat_ssim_forward / splat_dssim_l1_loss_grad at these sizes (0: invalid sizes / window) */
+size_t splat_ssim_scratch_bytes(int N, int Cp, int Hp, int Wp, int window);
+/* out_mean (1 float, optional) = the mean of the SSIM map over all N * Cp * Hp * Wp positions (size_average=True);
+ * out_per_image ([N], optional; at least one of the two) = each image's mean (size_average=False) */
+int splat_ssim_forward(int N, int Cp, int Hp, int Wp, int window, const float *img1, const int64_t *strides1,
+                       const float *img2, const int64_t *strides2, float *out_mean, float *out_per_image, void *scratch,
+                       splat_stream_t stream);
+/* gradient w.r.t. img1 (w.r.t. img2: the same call with the images swapped -- SSIM is symmetric) of
+ * grad_out[0] * mean (per_image = 0) or of sum_n grad_out[n] * mean_n (per_image = 1); grad_out is a DEVICE scalar / [N]
+ * (autograd's grad_output, never read on the host).  grad1 [N, Cp, Hp, Wp] with its own strides (must not overlap the
+ * images): written, or ADDED to (accumulate != 0).  One launch; nothing of the forward is stored: the moments are recomputed
+ * on the tile + window / 2, the inputs on the tile + 2 * (window / 2). */
+int splat_ssim_backward(int N, int Cp, int Hp, int Wp, int window, const float *img1, const int64_t *strides1,
+                        const float *img2, const int64_t *strides2, const float *grad_out, int per_image, float *grad1,
+                        const int64_t *grad_strides, int accumulate, splat_stream_t stream);
+/* The training step's RGB term in one pass over pred and gt (n = N * Cp * Hp * Wp):
+ *   grad = w_l1 * sign(pred - gt) / n + w_ssim * (-d mean(ssim) / d pred)     (written; own strides, not overlapping the inputs)
+ *   *l1_sum += sum |pred - gt|,  *ssim_sum += sum of the SSIM map              (device slots, each optional)
+ * i.e. the gradient of w_l1 * mean|pred - gt| + w_ssim * (1 - mean ssim).  One tile launch + the fixed-order reduction. */
+int splat_dssim_l1_loss_grad(int N, int Cp, int Hp, int Wp, int window, const float *pred, const int64_t *pred_strides,
+                             const float *gt, const int64_t *gt_strides, float w_l1, float w_ssim, float *grad,
+                             const int64_t *grad_strides, float *l1_sum, float *ssim_sum, void *scratch, splat_stream_t stream);
 
 #define SPLAT_ADAM_MAX_SEGMENTS 16
 int splat_adam_step(int64_t n, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int nseg,

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPLAT_LIB_PATH") or os.path.join(_HERE, "libsplat_hip.so")
 _lib: Optional[ctypes.CDLL] = None
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 # every symbol include/splat_hip.h declares (tests check the .so exports all of them)
 SYMBOLS = [
@@ -56,6 +56,7 @@ SYMBOLS = [
     "splat_arap_energy_batch", "splat_knn_brute_scratch_bytes", "splat_knn_brute_batch", "splat_l1_loss_grad",
     "splat_alpha_blending_backward_batch_sets_l1", "splat_bin_count_batch_reach", "splat_bin_sort_batch_reach",
     "splat_profile_enable", "splat_profile_reset", "splat_profile_read",
+    "splat_ssim_scratch_bytes", "splat_ssim_forward", "splat_ssim_backward", "splat_dssim_l1_loss_grad",
 ]
 
 # environment switches of earlier rounds, applied ONCE at load THROUGH the ABI (splat_set_option): the library itself reads no
@@ -107,6 +108,12 @@ def lib() -> ctypes.CDLL:
         L.splat_get_option.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
         L.splat_knn_brute_scratch_bytes.restype = ctypes.c_size_t
         L.splat_knn_brute_scratch_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        i, f, p, s4 = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)
+        L.splat_ssim_scratch_bytes.restype = ctypes.c_size_t
+        L.splat_ssim_scratch_bytes.argtypes = [i, i, i, i, i]
+        L.splat_ssim_forward.argtypes = [i, i, i, i, i, p, s4, p, s4, p, p, p, p]
+        L.splat_ssim_backward.argtypes = [i, i, i, i, i, p, s4, p, s4, p, i, p, s4, i, p]
+        L.splat_dssim_l1_loss_grad.argtypes = [i, i, i, i, i, p, s4, p, s4, f, f, p, s4, p, p, p, p]
         if L.splat_abi_version() != ABI_VERSION:
             raise SplatError("libsplat_hip.so ABI version mismatch; rebuild it")
         _lib = L

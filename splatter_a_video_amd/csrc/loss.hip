@@ -1,0 +1,442 @@
+// SSIM / D-SSIM image loss on gfx950: value, gradient and the training step's L1 + D-SSIM term, each in one tiled launch
+// (+ one fixed-order reduction launch for the sums).
+//
+// Semantics: the reference's `ssim` / `_ssim` (src/pointrix/model/loss.py:58-112): separable Gaussian window of `window` taps,
+// sigma 1.5, normalised to sum 1; zero padding of window / 2 (no renormalisation at the borders); C1 = 0.01^2, C2 = 0.03^2;
+// sigma^2 = E[x^2] - mu^2, sigma_xy = E[xy] - mu_x mu_y.  A "plane" is one (image, channel) pair of an [N, Cp, Hp, Wp] view
+// given by four element strides per tensor, so the reference's HWC call (channel = dim -3 = the image row) and the usual
+// per-colour image SSIM are the same kernels with other strides; nothing is copied.
+//
+// One workgroup = one output tile of one plane.  Everything a tile needs is staged in LDS and recomputed; no map goes to HBM:
+//   1. the inputs x, y on the moment region + r (clipped to the plane: outside the plane is zero padding)
+//   2. horizontal pass: 5 row sums (x, y, x^2, y^2, xy) on the moment region's columns
+//   3. vertical pass: the 5 moments on the moment region -> SSIM (value) and, for the gradient, the per-position partials
+//        B = ds/dsigma_x^2, Cm = ds/dsigma_xy, A = ds/dmu_x - 2 mu_x B - mu_y Cm   (times the upstream gradient of the map)
+//      value only: moment region = output tile; gradient: output tile + r (the positions whose window covers the tile)
+//   4. / 5. the same separable window over A, B, Cm (only map positions inside the plane: the transpose of the zero-padded
+//      correlation) -> dS/dx(p) = blur(A) + 2 x blur(B) + y blur(Cm)
+// Sums leave as one partial per workgroup; ssim_reduce_kernel adds them up in a fixed order (no float atomics: bit-reproducible).
+#include "common.h"
+
+#include <algorithm>
+
+namespace {
+
+constexpr int SSIM_MAX_R = 7;          // window sizes 1 .. 15 (odd)
+constexpr int SSIM_THREADS = 256;
+constexpr size_t SSIM_LDS_MAX = 65536;  // per workgroup: two workgroups of the largest tile share a CU's 160 KiB
+constexpr float SSIM_C1 = 0.01f * 0.01f, SSIM_C2 = 0.03f * 0.03f;
+
+// w[RT + j], j in [-RT, RT]; zero beyond the window's own radius (a 15-tap loop serves every smaller window)
+struct SsimWin {
+    float w[2 * SSIM_MAX_R + 1];
+};
+
+struct SsimImg {
+    const float *p;
+    long long s[4];
+};
+
+struct SsimArgs {
+    int Cp, Hp, Wp, r;
+    int TH, TW, tiles_x, tiles;   // tile, tiles along the plane's columns, tiles per plane
+    int row_fast;                 // global accesses walk the plane's rows fastest (stride of dim 2 below that of dim 3)
+    SsimImg a, b;                 // a: the image differentiated (pred); b: the other one
+    float *grad;                  // gradient w.r.t. a (modes 1, 2)
+    long long gs[4];
+    int accumulate;
+    const float *g_dev;           // mode 1: upstream gradient, device scalar or [N] (g_per_image)
+    int g_per_image;
+    float g_scale;                // mode 1: times g_dev; mode 2: the map's upstream gradient itself (-w_ssim / n)
+    float l1_scale;               // mode 2: w_l1 / n
+    float *partial;               // [blocks, 2]: sum of s, sum |a - b| over the tile (modes 0, 2)
+};
+
+// i -> (i / d, i % d) for i < 2^20 through a float reciprocal (exact there: the quotient's error stays far below 0.5 / d)
+__device__ __forceinline__ void split_idx(int i, int d, float inv, int &q, int &rem) {
+    q = (int)(((float)i + 0.5f) * inv);
+    rem = i - q * d;
+}
+
+__device__ __forceinline__ float block_sum(float v, float *red) {
+    v = wave_sum_to_lane63(v);
+    if ((threadIdx.x & 63) == 63) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const float t = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return t;
+}
+
+// MODE 0: value; 1: gradient of the (upstream-weighted) mean; 2: gradient of l1_scale * |a - b| + g_scale * s, with both sums
+template <int RT, int MODE>
+__global__ void __launch_bounds__(SSIM_THREADS) ssim_tile_kernel(SsimArgs A, SsimWin W) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    constexpr bool GRAD = MODE != 0;
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x;
+    const int plane = b / A.tiles, t = b - plane * A.tiles;
+    const int n = plane / A.Cp, c = plane - n * A.Cp;
+    const int ty = t / A.tiles_x, tx = t - ty * A.tiles_x;
+    const int r = A.r, Hp = A.Hp, Wp = A.Wp;
+    // output tile O, moment region M (O + r for the gradient), input region I = M + r; all clipped to the plane
+    const int oy0 = ty * A.TH, oy1 = imin_(oy0 + A.TH, Hp), ox0 = tx * A.TW, ox1 = imin_(ox0 + A.TW, Wp);
+    const int mr = GRAD ? r : 0;
+    const int my0 = imax_(oy0 - mr, 0), my1 = imin_(oy1 + mr, Hp), mx0 = imax_(ox0 - mr, 0), mx1 = imin_(ox1 + mr, Wp);
+    const int iy0 = imax_(my0 - r, 0), iy1 = imin_(my1 + r, Hp), ix0 = imax_(mx0 - r, 0), ix1 = imin_(mx1 + r, Wp);
+    const int ih = iy1 - iy0, iw = ix1 - ix0, mh = my1 - my0, mw = mx1 - mx0, oh = oy1 - oy0, ow = ox1 - ox0;
+
+    float *red = sm;                           // 16 floats (4 used)
+    float *X = sm + 16, *Y = X + ih * iw;       // [ih][iw]
+    float *Hs = Y + ih * iw;                    // 5 planes [ih][mw]
+    float *S3 = Hs + 5 * ih * mw;               // 3 planes [mh][mw] (gradient)
+    float *G = Hs;                              // 3 planes [mh][ow] (gradient; H is dead by then)
+    const int nH = ih * mw, nS = mh * mw, nG = mh * ow;
+
+    const float *pa = A.a.p + (long long)n * A.a.s[0] + (long long)c * A.a.s[1];
+    const float *pb = A.b.p + (long long)n * A.b.s[0] + (long long)c * A.b.s[1];
+
+    // ---- 1. inputs of the region I
+    {
+        const int tot = ih * iw;
+        const int d = A.row_fast ? ih : iw;
+        const float inv = 1.0f / (float)d;
+        for (int i = tid; i < tot; i += SSIM_THREADS) {
+            int q, rem, y, x;
+            split_idx(i, d, inv, q, rem);
+            if (A.row_fast) { y = rem; x = q; } else { y = q; x = rem; }
+            const long long ya = iy0 + y, xa = ix0 + x;
+            X[y * iw + x] = pa[ya * A.a.s[2] + xa * A.a.s[3]];
+            Y[y * iw + x] = pb[ya * A.b.s[2] + xa * A.b.s[3]];
+        }
+    }
+    __syncthreads();
+
+    // ---- 2. horizontal pass: rows of I, columns of M
+    {
+        const float inv = 1.0f / (float)mw;
+        for (int i = tid; i < nH; i += SSIM_THREADS) {
+            int y, x;
+            split_idx(i, mw, inv, y, x);
+            const float *xr = X + y * iw, *yr = Y + y * iw;
+            const int xc = mx0 - ix0 + x;
+            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
+#pragma unroll
+            for (int j = -RT; j <= RT; ++j) {
+                const int q = xc + j;
+                const bool ok = (unsigned)q < (unsigned)iw;
+                const int qc = ok ? q : 0;
+                const float u = ok ? xr[qc] : 0.f, v = ok ? yr[qc] : 0.f;
+                const float w = W.w[RT + j];
+                const float wu = w * u, wv = w * v;
+                s0 += wu; s1 += wv; s2 += wu * u; s3 += wv * v; s4 += wu * v;
+            }
+            Hs[i] = s0; Hs[nH + i] = s1; Hs[2 * nH + i] = s2; Hs[3 * nH + i] = s3; Hs[4 * nH + i] = s4;
+        }
+    }
+    __syncthreads();
+
+    // ---- 3. vertical pass: the moments on M, SSIM and (gradient) the map partials A, B, Cm
+    float acc_s = 0.f;
+    {
+        float gsc = 0.f;
+        if (MODE == 1) gsc = A.g_scale * A.g_dev[A.g_per_image ? n : 0];
+        if (MODE == 2) gsc = A.g_scale;
+        const float inv = 1.0f / (float)mw;
+        for (int i = tid; i < nS; i += SSIM_THREADS) {
+            int y, x;
+            split_idx(i, mw, inv, y, x);
+            const int yc = my0 - iy0 + y;
+            float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f, m4 = 0.f;
+#pragma unroll
+            for (int j = -RT; j <= RT; ++j) {
+                const int q = yc + j;
+                const bool ok = (unsigned)q < (unsigned)ih;
+                const int k = (ok ? q : 0) * mw + x;
+                const float w = ok ? W.w[RT + j] : 0.f;
+                m0 += w * Hs[k]; m1 += w * Hs[nH + k]; m2 += w * Hs[2 * nH + k]; m3 += w * Hs[3 * nH + k];
+                m4 += w * Hs[4 * nH + k];
+            }
+            const float mu1_sq = m0 * m0, mu2_sq = m1 * m1, mu12 = m0 * m1;
+            const float s1sq = m2 - mu1_sq, s2sq = m3 - mu2_sq, s12 = m4 - mu12;
+            const float a1 = 2.f * mu12 + SSIM_C1, a2 = 2.f * s12 + SSIM_C2;
+            const float b1 = mu1_sq + mu2_sq + SSIM_C1, b2 = s1sq + s2sq + SSIM_C2;
+            const float den = b1 * b2;
+            const float s = (a1 * a2) / den;
+            const int ya = my0 + y, xa = mx0 + x;
+            if (MODE != 1 && ya >= oy0 && ya < oy1 && xa >= ox0 && xa < ox1) acc_s += s;
+            if (GRAD) {
+                const float rden = 1.f / den;
+                const float Bv = -s / b2;
+                const float Cv = 2.f * a1 * rden;
+                const float dmu = 2.f * m1 * a2 * rden - 2.f * m0 * s / b1;
+                const float Av = dmu - 2.f * m0 * Bv - m1 * Cv;
+                S3[i] = gsc * Av; S3[nS + i] = gsc * Bv; S3[2 * nS + i] = gsc * Cv;
+            }
+        }
+    }
+
+    float acc_l1 = 0.f;
+    if (GRAD) {
+        __syncthreads();
+        // ---- 4. horizontal blur of A, B, Cm: rows of M, columns of O
+        {
+            const float inv = 1.0f / (float)ow;
+            for (int i = tid; i < nG; i += SSIM_THREADS) {
+                int y, x;
+                split_idx(i, ow, inv, y, x);
+                const float *r0 = S3 + y * mw;
+                const int xc = ox0 - mx0 + x;
+                float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+#pragma unroll
+                for (int j = -RT; j <= RT; ++j) {
+                    const int q = xc + j;
+                    const bool ok = (unsigned)q < (unsigned)mw;
+                    const int qc = ok ? q : 0;
+                    const float w = ok ? W.w[RT + j] : 0.f;
+                    g0 += w * r0[qc]; g1 += w * r0[nS + qc]; g2 += w * r0[2 * nS + qc];
+                }
+                G[i] = g0; G[nG + i] = g1; G[2 * nG + i] = g2;
+            }
+        }
+        __syncthreads();
+        // ---- 5. vertical blur on O, the gradient (and the L1 term)
+        {
+            const int tot = oh * ow;
+            const int d = A.row_fast ? oh : ow;
+            const float inv = 1.0f / (float)d;
+            float *pg = A.grad + (long long)n * A.gs[0] + (long long)c * A.gs[1];
+            for (int i = tid; i < tot; i += SSIM_THREADS) {
+                int q0, rem, y, x;
+                split_idx(i, d, inv, q0, rem);
+                if (A.row_fast) { y = rem; x = q0; } else { y = q0; x = rem; }
+                const int yc = oy0 - my0 + y;
+                float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+#pragma unroll
+                for (int j = -RT; j <= RT; ++j) {
+                    const int q = yc + j;
+                    const bool ok = (unsigned)q < (unsigned)mh;
+                    const int k = (ok ? q : 0) * ow + x;
+                    const float w = ok ? W.w[RT + j] : 0.f;
+                    g0 += w * G[k]; g1 += w * G[nG + k]; g2 += w * G[2 * nG + k];
+                }
+                const int li = (oy0 - iy0 + y) * iw + (ox0 - ix0 + x);
+                const float u = X[li], v = Y[li];
+                float g = g0 + 2.f * u * g1 + v * g2;
+                if (MODE == 2) {
+                    const float dl = u - v;
+                    acc_l1 += fabsf(dl);
+                    g += dl > 0.f ? A.l1_scale : (dl < 0.f ? -A.l1_scale : 0.f);
+                }
+                float *dst = pg + (long long)(oy0 + y) * A.gs[2] + (long long)(ox0 + x) * A.gs[3];
+                *dst = A.accumulate ? *dst + g : g;
+            }
+        }
+    }
+
+    if (MODE != 1) {
+        const float ts = block_sum(acc_s, red);
+        const float tl = MODE == 2 ? block_sum(acc_l1, red) : 0.f;
+        if (tid == 0) {
+            A.partial[2 * (long long)b] = ts;
+            A.partial[2 * (long long)b + 1] = tl;
+        }
+    }
+}
+
+// the per-workgroup partials of image n are blocks [n * bpi, (n + 1) * bpi): per-image means, the overall mean, and the sums
+// ADDED into the caller's slots -- one workgroup, a fixed order of additions
+__global__ void __launch_bounds__(SSIM_THREADS)
+ssim_reduce_kernel(int N, int bpi, const float *__restrict__ partial, float inv_count, float inv_total, float *mean,
+                   float *per_image, float *s_slot, float *l1_slot) {
+    __shared__ float red[16];
+    float tot_s = 0.f, tot_l = 0.f;
+    for (int n = 0; n < N; ++n) {
+        const float *p = partial + 2 * (long long)n * bpi;
+        float s = 0.f, l = 0.f;
+        for (int k = threadIdx.x; k < bpi; k += SSIM_THREADS) {
+            s += p[2 * k];
+            l += p[2 * k + 1];
+        }
+        s = block_sum(s, red);
+        l = block_sum(l, red);
+        if (threadIdx.x == 0) {
+            if (per_image) per_image[n] = s * inv_count;
+            tot_s += s;
+            tot_l += l;
+        }
+    }
+    if (threadIdx.x == 0) {
+        if (mean) *mean = tot_s * inv_total;
+        if (s_slot) *s_slot += tot_s;
+        if (l1_slot) *l1_slot += tot_l;
+    }
+}
+
+struct SsimPlan {
+    int TH, TW, tiles_x, tiles, blocks, bpi, r, RT;
+    size_t lds;
+};
+
+// LDS of a tile (upper bound over the plane's tiles: every region is clipped to the plane)
+size_t ssim_lds_bytes(bool grad, int TH, int TW, int Hp, int Wp, int r) {
+    const int mr = grad ? r : 0;
+    const long long mh = std::min(TH + 2 * mr, Hp), mw = std::min(TW + 2 * mr, Wp);
+    const long long ih = std::min((int)mh + 2 * r, Hp), iw = std::min((int)mw + 2 * r, Wp);
+    long long f = 16 + 2 * ih * iw + 5 * ih * mw;
+    if (grad) f += 3 * mh * mw;
+    return (size_t)f * sizeof(float);
+}
+
+int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// tile by plane shape: narrow planes (<= 8 columns, the reference's 854 x 3 HWC planes) as column strips of whole width,
+// flat ones (<= 8 rows) as row strips, the rest as 2-D tiles; tiles balanced over the plane, sized for the gradient's LDS
+// (the value kernel uses the same tiles, so one scratch size serves every entry point)
+bool ssim_plan(int N, int Cp, int Hp, int Wp, int window, SsimPlan &P) {
+    P.r = window / 2;
+    P.RT = P.r <= 5 ? 5 : SSIM_MAX_R;
+    int thmax, twmax;
+    if (Wp <= 8) { thmax = 512; twmax = Wp; }
+    else if (Hp <= 8) { thmax = Hp; twmax = 512; }
+    else if (P.RT == 5) { thmax = 16; twmax = 32; }
+    else { thmax = 16; twmax = 16; }
+    for (;;) {
+        P.TH = ceil_div(Hp, ceil_div(Hp, thmax));
+        P.TW = ceil_div(Wp, ceil_div(Wp, twmax));
+        P.lds = ssim_lds_bytes(true, P.TH, P.TW, Hp, Wp, P.r);
+        if (P.lds <= SSIM_LDS_MAX) break;
+        if (thmax >= twmax && thmax > 1) thmax = (thmax + 1) / 2;
+        else if (twmax > 1) twmax = (twmax + 1) / 2;
+        else return false;
+    }
+    P.tiles_x = ceil_div(Wp, P.TW);
+    const long long tiles = (long long)ceil_div(Hp, P.TH) * P.tiles_x;
+    const long long bpi = tiles * Cp, blocks = bpi * N;
+    if (blocks > 0x7fffffffLL) return false;
+    P.tiles = (int)tiles;
+    P.bpi = (int)bpi;
+    P.blocks = (int)blocks;
+    return true;
+}
+
+// the reference's window (gaussian(window_size, 1.5): float32 values normalised by their float32 sum), at RT + j
+SsimWin ssim_window(int window, int RT) {
+    SsimWin W;
+    for (int k = 0; k < 2 * SSIM_MAX_R + 1; ++k) W.w[k] = 0.f;
+    const int r = window / 2;
+    float g[2 * SSIM_MAX_R + 1], sum = 0.f;
+    for (int x = 0; x < window; ++x) {
+        g[x] = (float)exp(-(double)((x - r) * (x - r)) / (2.0 * 1.5 * 1.5));
+        sum += g[x];
+    }
+    for (int x = 0; x < window; ++x) W.w[RT + x - r] = g[x] / sum;
+    return W;
+}
+
+int ssim_check_common(int N, int Cp, int Hp, int Wp, int window, const float *img1, const int64_t *s1, const float *img2,
+                      const int64_t *s2, SsimPlan &P) {
+    SPLAT_CHECK_ARG(N >= 1 && Cp >= 1 && Hp >= 1 && Wp >= 1, "bad sizes (every size must be >= 1)");
+    SPLAT_CHECK_ARG(window >= 1 && window <= 2 * SSIM_MAX_R + 1 && (window & 1), "window must be odd, 1 .. 15");
+    SPLAT_CHECK_ARG(img1 && img2 && s1 && s2, "null pointer");
+    for (int k = 0; k < 4; ++k) SPLAT_CHECK_ARG(s1[k] >= 0 && s2[k] >= 0, "strides must be >= 0");
+    SPLAT_CHECK_ARG(ssim_plan(N, Cp, Hp, Wp, window, P), "too many planes / tiles");
+    return SPLAT_OK;
+}
+
+SsimArgs ssim_args(int Cp, int Hp, int Wp, const SsimPlan &P, const float *a, const int64_t *sa, const float *b,
+                   const int64_t *sb) {
+    SsimArgs A;
+    memset(&A, 0, sizeof(A));
+    A.Cp = Cp; A.Hp = Hp; A.Wp = Wp; A.r = P.r;
+    A.TH = P.TH; A.TW = P.TW; A.tiles_x = P.tiles_x; A.tiles = P.tiles;
+    A.a.p = a; A.b.p = b;
+    for (int k = 0; k < 4; ++k) { A.a.s[k] = sa[k]; A.b.s[k] = sb[k]; }
+    A.row_fast = sa[2] < sa[3];
+    return A;
+}
+
+template <int MODE>
+void ssim_launch(const SsimPlan &P, const SsimArgs &A, const SsimWin &W, hipStream_t s) {
+    const size_t lds = MODE == 0 ? ssim_lds_bytes(false, P.TH, P.TW, A.Hp, A.Wp, P.r) : P.lds;
+    if (P.RT == 5)
+        SPLAT_LAUNCH("ssim_tile", (ssim_tile_kernel<5, MODE>), dim3(P.blocks), dim3(SSIM_THREADS), lds, s, A, W);
+    else
+        SPLAT_LAUNCH("ssim_tile", (ssim_tile_kernel<SSIM_MAX_R, MODE>), dim3(P.blocks), dim3(SSIM_THREADS), lds, s, A, W);
+}
+
+}  // namespace
+
+extern "C" size_t splat_ssim_scratch_bytes(int N, int Cp, int Hp, int Wp, int window) {
+    SsimPlan P;
+    if (N < 1 || Cp < 1 || Hp < 1 || Wp < 1 || window < 1 || window > 2 * SSIM_MAX_R + 1 || !(window & 1)) return 0;
+    if (!ssim_plan(N, Cp, Hp, Wp, window, P)) return 0;
+    return ((size_t)P.blocks * 2 * sizeof(float) + 255) & ~(size_t)255;
+}
+
+extern "C" int splat_ssim_forward(int N, int Cp, int Hp, int Wp, int window, const float *img1, const int64_t *strides1,
+                                  const float *img2, const int64_t *strides2, float *out_mean, float *out_per_image,
+                                  void *scratch, splat_stream_t stream) {
+    SsimPlan P;
+    const int rc = ssim_check_common(N, Cp, Hp, Wp, window, img1, strides1, img2, strides2, P);
+    if (rc) return rc;
+    SPLAT_CHECK_ARG(scratch && (out_mean || out_per_image), "null pointer (scratch, or both outputs)");
+    SsimArgs A = ssim_args(Cp, Hp, Wp, P, img1, strides1, img2, strides2);
+    A.partial = (float *)scratch;
+    const SsimWin W = ssim_window(window, P.RT);
+    ssim_launch<0>(P, A, W, (hipStream_t)stream);
+    SPLAT_POST_LAUNCH();
+    const double count = (double)Cp * Hp * Wp;
+    SPLAT_LAUNCH("ssim_reduce", ssim_reduce_kernel, dim3(1), dim3(SSIM_THREADS), 0, (hipStream_t)stream, N, P.bpi,
+                 (const float *)scratch, (float)(1.0 / count), (float)(1.0 / (count * N)), out_mean, out_per_image,
+                 (float *)nullptr, (float *)nullptr);
+    SPLAT_POST_LAUNCH();
+    return SPLAT_OK;
+}
+
+extern "C" int splat_ssim_backward(int N, int Cp, int Hp, int Wp, int window, const float *img1, const int64_t *strides1,
+                                   const float *img2, const int64_t *strides2, const float *grad_out, int per_image,
+                                   float *grad1, const int64_t *grad_strides, int accumulate, splat_stream_t stream) {
+    SsimPlan P;
+    const int rc = ssim_check_common(N, Cp, Hp, Wp, window, img1, strides1, img2, strides2, P);
+    if (rc) return rc;
+    SPLAT_CHECK_ARG(grad_out && grad1 && grad_strides, "null pointer");
+    for (int k = 0; k < 4; ++k) SPLAT_CHECK_ARG(grad_strides[k] >= 0, "strides must be >= 0");
+    SsimArgs A = ssim_args(Cp, Hp, Wp, P, img1, strides1, img2, strides2);
+    A.grad = grad1;
+    for (int k = 0; k < 4; ++k) A.gs[k] = grad_strides[k];
+    A.accumulate = accumulate ? 1 : 0;
+    A.g_dev = grad_out;
+    A.g_per_image = per_image ? 1 : 0;
+    A.g_scale = (float)(1.0 / ((double)Cp * Hp * Wp * (per_image ? 1 : N)));
+    const SsimWin W = ssim_window(window, P.RT);
+    ssim_launch<1>(P, A, W, (hipStream_t)stream);
+    SPLAT_POST_LAUNCH();
+    return SPLAT_OK;
+}
+
+extern "C" int splat_dssim_l1_loss_grad(int N, int Cp, int Hp, int Wp, int window, const float *pred,
+                                        const int64_t *pred_strides, const float *gt, const int64_t *gt_strides, float w_l1,
+                                        float w_ssim, float *grad, const int64_t *grad_strides, float *l1_sum,
+                                        float *ssim_sum, void *scratch, splat_stream_t stream) {
+    SsimPlan P;
+    const int rc = ssim_check_common(N, Cp, Hp, Wp, window, pred, pred_strides, gt, gt_strides, P);
+    if (rc) return rc;
+    SPLAT_CHECK_ARG(grad && grad_strides && scratch, "null pointer");
+    for (int k = 0; k < 4; ++k) SPLAT_CHECK_ARG(grad_strides[k] >= 0, "strides must be >= 0");
+    SsimArgs A = ssim_args(Cp, Hp, Wp, P, pred, pred_strides, gt, gt_strides);
+    const double n = (double)N * Cp * Hp * Wp;
+    A.grad = grad;
+    for (int k = 0; k < 4; ++k) A.gs[k] = grad_strides[k];
+    A.g_scale = (float)(-(double)w_ssim / n);
+    A.l1_scale = (float)((double)w_l1 / n);
+    A.partial = (float *)scratch;
+    const SsimWin W = ssim_window(window, P.RT);
+    ssim_launch<2>(P, A, W, (hipStream_t)stream);
+    SPLAT_POST_LAUNCH();
+    if (l1_sum || ssim_sum) {
+        SPLAT_LAUNCH("ssim_reduce", ssim_reduce_kernel, dim3(1), dim3(SSIM_THREADS), 0, (hipStream_t)stream, N, P.bpi,
+                     (const float *)scratch, 0.f, 0.f, (float *)nullptr, (float *)nullptr, ssim_sum, l1_sum);
+        SPLAT_POST_LAUNCH();
+    }
+    return SPLAT_OK;
+}

@@ -19,7 +19,7 @@ void splat_set_error(const char *fmt, ...) {
 }
 
 extern "C" const char *splat_last_error(void) { return g_err; }
-extern "C" int splat_abi_version(void) { return 21; }
+extern "C" int splat_abi_version(void) { return SPLAT_ABI_VERSION; }
 
 #ifndef SPLAT_BUILD_ID
 #define SPLAT_BUILD_ID "unstamped"

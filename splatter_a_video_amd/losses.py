@@ -1,0 +1,144 @@
+"""SSIM and the L1 + D-SSIM image loss of the reference's training step, on the HIP kernels of csrc/loss.hip.
+
+``ssim`` has the signature and the semantics of the reference's ``pointrix.model.loss.ssim`` (src/pointrix/model/loss.py:58-112):
+the channel is dim -3, so the trainer's literal call ``ssim(pred.reshape(-1, h, w, 3), ...)`` (src/trainer_fragGS.py:576) slides
+the window over (x, colour) planes, one per image row, and gives the trainer's number.  Inputs are read in place through their
+strides (no copy).  ``dssim_l1`` is the trainer's RGB objective ``(1 - lam) * l1 + lam * (1 - ssim)`` (:575-578) in one launch.
+There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib as L
+
+LAYOUTS = ("reference", "image")
+
+
+def _check(t: torch.Tensor, name: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise ValueError(f"{name} must be a CUDA (ROCm) tensor (there is no CPU fallback)")
+    if L._cur_device is not None and t.device.index != L._cur_device():
+        raise ValueError(f"{name} lives on cuda:{t.device.index} but the current device is cuda:{L._cur_device()}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be torch.float32, got {t.dtype}")
+    return t
+
+
+def _strides(t: torch.Tensor):
+    return (ctypes.c_int64 * 4)(*t.stride())
+
+
+def _scratch(N: int, Cp: int, Hp: int, Wp: int, window: int, dev) -> torch.Tensor:
+    nbytes = L.lib().splat_ssim_scratch_bytes(N, Cp, Hp, Wp, window)
+    if nbytes == 0:
+        raise ValueError(f"ssim: unsupported sizes [{N}, {Cp}, {Hp}, {Wp}] / window {window} (odd windows 1 .. 15)")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+
+
+class _SSIM(torch.autograd.Function):
+    """mean SSIM (size_average) or per-image means of [N, Cp, Hp, Wp] views; saves only the inputs, the backward is one launch
+    per input that wants a gradient (SSIM is symmetric: the gradient w.r.t. img2 is the same kernel with the images swapped)"""
+
+    @staticmethod
+    def forward(ctx, img1, img2, window, size_average):
+        N, Cp, Hp, Wp = img1.shape
+        out = torch.empty(1 if size_average else N, dtype=torch.float32, device=img1.device)
+        L.check(L.lib().splat_ssim_forward(N, Cp, Hp, Wp, window, L.ptr(img1), _strides(img1), L.ptr(img2), _strides(img2),
+                                           L.ptr(out) if size_average else None, None if size_average else L.ptr(out),
+                                           L.ptr(_scratch(N, Cp, Hp, Wp, window, img1.device)), L.stream()))
+        ctx.save_for_backward(img1, img2)
+        ctx.window, ctx.size_average = window, size_average
+        return out[0] if size_average else out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        img1, img2 = ctx.saved_tensors
+        N, Cp, Hp, Wp = img1.shape
+        g = g.detach().to(torch.float32).contiguous()
+        grads = [None, None]
+        for k, (a, b) in enumerate(((img1, img2), (img2, img1))):
+            if ctx.needs_input_grad[k]:
+                d = torch.empty(a.shape, dtype=torch.float32, device=a.device)
+                L.check(L.lib().splat_ssim_backward(N, Cp, Hp, Wp, ctx.window, L.ptr(a), _strides(a), L.ptr(b), _strides(b),
+                                                    L.ptr(g), 0 if ctx.size_average else 1, L.ptr(d), _strides(d), 0,
+                                                    L.stream()))
+                grads[k] = d
+        return grads[0], grads[1], None, None
+
+
+def ssim(img1: torch.Tensor, img2: torch.Tensor, window_size: int = 11, size_average: bool = True) -> torch.Tensor:
+    """SSIM of two images [N, C, H, W] (or [C, H, W] with size_average=True); C = dim -3 is the channel, the window slides over
+    the last two dims.  size_average: the mean of the SSIM map (a 0-d tensor), else each image's mean ([N]).  Differentiable
+    w.r.t. both images (once)."""
+    _check(img1, "img1")
+    _check(img2, "img2")
+    if img1.shape != img2.shape:
+        raise ValueError(f"ssim: shapes differ: {tuple(img1.shape)} vs {tuple(img2.shape)}")
+    if img1.dim() == 3:
+        if not size_average:
+            raise ValueError("ssim: a [C, H, W] input has no per-image mean (size_average=False needs [N, C, H, W])")
+        img1, img2 = img1.unsqueeze(0), img2.unsqueeze(0)
+    if img1.dim() != 4:
+        raise ValueError(f"ssim: expected [N, C, H, W] or [C, H, W], got {tuple(img1.shape)}")
+    return _SSIM.apply(img1, img2, int(window_size), bool(size_average))
+
+
+def planes(t: torch.Tensor, layout: str) -> torch.Tensor:
+    """the [N, Cp, Hp, Wp] view of RGB frames [F, 3, H, W] whose planes the SSIM window slides over: "reference" -- the trainer's
+    ``ssim(pred.permute(1, 2, 0).reshape(-1, h, w, 3))``, planes of W x 3, one per image row; "image" -- per-colour H x W"""
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout must be one of {LAYOUTS}, got {layout!r}")
+    if t.dim() == 3:
+        t = t.unsqueeze(0)
+    return t.permute(0, 2, 3, 1) if layout == "reference" else t
+
+
+def dssim_l1_grad(pred: torch.Tensor, target: torch.Tensor, w_l1: float, w_ssim: float, layout: str, grad: torch.Tensor,
+                  l1_sum: torch.Tensor, ssim_sum: torch.Tensor) -> None:
+    """one launch (+ the sums' reduction): grad (dense, pred's shape) = the gradient of w_l1 * mean|pred - target| +
+    w_ssim * (1 - ssim(pred, target)) w.r.t. pred; sum |pred - target| and the sum of the SSIM map ADDED to the device slots"""
+    _check(pred, "pred")
+    _check(target, "target")
+    if pred.shape != target.shape or grad.shape != pred.shape:
+        raise ValueError(f"dssim_l1: pred {tuple(pred.shape)}, target {tuple(target.shape)} and grad {tuple(grad.shape)} differ")
+    p4, t4, g4 = planes(pred, layout), planes(target, layout), planes(grad, layout)
+    N, Cp, Hp, Wp = p4.shape
+    L.check(L.lib().splat_dssim_l1_loss_grad(N, Cp, Hp, Wp, 11, L.ptr(p4), _strides(p4), L.ptr(t4), _strides(t4), L.cf(w_l1),
+                                             L.cf(w_ssim), L.ptr(g4), _strides(g4), L.ptr(l1_sum), L.ptr(ssim_sum),
+                                             L.ptr(_scratch(N, Cp, Hp, Wp, 11, pred.device)), L.stream()))
+
+
+class _DSSIML1(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, lam, layout):
+        grad = torch.empty(pred.shape, dtype=torch.float32, device=pred.device)
+        sums = torch.zeros(2, dtype=torch.float32, device=pred.device)
+        dssim_l1_grad(pred, target, 1.0 - lam, lam, layout, grad, sums[0:1], sums[1:2])
+        ctx.save_for_backward(grad)
+        n = pred.numel()
+        return (1.0 - lam) * (sums[0] / n) + lam * (1.0 - sums[1] / n)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None, None
+
+
+def dssim_l1(pred: torch.Tensor, target: torch.Tensor, lam: float = 0.2, layout: str = "reference") -> torch.Tensor:
+    """the reference trainer's RGB loss ``(1 - lam) * l1_loss(pred, target) + lam * (1 - ssim(pred, target))`` of RGB frames
+    [F, 3, H, W] (or [3, H, W]; 11-tap window), its gradient w.r.t. pred computed in the same launch.  layout "reference": the
+    trainer's HWC call (planes of W x 3); "image": the usual per-colour SSIM.  target is ground truth: no gradient reaches it."""
+    _check(pred, "pred")
+    _check(target, "target")
+    if target.requires_grad:
+        raise ValueError("dssim_l1: target is ground truth; detach it (no gradient w.r.t. target is computed)")
+    planes(pred, layout)
+    return _DSSIML1.apply(pred, target, float(lam), layout)

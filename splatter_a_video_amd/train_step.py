@@ -14,6 +14,8 @@ K = 5 nearest neighbours + the ARAP energy of the pair (:671-675; src/geometry_u
         the attribute set = [track_gs (per frame) | attributes (shared)] read in place (feature sources)
     L1 losses and their gradients                       fused into the tile backward (splat_alpha_blending_backward_batch_sets_l1;
                                                         fused_l1=False: splat_l1_loss_grad + gradient images)
+        LossWeights.dssim > 0: the RGB term's L1 + D-SSIM gradient image from splat_dssim_l1_loss_grad, depth / attr by
+        splat_l1_loss_grad (the fused_l1=False path)
     three-set tile backward + Gaussian-side walk        (autograd of render_dynamic_sets)        row a10
         track_gs' per-frame gradient lands next to the ARAP gradient of position(ids2)
     both position gradients -> spline segments          splat_dynamic_positions_batch_backward
@@ -44,6 +46,7 @@ from .dynamics import (GAUSSIAN_MAJOR, SEGMENT_MAJOR, FrameClock, frame_table, p
 from .frames import FrameBatch
 from .gs.fused_ops import compute_sh_into
 from .gs.point_ops import project_point_ortho
+from .losses import dssim_l1_grad, planes
 from .optim import FlatAdam, OwnerShardedAdam, PatternLR
 from .parallel import (FlatGradBucket, OwnerShards, PositionExchangePlan, Zero1Shards, exchange_frames, gather_times, owner_gather,
                        owner_reduce, reduce_densify_batch)
@@ -78,6 +81,11 @@ class LossWeights:
     depth: float = 1.0
     attr: float = 1.0
     arap: float = 1e-3                  # rigid_error = cal_arap_error(...) / 1000 (src/trainer_fragGS.py:674)
+    # lambda of the RGB term rgb * ((1 - dssim) * l1 + dssim * (1 - ssim)) (src/trainer_fragGS.py:575-578: 0.2), SSIM = the mean
+    # over the step's local frames.  0: the L1 term alone (the step's code path and bits before the term existed).  > 0: the RGB
+    # gradient comes from splat_dssim_l1_loss_grad and the step takes the unfused L1 path (fused_l1 does not apply)
+    dssim: float = 0.0
+    ssim_layout: str = "reference"      # the planes of the SSIM (losses.planes): the trainer's HWC call, or "image"
 
 
 class _Phases:
@@ -118,6 +126,8 @@ class TrainingStep:
         self.dev = params["position"].device
         self.lr = dict(REFERENCE_LR if lr is None else lr)
         self.w = weights or LossWeights()
+        if self.w.dssim > 0:
+            planes(torch.empty(0, 3, 1, 1), self.w.ssim_layout)      # validates the layout name
         self.cfg = densify or DensifyConfig()
         self.K, self.knn_K, self.S, self.bg = int(K), int(knn_K), int(arap_samples), float(bg)
         self.timing = timing
@@ -227,6 +237,18 @@ class TrainingStep:
                                            L.cf(weight / (F * inner)), L.ptr(g), L.ptr(loss_slot), L.stream()))
         return g
 
+    def _rgb_loss_grad(self, pred: Tensor, target: Tensor, sums: Tensor) -> Tensor:
+        """(dssim > 0) gradient image [F, 3, H, W] of rgb * ((1 - lam) * mean|pred - target| + lam * (1 - ssim)) over the local
+        frames (one launch: splat_dssim_l1_loss_grad); sum |pred - target| added to sums[0], the sum of the SSIM map to sums[3]"""
+        F, c, H, W = pred.shape
+        if tuple(target.shape) != (F, c, H, W):
+            raise ValueError(f"ground truth must be [{F}, {c}, {H}, {W}]")
+        g = torch.empty(F, c, H, W, dtype=torch.float32, device=pred.device)
+        lam = self.w.dssim
+        dssim_l1_grad(pred.detach(), target, self.w.rgb * (1.0 - lam), self.w.rgb * lam, self.w.ssim_layout, g, sums[0:1],
+                      sums[3:4])
+        return g
+
     # ------------------------------------------------------------------ the step
     def step(self, times1: Sequence[float], times2: Sequence[float], gt: Dict[str, Tensor]) -> Dict[str, Tensor]:
         """one gradient step on the pairs (times1[f], times2[f]); ``gt``: rgb [F,3,H,W], depth [F,1,H,W], attr [F,3+A,H,W] of
@@ -277,7 +299,8 @@ class TrainingStep:
                                           opacity=p["opacity"], scaling=p["scaling"], cubic_layout=SEGMENT_MAJOR, K=self.K,
                                           grad_sink=sink)
         ph.mark("render_forward")
-        if self.fused_l1 and L.get_option("bwd_quarters"):
+        dssim = self.w.dssim > 0
+        if self.fused_l1 and not dssim and L.get_option("bwd_quarters"):
             # the L1 terms' gradient images are never materialised: the tile kernel derives them from the forward's output row and
             # the ground-truth frames where it hoists the image gradient (splat_alpha_blending_backward_batch_sets_l1)
             fsums = torch.empty(F, self.fb.T, 3, dtype=torch.float32, device=self.dev)      # per tile: every entry is written
@@ -286,8 +309,9 @@ class TrainingStep:
             torch.autograd.backward(list(out[:3]), self.fb.l1_placeholders([3, 1, self.C - 4]))
             sums = fsums.sum((0, 1))
         else:
-            sums = torch.zeros(3, dtype=torch.float32, device=self.dev)
-            grads = [self._l1(out[0], gt["rgb"], self.w.rgb, sums[0:1]), self._l1(out[1], gt["depth"], self.w.depth, sums[1:2]),
+            sums = torch.zeros(4 if dssim else 3, dtype=torch.float32, device=self.dev)
+            g_rgb = (self._rgb_loss_grad(out[0], gt["rgb"], sums) if dssim else self._l1(out[0], gt["rgb"], self.w.rgb, sums[0:1]))
+            grads = [g_rgb, self._l1(out[1], gt["depth"], self.w.depth, sums[1:2]),
                      self._l1(out[2], gt["attr"], self.w.attr, sums[2:3])]
             ph.mark("loss")
             torch.autograd.backward(list(out[:3]), grads)
@@ -327,6 +351,8 @@ class TrainingStep:
         hw = self.W * self.H
         self.last = {"l1_rgb": sums[0] / (F * 3 * hw), "l1_depth": sums[1] / (F * hw),
                      "l1_attr": sums[2] / (F * (self.C - 4) * hw), "arap": arap.mean()}
+        if dssim:
+            self.last["ssim_rgb"] = sums[3] / (F * 3 * hw)
         if self.timing:
             self._marks = ph
         return self.last
@@ -401,7 +427,10 @@ class TrainingStep:
     def loss(self) -> float:
         """weighted loss of the last step (host sync)"""
         l = self.last
-        return float(self.w.rgb * l["l1_rgb"] + self.w.depth * l["l1_depth"] + self.w.attr * l["l1_attr"] + self.w.arap * l["arap"])
+        rgb = l["l1_rgb"]
+        if "ssim_rgb" in l:
+            rgb = (1.0 - self.w.dssim) * rgb + self.w.dssim * (1.0 - l["ssim_rgb"])
+        return float(self.w.rgb * rgb + self.w.depth * l["l1_depth"] + self.w.attr * l["l1_attr"] + self.w.arap * l["arap"])
 
     # ------------------------------------------------------------------ structure
     def _gather(self):
