@@ -767,6 +767,28 @@ int splat_dssim_l1_loss_grad(int N, int Cp, int Hp, int Wp, int window, const fl
                              const float *gt, const int64_t *gt_strides, float w_l1, float w_ssim, float *grad,
                              const int64_t *grad_strides, float *l1_sum, float *ssim_sum, void *scratch, splat_stream_t stream);
 
+/* ---- 2-D track loss: the trainer's optical-flow term on the rendered track_gs (src/trainer_fragGS.py:528-569, with
+ *      parse_tapir_track_info and masked_l1_loss(mask=c, quantile) with its default normalize=True).  Frame f of the track image [F, C, H, W] (four
+ *      ELEMENT strides, read in place: a channel slice of a wider row works; channels 0, 1 are the normalised x, y) owns the
+ *      queries offsets[f] .. offsets[f + 1] (device int64 [F + 1]) of pixels (device int32 [Q], raster index y * W + x, strictly
+ *      ascending within a frame) and targets (device float32 [Q, 4] = x, y, occlusion logit, expected-distance logit; 16-byte
+ *      aligned).  Query i pairs the prediction at pixels[i] with target row i.  Per frame, over the visible queries
+ *      ((1 - sigmoid(occ)) (1 - sigmoid(dist)) > 0.5):
+ *        X = ((img[0] + 1) W) / 2, Y = ((img[1] + 1) H) / 2, r = (|X - tx| + |Y - ty|) / 2, c = (1 - sigmoid(dist)) w_f,
+ *        thr = torch.quantile(r, quantile), S = {r <= thr}, loss_f = sum_S c r / (sum_S c + 1e-8) / max(H, W)
+ *      (0 without a visible query; a NaN residual makes thr NaN and S empty: 0, as in the reference)
+ *      with w_f = frame_weights[f] (device float32 [F]).  Outputs (each optional): per_frame [F] = loss_f; *loss_slot +=
+ *      mean_f loss_f; counts int32 [F, 2] = (visible, selected); grad (own strides, C channels, must not overlap the inputs) =
+ *      scale * d(mean_f loss_f) / d track -- written (zeros outside S and in channels >= 2) or, accumulate != 0, ADDED at the
+ *      selected pixels only.  One workgroup per frame (+ a zeroing launch when grad is written, + one launch for the slot); no
+ *      float atomics, no host synchronisation: bit-reproducible and capturable.  Malformed offsets and pixel indices (out of range, or
+ *      not above the frame's previous index: a duplicate) are skipped on the device, never dereferenced.  Scratch: splat_track_loss_scratch_bytes(F, Q) bytes. ---- */
+size_t splat_track_loss_scratch_bytes(int F, int64_t Q);      /* 0: invalid sizes */
+int splat_track_loss_grad(int F, int H, int W, int C, const float *track, const int64_t *track_strides, const int64_t *offsets,
+                          const int32_t *pixels, const float *targets, int64_t Q, const float *frame_weights, float quantile,
+                          float scale, float *grad, const int64_t *grad_strides, int accumulate, float *per_frame,
+                          float *loss_slot, int32_t *counts, void *scratch, splat_stream_t stream);
+
 #define SPLAT_ADAM_MAX_SEGMENTS 16
 int splat_adam_step(int64_t n, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int nseg,
                     const int64_t *seg_end_host, const float *seg_lr_host, float beta1, float beta2, float eps,

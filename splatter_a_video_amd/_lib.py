@@ -57,6 +57,7 @@ SYMBOLS = [
     "splat_alpha_blending_backward_batch_sets_l1", "splat_bin_count_batch_reach", "splat_bin_sort_batch_reach",
     "splat_profile_enable", "splat_profile_reset", "splat_profile_read",
     "splat_ssim_scratch_bytes", "splat_ssim_forward", "splat_ssim_backward", "splat_dssim_l1_loss_grad",
+    "splat_track_loss_scratch_bytes", "splat_track_loss_grad",
 ]
 
 # environment switches of earlier rounds, applied ONCE at load THROUGH the ABI (splat_set_option): the library itself reads no
@@ -114,6 +115,9 @@ def lib() -> ctypes.CDLL:
         L.splat_ssim_forward.argtypes = [i, i, i, i, i, p, s4, p, s4, p, p, p, p]
         L.splat_ssim_backward.argtypes = [i, i, i, i, i, p, s4, p, s4, p, i, p, s4, i, p]
         L.splat_dssim_l1_loss_grad.argtypes = [i, i, i, i, i, p, s4, p, s4, f, f, p, s4, p, p, p, p]
+        L.splat_track_loss_scratch_bytes.restype = ctypes.c_size_t
+        L.splat_track_loss_scratch_bytes.argtypes = [i, ctypes.c_int64]
+        L.splat_track_loss_grad.argtypes = [i, i, i, i, p, s4, p, p, p, ctypes.c_int64, p, f, f, p, s4, i, p, p, p, p, p]
         if L.splat_abi_version() != ABI_VERSION:
             raise SplatError("libsplat_hip.so ABI version mismatch; rebuild it")
         _lib = L

@@ -440,3 +440,331 @@ extern "C" int splat_dssim_l1_loss_grad(int N, int Cp, int Hp, int Wp, int windo
     }
     return SPLAT_OK;
 }
+
+// ==================================================================================================================================
+// 2-D track loss: the trainer's optical-flow term on the rendered track_gs (src/trainer_fragGS.py:528-569).  Per frame f (one
+// workgroup of 1024 threads):
+//   1. every query e of the frame: visible when (1 - sigmoid(occ)) (1 - sigmoid(dist)) > 0.5 (parse_tapir_track_info); then
+//      X = ((img[0, p] + 1) W) / 2, Y = ((img[1, p] + 1) H) / 2 (util.denormalize_coords), r = (|X - tx| + |Y - ty|) / 2 and its
+//      float bits go to scratch as a uint32 key (r >= 0: the bits order as the values); invisible / malformed queries get
+//      TRK_NONE, above every key.  n = the visible count.  Malformed: a pixel index out of range, or not above the frame's
+//      previous one (the indices must ascend strictly, so no two queries of a frame share a pixel: the gradient's plain
+//      read-modify-write never races)
+//   2. radix select of rank k = floor(q (n - 1)) with four 8-bit LDS histograms, rank k + 1 by one more pass (count <= s_k,
+//      min > s_k); the threshold is torch.quantile's lerp in its float32 FMA form.  A NaN residual makes torch.quantile NaN:
+//      then thr = NaN, S is empty and the frame's loss is 0, as the reference's masked_l1_loss gives
+//   3. sums of c r and of c over S = {r <= thr}, c = (1 - sigmoid(dist)) w_f, per thread in a fixed order + a fixed-order
+//      workgroup sum; loss_f = sum c r / (sum c + 1e-8) / max(H, W) -- the trainer's masked_l1_loss(..., mask=c, quantile)
+//      with its default normalize=True, divided by max(h, w)
+//   4. the sparse gradient at the selected pixels (channels 0 and 1)
+// The scratch keys stay in L2 (100 KB at 25.6k queries).  No float atomics (LDS integer histograms only): bit-reproducible; n
+// and k never leave the device.  The residuals are computed with contraction off, so they are bit-equal to the float32 torch
+// ops they restate and the selected set can be compared exactly.
+namespace {
+
+constexpr int TRK_THREADS = 1024;
+constexpr unsigned TRK_NONE = 0xffffffffu;
+
+struct TrackArgs {
+    int H, W;
+    const float *img;
+    long long is[4];
+    const int64_t *offsets;
+    const int32_t *pixels;
+    const float4 *targets;
+    long long Q;
+    const float *fw;
+    float q, gscale;              // quantile; gradient weight per frame (scale / F)
+    float *grad;
+    long long gs[4];
+    float *per_frame, *part;      // per_frame: optional output; part: scratch [F] for the slot's sum
+    int32_t *counts;
+    unsigned *keys;
+};
+
+__device__ __forceinline__ float trk_one_minus_sigmoid(float x) {
+#pragma clang fp contract(off)
+    return 1.f - 1.f / (1.f + expf(-x));
+}
+
+// query e of frame f (whose queries start at o0): false when invisible or malformed (pixel out of range, or not above the
+// previous query's); else its residual parts and weight
+__device__ __forceinline__ bool trk_point(const TrackArgs &A, int f, long long o0, long long e, float w, float &dx, float &dy,
+                                          float &r, float &c, int &py, int &px) {
+#pragma clang fp contract(off)
+    const int p = A.pixels[e];
+    if (p < 0 || p >= A.H * A.W || (e > o0 && A.pixels[e - 1] >= p)) return false;
+    const float4 t = A.targets[e];
+    const float conf = trk_one_minus_sigmoid(t.w);
+    if (!(trk_one_minus_sigmoid(t.z) * conf > 0.5f)) return false;
+    py = p / A.W;
+    px = p - py * A.W;
+    const float *b = A.img + (long long)f * A.is[0] + (long long)py * A.is[2] + (long long)px * A.is[3];
+    const float X = ((b[0] + 1.f) * (float)A.W) / 2.f;
+    const float Y = ((b[A.is[1]] + 1.f) * (float)A.H) / 2.f;
+    dx = X - t.x;
+    dy = Y - t.y;
+    r = (fabsf(dx) + fabsf(dy)) / 2.f;
+    c = conf * w;
+    return true;
+}
+
+__device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__device__ __forceinline__ unsigned wave_min_u(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = umin_(v, __shfl_xor(v, o));
+    return v;
+}
+
+__global__ void __launch_bounds__(TRK_THREADS) track_loss_kernel(TrackArgs A) {
+#pragma clang fp contract(off)
+    __shared__ unsigned hist[256];
+    __shared__ unsigned su[4];
+    __shared__ float red[2][TRK_THREADS / WAVE];
+    __shared__ float sden;
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
+    long long o0 = A.offsets[f], o1 = A.offsets[f + 1];
+    if (!(0 <= o0 && o0 <= o1 && o1 <= A.Q)) o0 = o1 = 0;      // malformed offsets: an empty frame
+    const float w = A.fw[f];
+    const float maxhw = (float)(A.H > A.W ? A.H : A.W);
+
+    // ---- 1. keys, visible count, NaN residuals
+    if (tid == 0) { su[0] = 0; su[3] = 0; }
+    __syncthreads();
+    unsigned nloc = 0, nnan = 0;
+    for (long long e = o0 + tid; e < o1; e += TRK_THREADS) {
+        float dx, dy, r, c;
+        int py, px;
+        unsigned key = TRK_NONE;
+        if (trk_point(A, f, o0, e, w, dx, dy, r, c, py, px)) {
+            key = __float_as_uint(r);
+            ++nloc;
+            nnan += key > 0x7f800000u;
+        }
+        A.keys[e] = key;
+    }
+    nloc = wave_sum_u(nloc);
+    nnan = wave_sum_u(nnan);
+    if (lane == 0) {
+        atomicAdd(&su[0], nloc);
+        atomicAdd(&su[3], nnan);
+    }
+    __syncthreads();
+    const int n = (int)su[0];
+    const bool has_nan = su[3] != 0;
+    if (n == 0) {
+        if (tid == 0) {
+            if (A.per_frame) A.per_frame[f] = 0.f;
+            A.part[f] = 0.f;
+            if (A.counts) { A.counts[2 * f] = 0; A.counts[2 * f + 1] = 0; }
+        }
+        return;
+    }
+
+    // ---- 2. ranks k and k + 1 of the visible residuals, threshold (NaN when a residual is)
+    float thr = __builtin_nanf("");
+    if (!has_nan) {
+        const float pos = A.q * (float)(n - 1);
+        int k = (int)floorf(pos);
+        k = k < 0 ? 0 : (k > n - 1 ? n - 1 : k);
+        const float wgt = pos - (float)k;
+        unsigned prefix = 0, pmask = 0, kk = (unsigned)k;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) hist[tid] = 0;
+            __syncthreads();
+            for (long long e = o0 + tid; e < o1; e += TRK_THREADS) {
+                const unsigned key = A.keys[e];
+                if ((key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+            }
+            __syncthreads();
+            if (tid < WAVE) {     // lane l owns bins 4l .. 4l + 3; the lane whose range holds rank kk finds the bin
+                const unsigned h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
+                const unsigned s = (h0 + h1) + (h2 + h3);
+                unsigned incl = s;
+#pragma unroll
+                for (int o = 1; o < WAVE; o <<= 1) {
+                    const unsigned t = __shfl_up(incl, o);
+                    if (tid >= o) incl += t;
+                }
+                const unsigned excl = incl - s;
+                if (excl <= kk && kk < incl) {
+                    unsigned below = excl, b = 4 * tid;
+                    if (below + h0 <= kk) { below += h0; ++b;
+                        if (below + h1 <= kk) { below += h1; ++b;
+                            if (below + h2 <= kk) { below += h2; ++b; } } }
+                    su[1] = b;
+                    su[2] = below;
+                }
+            }
+            __syncthreads();
+            prefix |= su[1] << shift;
+            pmask |= 0xffu << shift;
+            kk -= su[2];
+            __syncthreads();
+        }
+        const unsigned sk = prefix;
+        if (tid == 0) { su[1] = 0; su[2] = TRK_NONE; }
+        __syncthreads();
+        {
+            unsigned cle = 0, mgt = TRK_NONE;
+            for (long long e = o0 + tid; e < o1; e += TRK_THREADS) {
+                const unsigned key = A.keys[e];
+                if (key <= sk) ++cle;
+                else mgt = umin_(mgt, key);
+            }
+            cle = wave_sum_u(cle);
+            mgt = wave_min_u(mgt);
+            if (lane == 0) {
+                atomicAdd(&su[1], cle);
+                atomicMin(&su[2], mgt);
+            }
+        }
+        __syncthreads();
+        const unsigned sk1 = (k + 1 >= n || su[1] >= (unsigned)k + 2u) ? sk : su[2];
+        const float a = __uint_as_float(sk), b = __uint_as_float(sk1), d = b - a;
+        thr = fabsf(wgt) < 0.5f ? fmaf(wgt, d, a) : fmaf(wgt - 1.f, d, b);
+    }
+
+    // ---- 3. sums of c r and of c over the selected set, |S|
+    float acc = 0.f, accc = 0.f;
+    unsigned sel = 0;
+    for (long long e = o0 + tid; e < o1; e += TRK_THREADS) {
+        const unsigned key = A.keys[e];
+        if (key == TRK_NONE) continue;
+        const float r = __uint_as_float(key);
+        if (!(r <= thr)) continue;
+        const float c = trk_one_minus_sigmoid(A.targets[e].w) * w;
+        acc += c * r;
+        accc += c;
+        ++sel;
+    }
+    acc = wave_sum_to_lane63(acc);
+    accc = wave_sum_to_lane63(accc);
+    sel = wave_sum_u(sel);
+    if (lane == WAVE - 1) {
+        red[0][wv] = acc;
+        red[1][wv] = accc;
+    }
+    __syncthreads();           // su[3] (the NaN count) was read by every thread before the passes' barriers
+    if (tid == 0) su[3] = 0;
+    __syncthreads();
+    if (lane == 0) atomicAdd(&su[3], sel);
+    __syncthreads();
+    const unsigned nsel = su[3];
+    if (tid == 0) {
+        float s = 0.f, sc = 0.f;
+        for (int i = 0; i < TRK_THREADS / WAVE; ++i) {
+            s += red[0][i];
+            sc += red[1][i];
+        }
+        const float den = sc + 1e-8f;          // ndim (= 1) * sum_S c + 1e-8 (masked_l1_loss, normalize=True)
+        const float loss = (s / den) / maxhw;
+        sden = den;
+        if (A.per_frame) A.per_frame[f] = loss;
+        A.part[f] = loss;
+        if (A.counts) { A.counts[2 * f] = n; A.counts[2 * f + 1] = (int)nsel; }
+    }
+    if (!A.grad || nsel == 0) return;
+    __syncthreads();
+
+    // ---- 4. d(gscale * loss_f)/d img at the selected pixels: c / ((sum_S c + 1e-8) max(H, W)) / 2 * sign(d) * (W or H) / 2
+    const float base = A.gscale / (sden * maxhw) * 0.5f;
+    const float hx = 0.5f * (float)A.W, hy = 0.5f * (float)A.H;
+    for (long long e = o0 + tid; e < o1; e += TRK_THREADS) {
+        float dx, dy, r, c;
+        int py, px;
+        if (!trk_point(A, f, o0, e, w, dx, dy, r, c, py, px) || !(r <= thr)) continue;
+        const float g = base * c;
+        float *gp = A.grad + (long long)f * A.gs[0] + (long long)py * A.gs[2] + (long long)px * A.gs[3];
+        gp[0] += dx > 0.f ? g * hx : (dx < 0.f ? -(g * hx) : 0.f);
+        gp[A.gs[1]] += dy > 0.f ? g * hy : (dy < 0.f ? -(g * hy) : 0.f);
+    }
+}
+
+// zero the gradient image [F, C, H, W] (its own strides) before the sparse entries land; grid.y walks the planes
+__global__ void __launch_bounds__(256) track_grad_zero_kernel(float *g, long long s0, long long s1, long long s2, long long s3, int C,
+                                                              int H, int W, int planes) {
+    const int hw = H * W;
+    for (int pl = blockIdx.y; pl < planes; pl += gridDim.y) {
+        float *gp = g + (long long)(pl / C) * s0 + (long long)(pl % C) * s1;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < hw; i += gridDim.x * 256) {
+            const int y = i / W, x = i - y * W;
+            gp[(long long)y * s2 + (long long)x * s3] = 0.f;
+        }
+    }
+}
+
+// *slot += the mean of the per-frame losses, added in frame order
+__global__ void track_loss_slot_kernel(int F, const float *part, float *slot) {
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int f = 0; f < F; ++f) s += part[f];
+        *slot += s / (float)F;
+    }
+}
+
+size_t trk_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" size_t splat_track_loss_scratch_bytes(int F, int64_t Q) {
+    if (F < 1 || Q < 0 || Q > 0x7fffffffLL) return 0;
+    return trk_align((size_t)Q * sizeof(unsigned)) + trk_align((size_t)F * sizeof(float));
+}
+
+extern "C" int splat_track_loss_grad(int F, int H, int W, int C, const float *track, const int64_t *track_strides,
+                                     const int64_t *offsets, const int32_t *pixels, const float *targets, int64_t Q,
+                                     const float *frame_weights, float quantile, float scale, float *grad,
+                                     const int64_t *grad_strides, int accumulate, float *per_frame, float *loss_slot,
+                                     int32_t *counts, void *scratch, splat_stream_t stream) {
+    SPLAT_CHECK_ARG(F >= 1 && H >= 1 && W >= 1 && C >= 2 && Q >= 0, "bad sizes (F, H, W >= 1, C >= 2, Q >= 0)");
+    SPLAT_CHECK_ARG((long long)H * W <= 0x7fffffffLL && Q <= 0x7fffffffLL && F <= (1 << 24) && (long long)F * C <= 0x7fffffffLL,
+                    "sizes too large");
+    SPLAT_CHECK_ARG(quantile >= 0.f && quantile <= 1.f, "quantile must be in [0, 1]");
+    SPLAT_CHECK_ARG(track && track_strides && offsets && frame_weights && scratch, "null pointer");
+    SPLAT_CHECK_ARG(Q == 0 || (pixels && targets), "null pointer (pixels / targets)");
+    SPLAT_CHECK_ARG(((uintptr_t)targets & 15) == 0, "targets must be 16-byte aligned [Q, 4] float32");
+    for (int k = 0; k < 4; ++k) SPLAT_CHECK_ARG(track_strides[k] >= 0, "strides must be >= 0");
+    if (grad) {
+        SPLAT_CHECK_ARG(grad_strides, "null pointer (grad_strides)");
+        for (int k = 0; k < 4; ++k) SPLAT_CHECK_ARG(grad_strides[k] >= 0, "strides must be >= 0");
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    TrackArgs A;
+    memset(&A, 0, sizeof(A));
+    A.H = H; A.W = W;
+    A.img = track;
+    for (int k = 0; k < 4; ++k) A.is[k] = track_strides[k];
+    A.offsets = offsets; A.pixels = pixels; A.targets = (const float4 *)targets; A.Q = Q;
+    A.fw = frame_weights;
+    A.q = quantile;
+    A.gscale = scale / (float)F;
+    A.grad = grad;
+    if (grad) for (int k = 0; k < 4; ++k) A.gs[k] = grad_strides[k];
+    A.per_frame = per_frame;
+    A.counts = counts;
+    A.keys = (unsigned *)scratch;
+    A.part = (float *)((char *)scratch + trk_align((size_t)Q * sizeof(unsigned)));
+    if (grad && !accumulate) {
+        const long long planes = (long long)F * C, hw = (long long)H * W;
+        long long bx = (hw + 255) / 256;
+        if (bx > 64) bx = 64;
+        const unsigned by = (unsigned)(planes < 65535 ? planes : 65535);
+        SPLAT_LAUNCH("track_grad_zero", track_grad_zero_kernel, dim3((unsigned)bx, by), dim3(256), 0, s, grad,
+                     (long long)grad_strides[0], (long long)grad_strides[1], (long long)grad_strides[2], (long long)grad_strides[3],
+                     C, H, W, (int)planes);
+        SPLAT_POST_LAUNCH();
+    }
+    SPLAT_LAUNCH("track_loss", track_loss_kernel, dim3(F), dim3(TRK_THREADS), 0, s, A);
+    SPLAT_POST_LAUNCH();
+    if (loss_slot) {
+        SPLAT_LAUNCH("track_loss_slot", track_loss_slot_kernel, dim3(1), dim3(WAVE), 0, s, F, (const float *)A.part, loss_slot);
+        SPLAT_POST_LAUNCH();
+    }
+    return SPLAT_OK;
+}

@@ -142,3 +142,75 @@ def dssim_l1(pred: torch.Tensor, target: torch.Tensor, lam: float = 0.2, layout:
         raise ValueError("dssim_l1: target is ground truth; detach it (no gradient w.r.t. target is computed)")
     planes(pred, layout)
     return _DSSIML1.apply(pred, target, float(lam), layout)
+
+
+# ---------------------------------------------------------------------------------------------------------- the 2-D track loss
+def track_loss_grad(track: torch.Tensor, targets, frame_weights: torch.Tensor, quantile: float = 0.98, scale: float = 1.0,
+                    grad: torch.Tensor = None, accumulate: bool = False, per_frame: torch.Tensor = None,
+                    loss_slot: torch.Tensor = None, counts: torch.Tensor = None) -> None:
+    """one launch of splat_track_loss_grad (include/splat_hip.h) on the track image [F, C, H, W] (C >= 2, any strides: a channel
+    slice of a wider row is read in place) and the ``tracks.TrackTargets`` of its F frame pairs.  Each output is optional:
+    ``grad`` (track's shape, own strides) = scale * d(mean_f loss_f) / d track, written (accumulate=False: zeros elsewhere) or
+    added at the selected pixels; ``per_frame`` [F] = loss_f; ``loss_slot`` (1 element) += mean_f loss_f; ``counts`` int32 [F, 2]
+    = (visible, selected) queries per frame."""
+    _check(track, "track")
+    if track.dim() != 4 or track.shape[1] < 2:
+        raise ValueError(f"track must be [F, C >= 2, H, W], got {tuple(track.shape)}")
+    F, C, H, W = track.shape
+    if (targets.F, targets.H, targets.W) != (F, H, W):
+        raise ValueError(f"track targets of {targets.F} frames of {targets.W} x {targets.H} for a track image {tuple(track.shape)}")
+    if targets.device != track.device:
+        raise ValueError(f"track targets live on {targets.device}, the image on {track.device}")
+    if not 0.0 <= float(quantile) <= 1.0:
+        raise ValueError(f"quantile must be in [0, 1], got {quantile}")
+    fw = frame_weights
+    if not isinstance(fw, torch.Tensor) or fw.numel() != F:
+        raise ValueError(f"frame_weights must be a tensor of {F} weights")
+    fw = fw.to(device=track.device, dtype=torch.float32).reshape(F).contiguous()
+    if grad is not None:
+        _check(grad, "grad")
+        if grad.shape != track.shape:
+            raise ValueError(f"grad {tuple(grad.shape)} must have the track image's shape {tuple(track.shape)}")
+    for t, name, n in ((per_frame, "per_frame", F), (loss_slot, "loss_slot", 1)):
+        if t is not None and (_check(t, name).numel() != n or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous float32 tensor of {n} elements")
+    if counts is not None and (counts.dtype != torch.int32 or counts.numel() != 2 * F or not counts.is_contiguous()
+                               or counts.device != track.device):
+        raise ValueError(f"counts must be a contiguous int32 [{F}, 2] tensor on the image's device")
+    lib = L.lib()
+    nbytes = lib.splat_track_loss_scratch_bytes(F, targets.Q)
+    if nbytes == 0:
+        raise ValueError(f"track loss: unsupported sizes (F = {F}, Q = {targets.Q})")
+    scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=track.device)
+    L.check(lib.splat_track_loss_grad(F, H, W, C, L.ptr(track), _strides(track), L.ptr(targets.offsets), L.ptr(targets.pixels),
+                                      L.ptr(targets.targets), ctypes.c_int64(targets.Q), L.ptr(fw), L.cf(quantile), L.cf(scale),
+                                      L.ptr(grad), _strides(grad) if grad is not None else None, 1 if accumulate else 0,
+                                      L.ptr(per_frame), L.ptr(loss_slot), L.ptr(counts), L.ptr(scratch), L.stream()))
+
+
+class _TrackLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, track, targets, frame_weights, quantile):
+        loss = torch.zeros(1, dtype=torch.float32, device=track.device)
+        grad = torch.empty(track.shape, dtype=torch.float32, device=track.device) if ctx.needs_input_grad[0] else None
+        track_loss_grad(track.detach(), targets, frame_weights, quantile, 1.0, grad, loss_slot=loss)
+        ctx.save_for_backward(grad)
+        return loss[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None, None
+
+
+def track_loss(track_image: torch.Tensor, targets, frame_weights: torch.Tensor, quantile: float = 0.98) -> torch.Tensor:
+    """the reference trainer's optical-flow term (src/trainer_fragGS.py:528-569) of F frame pairs, averaged over the pairs: per
+    pair f, over the visible queries of ``targets`` (``tracks.TrackTargets``), masked_l1_loss(denormalize_coords(pred), track,
+    mask=c w_f, quantile) / max(H, W) with masked_l1_loss's default normalize=True, i.e. the weighted mean
+    sum_S c r / (sum_S c + 1e-8) / max(H, W), the prediction read from channels 0, 1 of ``track_image`` [F, C, H, W] (the
+    rendered track_gs) at the query pixels; 0 for a pair without a visible query.  ``frame_weights`` [F]: the
+    ``tracks.frame_weights`` of the pairs.  Differentiable w.r.t. the image (the quantile's selection is a constant); the
+    gradient comes from the same launch."""
+    _check(track_image, "track_image")
+    return _TrackLoss.apply(track_image, targets, frame_weights, float(quantile))

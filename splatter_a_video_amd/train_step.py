@@ -16,6 +16,8 @@ K = 5 nearest neighbours + the ARAP energy of the pair (:671-675; src/geometry_u
                                                         fused_l1=False: splat_l1_loss_grad + gradient images)
         LossWeights.dssim > 0: the RGB term's L1 + D-SSIM gradient image from splat_dssim_l1_loss_grad, depth / attr by
         splat_l1_loss_grad (the fused_l1=False path)
+        LossWeights.track > 0: the 2-D track loss on track_gs (gt["tracks"]) from splat_track_loss_grad; the attribute L1
+        covers the A attribute channels only (the fused_l1=False path)
     three-set tile backward + Gaussian-side walk        (autograd of render_dynamic_sets)        row a10
         track_gs' per-frame gradient lands next to the ARAP gradient of position(ids2)
     both position gradients -> spline segments          splat_dynamic_positions_batch_backward
@@ -46,10 +48,11 @@ from .dynamics import (GAUSSIAN_MAJOR, SEGMENT_MAJOR, FrameClock, frame_table, p
 from .frames import FrameBatch
 from .gs.fused_ops import compute_sh_into
 from .gs.point_ops import project_point_ortho
-from .losses import dssim_l1_grad, planes
+from .losses import dssim_l1_grad, planes, track_loss_grad
 from .optim import FlatAdam, OwnerShardedAdam, PatternLR
 from .parallel import (FlatGradBucket, OwnerShards, PositionExchangePlan, Zero1Shards, exchange_frames, gather_times, owner_gather,
                        owner_reduce, reduce_densify_batch)
+from .tracks import TrackTargets, _upload, frame_weights
 
 TRAINABLE = ("pos_cubic_node", "rotation", "opacity", "scaling", "shs", "attrs")
 FROZEN = ("position", "rot_poly_feat", "rot_fourier_feat")          # :90 position is not optimised; :195-197 detached tables
@@ -86,6 +89,12 @@ class LossWeights:
     # gradient comes from splat_dssim_l1_loss_grad and the step takes the unfused L1 path (fused_l1 does not apply)
     dssim: float = 0.0
     ssim_layout: str = "reference"      # the planes of the SSIM (losses.planes): the trainer's HWC call, or "image"
+    # weight of the 2-D track loss on track_gs (src/trainer_fragGS.py:528-569; loss_flow_weight = 2.0 in src/configs/config.txt),
+    # the mean over the step's local pairs.  0: no track term (the step's code path and bits before the term existed).  > 0:
+    # gt["tracks"] is required, the track channels get only this term's gradient, the attribute L1 covers the A attribute
+    # channels, and the step takes the unfused L1 path (fused_l1 does not apply)
+    track: float = 0.0
+    track_quantile: float = 0.98       # masked_l1_loss(..., quantile=0.98): the worst 2 % of the residuals are trimmed
 
 
 class _Phases:
@@ -249,15 +258,48 @@ class TrainingStep:
                       sums[3:4])
         return g
 
+    def _track_loss_grad(self, pred: Tensor, tracks: TrackTargets, weights: Tensor, grad: Tensor, slot: Tensor) -> None:
+        """(track > 0) the track channels' gradient image: ``grad`` [F, 3, H, W] (a view, written in full) = track * the gradient
+        of the mean over the local pairs of the 2-D track loss of ``pred`` [F, 3, H, W] (the rendered track_gs) w.r.t. pred;
+        that mean (unweighted) added to ``slot`` (one launch: splat_track_loss_grad)"""
+        track_loss_grad(pred.detach(), tracks, weights, self.w.track_quantile, self.w.track, grad, loss_slot=slot)
+
+    def _attr_l1(self, pred: Tensor, target: Tensor, grad: Tensor, loss_slot: Tensor) -> None:
+        """(track > 0) the attribute L1 over channels 3.. of the attribute set: grad[:, 3:] = attr * the gradient of their mean
+        |pred - target| over the local frames, the sum of |.| added to ``loss_slot``; one splat_l1_loss_grad per frame (a frame's
+        attribute channels are one contiguous block of the row, the ground truth and the gradient image)"""
+        import ctypes
+        F, c, H, W = grad.shape
+        inner = (c - 3) * H * W
+        if inner == 0:
+            return
+        if pred.stride(1) != H * W or pred.stride(2) != W or pred.stride(3) != 1:
+            pred = pred.contiguous()
+        target = L.need(target, "ground truth")
+        if tuple(target.shape) != (F, c, H, W):
+            raise ValueError(f"ground truth must be [{F}, {c}, {H}, {W}]")
+        lib = L.lib()
+        for f in range(F):
+            L.check(lib.splat_l1_loss_grad(1, ctypes.c_int64(inner), L.ptr(pred[f, 3:]), ctypes.c_int64(inner), L.ptr(target[f, 3:]),
+                                           L.cf(self.w.attr / (F * inner)), L.ptr(grad[f, 3:]), L.ptr(loss_slot), L.stream()))
+
     # ------------------------------------------------------------------ the step
     def step(self, times1: Sequence[float], times2: Sequence[float], gt: Dict[str, Tensor]) -> Dict[str, Tensor]:
         """one gradient step on the pairs (times1[f], times2[f]); ``gt``: rgb [F,3,H,W], depth [F,1,H,W], attr [F,3+A,H,W] of
-        the frames times1 (attr: track_gs of the pair in its first three channels).  Returns device scalars (no host sync):
-        the L1 sums of the three images, the ARAP energies.  The order of the pairs inside a step does not change the result;
+        the frames times1 (attr: track_gs of the pair in its first three channels); with LossWeights.track > 0 also
+        tracks: the ``tracks.TrackTargets`` of the F pairs, in pair order (attr's first three channels are then not supervised by
+        the L1).  Returns device scalars (no host sync): the L1 sums of the three images, the ARAP energies (and the track
+        loss).  The order of the pairs inside a step does not change the result;
         sorted by times1 the Gaussian-side backward shares its projection / EWA chain between consecutive frames of one spline
         segment."""
         if len(times1) != self.F or len(times2) != self.F:
             raise ValueError(f"the step takes {self.F} frame pairs")
+        track = self.w.track > 0
+        if track:
+            tt = gt.get("tracks")
+            if not isinstance(tt, TrackTargets) or (tt.F, tt.H, tt.W) != (self.F, self.H, self.W):
+                raise ValueError(f"LossWeights.track > 0 needs gt['tracks']: the TrackTargets of the {self.F} pairs at "
+                                 f"{self.W} x {self.H}")
         ph = _Phases(self.timing)
         ph.mark("start")
         F, N, I = self.F, self.N, self.clock.interval_num
@@ -300,7 +342,7 @@ class TrainingStep:
                                           grad_sink=sink)
         ph.mark("render_forward")
         dssim = self.w.dssim > 0
-        if self.fused_l1 and not dssim and L.get_option("bwd_quarters"):
+        if self.fused_l1 and not dssim and not track and L.get_option("bwd_quarters"):
             # the L1 terms' gradient images are never materialised: the tile kernel derives them from the forward's output row and
             # the ground-truth frames where it hoists the image gradient (splat_alpha_blending_backward_batch_sets_l1)
             fsums = torch.empty(F, self.fb.T, 3, dtype=torch.float32, device=self.dev)      # per tile: every entry is written
@@ -309,10 +351,17 @@ class TrainingStep:
             torch.autograd.backward(list(out[:3]), self.fb.l1_placeholders([3, 1, self.C - 4]))
             sums = fsums.sum((0, 1))
         else:
-            sums = torch.zeros(4 if dssim else 3, dtype=torch.float32, device=self.dev)
+            sums = torch.zeros(5 if track else (4 if dssim else 3), dtype=torch.float32, device=self.dev)
             g_rgb = (self._rgb_loss_grad(out[0], gt["rgb"], sums) if dssim else self._l1(out[0], gt["rgb"], self.w.rgb, sums[0:1]))
-            grads = [g_rgb, self._l1(out[1], gt["depth"], self.w.depth, sums[1:2]),
-                     self._l1(out[2], gt["attr"], self.w.attr, sums[2:3])]
+            if track:
+                # the track channels: the 2-D track loss alone; the attribute channels: their L1
+                g_attr = torch.empty(F, self.C - 4, self.H, self.W, dtype=torch.float32, device=self.dev)
+                wts = _upload(frame_weights(times1, times2, self.clock.num_frames), self.dev)
+                self._track_loss_grad(out[2][:, :3], gt["tracks"], wts, g_attr[:, :3], sums[4:5])
+                self._attr_l1(out[2], gt["attr"], g_attr, sums[2:3])
+            else:
+                g_attr = self._l1(out[2], gt["attr"], self.w.attr, sums[2:3])
+            grads = [g_rgb, self._l1(out[1], gt["depth"], self.w.depth, sums[1:2]), g_attr]
             ph.mark("loss")
             torch.autograd.backward(list(out[:3]), grads)
         # ---- both position gradients of every pair (ARAP on ids1 and ids2, track_gs on ids2) reach the spline segments
@@ -353,6 +402,10 @@ class TrainingStep:
                      "l1_attr": sums[2] / (F * (self.C - 4) * hw), "arap": arap.mean()}
         if dssim:
             self.last["ssim_rgb"] = sums[3] / (F * 3 * hw)
+        if track:
+            A = self.C - 7
+            self.last["l1_attr"] = sums[2] / (F * A * hw) if A > 0 else sums[2]      # A = 0: no attribute term (0)
+            self.last["track"] = sums[4]
         if self.timing:
             self._marks = ph
         return self.last
@@ -430,7 +483,10 @@ class TrainingStep:
         rgb = l["l1_rgb"]
         if "ssim_rgb" in l:
             rgb = (1.0 - self.w.dssim) * rgb + self.w.dssim * (1.0 - l["ssim_rgb"])
-        return float(self.w.rgb * rgb + self.w.depth * l["l1_depth"] + self.w.attr * l["l1_attr"] + self.w.arap * l["arap"])
+        tot = self.w.rgb * rgb + self.w.depth * l["l1_depth"] + self.w.attr * l["l1_attr"] + self.w.arap * l["arap"]
+        if "track" in l:
+            tot = tot + self.w.track * l["track"]
+        return float(tot)
 
     # ------------------------------------------------------------------ structure
     def _gather(self):
