@@ -60,7 +60,6 @@ int splat_fill_f32(float *dst, size_t n, float value, splat_stream_t stream);
 /* Process-wide options, set THROUGH THE ABI (the library reads no environment variable).  Keys (default):
      "bwd_quarters"   (1)  backward tile kernels walk one survivor list per 4x4 quarter when the forward's cull words are given;
                            0: the block-level matrix-core kernels everywhere (what a caller without cull words gets)
-     "bwd_kernel_dpp" (0)  1: the DPP-reduction pair kernel instead of the matrix-core kernels (A/B measurements)
      "sets_std"       (1)  the three-set backward's float4 record stores + the forward's packed records for the renderer's own
                            plan (rgb 0-2 | depth 3 | 19 attributes 4-22); 0: the generic slot -> channel routing for every plan
      "bin_slot_keys"  (0)  1: pair-slot sort keys + owner array also where the packed (id, k) keys fit (tests: small sizes)

@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# SPLAT_LIB_PATH: alternative build of the same ABI (kernel tuning A/B runs); default = in-tree library
+# SPLAT_LIB_PATH: another build of the same ABI to load instead; default = in-tree library
 LIB_PATH = os.environ.get("SPLAT_LIB_PATH") or os.path.join(_HERE, "libsplat_hip.so")
 _lib: Optional[ctypes.CDLL] = None
 
@@ -59,11 +59,6 @@ SYMBOLS = [
     "splat_ssim_scratch_bytes", "splat_ssim_forward", "splat_ssim_backward", "splat_dssim_l1_loss_grad",
     "splat_track_loss_scratch_bytes", "splat_track_loss_grad",
 ]
-
-# environment switches of earlier rounds, applied ONCE at load THROUGH the ABI (splat_set_option): the library itself reads no
-# environment variable.  {variable: (option key, value that turns the non-default on, option value)}
-_ENV_OPTIONS = {"SPLAT_BWD_QUARTERS": ("bwd_quarters", "0", 0), "SPLAT_BWD_KERNEL": ("bwd_kernel_dpp", "dpp", 1),
-                "SPLAT_SETS_STD": ("sets_std", "0", 0), "SPLAT_BIN_SLOT_KEYS": ("bin_slot_keys", "1", 1)}
 
 
 class SplatError(RuntimeError):
@@ -121,9 +116,6 @@ def lib() -> ctypes.CDLL:
         if L.splat_abi_version() != ABI_VERSION:
             raise SplatError("libsplat_hip.so ABI version mismatch; rebuild it")
         _lib = L
-        for var, (key, on, value) in _ENV_OPTIONS.items():
-            if os.environ.get(var) == on:
-                check(L.splat_set_option(key.encode(), ctypes.c_int(value)))
     return _lib
 
 
@@ -176,8 +168,8 @@ def build_id() -> str:
 
 
 def set_option(key: str, value: int) -> None:
-    """process-wide option of the library (include/splat_hip.h: splat_set_option): "bwd_quarters", "bwd_kernel_dpp", "sets_std",
-    "bin_slot_keys", "deterministic"; read at launch time"""
+    """process-wide option of the library (include/splat_hip.h: splat_set_option): "bwd_quarters", "sets_std", "bin_slot_keys",
+    "deterministic"; read at launch time"""
     check(lib().splat_set_option(key.encode(), ctypes.c_int(int(value))))
 
 

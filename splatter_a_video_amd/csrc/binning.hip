@@ -25,22 +25,12 @@
 
 #define BIN_BLOCK 256
 #define BIN_MAX_NB 512          // rows of the count matrix (= workgroups of K1/K3)
-#ifndef BIN_CHUNK
 #define BIN_CHUNK 512           // Gaussians per row (chunk) before BIN_MAX_NB caps the row count
-#endif
-#ifndef BIN_CHUNK_BATCH
 #define BIN_CHUNK_BATCH 2048    // ... in a frame batch of at least BIN_BATCH_FRAMES frames (see make_plan)
-#endif
 #define BIN_BATCH_FRAMES 4
 #define BIN_LDS_TILES 12288     // <= 48 KB of LDS counters; larger tile grids use global atomics
 #define BIN_GLOBAL_BLOCKS 2048   // grid of K1/K3 on the global-atomic path
 #define SORT_BLOCK 256
-#ifndef SORT_SWIZZLE_ALL
-#define SORT_SWIZZLE_ALL 0
-#endif
-#ifndef SORT_SWIZZLE4
-#define SORT_SWIZZLE4 1         // thread distance 4: ds_swizzle (one LDS-crossbar instruction per word) instead of two DPP moves + a select
-#endif
 #define SORT_LDS_KEYS 2048      // 16 KB of LDS per sort workgroup: the exchange buffer of the two widest strides of a 2048-key block
 
 struct BinPlan {
@@ -68,16 +58,12 @@ static int bits_for(long long n) {  // bits that hold 0 .. n - 1
 }
 
 // Pair-map keys.  The low key word has to order a tile's equal depths by ascending Gaussian id and to lead the sort to both
-// the Gaussian and its pair slot.  BIN_PACKED_KEYS: the word is (id << kbits) | k, k = index of the tile inside the splat's
+// the Gaussian and its pair slot.  Packed keys: the word is (id << kbits) | k, k = index of the tile inside the splat's
 // rectangle (k < T): the sort reads the slot as goff_excl[id] + k from the per-Gaussian prefix the scatter writes anyway
 // (4 P bytes per frame, L2-resident) -- no `owner` array written per pair by the scatter and gathered per pair, at sector
 // granularity, by the sort.  When id and k do not fit 32 bits (1M Gaussians on more than 4096 tiles) the word is the pair
 // slot and `owner` resolves the id as before.  Both forms sort identically (slots grow with (id, k)).
-#ifndef BIN_PACKED_KEYS
-#define BIN_PACKED_KEYS 1
-#endif
 static int pair_key_kbits(int P, int T) {
-    if (!BIN_PACKED_KEYS) return 0;
     const bool slot_keys = splat_option(SPLAT_OPT_BIN_SLOT_KEYS) != 0;   // the slot form everywhere -- how the tests reach it at small sizes
     if (slot_keys) return 0;
     const int kb = bits_for(T), ib = bits_for(P);
@@ -269,9 +255,7 @@ __device__ __forceinline__ int wave_incl_scan_i(int v, int lane) {
 // 32 tile columns x 32 row groups per workgroup: every thread loads its (at most 16) rows of one column in one
 // batch -- a wave reads two 128-byte row segments per instruction --, scans them in registers, and the group totals
 // are exchanged through LDS.  The matrix is read once and written once.
-#ifndef COLSCAN_COLS
 #define COLSCAN_COLS 32
-#endif
 #define COLSCAN_GROUPS (1024 / COLSCAN_COLS)
 #define COLSCAN_ROWS (BIN_MAX_NB / COLSCAN_GROUPS)
 __global__ void __launch_bounds__(COLSCAN_COLS * COLSCAN_GROUPS)
@@ -483,19 +467,10 @@ __device__ __forceinline__ unsigned dpp_u(unsigned v) {
 
 template <int D>
 __device__ __forceinline__ unsigned lane_xor_u(unsigned v, int lane) {
-#if SORT_SWIZZLE_ALL
-    if (D <= 16) return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, 0x001F | (D << 10));   // bit mode: xor D inside 32 lanes
-#endif
     if (D == 1) return dpp_u<0xB1>(v);   // quad_perm:[1,0,3,2]
     if (D == 2) return dpp_u<0x4E>(v);   // quad_perm:[2,3,0,1]
-    if (D == 4) {                        // inside a row of 16: lanes with bit 2 clear read lane+4, the others lane-4
-#if SORT_SWIZZLE4
-        return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, 0x101F);   // bit mode: and 0x1f, or 0, xor 4 -- the LDS crossbar, no VALU
-#else
-        const unsigned up = dpp_u<0x104>(v), dn = dpp_u<0x114>(v);  // row_shl:4 / row_shr:4
-        return (lane & 4) ? dn : up;
-#endif
-    }
+    // inside a row of 16: ds_swizzle (one LDS-crossbar instruction per word) instead of two DPP moves + a select
+    if (D == 4) return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, 0x101F);   // bit mode: and 0x1f, or 0, xor 4 -- no VALU
     if (D == 8) return dpp_u<0x128>(v);  // row_ror:8
     if (D == 16) {
         const u32x2_t r = __builtin_amdgcn_permlane16_swap(v, v, false, false);  // r[0] rows: x0 x0 x2 x2, r[1]: x1 x1 x3 x3
@@ -515,7 +490,7 @@ __device__ __forceinline__ u64 lane_xor_key(u64 k, int lane) {
 template <int R, int D>
 __device__ __forceinline__ void xthread_stage(u64 (&k)[R], int t, bool up, u64 *xbuf) {
     const bool take_min = ((t & D) == 0) == up;
-    if ((D == 16 && !SORT_SWIZZLE_ALL) || D == 32) {
+    if (D == 16 || D == 32) {
         // a swap of (k, k) leaves the pair's LOWER thread's key in the first result and the upper thread's in the second, in
         // both threads: the pair's minimum / maximum needs one compare of the two results and no partner select (the generic
         // form below selects the partner's words first: two selects and two register copies more per key)
@@ -799,10 +774,8 @@ tile_sort_kernel(int T, int *__restrict__ tile_range, long long capacity, unsign
     if (n <= 0) return;
     unsigned long long *g = keys + r0;
     // low key word: Gaussian id, or (pair-map mode) the pair slot whose owner is the Gaussian id
-#ifndef SORT_R2
-#define SORT_R2 1   // tiles of at most 512 keys: two keys per thread (45 stages, all four waves live) instead of four (55 stages, two waves live)
-#endif
-    if (SORT_R2 && n <= 2 * SORT_BLOCK) {
+    // tiles of at most 512 keys: two keys per thread (45 stages, all four waves live) instead of four (55 stages, two waves live)
+    if (n <= 2 * SORT_BLOCK) {
         tile_sort_regs<2>(g, n, r0, pk, idx_sorted, slot_sorted, sk);
     } else if (n <= 4 * SORT_BLOCK) {
         tile_sort_regs<4>(g, n, r0, pk, idx_sorted, slot_sorted, sk);

@@ -31,87 +31,6 @@
 
 #include "common.h"
 
-// tuning knobs (compile time; tools/build_variants.sh builds alternatives for A/B runs)
-#ifndef BLEND_FWD8_MINW
-#define BLEND_FWD8_MINW 4  // 5 .. 8 channels (the trainer's small plans: rgb + depth + 1 .. 4 attributes, with the K = 20 id lists): at the
-                           // narrow rows' 80 registers the enhanced instantiation spills 172 bytes per lane (128 us per frame at c2)
-#endif
-#ifndef BLEND_FWD_U
-#define BLEND_FWD_U 2      // survivors evaluated per trip in the forward (narrow channel counts).  Round 6: 4 -> 2 (the quarter lists of a
-                           // wave are padded to a multiple of U: with the denser lists of the reach masks 46.4 -> 44.9 us per frame)
-#endif
-#ifndef BLEND_FWD_QDONE
-#define BLEND_FWD_QDONE 1      // forward: a 4x4 quarter whose pixels are all saturated keeps no further entries (its block's may go on)
-#endif
-#ifndef BLEND_FWD_TRIPTEST
-#define BLEND_FWD_TRIPTEST 0   // forward: skip a trip's compositing when no lane of the wave has a splat to apply (see the kernel)
-#endif
-#ifndef BLEND_FWD_SB
-#define BLEND_FWD_SB 128   // forward super-batch (narrow channel counts): 14 KB of LDS per workgroup
-#endif
-#ifndef BLEND_FWD_MINW
-#define BLEND_FWD_MINW 6   // __launch_bounds__ min waves per SIMD for the forward: 80 VGPRs, 6 workgroups per CU (with the
-                           // frame batch's 40 500 tiles per launch; 7 -- all tiles of ONE 480p frame resident -- costs 18
-                           // spilled registers once the cull flags are written: 84 vs 77 us per frame; 5: 80 us, 4: 88 us)
-#endif
-#ifndef BLEND_BWD_U
-#define BLEND_BWD_U 2
-#endif
-#ifndef BLEND_BWD_MINW
-#define BLEND_BWD_MINW 1
-#endif
-#ifndef BLEND_MFMA_SB
-#define BLEND_MFMA_SB 128  // super-batch of the MFMA backward (narrow channel counts)
-#endif
-#ifndef BLEND_MFMA_MINW
-#define BLEND_MFMA_MINW 4  // 128 VGPRs: 4 workgroups per CU (what 40 KB of LDS allow as well)
-#endif
-#ifndef BLEND_WIDE_SB
-#define BLEND_WIDE_SB 64
-#endif
-#ifndef BLEND_WIDE_MINW
-#define BLEND_WIDE_MINW 1
-#endif
-#ifndef BLEND_CARRY
-#define BLEND_CARRY 1
-#endif
-#ifndef BLEND_WIDE_HOIST
-#define BLEND_WIDE_HOIST 1
-#endif
-#ifndef BLEND_ABL
-#define BLEND_ABL 0        // ablation of the matrix-core backward for timing experiments (1: no combine, 2: no chunks); results invalid
-#endif
-#ifndef BLEND_SETS_MINW
-#define BLEND_SETS_MINW 2  // waves per SIMD the three-set backward is compiled for (3: 168 registers = 39 scratch accesses
-                           // inside the chunk loop, 1061 instead of 615 us per frame; its LDS would allow 3)
-#endif
-#ifndef BLEND_SETS_CAP
-#define BLEND_SETS_CAP 32  // slab rows per wave of the three-set backward (list positions per round)
-#endif
-#ifndef BLEND_SETS_LE_AHEAD
-#define BLEND_SETS_LE_AHEAD 0  // three-set quarter kernel: read a step's list entry one step ahead (1) or at the top of the step (0).
-                               // Measured (round 4, c2 training frame): 438 vs 434 us per frame -- the round trip it saves is hidden
-                               // by the second wave of the SIMD, the address arithmetic it adds is not
-#endif
-#ifndef BLEND_SETS_TWO_BARRIERS
-#define BLEND_SETS_TWO_BARRIERS 1  // three-set quarter kernel: no barrier behind the combine (it reads the staged geometry in front of its barrier)
-#endif
-#ifndef BLEND_SETS_EARLY_ROWS
-#define BLEND_SETS_EARLY_ROWS 1  // three-set quarter kernel: request the survivor's slab row at the top of the step (13 registers
-                                 // across the step) instead of in front of the epilogue's adds
-#endif
-#ifndef BLEND_LATE_STAGE
-#define BLEND_LATE_STAGE 1 // matrix-core backward: gather the next super-batch's records behind the chunk loop (1) or in front of it (0)
-#endif
-#ifndef BLEND_SLOT_EARLY
-#define BLEND_SLOT_EARLY 0 // matrix-core backward: load the combine's pair slots at the top of the super-batch (1) or behind the chunks (0)
-#endif
-#ifndef BLEND_REC_SWZ
-#define BLEND_REC_SWZ 1    // strip-walk backward kernels: XOR swizzle of the staged records' 16-byte parts (bank conflicts)
-#endif
-#ifndef BLEND_STATE_SKEW
-#define BLEND_STATE_SKEW 1 // strip-walk backward kernels: per-pixel replay state rows skewed by lane group (bank conflicts)
-#endif
 // The reference skips a splat when power > 0 (src/alpha_blending.cu:93).  power is a negative-semidefinite form -- EWA only
 // emits positive-definite conics (cov2d + 0.3 I) -- so it exceeds 0 by rounding only (the expanded polynomial carries ~1e-5 of
 // absolute noise in log2 units; at a splat's centre the reference evaluates exp(0) = 1).  No compare per (pixel, splat) is spent
@@ -462,24 +381,14 @@ struct Stager {
 // SUB: the flag byte of a kept block carries one bit per 4x4 quarter (bit sx + 2 sy) from a bounding-box test of the
 // quarter's pixel centres, for kernels that keep a survivor list per quarter; otherwise the byte is 0 / 1.
 // gflags: optional global copy of the staged entries' keep words (BlendArgs::cull_flags + the super-batch's first position).
-// Quarter bits of a kept block: bounding-box test of the quarter's pixel centres, and -- rows of 16 channels and more
-// (BLEND_EXACTQ 1) -- the exact ellipse test of cull_test on the quarter's rectangle for the quarters the box lets through:
-// 12 % fewer list entries and 7 % fewer steps in the three-set backward (391 -> 364 us per frame at c2) for + 10 us in the
-// 24-channel forward, whose cull threads own two blocks each.  Narrow rows (BLEND_EXACTQ 2) lose: the forward's cull is a
-// quarter of the little it does per super-batch (+ 17 us against - 6.5 us in the backward).
-#ifndef BLEND_EXACTQ
-#define BLEND_EXACTQ 1
-#endif
-#ifndef BLEND_TANQ
-#define BLEND_TANQ 1     // rows below 16 channels: tangent-plane test of the quarters the bounding box lets through (see tile_cull)
-#endif
-#ifndef BLEND_TANQ_NOBOX
-#define BLEND_TANQ_NOBOX 0
-#endif
-#ifndef BLEND_TANQ_GATE
-#define BLEND_TANQ_GATE 0   // ... behind the exact test of the 8x8 block (1) or on their own (0: narrow forward 60.2 -> 54.9 us per frame,
-                            // backward 130.7 -> 132.8 at c2: the block test cost the cull threads more than the 1.7 % of entries it removed)
-#endif
+// Quarter bits of a kept block: bounding-box test of the quarter's pixel centres, then
+//   * rows below 16 channels: the tangent-plane test of the quarters the box lets through, on its own rather than behind the
+//     exact test of the 8x8 block (narrow forward 60.2 -> 54.9 us per frame, backward 130.7 -> 132.8 at c2: the block test cost
+//     the cull threads more than the 1.7 % of entries it removed);
+//   * rows of 16 channels and more: the exact ellipse test of cull_test on the quarter's rectangle: 12 % fewer list entries and
+//     7 % fewer steps in the three-set backward (391 -> 364 us per frame at c2) for + 10 us in the 24-channel forward, whose cull
+//     threads own two blocks each.  Narrow rows lose with it: the forward's cull is a quarter of the little it does per
+//     super-batch (+ 17 us against - 6.5 us in the backward).
 __device__ __forceinline__ unsigned live_quarters(bool b) { return b ? 15u : 0u; }
 __device__ __forceinline__ unsigned live_quarters(unsigned m) { return m; }
 
@@ -519,14 +428,12 @@ __device__ __forceinline__ void tile_cull(TileLDS<CH, SB, COEF, XR, SWZ, RQL, CS
                 const float x0 = tx0 + (float)(8 * (ww & 1)), y0 = ty0 + (float)(8 * (ww >> 1));
                 // quarter bits from per-quarter tests that are exact on their own (rows of 16 channels and more) subsume the block's
                 // exact test -- the quarters' rectangles of pixel centres tile the block's -- so the block is not tested there
-                // (70 VALU per thread and super-batch less in the wide forward's cull); BLEND_TANQ_GATE 0: the same for the
-                // tangent-plane quarters of the narrow rows (3.00 instead of 2.95 quarters per pair, tools/cull_model.py)
-                constexpr bool QEX = BLEND_EXACTQ == 2 || (BLEND_EXACTQ == 1 && CH >= 16);
-                constexpr bool GATE = !(SUB && (QEX || (BLEND_TANQ && CH < 16 && !BLEND_TANQ_GATE)));
+                // (70 VALU per thread and super-batch less in the wide forward's cull); the same for the tangent-plane quarters
+                // of the narrow rows (3.00 instead of 2.95 quarters per pair, tools/cull_model.py)
                 // pred: does block ww still need entry e?  bool, or (forward) the mask of its 4x4 quarters that do -- a quarter whose 16
                 // pixels are all saturated keeps nothing while the block's other quarters go on
                 const unsigned live = live_quarters(pred(e, ww));
-                const bool kb = live != 0u && (!GATE || cull_test(a0.x, a0.y, a0.z, a0.w, a1.x, cp, x0, x0 + 7.f, y0, y0 + 7.f));
+                const bool kb = live != 0u && (SUB || cull_test(a0.x, a0.y, a0.z, a0.w, a1.x, cp, x0, x0 + 7.f, y0, y0 + 7.f));
                 if (SUB) {
                     unsigned m = 0u;
                     if (kb) {
@@ -535,10 +442,7 @@ __device__ __forceinline__ void tile_cull(TileLDS<CH, SB, COEF, XR, SWZ, RQL, CS
                         const float ay0 = fmaxf(fmaxf(y0 - a0.y, a0.y - (y0 + 3.f)), 0.f), ay1 = fmaxf(fmaxf(y0 + 4.f - a0.y, a0.y - (y0 + 7.f)), 0.f);
                         const bool bx0_ = ax0 <= cp.hx, bx1_ = ax1 <= cp.hx, by0_ = ay0 <= cp.hy, by1_ = ay1 <= cp.hy;
                         m = (bx0_ && by0_ ? 1u : 0u) | (bx1_ && by0_ ? 2u : 0u) | (bx0_ && by1_ ? 4u : 0u) | (bx1_ && by1_ ? 8u : 0u);
-#if BLEND_TANQ_NOBOX
-                        if (BLEND_TANQ && CH < 16) m = cp.hx < 0.f ? 0u : 15u;   // experiment: the tangent test alone
-#endif
-                        if (BLEND_TANQ && CH < 16) {
+                        if (CH < 16) {
                             // TANGENT-PLANE test of the four quarters, branch-free: q(d) = d^T Q d is convex, so over the quarter's
                             // rectangle of pixel centres (half extents 1.5 around its centre c) q >= q(c) - 3 (|Qc|_x + |Qc|_y); a
                             // quarter whose bound exceeds tau holds no pixel with alpha >= 1/255.  Keeps 2.95 quarters per (tile,
@@ -557,7 +461,7 @@ __device__ __forceinline__ void tile_cull(TileLDS<CH, SB, COEF, XR, SWZ, RQL, CS
                                 if (qc - 3.f * (fabsf(tx) + fabsf(ty)) > thr) m &= ~(1u << q);   // (NaN / inf threshold: kept)
                             }
                         }
-                        if (BLEND_EXACTQ == 2 || (BLEND_EXACTQ == 1 && CH >= 16)) {
+                        if (CH >= 16) {
 #pragma unroll
                             for (int q = 0; q < 4; ++q) {
                                 const float qx0 = x0 + (float)(4 * (q & 1)), qy0 = y0 + (float)(4 * (q >> 1));
@@ -684,10 +588,20 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <int CH>
 struct FwdCfg {
-    static constexpr int SB = CH <= 8 ? BLEND_FWD_SB : 128;
+    static constexpr int SB = 128;   // super-batch: 14 KB of LDS per workgroup at narrow channel counts
+    // survivors evaluated per trip by the lane = pixel loop.  Round 6: 4 -> 2 (the quarter lists of a wave are padded to a
+    // multiple of U: with the denser lists of the reach masks 46.4 -> 44.9 us per frame)
+    static constexpr int U = 2;
+    // __launch_bounds__ min waves per SIMD
+    //   * up to 4 channels: 80 VGPRs, 6 workgroups per CU (with the frame batch's 40 500 tiles per launch; 7 -- all tiles of ONE
+    //     480p frame resident -- costs 18 spilled registers once the cull flags are written: 84 vs 77 us per frame; 5: 80 us,
+    //     4: 88 us)
+    //   * 5 .. 8 channels (the trainer's small plans: rgb + depth + 1 .. 4 attributes, with the K = 20 id lists): 4.  At the
+    //     narrow rows' 80 registers the enhanced instantiation spills 172 bytes per lane (128 us per frame at c2)
+    static constexpr int MINW = CH <= 4 ? 6 : CH <= 16 ? 4 : 3;
 };
 
-// Wide rows (16 .. 32 channels), BLEND_FWD_MFMA: the channel sums F[p, c] += w[p, s] f[s, c] are a product over (pixels x
+// Wide rows (16 .. 32 channels) without a bias: the channel sums F[p, c] += w[p, s] f[s, c] are a product over (pixels x
 // splats x channels) and run on the matrix pipe.  Lane = pixel as before for the alpha / transmittance chain, but the 16 lanes of
 // a DPP row ARE one 4x4 quarter (lane -> pixel map below), a trip evaluates four survivors of the quarter's list, and a 4x4
 // transpose of the four weight registers across the rows (two v_permlane32_swap + two v_permlane16_swap) yields the A operand
@@ -696,20 +610,13 @@ struct FwdCfg {
 // An f32 MFMA is the ascending fma chain over k starting from C (profiles/r02_mfma_fma_chain_probe.json), i.e. bit for bit the
 // F += f * w chain of the lane = pixel loop in the same splat order.  Per four survivors: 8 MFMAs (256 FP32-pipe cycles; 4 with
 // 16 channels) + 4 swaps instead of 4 x CH FMAs (384 cycles at 24 channels, 512 at 32) and CH / 4 broadcast ds_read_b128 each.
-#ifndef BLEND_FWD_MFMA
-#define BLEND_FWD_MFMA 1
-#endif
-
-#ifndef BLEND_FWD_MF_MINW
-#define BLEND_FWD_MF_MINW 3
-#endif
 template <int CH, bool ENH, bool BIAS, bool EXACT>
-__global__ void __launch_bounds__(256, (CH <= 4 ? BLEND_FWD_MINW : CH <= 8 ? BLEND_FWD8_MINW : CH <= 16 ? 4 : (BLEND_FWD_MFMA && !BIAS) ? BLEND_FWD_MF_MINW : 3))
+__global__ void __launch_bounds__(256, FwdCfg<CH>::MINW)
 blend_fwd_kernel(const BlendArgs B) {
     constexpr int SB = FwdCfg<CH>::SB;
-    constexpr bool MF = BLEND_FWD_MFMA && CH >= 16 && !BIAS;
+    constexpr bool MF = CH >= 16 && !BIAS;
     constexpr int NCB = (CH + 15) / 16;           // MF: 16-channel blocks of the product
-    constexpr int U = MF ? 4 : CH <= 8 ? BLEND_FWD_U : 2;  // survivors evaluated per trip
+    constexpr int U = MF ? 4 : FwdCfg<CH>::U;     // survivors evaluated per trip
     constexpr int RB = Rec<CH>::RS * 4;           // bytes per record
     constexpr int RM = RB / 32;                   // record offset = RM * coefficient-block offset
     // rows of at most four channels carry them in the coefficient block (48 bytes): the survivor's block offset is the only
@@ -786,7 +693,7 @@ blend_fwd_kernel(const BlendArgs B) {
         __syncthreads();
         if ((s_done[0] & s_done[1] & s_done[2] & s_done[3]) == 15) break;  // every pixel of the tile is saturated
         // (the keep words also go to A.cull_flags: what the backward needs of this cull -- a saturated block keeps nothing)
-        tile_cull<CH, SB, BIAS, true, !BIAS>(L, tid, nb, (float)(tx * TILE), (float)(ty * TILE), [&](int, int ww) -> unsigned { return BLEND_FWD_QDONE ? 15u & ~(unsigned)s_done[ww] : (s_done[ww] != 15 ? 15u : 0u); },
+        tile_cull<CH, SB, BIAS, true, !BIAS>(L, tid, nb, (float)(tx * TILE), (float)(ty * TILE), [&](int, int ww) -> unsigned { return 15u & ~(unsigned)s_done[ww]; },
                                              A.cull_flags ? A.cull_flags + range.x + base : nullptr);
         __syncthreads();
         if (!alld) {
@@ -852,7 +759,6 @@ blend_fwd_kernel(const BlendArgs B) {
                     g0[u] = *reinterpret_cast<const float4 *>(src);
                     g1[u] = *reinterpret_cast<const float4 *>(src + 16);
                 }
-                bool any = false;
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     if (BIAS) {
@@ -867,9 +773,7 @@ blend_fwd_kernel(const BlendArgs B) {
                         aok[u] = pw_ok && !(a < (1.0f / 255.0f));
                         alpha[u] = aok[u] ? a : 0.f;
                     }
-                    if (BLEND_FWD_TRIPTEST) any = any || (alpha[u] > 0.f);
                 }
-                if (BLEND_FWD_TRIPTEST && __builtin_amdgcn_ballot_w64(any && T > 0.f) == 0ull) continue;
                 // Branch-free compositing.  A finished pixel carries its final T NEGATED: T (1 - alpha) < 0.0001 holds for it
                 // again ("saturated"), so nothing applies and no `done` predicate is kept; alpha = 0 (splat skipped on this
                 // pixel) multiplies T by 1 and adds f * 0: the pixel's values do not change by a bit.
@@ -1070,14 +974,14 @@ struct PairCfg {
     static constexpr int NC = NG + CH;       // used floats per pair record
     static constexpr int NCP = PAIR_STRIDE(NC);  // record stride in pair_buf
     static constexpr int SB = 64;
+    static constexpr int U = CH <= 8 ? 2 : 1;    // survivors evaluated per trip
 };
 
 template <int CH, bool ABS, bool BIAS, bool EXACT>
-__global__ void __launch_bounds__(256, (CH <= 8 ? BLEND_BWD_MINW : 1))
+__global__ void __launch_bounds__(256, 1)
 blend_bwd_pair_kernel(const BlendArgs B) {
     using Cfg = PairCfg<CH, ABS, BIAS>;
-    constexpr int SB = Cfg::SB, NC = Cfg::NC, NCP = Cfg::NCP;
-    constexpr int U = CH <= 8 ? BLEND_BWD_U : 1;
+    constexpr int SB = Cfg::SB, NC = Cfg::NC, NCP = Cfg::NCP, U = Cfg::U;
     __shared__ TileLDS<CH, SB, !BIAS> L;
     __shared__ float s_acc[4][SB * NC];          // private slab per wave: plain stores, no atomics
     __shared__ unsigned long long s_mask[4];     // which entries of the super-batch the wave wrote
@@ -1327,7 +1231,10 @@ struct MfmaCfg {
     static constexpr int NG = GradLayout<ABS, false>::NG;
     static constexpr int NC = NG + CH;
     static constexpr int NCP = PAIR_STRIDE(NC);
-    static constexpr int SB = CH <= 8 ? BLEND_MFMA_SB : (CH <= 20 ? BLEND_WIDE_SB : 64);
+    static constexpr int SB = CH <= 8 ? 128 : 64;
+    // __launch_bounds__ min waves per SIMD: up to 3 channels 128 VGPRs, 4 workgroups per CU (what 40 KB of LDS allow as well);
+    // 8 channels: the registers of two waves per SIMD
+    static constexpr int MINW = CH <= 3 ? 4 : CH <= 8 ? 2 : 1;
     static constexpr int PZ = CH;                 // a zero slot (lanes without a channel feed it to the MFMAs)
     static constexpr int PS = (CH + 1 + 3) & ~3;  // state block [T_final*bg.g, ncontrib, T_state, R_state] (16-B aligned)
     static constexpr int PW = PS + 4;             // floats per pixel record: g[CH], 0.., state block
@@ -1424,7 +1331,7 @@ __device__ __forceinline__ void row_shr1_add4(float (&R)[4], const float (&rs)[4
 }
 
 template <int CH, bool ABS, bool EXACT>
-__global__ void __launch_bounds__(256, (CH <= 3 ? BLEND_MFMA_MINW : CH <= 8 ? 2 : (CH <= 20 ? BLEND_WIDE_MINW : 1)))   // (8 channels: the registers of two waves per SIMD)
+__global__ void __launch_bounds__(256, (MfmaCfg<CH, ABS>::MINW))
 blend_bwd_mfma_kernel(const BlendArgs B) {
     using Cfg = MfmaCfg<CH, ABS>;
     constexpr int SB = Cfg::SB, NG = Cfg::NG, NC = Cfg::NC, NCP = Cfg::NCP, PW = Cfg::PW, NA = Cfg::NA, NK = Cfg::NK;
@@ -1432,7 +1339,7 @@ blend_bwd_mfma_kernel(const BlendArgs B) {
     constexpr int I_ABS = GradLayout<ABS, false>::I_ABS;
     constexpr bool SHARED = Cfg::SHARED;
     // survivors that do not fill a chunk are carried into the next super-batch (CarryLDS)
-    constexpr bool CARRY = BLEND_CARRY && CH <= 20;
+    constexpr bool CARRY = CH <= 20;
     constexpr int CQ = CarryLDS<SB>::CQ, XR = CARRY ? 4 * CQ : 0;
     // private slabs (16 / 20 channels): rows by list position, CAP per wave (whole chunks; a longer list takes another round);
     // shared slab: one row per staged entry + one per carry row, no limit
@@ -1440,7 +1347,7 @@ blend_bwd_mfma_kernel(const BlendArgs B) {
     // the combine gives TPR threads to a record, three floats each (one 12-byte store per thread); shared slab: rows of NCS floats
     constexpr int TPR = (NC + 2) / 3, NCS = SHARED ? 3 * TPR : NC;
     constexpr int SROWS = SHARED ? SB + XR : CAP + (CARRY ? 1 : 0);
-    __shared__ TileLDS<CH, SB, false, XR, BLEND_REC_SWZ != 0> L;
+    __shared__ TileLDS<CH, SB, false, XR, true> L;
     __shared__ CarryLDS<SB, !SHARED> CL;
     // narrow feature rows: dL_dfeature = sum_p g[p,c] w[p,n] as per-lane FMAs over the lane's own pixels + one cross-row sum
     // per chunk, instead of four MFMAs per strip whose A operand would use 3 of its 16 rows (the matrix pipe's time is on
@@ -1453,7 +1360,7 @@ blend_bwd_mfma_kernel(const BlendArgs B) {
     // float G * GS + kk * KS + i * PW.  The four lane groups kk of a wave read / write the rows of their own pixels in one
     // instruction; with dense rows (KS = 4 PW, a multiple of 32 dwords) all four hit the same banks (ds_write2_b32 from
     // lanes 15 / 31 / 47 / 63: 4-way) -- 8 floats of skew per group spread them
-    constexpr int KS = 4 * PW + (BLEND_STATE_SKEW ? 8 : 0), GS = 4 * KS;
+    constexpr int KS = 4 * PW + 8, GS = 4 * KS;
     __shared__ __attribute__((aligned(16))) float s_pix[4][4 * GS];
     auto pixoff = [](int q) { return (q >> 4) * GS + ((q >> 2) & 3) * KS + (q & 3) * PW; };
     __shared__ float s_mom[16 * 64];         // A operand of the moment product: [step 4 G + i][lane]
@@ -1570,7 +1477,7 @@ blend_bwd_mfma_kernel(const BlendArgs B) {
 
     // wide rows: the A operands of the colour and feature-gradient products are the same in every chunk (dL_dout of the
     // wave's pixels) -- held in registers instead of re-read from LDS per chunk
-    constexpr bool HOIST = BLEND_WIDE_HOIST && CH > 8;
+    constexpr bool HOIST = CH > 8;
     float hcg[HOIST ? 4 : 1][HOIST ? NK : 1], hft[HOIST ? 16 : 1][HOIST ? NA : 1], hmom[HOIST ? 16 : 1];
     if (HOIST) {
 #pragma unroll
@@ -1603,10 +1510,6 @@ blend_bwd_mfma_kernel(const BlendArgs B) {
     for (int top = n - 1; top >= 0; top -= SB, ++batch) {
         const int nb = imin_(SB, top + 1);
         st.park(L, tid);
-        if (!BLEND_LATE_STAGE) {
-            st.load_payload(A, tid);                       // payload of the next super-batch
-            st.load_ids(A, tid, range.x, pos, batch + 2);  // ids two ahead
-        }
         const unsigned fl = fl_next;
         fl_next = load_flags(top - SB);
         // pair slots of the entries this thread writes in the combine: loaded ahead of the barrier in front of it (the
@@ -1621,7 +1524,6 @@ blend_bwd_mfma_kernel(const BlendArgs B) {
                 }
             }
         };
-        if (BLEND_SLOT_EARLY) load_slots();
         if (A.cull_flags) {
             // (the forward's keep words need nothing of the staged records: one barrier serves the park and the keep words)
             keep_from_flags(L, tid, nb, fl, [&](int e, int ww) { return top - e < s_wmax[ww]; });
@@ -1637,7 +1539,7 @@ blend_bwd_mfma_kernel(const BlendArgs B) {
         const int nproc = (!CARRY || top - SB < 0) ? total : (total & ~15);  // whole chunks; the tile's last batch pads
         float *slab = s_acc[SHARED ? 0 : w];
         for (int p0 = 0;; p0 += CAP) {  // rounds of at most CAP list positions (one, unless more than CAP survive)
-        const int p1 = (BLEND_ABL & 2) ? p0 : CARRY ? imin_(nproc, p0 + CAP) : nproc;
+        const int p1 = CARRY ? imin_(nproc, p0 + CAP) : nproc;
         for (int j0 = p0; j0 < p1; j0 += 16) {
             const int e = L.list[w][j0 + nl];  // ascending e = back to front; slot SB (inert) past the end
             const float4 g0 = L.g0(e), g1 = L.g1(e);
@@ -1809,8 +1711,8 @@ blend_bwd_mfma_kernel(const BlendArgs B) {
             ncarry = left;
         }
         if (CARRY && !SHARED && lane == 0) CL.more[w] = nproc > p0 + CAP;
-        if (!BLEND_SLOT_EARLY && p0 == 0) load_slots();
-        if (BLEND_LATE_STAGE && p0 == 0) {
+        if (p0 == 0) {
+            load_slots();
             // the next super-batch's payload (8 registers) is requested behind the chunks, not across them: its latency
             // hides under the barrier, the combine and the other workgroups of the CU
             st.load_payload(A, tid);
@@ -1819,7 +1721,7 @@ blend_bwd_mfma_kernel(const BlendArgs B) {
         __syncthreads();
         // ---- combine the four slabs: thread (ce, cc) sums component cc of every EPI-th entry and stores it at the
         //      entry's pair slot (the NCP - NC pad floats of a record are never written; pair_reduce ignores them)
-        if (ce < EPI && !(BLEND_ABL & 1)) {
+        if (ce < EPI) {
             const int lo = top - nb + 1;
             if (SHARED) {
                 // one row per entry: read it out, clear it for the next super-batch, store it at the entry's pair slot
@@ -1895,27 +1797,15 @@ blend_bwd_mfma_kernel(const BlendArgs B) {
 // everywhere at 64 rows, 138 -> 166 us per frame; 128 rows do not fit four workgroups per CU.)
 // Same arithmetic as blend_bwd_mfma_kernel per (pixel, splat): exponent chain, guards, scans.  Narrow rows; ABS: with the |d uv|
 // sums of the abs taps (two more products per step for conic (centre - pixel), as in blend_bwd_sets_quarter_kernel).
-#ifndef BLEND_Q_SB
-#define BLEND_Q_SB 128
-#endif
-#ifndef BLEND_Q_CAP
-#define BLEND_Q_CAP 80   // slab rows per wave and round (a second round costs a list rebuild, two barriers and a combine).  Round 6: with
-                         // reach masks a super-batch of 128 entries keeps 59 rows per wave on average (39 before): 64 rows -> 80 (137 -> 132 us per
-                         // frame; 45 KB of LDS = three workgroups per CU, which the compiler answers with 155 registers; 112 rows = two: 167 us)
-#endif
-#ifndef BLEND_Q_SWZ
-#define BLEND_Q_SWZ 1   // part p of entry e at 4 e + (p ^ ((e >> 2) & 3)): 16 survivors' reads of one part spread over the banks
-#endif
-#ifndef BLEND_Q_MINW
-#define BLEND_Q_MINW 4
-#endif
-#ifndef BLEND_QABL
-#define BLEND_QABL 0    // timing ablation of the quarter-list backward (1: no steps, 2: no combine); results invalid
-#endif
 template <int CH, bool ABS = false>
 struct QuarterCfg {
     static_assert(CH <= 3 && Rec<CH>::RQ == 4 && Rec<CH>::CULL >= 11, "floats 11-15 of the record (cull parameters) are free for the coefficients");
-    static constexpr int SB = BLEND_Q_SB, CAP = BLEND_Q_CAP;
+    static constexpr int SB = 128;
+    // slab rows per wave and round (a second round costs a list rebuild, two barriers and a combine).  Round 6: with reach masks a
+    // super-batch of 128 entries keeps 59 rows per wave on average (39 before): 64 rows -> 80 (137 -> 132 us per frame; 45 KB of
+    // LDS = three workgroups per CU, which the compiler answers with 155 registers; 112 rows = two: 167 us)
+    static constexpr int CAP = 80;
+    static constexpr int MINW = 4;  // __launch_bounds__ min waves per SIMD
     static constexpr int NG = GradLayout<ABS, false>::NG, NC = NG + CH, NCP = PAIR_STRIDE(NC);
     // slab row.  ABS: [M0 Mx My Mxx | Mxy Myy ax ay | f0 f1 f2 . of lane groups 0 + 2 | of lane groups 1 + 3], two float4 per lane
     // group 0 / 1.  Without the abs taps (round 6): 12 floats, THREE per lane group -- [M0 Mx My | Mxx Mxy Myy | f of groups 0 + 2 | f
@@ -1926,13 +1816,14 @@ struct QuarterCfg {
 };
 
 template <int CH, bool ABS, bool EXACT>
-__global__ void __launch_bounds__(256, BLEND_Q_MINW)
+__global__ void __launch_bounds__(256, (QuarterCfg<CH, ABS>::MINW))
 blend_bwd_quarter_kernel(const BlendArgs B) {
     using Cfg = QuarterCfg<CH, ABS>;
     constexpr int SB = Cfg::SB, CAP = Cfg::CAP, NCP = Cfg::NCP, RW = Cfg::RW, PW = Cfg::PW, RQ = 4;
     static_assert(SB <= 128 && CAP < 255, "list entries are (entry | position << 8) in 16 bits");
     __shared__ float4 s_rec[(SB + 1) * RQ];              // staged records, slot SB = inert; part p of entry e at qpart(e, p)
-    auto qpart = [](int e, int p) { return BLEND_Q_SWZ ? 4 * e + (p ^ ((e >> 2) & 3)) : 4 * e + p; };
+    // part p of entry e at 4 e + (p ^ ((e >> 2) & 3)): 16 survivors' reads of one part spread over the banks
+    auto qpart = [](int e, int p) { return 4 * e + (p ^ ((e >> 2) & 3)); };
     __shared__ unsigned int s_keep[SB];
     __shared__ unsigned short s_qlist[4][4][CAP + 16];   // [wave][quarter], entries of the current round: entry | (slab row) << 8
     __shared__ unsigned int s_pos4[SB];                  // byte w: position of entry e in wave w's block-level list (255: none)
@@ -2141,12 +2032,12 @@ blend_bwd_quarter_kernel(const BlendArgs B) {
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int G = 0; G < 4; ++G) {
-                for (int j0 = 0; j0 < ((BLEND_QABL & 1) ? 0 : cq[G]); j0 += 16) {
+                for (int j0 = 0; j0 < cq[G]; j0 += 16) {
                     const unsigned le = s_qlist[w][G][j0 + nl];
                     const int e = le & 0xffu, row = le >> 8;
                     const int qn = top - e;
                     const float *er = reinterpret_cast<const float *>(s_rec) + e * (4 * RQ);
-                    const int sw = BLEND_Q_SWZ ? 4 * ((e >> 2) & 3) : 0;   // float offset of part p: 4 p ^ sw
+                    const int sw = 4 * ((e >> 2) & 3);   // float offset of part p: 4 p ^ sw
                     const float bq1 = er[(12 ^ sw) + kk];           // q0 qx qy qxx
                     const float bq2 = er[(4 ^ sw) + 2 + (kk & 1)];  // qxy qyy (lane groups 2, 3: their monomial operand is zero)
                     const float bf = er[(8 ^ sw) + kk];             // feature kk (zero past CH)
@@ -2258,7 +2149,7 @@ blend_bwd_quarter_kernel(const BlendArgs B) {
             }
             __syncthreads();
             // ---- combine: thread e sums entry e's rows of the four slabs and maps the raw moments to the record
-            if (tid < nb && !(BLEND_QABL & 2)) {
+            if (tid < nb) {
                 const int e = tid;
                 const unsigned int p4 = s_pos4[e];
                 float s[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -2339,6 +2230,10 @@ struct SetsCfg {
     static constexpr int CH = 28, NK = 7, NA = 2, SB = 64;
     static constexpr int NG = SETS_NG, NCMAX = NG + CH;
     static constexpr int PS = 8;  // state floats per pixel: [. . . ncontrib | T, R of set 0 1 2 (starting from T_final bg.g)]
+    // waves per SIMD the three-set backward is compiled for (3: 168 registers = 39 scratch accesses inside the chunk loop, 1061
+    // instead of 615 us per frame; its LDS would allow 3)
+    static constexpr int MINW = 2;
+    static constexpr int CAP = 32;  // blend_bwd_sets_kernel: slab rows per wave (list positions per round)
 };
 
 // Float of feature slot s inside the packed SETS record (and its staged copy): the 28 slots are stored TRANSPOSED -- slot
@@ -2405,21 +2300,21 @@ pack_sets_kernel(const BlendArgs B) {
 }
 
 template <bool ABS>
-__global__ void __launch_bounds__(256, BLEND_SETS_MINW)
+__global__ void __launch_bounds__(256, SetsCfg::MINW)
 blend_bwd_sets_kernel(const BlendArgs B) {
     using Cfg = SetsCfg;
     constexpr int CH = Cfg::CH, SB = Cfg::SB, NG = Cfg::NG, NK = Cfg::NK, NA = Cfg::NA, PS = Cfg::PS;
     // private slab per wave, rows by the wave's list POSITION (CAP rows + a zero row; a longer survivor list takes another round
     // of chunks + combine): 25 KB instead of the 39 KB of one row per staged entry -- three workgroups per CU.  (First: staging
     // of the wave's dL_dout, half a block at a time.)
-    constexpr int CAP = BLEND_SETS_CAP;
+    constexpr int CAP = Cfg::CAP;
     static_assert(CAP % 16 == 0 && (CAP + 1) * Cfg::NCMAX >= 32 * CH, "whole chunks; the staging of 32 pixels fits a slab");
-    __shared__ TileLDS<CH, SB, false, 0, BLEND_REC_SWZ != 0> L;
+    __shared__ TileLDS<CH, SB, false, 0, true> L;
     __shared__ CarryLDS<SB, true> CL;              // (position bytes of the entries; nothing is carried here)
     __shared__ float s_acc[4][(CAP + 1) * Cfg::NCMAX];
     // replay state rows (8 floats per pixel), pixel q = 16 G + 4 kk + i at float G * GS + kk * KS + i * PS: 8 floats of skew
     // per lane group, or the four groups' rows of one step share their banks (see blend_bwd_mfma_kernel)
-    constexpr int KS = 4 * PS + (BLEND_STATE_SKEW ? 8 : 0), GS = 4 * KS;
+    constexpr int KS = 4 * PS + 8, GS = 4 * KS;
     __shared__ __attribute__((aligned(16))) float s_state[4][4 * GS];
     auto pixoff = [](int q) { return (q >> 4) * GS + ((q >> 2) & 3) * KS + (q & 3) * PS; };
     __shared__ float s_mom[16 * 64];             // A operand of the moment product: [step 4 G + i][lane]
@@ -2797,6 +2692,10 @@ struct SetsQCfg {
     // lx = -c0x cA cB 0, ly = -c0y cB cC 0 (the tap factor) | part 14 padding: 15 parts, an ODD number of 16-byte slots, so
     // consecutive entries start on different slots of the 256-byte bank row and no swizzle is needed
     static constexpr int RQL = 15;
+    static constexpr int MINW = SetsCfg::MINW;
+    // SMALL (see the kernel): super-batch (= slab rows per wave) with which 36-float rows leave 50.9 KB of LDS = three workgroups per
+    // CU (52 entries are 54.3 KB: three on paper, two on the chip -- 313 us per frame against 256 at 48; 40: 270)
+    static constexpr int SMALL_SB = 48, SMALL_MINW = 3;
 };
 
 // STD: the renderer's own plan -- rgb (3 channels, taps) at row channels 0-2, the depth at channel 3, 19 detached attributes
@@ -2810,15 +2709,8 @@ struct SetsQCfg {
 // K-slabs j >= SMALL of the colour dot product, the second 16-slot block of the feature-gradient product, their hoisted operands
 // (28 / 32 registers instead of 88) and their slab traffic are skipped; records and staging keep the 28-slot layout, the slab rows
 // hold 16 slots (36 floats).
-#ifndef BLEND_SETS_SMALL_SB
-#define BLEND_SETS_SMALL_SB 48   // SMALL: super-batch (= slab rows per wave) with which 36-float rows leave 50.9 KB of LDS = three workgroups per
-                                 // CU (52 entries are 54.3 KB: three on paper, two on the chip -- 313 us per frame against 256 at 48; 40: 270)
-#endif
-#ifndef BLEND_SETS_SMALL_MINW
-#define BLEND_SETS_SMALL_MINW 3
-#endif
 template <bool ABS, bool STD, bool FWDREC = false, int SMALL = 0>   // SMALL: K-slabs of the colour product in use (3 / 4; 0: all seven)
-__global__ void __launch_bounds__(256, (SMALL ? BLEND_SETS_SMALL_MINW : BLEND_SETS_MINW))
+__global__ void __launch_bounds__(256, (SMALL ? SetsQCfg::SMALL_MINW : SetsQCfg::MINW))
 blend_bwd_sets_quarter_kernel(const BlendArgs B) {
     static_assert(!FWDREC || STD, "the forward's records are only understood for the renderer's own plan");
     static_assert(!SMALL || !STD, "the renderer's own plan fills the 28 slots");
@@ -2829,8 +2721,8 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
     // SMALL (round 6): slots 12 .. 27 are empty, so a slab row is 20 + 12 (+ 4: an odd number of float4) floats instead of 52, and
     // with a 48-entry super-batch the workgroup holds 50.9 instead of 81 KB of LDS -- THREE workgroups per CU at 168 registers
     // (the full plans' hoisted operands keep them at 220 registers and two): 3|1|4 plan backward 310 -> 256 us per frame
-    constexpr int SB = (SMALL && BLEND_SETS_SMALL_MINW >= 3) ? BLEND_SETS_SMALL_SB : Cfg::SB, CAP = SB;
-    constexpr int RW = (SMALL && BLEND_SETS_SMALL_MINW >= 3) ? 36 : Cfg::RW;
+    constexpr int SB = SMALL ? Cfg::SMALL_SB : Cfg::SB, CAP = SB;
+    constexpr int RW = SMALL ? 36 : Cfg::RW;
     constexpr int RQL = Cfg::RQL;
     static_assert(RQ == 12 && Rec<CH>::CULL == 43 && SB <= 64 && CAP * RW >= 32 * CH, "record floats 40-42 are free; the staging of 32 pixels fits a slab");
     __shared__ float4 s_rec[(SB + 1) * RQL];            // staged records (SetsQCfg::RQL parts each), slot SB = inert
@@ -2904,9 +2796,6 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
             const int c = sets_slot_channel(A, k);
             const int gi = k < 4 ? 0 : k < 8 ? 1 : 2;
             const int cc = c >= 0 ? c : 0;
-#if BLEND_ABL == 3
-            gpix[k] = 0.001f * (float)(k + lane); tgt[k] = 0.f; continue;   // timing ablation: no image loads (results invalid)
-#endif
             if (A.dL_dout) {
                 gpix[k] = A.dL_dout[(size_t)cc * HW + pix];
             } else {
@@ -3138,30 +3027,12 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        // the list entry of a step is read ONE STEP AHEAD (the step's operand reads hang on it: one LDS round trip less on the
-        // step's critical path).  Steps in walk order: quarter 0's, then quarter 1's ...; the entry behind the last step of a
-        // quarter is the first of the next quarter that has any (read past the last list: slack, unused).
-#if BLEND_SETS_LE_AHEAD
-        int gfirst = 0;
-#pragma unroll
-        for (int q = 3; q >= 0; --q) gfirst = cq[q] > 0 ? q : gfirst;
-        unsigned le_next = s_qlist[(4 * w + gfirst) * QL + nl];
-#endif
+        // the list entry of a step is read at the top of the step.  Reading it one step ahead (round 4, c2 training frame): 438
+        // vs 434 us per frame -- the round trip it saves is hidden by the second wave of the SIMD, the address arithmetic it adds is not
 #pragma unroll
         for (int G = 0; G < 4; ++G) {
-            for (int j0 = 0; j0 < ((BLEND_QABL & 4) ? 0 : cq[G]); j0 += 16) {   // (BLEND_QABL 4: timing ablation, no steps)
-#if BLEND_SETS_LE_AHEAD
-                const unsigned le = le_next;
-                {
-                    int gn = 4;       // the next quarter with a list (4: none -- the slack list, or the next wave's first)
-#pragma unroll
-                    for (int q = 3; q > G; --q) gn = cq[q] > 0 ? q : gn;
-                    const bool lastq = j0 + 16 >= cq[G];
-                    le_next = s_qlist[(lastq ? (4 * w + gn) * QL : (4 * w + G) * QL + j0 + 16) + nl];
-                }
-#else
+            for (int j0 = 0; j0 < cq[G]; j0 += 16) {
                 const unsigned le = s_qlist[(4 * w + G) * QL + j0 + nl];
-#endif
                 const int e = le & 0xffu, row = le >> 8;
                 const int qn = top - e;
                 // the step's B operands of this lane group: three 16-byte reads (Q[kk], slots kk 4+kk 8+kk 12+kk, slots 16+kk 20+kk 24+kk)
@@ -3172,16 +3043,15 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
                 float bf[NK];
                 bf[0] = t0.x; bf[1] = t0.y; bf[2] = t0.z; bf[3] = t0.w; bf[4] = t1.x; bf[5] = t1.y; bf[6] = t1.z;
                 static_assert(NK == 7, "slots 4 j + kk, j = 0 .. 6");
-#if BLEND_SETS_EARLY_ROWS
                 // the survivor's slab row -- what the step's epilogue adds into -- is requested NOW (a padded list slot reads the
-                // zero row), so that its LDS round trip runs under the step instead of in front of the epilogue's adds
+                // zero row), so that its LDS round trip runs under the step instead of in front of the epilogue's adds (13 registers
+                // across the step)
                 float *const rr = slab + row * RW;
                 float4 *const p1 = reinterpret_cast<float4 *>(rr + 4 * kk);
                 float4 *const pf = reinterpret_cast<float4 *>(rr + 20 + 4 * kk);   // slots 4 kk .. (q = 0) and 16 + 4 kk .. (q = 1)
                 const float4 o1_in = *p1, f0_in = pf[0];
                 const float4 f1_in = SMALL ? make_float4(0.f, 0.f, 0.f, 0.f) : pf[4];   // (lane group 3: pf[4] is the row's padding)
                 const float ay_in = rr[16];
-#endif
                 f32x4 d_mom = {0.f, 0.f, 0.f, 0.f};
                 f32x4 d_f[NAU];
 #pragma unroll
@@ -3264,7 +3134,6 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
                 };
                 s_op = half(s_op); s_tx = half(s_tx); s_ty = half(s_ty);
                 if (ABS) { s_ax = half(s_ax); s_ay = half(s_ay); }
-#if BLEND_SETS_EARLY_ROWS
                 if (j0 + nl < cq[G]) {
                     float4 o1 = o1_in;
                     o1.x += kk < 2 ? d_mom[0] : s_op;
@@ -3282,30 +3151,6 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
                         pf[4] = f1;
                     }
                 }
-#else
-                if (j0 + nl < cq[G]) {
-                    float *rr = slab + row * RW;
-                    float4 v1;
-                    v1.x = kk < 2 ? d_mom[0] : s_op;
-                    v1.y = kk < 2 ? d_mom[1] : s_tx;
-                    v1.z = kk == 0 ? d_mom[2] : kk == 1 ? s_ay : s_ty;
-                    v1.w = kk == 0 ? d_mom[3] : kk == 1 ? 0.f : s_ax;
-                    float4 *p1 = reinterpret_cast<float4 *>(rr + 4 * kk);
-                    float4 o1 = *p1;
-                    o1.x += v1.x; o1.y += v1.y; o1.z += v1.z; o1.w += v1.w;
-                    *p1 = o1;
-                    if (ABS && kk == 2) rr[16] += s_ay;
-                    float4 *pf = reinterpret_cast<float4 *>(rr + 20 + 4 * kk);   // slots 4 kk .. (q = 0) and 16 + 4 kk .. (q = 1)
-                    float4 f0 = pf[0];
-                    f0.x += d_f[0][0]; f0.y += d_f[0][1]; f0.z += d_f[0][2]; f0.w += d_f[0][3];
-                    pf[0] = f0;
-                    if (!SMALL && kk < 3) {
-                        float4 f1 = pf[4];
-                        f1.x += d_f[NAU - 1][0]; f1.y += d_f[NAU - 1][1]; f1.z += d_f[NAU - 1][2]; f1.w += d_f[NAU - 1][3];
-                        pf[4] = f1;
-                    }
-                }
-#endif
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
             }
@@ -3313,7 +3158,6 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
         const int slot_mine = ce < nb ? slots[top - ce] : 0;   // entry ce of the combine
         SETSQ_STAGE_PAYLOAD();
         SETSQ_STAGE_IDS(batch + 2);
-#if BLEND_SETS_TWO_BARRIERS
         // the combine's only reads of the staged records, taken BEFORE the barrier: behind it a fast wave may already park the next
         // super-batch over them while a slow one still combines (the combine otherwise reads the slabs and position bytes, which
         // nobody writes before the next super-batch's barrier) -- two barriers per super-batch instead of three
@@ -3324,17 +3168,7 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
             const float4 t_ = s_rec[qpart(ce, 1)];
             cgC = t_.x; cgo = t_.y;
         }
-#endif
         __syncthreads();
-#if !BLEND_SETS_TWO_BARRIERS
-        float4 cg0 = make_float4(0.f, 0.f, 0.f, 0.f);
-        float cgC = 0.f, cgo = 0.f;
-        if (cp <= 1) {
-            cg0 = s_rec[qpart(ce, 0)];
-            const float4 t_ = s_rec[qpart(ce, 1)];
-            cgC = t_.x; cgo = t_.y;
-        }
-#endif
         // ---- combine: entry ce = lane, role cp = wave -- wave 0: the geometry part of the record, waves 1 .. 3: the channel
         //      gradients.  Wave-uniform roles: a wave runs ONE of the two paths (four parts per entry in neighbouring lanes made
         //      every wave run both).
@@ -3480,9 +3314,6 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
                 // (floats NC .. NCP - 1 of a record are padding)
             }
         }
-#if !BLEND_SETS_TWO_BARRIERS
-        __syncthreads();
-#endif
     }
     if (A.dbg_T_front) {
         const int px = tx * TILE + lx, py = ty * TILE + ly;
@@ -4056,7 +3887,6 @@ static int launch_fwd(const BlendArgs &A, int T, bool enh, bool bias, hipStream_
 }
 
 // kernel selection: options of the ABI (splat_set_option), read at launch time
-static bool bwd_use_mfma() { return splat_option(SPLAT_OPT_BWD_KERNEL_DPP) == 0; }        // 1: the DPP-reduction pair kernel (A/B)
 static bool bwd_use_quarters() { return splat_option(SPLAT_OPT_BWD_QUARTERS) != 0; }      // 0: block-level kernels everywhere
 static bool sets_std_plan_enabled() { return splat_option(SPLAT_OPT_SETS_STD) != 0; }     // 0: generic slot -> channel routing
 
@@ -4064,17 +3894,17 @@ template <int CH, bool ABS, bool BIAS>
 static int launch_bwd_ab(const BlendArgs &A, int T, bool pair, hipStream_t s) {
     const dim3 grid((unsigned)(T * A.F)), block(256);
     const bool exact = A.cn == CH;
-    if (pair && !BIAS && CH <= 3 && A.cull_flags && bwd_use_mfma() && bwd_use_quarters()) {
+    if (pair && !BIAS && CH <= 3 && A.cull_flags && bwd_use_quarters()) {
         // narrow row with the forward's cull words: one survivor list per 4x4 quarter
         constexpr int QC = CH <= 3 ? CH : 3;
         if (exact) SPLAT_LAUNCH("blend_bwd", (blend_bwd_quarter_kernel<QC, ABS, true>), grid, block, 0, s, A);
         else SPLAT_LAUNCH("blend_bwd", (blend_bwd_quarter_kernel<QC, ABS, false>), grid, block, 0, s, A);
-    } else if (pair && !BIAS && !ABS && CH >= 16 && A.cull_flags && !A.rec_stride && bwd_use_mfma() && bwd_use_quarters()) {
+    } else if (pair && !BIAS && !ABS && CH >= 16 && A.cull_flags && !A.rec_stride && bwd_use_quarters()) {
         // frame batch, wide row without |taps|: quarter lists
         constexpr int WC = CH >= 16 ? CH : 16;
         if (exact) SPLAT_LAUNCH("blend_bwd", (blend_bwd_wide_quarter_kernel<WC, true>), grid, block, 0, s, A);
         else SPLAT_LAUNCH("blend_bwd", (blend_bwd_wide_quarter_kernel<WC, false>), grid, block, 0, s, A);
-    } else if (pair && !BIAS && bwd_use_mfma() && !(BLEND_CARRY && splat_deterministic())) {
+    } else if (pair && !BIAS && !splat_deterministic()) {   // (its carried survivors add into pair_buf with float atomics)
         if (exact) SPLAT_LAUNCH("blend_bwd", (blend_bwd_mfma_kernel<CH, ABS, true>), grid, block, 0, s, A);
         else SPLAT_LAUNCH("blend_bwd", (blend_bwd_mfma_kernel<CH, ABS, false>), grid, block, 0, s, A);
     } else if (pair) {

@@ -33,7 +33,7 @@ void splat_set_error(const char *fmt, ...);
 
 bool splat_deterministic();   // splat_set_deterministic (runtime.hip)
 // splat_set_option keys (runtime.hip): kernel selection through the ABI, read at launch time
-enum { SPLAT_OPT_BWD_QUARTERS = 0, SPLAT_OPT_BWD_KERNEL_DPP, SPLAT_OPT_SETS_STD, SPLAT_OPT_BIN_SLOT_KEYS, SPLAT_OPT_COUNT };
+enum { SPLAT_OPT_BWD_QUARTERS = 0, SPLAT_OPT_SETS_STD, SPLAT_OPT_BIN_SLOT_KEYS, SPLAT_OPT_COUNT };
 int splat_option(int id);
 
 // ---------------------------------------------------------------- profiled launches
@@ -191,23 +191,17 @@ struct GradLayout {
 // renderer's 23 channels the stride stays PAIR_STRIDE(12 + 23) = 36 floats)
 constexpr int SETS_NG = 12;
 // Workgroups are handed to the 8 XCDs round-robin by linear block id, and every XCD has its own L2.  Neighbouring
-// tiles gather largely the same packed records (a splat touches ~4 tiles), so runs of BLEND_XCD_RUN consecutive tiles
+// tiles gather largely the same packed records (a splat touches ~4 tiles), so runs of XCD_RUN consecutive tiles
 // of the row-major order go to the same XCD (its consecutive blocks, i.e. roughly concurrently resident), and the runs
 // are dealt round-robin so that every XCD sees the whole image (a contiguous band per XCD halves the HBM reads as
 // well but leaves the XCDs that own the image borders idle early).  Block b = XCD b & 7, its (b >> 3)-th block.
-#ifndef BLEND_XCD_RUN
-#define BLEND_XCD_RUN 64   // a run is about one tile row of a 480p frame plus the start of the next (54 tiles per row)
-#endif
+constexpr int XCD_RUN = 64;   // a run is about one tile row of a 480p frame plus the start of the next (54 tiles per row)
 __device__ __forceinline__ int xcd_tile(int b, int T) {
-#if BLEND_XCD_RUN > 1
-    constexpr int S = BLEND_XCD_RUN;
+    constexpr int S = XCD_RUN;
     const int full = (T / (8 * S)) * (8 * S);  // tiles covered by complete rounds of 8 runs; the tail maps linearly
     if (b >= full) return b;
     const int x = b & 7, q = b >> 3;
     return ((q / S) * 8 + x) * S + (q % S);
-#else
-    return b;
-#endif
 }
 
 

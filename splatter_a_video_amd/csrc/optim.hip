@@ -10,9 +10,6 @@
 
 #include "common.h"
 
-#ifndef ADAM_NONTEMPORAL
-#define ADAM_NONTEMPORAL 1   // streaming loads / stores: 12.1 -> 10.7 us per frame on the 1.48 GB dynamic-model buffer, neutral on the static one
-#endif
 namespace {
 constexpr int ADAM_MAX_SEG = SPLAT_ADAM_MAX_SEGMENTS;
 struct AdamSegs {
@@ -49,31 +46,21 @@ adam_kernel(long long n, float *__restrict__ p, const float *__restrict__ g, flo
             AdamSegs S, float b1, float b2, float rbc2, float eps, float gscale) {
     const long long n4 = n >> 2;
     for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long long)gridDim.x * 256) {
-#if ADAM_NONTEMPORAL
-        // a pure stream: every byte is touched once per step -- keep it out of the caches the next forward wants
+        // a pure stream: every byte is touched once per step -- keep it out of the caches the next forward wants (streaming loads
+        // / stores: 12.1 -> 10.7 us per frame on the 1.48 GB dynamic-model buffer, neutral on the static one)
         typedef float nt4 __attribute__((ext_vector_type(4)));
         const nt4 p_ = __builtin_nontemporal_load(reinterpret_cast<const nt4 *>(p) + q), m_ = __builtin_nontemporal_load(reinterpret_cast<const nt4 *>(m) + q);
         const nt4 v_ = __builtin_nontemporal_load(reinterpret_cast<const nt4 *>(v) + q), g_ = __builtin_nontemporal_load(reinterpret_cast<const nt4 *>(g) + q);
         float4 P = make_float4(p_.x, p_.y, p_.z, p_.w), M = make_float4(m_.x, m_.y, m_.z, m_.w), V = make_float4(v_.x, v_.y, v_.z, v_.w);
         const float4 G = make_float4(g_.x, g_.y, g_.z, g_.w);
-#else
-        float4 P = reinterpret_cast<float4 *>(p)[q], M = reinterpret_cast<float4 *>(m)[q], V = reinterpret_cast<float4 *>(v)[q];
-        const float4 G = reinterpret_cast<const float4 *>(g)[q];
-#endif
         const long long i = q << 2;
         adam1(P.x, G.x * gscale, M.x, V.x, seg_step(S, i), b1, b2, rbc2, eps);
         adam1(P.y, G.y * gscale, M.y, V.y, seg_step(S, i + 1), b1, b2, rbc2, eps);
         adam1(P.z, G.z * gscale, M.z, V.z, seg_step(S, i + 2), b1, b2, rbc2, eps);
         adam1(P.w, G.w * gscale, M.w, V.w, seg_step(S, i + 3), b1, b2, rbc2, eps);
-#if ADAM_NONTEMPORAL
         __builtin_nontemporal_store((nt4){P.x, P.y, P.z, P.w}, reinterpret_cast<nt4 *>(p) + q);
         __builtin_nontemporal_store((nt4){M.x, M.y, M.z, M.w}, reinterpret_cast<nt4 *>(m) + q);
         __builtin_nontemporal_store((nt4){V.x, V.y, V.z, V.w}, reinterpret_cast<nt4 *>(v) + q);
-#else
-        reinterpret_cast<float4 *>(p)[q] = P;
-        reinterpret_cast<float4 *>(m)[q] = M;
-        reinterpret_cast<float4 *>(v)[q] = V;
-#endif
     }
     if (blockIdx.x == 0 && threadIdx.x < (int)(n & 3)) {  // tail
         const long long i = (n4 << 2) + threadIdx.x;

@@ -377,18 +377,7 @@ inline dim3 dyn_grid(int P) { return dim3((unsigned)(((size_t)P * 4 + DYN_BLOCK 
 // of the bench scene's splats touch more than six tiles (most waves hold one).  Narrow (one-chunk-per-lane) records: U = 6
 // (17.4 us per frame at 4, 16.5 at 6, 16.2 at 8 with the tail two at a time), TAIL = 6 (17.2 -> 14.4); wide records: U = 2 (at
 // four the registers cost more waves than the loads in flight gain), TAIL = 4 (c5: 43.6 -> 40.9 us per frame).
-#ifndef GAUSS_BWD_U
-#define GAUSS_BWD_U 6
-#endif
-#ifndef GAUSS_BWD_TAIL
-#define GAUSS_BWD_TAIL 6
-#endif
-#ifndef GAUSS_BWD_U_WIDE
-#define GAUSS_BWD_U_WIDE 2
-#endif
-#ifndef GAUSS_BWD_TAIL_WIDE
-#define GAUSS_BWD_TAIL_WIDE 4
-#endif
+constexpr int GAUSS_BWD_U = 6, GAUSS_BWD_TAIL = 6, GAUSS_BWD_U_WIDE = 2, GAUSS_BWD_TAIL_WIDE = 4;
 struct GaussBwdArgs {
     int F, P, W, H;
     int C, cn;              // row stride of d_feature, channels carried by the records
@@ -771,10 +760,9 @@ frame_preprocess_fwd_batch_kernel(int F, int P, int I, int layout, const DynTab 
 // cov3d backward and chains through the activations -- scale = exp, rotation = normalize(raw + detached sums), opacity =
 // sigmoid, position = base + cubic segment.  Everything accumulates in registers; the spline segment's four coefficient
 // rows are flushed when the walk leaves the segment (frames of a batch are time-ordered: a handful of flushes).
-#ifndef GAUSS_DYN_MINW
-#define GAUSS_DYN_MINW 3   // 168 registers, no scratch (4: 128 registers and 156 bytes of scratch per lane -- 62 vs 54 us per frame for the
-                           // three-set records at c2, round 4)
-#endif
+// 168 registers, no scratch (4: 128 registers and 156 bytes of scratch per lane -- 62 vs 54 us per frame for the three-set
+// records at c2, round 4)
+constexpr int GAUSS_DYN_MINW = 3;
 struct GaussDynArgs {
     int F, P, W, H, I, layout;
     int C, cn;

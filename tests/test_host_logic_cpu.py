@@ -63,6 +63,8 @@ def test_library_options_through_the_abi(built_lib=None):
     L.set_option("deterministic", 0)
     with pytest.raises(L.SplatError, match="unknown key"):
         L.set_option("no_such_option", 1)
+    with pytest.raises(L.SplatError, match="unknown key"):   # the DPP pair kernel is no longer selectable
+        L.set_option("bwd_kernel_dpp", 1)
     i3 = __import__("ctypes").c_int32 * 3
     q = L.lib().splat_blend_sets_uses_forward_pack
     assert q(L.ci(23), i3(0, 3, 4), i3(3, 1, 19), L.ci(1)) == 1 and q(L.ci(23), i3(0, 3, 4), i3(3, 1, 19), L.ci(0)) == 0
