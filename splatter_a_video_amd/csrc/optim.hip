@@ -34,11 +34,15 @@ __device__ __forceinline__ float seg_step(const AdamSegs &S, long long i) {
     return s;
 }
 
+// The fused multiply-adds are spelled out and nothing else may be contracted: left to the compiler, the float4 body and the
+// scalar tail were contracted differently (the tail's v rounded twice), so an element's bits depended on whether its cut of the
+// buffer put it in the tail -- ZeRO-1 blocks and FlatAdam must agree bit for bit.
 __device__ __forceinline__ void adam1(float &p, float g, float &m, float &v, float ss, float b1, float b2, float rbc2,
                                       float eps) {
-    m = b1 * m + (1.f - b1) * g;
-    v = b2 * v + (1.f - b2) * g * g;
-    p -= ss * m / (sqrtf(v) * rbc2 + eps);
+#pragma clang fp contract(off)
+    m = fmaf(b1, m, (1.f - b1) * g);
+    v = fmaf(b2, v, (1.f - b2) * g * g);
+    p -= ss * m / fmaf(sqrtf(v), rbc2, eps);
 }
 
 __global__ void __launch_bounds__(256)

@@ -179,12 +179,16 @@ class OwnerShardedAdam:
     def _segments(self, lo: int, hi: int):
         """learning-rate segments (+ patterns) of the sub-buffer [lo, hi), relative to lo.  A block that starts INSIDE a
         ``PatternLR`` group (ZeRO-1 cuts the buffer anywhere) starts mid-period: the rest of that period becomes a segment of its
-        own (what is left of the head keeps the head rate), the whole periods behind it keep the pattern."""
+        own (what is left of the head keeps the head rate), the whole periods behind it keep the pattern.  The padding behind the
+        last slice (``FlatGradBucket(pad_to=...)``: no parameter's, zero gradients) is a segment of rate 0, so the segments end at
+        hi - lo; a block of padding only has no segment at all."""
         sl, lrs = {}, {}
+        end = 0
         for n, (a, b) in self.bucket.slices.items():
             s0, s1 = max(a, lo), min(b, hi)
             if s1 <= s0:
                 continue
+            end = s1 - lo
             r = self.lr[n]
             if isinstance(r, PatternLR) and (s0 - a) % r.period:
                 ph = (s0 - a) % r.period
@@ -195,14 +199,18 @@ class OwnerShardedAdam:
                     sl[n], lrs[n] = (cut - lo, s1 - lo), r
             else:
                 sl[n], lrs[n] = (s0 - lo, s1 - lo), r
+        if sl and end < hi - lo:
+            sl["#pad"], lrs["#pad"] = (end, hi - lo), 0.0
         return lr_segments(sl, lrs, patterns=True)
 
     def _step(self, lo: int, hi: int, m, v, grad_scale: float) -> None:
         if hi <= lo:
             return
-        p, g = self.bucket.flat_param[lo:hi], self.bucket.flat_grad[lo:hi]
         ends, rates, pat = self._segments(lo, hi)
         n = len(ends)
+        if n == 0:              # padding only: nothing to step
+            return
+        p, g = self.bucket.flat_param[lo:hi], self.bucket.flat_grad[lo:hi]
         c_ends, c_rates = (ctypes.c_int64 * n)(*ends), (ctypes.c_float * n)(*rates)
         if any(q[0] for q in pat):
             L.check(L.lib().splat_adam_step_pattern(

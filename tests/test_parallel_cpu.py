@@ -506,3 +506,88 @@ def test_a_block_that_starts_inside_a_pattern_group_keeps_the_pattern():
         o = Stub(); o.bucket, o.lr = Stub(), lr; o.bucket.slices = slices
         ends, rates, pats = OwnerShardedAdam._segments(o, lo, total)
         assert [rate_of(ends, rates, pats, i) for i in range(total - lo)] == flat[lo:]
+
+
+def _segment_rates(ends, rates, pats, n):
+    """per-element learning rate of (segment ends, rates, patterns) over [0, n): what the Adam kernel looks up"""
+    out, start = np.zeros(n), 0
+    for e, r, (per, head, hr) in zip(ends, rates, pats):
+        k = np.arange(e - start)
+        out[start:e] = np.where((k % per < head) if per else False, hr, r)
+        start = e
+    return out
+
+
+def test_zero1_blocks_cover_the_padding_with_a_rate_0_segment():
+    """host logic of OwnerShardedAdam._segments on the UNCLIPPED blocks of Zero1Shards: FlatGradBucket(pad_to=4 * world) adds
+    floats behind the last slice that belong to no parameter.  Every block's segments must tile [0, hi - lo) -- the kernel refuses
+    segments that end before its n -- with the flat rate on real elements and 0 on the padding; a block of padding only launches
+    nothing (no segment).  The flat rate comes from adam_ref.rate_map, which does not go through lr_segments."""
+    from adam_ref import rate_map
+    from splatter_a_video_amd.optim import OwnerShardedAdam, PatternLR
+    from splatter_a_video_amd.parallel import Zero1Shards
+
+    class Stub:            # what _segments reads
+        pass
+    N, I = 7, 3
+    cases = [   # the TrainingStep layout with A = 1 and an odd N (12 I + 57 floats per Gaussian); the two reproductions of the bug
+        ({"cubic": (I, N, 4, 3), "rotation": (N, 4), "opacity": (N, 1), "scaling": (N, 3), "shs": (N, 16, 3), "attrs": (N, 1)},
+         {"cubic": 6e-5, "rotation": 1e-3, "opacity": 5e-2, "scaling": 5e-3, "attrs": 1e-3,
+          "shs": PatternLR(1.25e-4, head_lr=2.5e-3, period=48, head=3)}),
+        ({"a": (21,), "shs": (7, 16, 3)}, {"a": 1e-3, "shs": PatternLR(1.25e-4, head_lr=2.5e-3, period=48, head=3)}),
+        ({"x": (3,)}, {"x": 1e-3}),
+        ({"a": (5,), "p7": (2, 7), "b": (6,)}, {"a": 1e-2, "p7": PatternLR(1e-3, head_lr=4e-3, period=7, head=2), "b": 0.0}),
+    ]
+    for shapes, lr in cases:
+        real = sum(int(np.prod(s)) for s in shapes.values())
+        for world in range(1, 9):
+            bucket = FlatGradBucket({k: torch.zeros(s) for k, s in shapes.items()}, pad_to=4 * world)
+            total = bucket.flat_param.numel()
+            flat = rate_map(bucket.slices, lr, total)
+            assert flat[real:].max(initial=0.0) == 0.0
+            for r in range(world):
+                lo, hi = Zero1Shards(bucket, world, r).own
+                o = Stub()
+                o.bucket, o.lr = bucket, lr
+                ends, rates, pats = OwnerShardedAdam._segments(o, lo, hi)
+                if lo >= real:
+                    assert ends == [], (shapes, world, r)         # padding only: no launch
+                    continue
+                assert ends[-1] == hi - lo and all(a < b for a, b in zip([0] + ends, ends)), (world, r, ends, lo, hi)
+                assert np.array_equal(_segment_rates(ends, rates, pats, hi - lo), flat[lo:hi]), (shapes, world, r)
+
+
+def test_the_float64_adam_reference_is_torch_adam():
+    """tests/adam_ref.py (the float64 statement the GPU Adam tests compare the kernels with) against torch.optim.Adam in float64:
+    per-group rates, a PatternLR group split into the two tensors the reference keeps (phase from the group's start, which does
+    not sit at a multiple of the period), a grad_scale, an all-zero gradient step and a learning-rate change"""
+    from adam_ref import Adam64, rate_map
+    from splatter_a_video_amd.optim import PatternLR
+    g = torch.Generator().manual_seed(0)
+    N = 5
+    init = {"a": torch.randn(13, generator=g, dtype=torch.float64), "shs": torch.randn(N, 16, 3, generator=g, dtype=torch.float64)}
+    slices = {"a": (0, 13), "shs": (13, 13 + N * 48)}
+    lr = {"a": 1e-2, "shs": PatternLR(1.25e-4, head_lr=2.5e-3, period=48, head=3)}
+    a = init["a"].clone().requires_grad_(True)
+    dc = init["shs"][:, :1].clone().requires_grad_(True)
+    rest = init["shs"][:, 1:].clone().requires_grad_(True)
+    opt = torch.optim.Adam([{"params": [a], "lr": 1e-2}, {"params": [dc], "lr": 2.5e-3}, {"params": [rest], "lr": 1.25e-4}],
+                           betas=(0.9, 0.999), eps=1e-15)
+    ref = Adam64(torch.cat([init["a"], init["shs"].reshape(-1)]).numpy(), betas=(0.9, 0.999), eps=1e-15)
+    for step in range(6):
+        scale = 0.5 if step % 2 else 1.0
+        if step == 4:
+            lr["a"] = 3e-3
+            opt.param_groups[0]["lr"] = 3e-3
+        ga, gs = torch.randn(13, generator=g, dtype=torch.float64), torch.randn(N, 16, 3, generator=g, dtype=torch.float64)
+        if step == 2:
+            ga.zero_(), gs.zero_()
+        a.grad, dc.grad, rest.grad = ga * scale, (gs[:, :1] * scale).clone(), (gs[:, 1:] * scale).clone()
+        opt.step()
+        ref.step(torch.cat([ga, gs.reshape(-1)]).numpy(), rate_map(slices, lr, 13 + N * 48), grad_scale=scale)
+        got = torch.cat([a.detach(), torch.cat([dc.detach(), rest.detach()], 1).reshape(-1)]).numpy()
+        np.testing.assert_allclose(ref.p, got, rtol=1e-13, atol=1e-15)
+        m = torch.cat([opt.state[a]["exp_avg"], torch.cat([opt.state[dc]["exp_avg"], opt.state[rest]["exp_avg"]], 1).reshape(-1)])
+        v = torch.cat([opt.state[a]["exp_avg_sq"], torch.cat([opt.state[dc]["exp_avg_sq"], opt.state[rest]["exp_avg_sq"]], 1).reshape(-1)])
+        np.testing.assert_allclose(ref.m, m.numpy(), rtol=1e-13, atol=1e-15)      # (torch: lerp; here b1 m + (1 - b1) g)
+        np.testing.assert_allclose(ref.v, v.numpy(), rtol=1e-13, atol=1e-15)
