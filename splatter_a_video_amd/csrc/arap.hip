@@ -2,7 +2,7 @@
 // src/geometry_utils.py:50-123 (estimate_rotation: per-vertex covariance of source / target edge matrices, torch.svd,
 // rotation W U^T with the reflection fix; cal_arap_error: sum_k w_k |e_tgt_k - R e_src_k|^2 over the sampled vertices and
 // the frames t >= 1) -- ~50 small launches per frame pair -- by ONE launch: a thread per (sampled vertex, frame) builds
-// the 3x3 covariance, extracts the rotation (Jacobi eigen-decomposition of S^T S -> SVD -> Kabsch rotation with
+// the 3x3 covariance, extracts the rotation (one-sided Jacobi SVD of S -> Kabsch rotation with
 // det = +1), accumulates the energy and scatters d energy / d nodes (the rotation is a constant of the gradient: the
 // reference estimates it under torch.no_grad()).
 #include "common.h"
@@ -10,9 +10,16 @@
 namespace {
 constexpr int ARAP_MAXK = 16;
 
+// One-sided (Hestenes) Jacobi rotation: columns p, q of A = S V are rotated until they are orthogonal, V accumulates the
+// rotations; at convergence the columns of A are sigma_c u_c and those of V the right singular vectors.  (An eigen-decomposition
+// of S^T S squares the condition number: with two nearly collinear edges, sigma_2 ~ 1e-3 sigma_1, its float32 eigenvectors of
+// the two small eigenvalues were off by ~0.05 rad and the energy 16 u scale above the optimum -- tests/test_gpu_arap_reference.py.)
 __device__ __forceinline__ void jacobi_rot(float A[3][3], float V[3][3], int p, int q) {
-    if (fabsf(A[p][q]) < 1e-30f) return;
-    const float theta = (A[q][q] - A[p][p]) / (2.f * A[p][q]);
+    const float a = A[0][p] * A[0][p] + A[1][p] * A[1][p] + A[2][p] * A[2][p];
+    const float b = A[0][q] * A[0][q] + A[1][q] * A[1][q] + A[2][q] * A[2][q];
+    const float g = A[0][p] * A[0][q] + A[1][p] * A[1][q] + A[2][p] * A[2][q];
+    if (!(fabsf(g) > 1e-8f * (sqrtf(a) * sqrtf(b)))) return;  // orthogonal to rounding (a zero column, NaN input)
+    const float theta = (b - a) / (2.f * g);
     const float t = (theta >= 0.f ? 1.f : -1.f) / (fabsf(theta) + sqrtf(theta * theta + 1.f));
     const float c = 1.f / sqrtf(t * t + 1.f), s = t * c;
 #pragma unroll
@@ -20,12 +27,6 @@ __device__ __forceinline__ void jacobi_rot(float A[3][3], float V[3][3], int p, 
         const float akp = A[k][p], akq = A[k][q];
         A[k][p] = c * akp - s * akq;
         A[k][q] = s * akp + c * akq;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {  // A <- J^T A (rows p, q)
-        const float apk = A[p][k], aqk = A[q][k];
-        A[p][k] = c * apk - s * aqk;
-        A[q][k] = s * apk + c * aqk;
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -42,14 +43,16 @@ __device__ void kabsch_rotation(const float S[3][3], float R[3][3]) {
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) A[i][j] = S[0][i] * S[0][j] + S[1][i] * S[1][j] + S[2][i] * S[2][j];  // S^T S
+        for (int j = 0; j < 3; ++j) A[i][j] = S[i][j];
     for (int sweep = 0; sweep < 6; ++sweep) {
         jacobi_rot(A, V, 0, 1);
         jacobi_rot(A, V, 0, 2);
         jacobi_rot(A, V, 1, 2);
     }
-    // order the eigenpairs by descending eigenvalue (columns of V = right singular vectors W)
-    float lam[3] = {A[0][0], A[1][1], A[2][2]};
+    // order the columns by descending singular value (columns of V = right singular vectors W)
+    float lam[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) lam[c] = A[0][c] * A[0][c] + A[1][c] * A[1][c] + A[2][c] * A[2][c];
     int o[3] = {0, 1, 2};
     if (lam[o[0]] < lam[o[1]]) { const int t = o[0]; o[0] = o[1]; o[1] = t; }
     if (lam[o[0]] < lam[o[2]]) { const int t = o[0]; o[0] = o[2]; o[2] = t; }
@@ -59,27 +62,37 @@ __device__ void kabsch_rotation(const float S[3][3], float R[3][3]) {
     for (int c = 0; c < 3; ++c) {
 #pragma unroll
         for (int r = 0; r < 3; ++r) W[r][c] = V[r][o[c]];
-        sig[c] = sqrtf(fmaxf(lam[o[c]], 0.f));
+        sig[c] = sqrtf(lam[o[c]]);
     }
-    // left singular vectors u_c = S w_c / sigma_c; degenerate directions are completed to an orthonormal basis
+    // left singular vectors u_c = (S w_c) / sigma_c; degenerate directions are completed to an orthonormal basis
     const float tiny = 1e-12f * fmaxf(sig[0], 1e-30f) + 1e-30f;
     float u0[3] = {1.f, 0.f, 0.f}, u1[3] = {0.f, 1.f, 0.f}, u2[3];
     if (sig[0] > tiny) {
 #pragma unroll
-        for (int r = 0; r < 3; ++r) u0[r] = (S[r][0] * W[0][0] + S[r][1] * W[1][0] + S[r][2] * W[2][0]) / sig[0];
+        for (int r = 0; r < 3; ++r) u0[r] = A[r][o[0]] / sig[0];
         float n = rsqrtf(fmaxf(u0[0] * u0[0] + u0[1] * u0[1] + u0[2] * u0[2], 1e-30f));
         u0[0] *= n; u0[1] *= n; u0[2] *= n;
-        if (sig[1] > tiny) {
+        bool have = sig[1] > tiny;
+        if (have) {
 #pragma unroll
-            for (int r = 0; r < 3; ++r) u1[r] = (S[r][0] * W[0][1] + S[r][1] * W[1][1] + S[r][2] * W[2][1]) / sig[1];
-        } else {  // any unit vector orthogonal to u0
-            const int m = fabsf(u0[0]) <= fabsf(u0[1]) ? (fabsf(u0[0]) <= fabsf(u0[2]) ? 0 : 2) : (fabsf(u0[1]) <= fabsf(u0[2]) ? 1 : 2);
-            u1[0] = m == 0 ? 1.f : 0.f; u1[1] = m == 1 ? 1.f : 0.f; u1[2] = m == 2 ? 1.f : 0.f;
+            for (int r = 0; r < 3; ++r) u1[r] = A[r][o[1]] / sig[1];
         }
-        const float d = u1[0] * u0[0] + u1[1] * u0[1] + u1[2] * u0[2];
-        u1[0] -= d * u0[0]; u1[1] -= d * u0[1]; u1[2] -= d * u0[2];
-        n = rsqrtf(fmaxf(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2], 1e-30f));
-        u1[0] *= n; u1[1] *= n; u1[2] *= n;
+        // Gram-Schmidt against u0, twice (once leaves |u0 . u1| at u / |what is left of u1|: a second column that is rounding
+        // noise of a rank-1 covariance gave |R R^T - I| up to 385 u); noise all but parallel to u0 is no direction at all
+        for (int pass = 0; pass < 2; ++pass) {
+            float d = u1[0] * u0[0] + u1[1] * u0[1] + u1[2] * u0[2];
+            float v[3] = {u1[0] - d * u0[0], u1[1] - d * u0[1], u1[2] - d * u0[2]};
+            float n2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+            if (!have || !(n2 > 1e-6f)) {  // any unit vector orthogonal to u0: start from the axis u0 has least of
+                const int m = fabsf(u0[0]) <= fabsf(u0[1]) ? (fabsf(u0[0]) <= fabsf(u0[2]) ? 0 : 2) : (fabsf(u0[1]) <= fabsf(u0[2]) ? 1 : 2);
+                d = u0[m];
+                v[0] = (m == 0 ? 1.f : 0.f) - d * u0[0]; v[1] = (m == 1 ? 1.f : 0.f) - d * u0[1]; v[2] = (m == 2 ? 1.f : 0.f) - d * u0[2];
+                n2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+                have = true;
+            }
+            n = rsqrtf(fmaxf(n2, 1e-30f));
+            u1[0] = v[0] * n; u1[1] = v[1] * n; u1[2] = v[2] * n;
+        }
     }
     u2[0] = u0[1] * u1[2] - u0[2] * u1[1];
     u2[1] = u0[2] * u1[0] - u0[0] * u1[2];
