@@ -625,6 +625,15 @@ blend_fwd_kernel(const BlendArgs B) {
     constexpr int CSB = 16 * CS;                  // bytes per coefficient block = unit of the list entries
     static_assert((SB + 1) * CSB <= 65536 && SB % U == 0 && RB % 32 == 0, "offsets must fit the 16-bit list entries");
     static_assert(BIAS ? CSB == 32 : true, "with a bias the list entries address the records (32-byte unit)");
+    // Those rows (BC) take a survivor's operands from a lane of the DPP row instead of from LDS: the 16 lanes of a row are one 4x4
+    // quarter (as in MF), a quarter's list is FETCHED 16 entries at a time -- lane l of the row holds entry j0 + l's 48-byte
+    // block -- and evaluation u of the chunk reads coefficient and channel operands from lane u of the row inside the consuming
+    // instruction (v_fmac_f32_dpp .. row_newbcast:u).  The reads that returned one block to all 16 lanes of a quarter (30 LDS-array
+    // cycles per two evaluations) become 14 cycles per 16 evaluations; the arithmetic per (pixel, survivor) and its order stay.
+    constexpr bool BC = !MF && CS == 3;
+    constexpr bool QM = MF || BC;                 // quarter-major lanes
+    constexpr int FW = BC ? 16 : U;               // list entries fetched at a time: the lists are padded to a multiple of it
+    static_assert(SB % FW == 0, "a padded list fits its SB entries");
     __shared__ TileLDS<CH, SB, !BIAS, 0, false, Rec<CH>::RQ, CS> L;
     __shared__ __attribute__((aligned(16))) unsigned int s_qlist[4][4][SB];  // [wave][quarter] survivor lists (32 e: coefficient-block byte offsets)
     __shared__ int s_done[4];
@@ -634,14 +643,14 @@ blend_fwd_kernel(const BlendArgs B) {
     const BlendArgs A = frame_args(B, frame);
     const int tx = tile % A.gx, ty = tile / A.gx;
     const int bx = tx * TILE + (w & 1) * 8, by = ty * TILE + (w >> 1) * 8;
-    // pixel of the lane inside the wave's 8x8 block: row-major, or (MF) quarter-major -- DPP row q = lanes 16 q .. 16 q + 15 = the
+    // pixel of the lane inside the wave's 8x8 block: row-major, or (QM) quarter-major -- DPP row q = lanes 16 q .. 16 q + 15 = the
     // 4x4 quarter q (x half = q & 1, y half = q >> 1), row-major inside it
-    const int lx = MF ? ((lane >> 4) & 1) * 4 + (lane & 3) : (lane & 7);
-    const int ly = MF ? (lane >> 5) * 4 + ((lane >> 2) & 3) : (lane >> 3);
+    const int lx = QM ? ((lane >> 4) & 1) * 4 + (lane & 3) : (lane & 7);
+    const int ly = QM ? (lane >> 5) * 4 + ((lane >> 2) & 3) : (lane >> 3);
     const int px = bx + lx, py = by + ly;
     const float pxf = (float)px, pyf = (float)py;
     // pixel relative to the tile centre and its monomials (exact in f32)
-    const float x = (float)((w & 1) * 8 + lx) - 7.5f, y = (float)((w >> 1) * 8 + ly) - 7.5f;
+    float x = (float)((w & 1) * 8 + lx) - 7.5f, y = (float)((w >> 1) * 8 + ly) - 7.5f;
     const float xx = x * x, xy = x * y, yy = y * y;
     const int cn = EXACT ? CH : A.cn;
     f32x4 D[MF ? 4 : 1][MF ? NCB : 1];   // MF: D[g][c][j] = sum of pixel 4 (lane >> 4) + j of quarter g, channel 16 c + (lane & 15)
@@ -675,7 +684,7 @@ blend_fwd_kernel(const BlendArgs B) {
         unsigned qd;
         {
             const unsigned long long dm = __ballot(T < 0.f);
-            if (MF) {   // DPP row q = quarter q
+            if (QM) {   // DPP row q = quarter q
                 qd = ((dm & 0xffffull) == 0xffffull ? 1u : 0u) | (((dm >> 16) & 0xffffull) == 0xffffull ? 2u : 0u) |
                      (((dm >> 32) & 0xffffull) == 0xffffull ? 4u : 0u) | ((dm >> 48) == 0xffffull ? 8u : 0u);
             } else {    // lane = 8 y + x: quarter (x >> 2) + 2 (y >> 2)
@@ -719,124 +728,190 @@ blend_fwd_kernel(const BlendArgs B) {
                 }
             }
             const int cnt = imax_(imax_(cq[0], cq[1]), imax_(cq[2], cq[3]));
-            const int cntU = (cnt + U - 1) / U * U;
+            const int cntU = (cnt + U - 1) / U * U;       // evaluations of the wave
+            const int cntF = (cnt + FW - 1) / FW * FW;    // entries fetched (BC: past cntU they are read and never evaluated)
 #pragma unroll
             for (int q = 0; q < 4; ++q)
 #pragma unroll 1
-                for (int i = cq[q] + lane; i < cntU; i += WAVE) s_qlist[w][q][i] = (unsigned)(SB * CSB);  // log2(o) = -inf -> alpha 0
+                for (int i = cq[q] + lane; i < cntF; i += WAVE) s_qlist[w][q][i] = (unsigned)(SB * CSB);  // log2(o) = -inf -> alpha 0
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            const int myq = MF ? (lane >> 4) : ((lane >> 2) & 1) + 2 * ((lane >> 5) & 1);  // quarter of this lane's pixel
+            const int myq = QM ? (lane >> 4) : ((lane >> 2) & 1) + 2 * ((lane >> 5) & 1);  // quarter of this lane's pixel
             const unsigned int *mylist = s_qlist[w][myq];
             const char *recb = reinterpret_cast<const char *>(L.rec);
             const char *cfb = reinterpret_cast<const char *>(L.coef);
-            int lastoff = -1;  // block offset of the last splat applied in this super-batch
-            // MF: byte offsets of this lane's column (channel) in the B operands of block 0 and, relative to it, of block 1
-            const int chan_off = 4 * (lane & 15);
-            const int chan_off1 = (16 + (lane & 15) < CH) ? 64 : -chan_off;
-            for (int j0 = 0; j0 < cntU; j0 += U) {
-                unsigned off[U];
-                static_assert(U == 2 || U == 4, "a trip reads its list entries as one 8- or 16-byte word");
-#pragma unroll
-                for (int u = 0; u < U; ++u) off[u] = mylist[j0 + u];  // adjacent 32-bit entries: one ds_read_b64 / b128 per trip, no unpacking
-                float bq[MF ? 4 : 1][MF ? NCB : 1];   // MF: B operands, requested before the trip's arithmetic (two LDS round trips)
-                if constexpr (MF) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const unsigned og = s_qlist[w][g][j0 + (lane >> 4)];   // quarter g's survivor of trip lane >> 4
-                        const char *fb = recb + og * RM + 32 + chan_off;
-                        // (block 1 of a 20 / 24-channel row: columns past the row read channel 0 again -- finite, never stored)
-#pragma unroll
-                        for (int c = 0; c < NCB; ++c) bq[g][c] = *reinterpret_cast<const float *>(fb + (c == 0 ? 0 : chan_off1));
-                    }
-                }
-                float4 g0[U], g1[U];
-                float alpha[U];  // 0 where the splat does not touch the pixel
-                bool aok[U];     // alpha[u] != 0 (a wave mask in scalar registers: the compare that zeroed alpha[u])
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const char *src = BIAS ? recb + off[u] * RM : cfb + off[u];
-                    g0[u] = *reinterpret_cast<const float4 *>(src);
-                    g1[u] = *reinterpret_cast<const float4 *>(src + 16);
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    if (BIAS) {
-                        const float q = neg_power_factored(g0[u].x - pxf, g0[u].y - pyf, g0[u].z, g0[u].w, g1[u].x);
-                        const float a = fminf(0.99f, __builtin_fmaf(g1[u].y, exp_neg(q), g1[u].z));
-                        aok[u] = !(q < 0.f) && !(a < (1.0f / 255.0f));
-                        alpha[u] = aok[u] ? a : 0.f;
-                    } else {
-                        const float pw = power_poly(g0[u], g1[u], x, y, xx, xy, yy);
+            if constexpr (BC) {
+                // list position of the last splat applied in this super-batch, relative to the chunk in hand (the chunk's u is an
+                // inline constant of the select; one subtraction per chunk keeps it relative); far below zero: none yet
+                int lastrel = -(1 << 20);
+                int j0 = 0;
+                // the monomials are made here, once per super-batch, from an x and y the compiler cannot see through: three registers
+                // less that live through the staging and the cull, where this kernel's register pressure peaks
+                asm volatile("" : "+v"(x), "+v"(y));
+                const float xx = x * x, xy = x * y, yy = y * y;
+                const unsigned int *mine = mylist + (lane & 15);
+                for (; j0 < cntU; j0 += 16, lastrel -= 16) {
+                    // lane l of the row: entry j0 + l of its quarter's list and that survivor's block (16 different survivors per row)
+                    const unsigned off = mine[j0];
+                    const float4 c0 = *reinterpret_cast<const float4 *>(cfb + off);        // q0 qx qy qxx
+                    const float4 c1 = *reinterpret_cast<const float4 *>(cfb + off + 16);   // qxy qyy o id
+                    const float4 c2 = *reinterpret_cast<const float4 *>(cfb + off + 32);   // channels 0 .. 3
+                    const float fc[4] = {c2.x, c2.y, c2.z, c2.w};
+                    const int rem = cntU - j0;   // evaluations left (even): the wave leaves the chunk after them
+                    // evaluation u: the survivor in lane u of the row.  Same operations in the same order as the lane = pixel loop
+                    // below -- fma(qx, x, q0) and fma(x, qx, q0) are the same bits.  EXEC is all ones here (uniform flow, branch-free
+                    // compositing), so every lane a row_newbcast names is a live one.
+                    auto eval = [&](auto uc) {
+                        constexpr int u = decltype(uc)::value;
+                        float pw;
+                        // (s_nop 1: the two wait states between a VALU write of a register and a DPP read of it, should the
+                        // compiler have copied a coefficient just in front)
+                        asm("s_nop 1\n\t"
+                            "v_mov_b32_dpp %0, %1 row_newbcast:%c12 row_mask:0xf bank_mask:0xf\n\t"
+                            "v_fmac_f32_dpp %0, %2, %7 row_newbcast:%c12 row_mask:0xf bank_mask:0xf\n\t"
+                            "v_fmac_f32_dpp %0, %3, %8 row_newbcast:%c12 row_mask:0xf bank_mask:0xf\n\t"
+                            "v_fmac_f32_dpp %0, %4, %9 row_newbcast:%c12 row_mask:0xf bank_mask:0xf\n\t"
+                            "v_fmac_f32_dpp %0, %5, %10 row_newbcast:%c12 row_mask:0xf bank_mask:0xf\n\t"
+                            "v_fmac_f32_dpp %0, %6, %11 row_newbcast:%c12 row_mask:0xf bank_mask:0xf"
+                            : "=&v"(pw)
+                            : "v"(c0.x), "v"(c0.y), "v"(c0.z), "v"(c0.w), "v"(c1.x), "v"(c1.y), "v"(x), "v"(y), "v"(xx), "v"(xy), "v"(yy), "n"(u));
                         bool pw_ok;
                         const float a = fminf(0.99f, exp2_guard(pw, pw_ok));
-                        aok[u] = pw_ok && !(a < (1.0f / 255.0f));
-                        alpha[u] = aok[u] ? a : 0.f;
-                    }
+                        const bool aok = pw_ok && !(a < (1.0f / 255.0f));
+                        const float alpha = aok ? a : 0.f;
+                        const float nT = T * (1.f - alpha);
+                        const bool sat = nT < 0.0001f;
+                        const float wgt = sat ? 0.f : alpha * T;
+                        const bool app = aok && !sat;
+#pragma unroll
+                        for (int k = 0; k < CH; ++k)   // F[k] += f[k] * wgt (the DPP operand is a register no VALU instruction writes)
+                            asm("v_fmac_f32_dpp %0, %1, %2 row_newbcast:%c3 row_mask:0xf bank_mask:0xf" : "+v"(F[k]) : "v"(fc[k]), "v"(wgt), "n"(u));
+                        T = sat ? -fabsf(T) : nT;
+                        lastrel = app ? u : lastrel;
+                        if (ENH) {
+                            const int id = __builtin_amdgcn_update_dpp(0, __float_as_int(c1.w), 0x150 + u, 0xf, 0xf, true);   // row_newbcast:u
+                            if (app && (A.trunc || layer < A.K)) {
+                                const size_t pix = (size_t)A.W * (size_t)py + px;
+                                A.gs_idx[pix * A.K + layer] = id;
+                                layer++;
+                                if (A.trunc && layer >= A.K) T = -T;
+                            }
+                        }
+                    };
+#define FWD_EVAL2(u) eval(std::integral_constant<int, u>{}); eval(std::integral_constant<int, u + 1>{});
+#define FWD_NEXT2(u) if (rem <= u) break; FWD_EVAL2(u)
+                    FWD_EVAL2(0) FWD_NEXT2(2) FWD_NEXT2(4) FWD_NEXT2(6) FWD_NEXT2(8) FWD_NEXT2(10) FWD_NEXT2(12) FWD_NEXT2(14)
+#undef FWD_NEXT2
+#undef FWD_EVAL2
                 }
-                // Branch-free compositing.  A finished pixel carries its final T NEGATED: T (1 - alpha) < 0.0001 holds for it
-                // again ("saturated"), so nothing applies and no `done` predicate is kept; alpha = 0 (splat skipped on this
-                // pixel) multiplies T by 1 and adds f * 0: the pixel's values do not change by a bit.
-                float wq[MF ? U : 1];   // MF: the trip's weights, then (transposed) the quarters' A operands
+                const int lastpos = j0 + lastrel;   // (both exits leave lastrel relative to j0)
+                const int lastoff = (int)mine[imax_(lastpos, 0) - (lane & 15)];
+                last = lastpos >= 0 ? base + lastoff / CSB + 1 : last;
+            } else {
+                int lastoff = -1;  // block offset of the last splat applied in this super-batch
+                // MF: byte offsets of this lane's column (channel) in the B operands of block 0 and, relative to it, of block 1
+                const int chan_off = 4 * (lane & 15);
+                const int chan_off1 = (16 + (lane & 15) < CH) ? 64 : -chan_off;
+                for (int j0 = 0; j0 < cntU; j0 += U) {
+                    unsigned off[U];
+                    static_assert(U == 2 || U == 4, "a trip reads its list entries as one 8- or 16-byte word");
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    float f[MF ? 1 : CH];
-                    if (!MF) {
-                        // (CS == 3: the address is ready with the list entry -- without this tie to alpha[u] the scheduler requests
-                        // the channels of all U survivors up front and the twelve registers they hold spill elsewhere)
-                        if (CS == 3) asm volatile("" : "+v"(off[u]) : "v"(alpha[u]));
-                        const float4 *fq = CS == 3 ? reinterpret_cast<const float4 *>(cfb + off[u] + 32)             // behind the coefficients
-                                                   : reinterpret_cast<const float4 *>(recb + off[u] * RM + 32);  // 16-byte chunks of the record
+                    for (int u = 0; u < U; ++u) off[u] = mylist[j0 + u];  // adjacent 32-bit entries: one ds_read_b64 / b128 per trip, no unpacking
+                    float bq[MF ? 4 : 1][MF ? NCB : 1];   // MF: B operands, requested before the trip's arithmetic (two LDS round trips)
+                    if constexpr (MF) {
 #pragma unroll
-                        for (int k = 0; k < CH; k += 4) {
-                            const float4 v = fq[k / 4];
-                            if (k + 0 < CH) f[k + 0] = v.x;
-                            if (k + 1 < CH) f[k + 1] = v.y;
-                            if (k + 2 < CH) f[k + 2] = v.z;
-                            if (k + 3 < CH) f[k + 3] = v.w;
+                        for (int g = 0; g < 4; ++g) {
+                            const unsigned og = s_qlist[w][g][j0 + (lane >> 4)];   // quarter g's survivor of trip lane >> 4
+                            const char *fb = recb + og * RM + 32 + chan_off;
+                            // (block 1 of a 20 / 24-channel row: columns past the row read channel 0 again -- finite, never stored)
+#pragma unroll
+                            for (int c = 0; c < NCB; ++c) bq[g][c] = *reinterpret_cast<const float *>(fb + (c == 0 ? 0 : chan_off1));
                         }
                     }
-                    const float nT = T * (1.f - alpha[u]);
-                    const bool sat = nT < 0.0001f;   // reference: the splat that would take T below 1e-4 ends the pixel, unapplied
-                    const float wgt = sat ? 0.f : alpha[u] * T;
-                    // applied: alpha >= 1/255 and not saturating -- then T (1 - alpha) >= 1e-4, so T > 0 and alpha T > 0: the
-                    // same predicate as wgt > 0, from the two masks already in scalar registers (no third compare)
-                    // (narrow rows; the wide kernels keep the compare: their scalar unit is the busier one)
-                    const bool app = CH <= 8 ? (aok[u] && !sat) : wgt > 0.f;
-                    if (MF) {
-                        wq[u] = wgt;
-                    } else {
+                    float4 g0[U], g1[U];
+                    float alpha[U];  // 0 where the splat does not touch the pixel
+                    bool aok[U];     // alpha[u] != 0 (a wave mask in scalar registers: the compare that zeroed alpha[u])
 #pragma unroll
-                        for (int k = 0; k < CH; ++k) F[k] += f[k] * wgt;
+                    for (int u = 0; u < U; ++u) {
+                        const char *src = BIAS ? recb + off[u] * RM : cfb + off[u];
+                        g0[u] = *reinterpret_cast<const float4 *>(src);
+                        g1[u] = *reinterpret_cast<const float4 *>(src + 16);
                     }
-                    T = sat ? -fabsf(T) : nT;
-                    lastoff = app ? (int)off[u] : lastoff;
-                    if (ENH) {
-                        if (app && (A.trunc || layer < A.K)) {
-                            // (staging the ids in LDS and writing the tile's rows coalesced at the end was slower:
-                            // 23-channel row, K = 20: 179 vs 161 us per frame)
-                            const size_t pix = (size_t)A.W * (size_t)py + px;
-                            A.gs_idx[pix * A.K + layer] = __float_as_int(g1[u].w);
-                            layer++;
-                            if (A.trunc && layer >= A.K) T = -T;
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        if (BIAS) {
+                            const float q = neg_power_factored(g0[u].x - pxf, g0[u].y - pyf, g0[u].z, g0[u].w, g1[u].x);
+                            const float a = fminf(0.99f, __builtin_fmaf(g1[u].y, exp_neg(q), g1[u].z));
+                            aok[u] = !(q < 0.f) && !(a < (1.0f / 255.0f));
+                            alpha[u] = aok[u] ? a : 0.f;
+                        } else {
+                            const float pw = power_poly(g0[u], g1[u], x, y, xx, xy, yy);
+                            bool pw_ok;
+                            const float a = fminf(0.99f, exp2_guard(pw, pw_ok));
+                            aok[u] = pw_ok && !(a < (1.0f / 255.0f));
+                            alpha[u] = aok[u] ? a : 0.f;
                         }
                     }
-                }
-                if constexpr (MF) {
-                    // rows <-> registers: wq[g] becomes (w_0 | w_1 | w_2 | w_3)[row g] = quarter g's A operand
-                    typedef unsigned u32x2_f __attribute__((ext_vector_type(2)));
-                    const u32x2_f s02 = __builtin_amdgcn_permlane32_swap(__float_as_uint(wq[0]), __float_as_uint(wq[2]), false, false);
-                    const u32x2_f s13 = __builtin_amdgcn_permlane32_swap(__float_as_uint(wq[1]), __float_as_uint(wq[3]), false, false);
-                    const u32x2_f a01 = __builtin_amdgcn_permlane16_swap(s02[0], s13[0], false, false);
-                    const u32x2_f a23 = __builtin_amdgcn_permlane16_swap(s02[1], s13[1], false, false);
-                    const float Aq[4] = {__uint_as_float(a01[0]), __uint_as_float(a01[1]), __uint_as_float(a23[0]), __uint_as_float(a23[1])};
+                    // Branch-free compositing.  A finished pixel carries its final T NEGATED: T (1 - alpha) < 0.0001 holds for it
+                    // again ("saturated"), so nothing applies and no `done` predicate is kept; alpha = 0 (splat skipped on this
+                    // pixel) multiplies T by 1 and adds f * 0: the pixel's values do not change by a bit.
+                    float wq[MF ? U : 1];   // MF: the trip's weights, then (transposed) the quarters' A operands
 #pragma unroll
-                    for (int g = 0; g < 4; ++g)
+                    for (int u = 0; u < U; ++u) {
+                        float f[MF ? 1 : CH];
+                        if (!MF) {
+                            const float4 *fq = reinterpret_cast<const float4 *>(recb + off[u] * RM + 32);  // 16-byte chunks of the record
 #pragma unroll
-                        for (int c = 0; c < NCB; ++c) D[g][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(Aq[g], bq[g][c], D[g][c], 0, 0, 0);
+                            for (int k = 0; k < CH; k += 4) {
+                                const float4 v = fq[k / 4];
+                                if (k + 0 < CH) f[k + 0] = v.x;
+                                if (k + 1 < CH) f[k + 1] = v.y;
+                                if (k + 2 < CH) f[k + 2] = v.z;
+                                if (k + 3 < CH) f[k + 3] = v.w;
+                            }
+                        }
+                        const float nT = T * (1.f - alpha[u]);
+                        const bool sat = nT < 0.0001f;   // reference: the splat that would take T below 1e-4 ends the pixel, unapplied
+                        const float wgt = sat ? 0.f : alpha[u] * T;
+                        // applied: alpha >= 1/255 and not saturating -- then T (1 - alpha) >= 1e-4, so T > 0 and alpha T > 0: the
+                        // same predicate as wgt > 0, from the two masks already in scalar registers (no third compare)
+                        // (narrow rows; the wide kernels keep the compare: their scalar unit is the busier one)
+                        const bool app = CH <= 8 ? (aok[u] && !sat) : wgt > 0.f;
+                        if (MF) {
+                            wq[u] = wgt;
+                        } else {
+#pragma unroll
+                            for (int k = 0; k < CH; ++k) F[k] += f[k] * wgt;
+                        }
+                        T = sat ? -fabsf(T) : nT;
+                        lastoff = app ? (int)off[u] : lastoff;
+                        if (ENH) {
+                            if (app && (A.trunc || layer < A.K)) {
+                                // (staging the ids in LDS and writing the tile's rows coalesced at the end was slower:
+                                // 23-channel row, K = 20: 179 vs 161 us per frame)
+                                const size_t pix = (size_t)A.W * (size_t)py + px;
+                                A.gs_idx[pix * A.K + layer] = __float_as_int(g1[u].w);
+                                layer++;
+                                if (A.trunc && layer >= A.K) T = -T;
+                            }
+                        }
+                    }
+                    if constexpr (MF) {
+                        // rows <-> registers: wq[g] becomes (w_0 | w_1 | w_2 | w_3)[row g] = quarter g's A operand
+                        typedef unsigned u32x2_f __attribute__((ext_vector_type(2)));
+                        const u32x2_f s02 = __builtin_amdgcn_permlane32_swap(__float_as_uint(wq[0]), __float_as_uint(wq[2]), false, false);
+                        const u32x2_f s13 = __builtin_amdgcn_permlane32_swap(__float_as_uint(wq[1]), __float_as_uint(wq[3]), false, false);
+                        const u32x2_f a01 = __builtin_amdgcn_permlane16_swap(s02[0], s13[0], false, false);
+                        const u32x2_f a23 = __builtin_amdgcn_permlane16_swap(s02[1], s13[1], false, false);
+                        const float Aq[4] = {__uint_as_float(a01[0]), __uint_as_float(a01[1]), __uint_as_float(a23[0]), __uint_as_float(a23[1])};
+#pragma unroll
+                        for (int g = 0; g < 4; ++g)
+#pragma unroll
+                            for (int c = 0; c < NCB; ++c) D[g][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(Aq[g], bq[g][c], D[g][c], 0, 0, 0);
+                    }
                 }
+                last = lastoff >= 0 ? base + lastoff / CSB + 1 : last;
             }
-            last = lastoff >= 0 ? base + lastoff / CSB + 1 : last;
         }
         __syncthreads();
     }
@@ -1797,6 +1872,28 @@ blend_bwd_mfma_kernel(const BlendArgs B) {
 // everywhere at 64 rows, 138 -> 166 us per frame; 128 rows do not fit four workgroups per CU.)
 // Same arithmetic as blend_bwd_mfma_kernel per (pixel, splat): exponent chain, guards, scans.  Narrow rows; ABS: with the |d uv|
 // sums of the abs taps (two more products per step for conic (centre - pixel), as in blend_bwd_sets_quarter_kernel).
+// acc += (src of lane n of the lane's own 16-lane row) * w as ONE instruction, and a row's lane-n value: the operand comes out
+// of the DPP row inside the instruction, no LDS read and no copy.  n is a constant once the callers' loops are unrolled (the
+// DPP control is an immediate).  src must not be the result of a VALU instruction just in front (two wait states): the callers
+// pass registers that are written once, before their loops.  EXEC all ones in the callers.
+#define ROW_LANES(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
+__device__ __forceinline__ void fmac_row_lane(int n, float &acc, float src, float w) {
+    switch (n) {
+#define ROW_CASE(N) case N: asm("v_fmac_f32_dpp %0, %1, %2 row_newbcast:" #N " row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(w)); break;
+        ROW_LANES(ROW_CASE)
+#undef ROW_CASE
+    }
+}
+__device__ __forceinline__ int row_lane(int n, int v) {
+    switch (n) {
+#define ROW_CASE(N) case N: return __builtin_amdgcn_update_dpp(0, v, 0x150 + N, 0xf, 0xf, true);
+        ROW_LANES(ROW_CASE)
+#undef ROW_CASE
+    }
+    return v;
+}
+#undef ROW_LANES
+
 template <int CH, bool ABS = false>
 struct QuarterCfg {
     static_assert(CH <= 3 && Rec<CH>::RQ == 4 && Rec<CH>::CULL >= 11, "floats 11-15 of the record (cull parameters) are free for the coefficients");
@@ -1921,6 +2018,16 @@ blend_bwd_quarter_kernel(const BlendArgs B) {
         return;
     }
     float *pixrow = s_pix[w] + kk * KS;            // own pixel of step (G, i): pixrow + G * GS + i * PW
+    // dL_dout and ncontrib never change: lane (kk, nl) keeps those of pixel (quarter nl >> 2, row kk, column nl & 3) for the
+    // kernel's lifetime, and step (G, i) takes its pixel's from lane 4 G + i of the lane's own DPP row inside the consuming
+    // instruction (row_newbcast) -- the LDS pixel row is read for the replay state [T_state R_state] alone
+    float gpix[3];
+    int lastpix;
+    {
+        const float *r = s_pix[w] + (nl >> 2) * GS + kk * KS + (nl & 3) * PW;
+        gpix[0] = r[0]; gpix[1] = r[1]; gpix[2] = r[2];
+        lastpix = __float_as_int(r[5]);
+    }
     const float *pixcol = s_pix[w] + pixoff(nl);   // pixel nl of quarter G: pixcol + G * GS
     const float *momrow = s_mom + 8 * kk + (nl & 7);
     const int kch = kk < CH ? kk : 4;              // K index of the cg product (slot 4 of a pixel row is zero)
@@ -2060,15 +2167,13 @@ blend_bwd_quarter_kernel(const BlendArgs B) {
                     pw = __builtin_amdgcn_mfma_f32_16x16x4f32(phi2[G], bq2, pw, 0, 0, 0);
                     cgv = __builtin_amdgcn_mfma_f32_16x16x4f32(pixcol[G * GS + kch], bf, cgv, 0, 0, 0);
                     float cg[4], araw[4], a[4], r1a[4], rp[4], Ts4[4], Rs4[4];
-                    float4 gq[4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        gq[i] = *reinterpret_cast<const float4 *>(pixrow + G * GS + i * PW);
-                        const float4 stv = *reinterpret_cast<const float4 *>(pixrow + G * GS + i * PW + 4);
+                        const float2 stv = *reinterpret_cast<const float2 *>(pixrow + G * GS + i * PW + 6);
                         cg[i] = cgv[i];
-                        const int last = __float_as_int(stv.y);
-                        Ts4[i] = stv.z;
-                        Rs4[i] = stv.w;
+                        const int last = row_lane(4 * G + i, lastpix);
+                        Ts4[i] = stv.x;
+                        Rs4[i] = stv.y;
                         bool pw_ok;
                         araw[i] = exp2_guard(pw[i], pw_ok);
                         const bool ok = (qn < last) && pw_ok && !(araw[i] < (1.0f / 255.0f));
@@ -2103,9 +2208,9 @@ blend_bwd_quarter_kernel(const BlendArgs B) {
                             s_ax += fabsf(dLp * lx4[i]);
                             s_ay += fabsf(dLp * ly4[i]);
                         }
-                        dfv[0] = __builtin_fmaf(gq[i].x, wgt[i], dfv[0]);
-                        if (CH > 1) dfv[1 % CH] = __builtin_fmaf(gq[i].y, wgt[i], dfv[1 % CH]);
-                        if (CH > 2) dfv[2 % CH] = __builtin_fmaf(gq[i].z, wgt[i], dfv[2 % CH]);
+#pragma unroll
+                        for (int c = 0; c < CH; ++c)   // dfv[c] = fma(g_c of the step's pixel, wgt[i], dfv[c]); gpix is written once, before the loops
+                            fmac_row_lane(4 * G + i, dfv[c], gpix[c], wgt[i]);
                     }
                     // ---- step epilogue: raw sums into the survivor's row (this wave's quarters run one after the other: plain
                     //      read-add-write; lane group kk owns floats 4 kk .. 4 kk + 3 of the row)

@@ -1,6 +1,17 @@
 """rocprofv3 --pmc counter_collection CSVs (several passes) of tools/blend_bench.py -> one JSON with per-launch counters of
 the two compositing kernels and the utilisation figures derived from them.
-   python tools/pmc_blend_counters.py <out.json> <pass dir> [<pass dir> ...]"""
+   python tools/pmc_blend_counters.py <out.json> <pass dir> [<pass dir> ...]
+
+Which of `derived` says how busy a unit is:
+  * lds_busy_frac   = SQ_LDS_IDX_ACTIVE / (CUs x duration): cycles the CU's one LDS array worked, of the kernel's cycles -- a
+                      pipe utilisation; lds_conflict_frac = SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE, the share of those cycles
+                      spent on bank conflicts;
+  * valu_issue_frac = 2 x SQ_INSTS_VALU / (SIMDs x duration): a wave64 VALU instruction occupies its SIMD's issue for two
+                      cycles -- the VALU's share of the issue slots, at most 1;
+  * mfma_busy_frac  = SQ_VALU_MFMA_BUSY_CYCLES / (SIMDs x duration);
+  * valu_busy_frac is NOT one: SQ_ACTIVE_INST_VALU is the time waves spend with a VALU instruction active, summed over the
+    waves of a SIMD, so with several waves per SIMD it exceeds 1 (1.14 for the narrow forward at six waves).  It says that
+    waves are mostly inside VALU instructions, not that the VALU is the unit that limits the kernel."""
 import csv
 import glob
 import json
@@ -39,7 +50,7 @@ res.update({"source": os.environ.get("PMC_SOURCE", "rocprofv3 --pmc, three passe
                  "XCDs; SQ_ACTIVE_INST_* / SQ_WAIT_* / SQ_WAVE_CYCLES in quad-cycles (guides/MI355X_MICROARCH.md)"),
        "config": os.environ.get("PMC_CONFIG"),
        "kernels": {}})
-SIMDS, WAVE_SLOTS, XCDS = 1024, 256 * 16, 8
+SIMDS, CUS, WAVE_SLOTS, XCDS = 1024, 256, 256 * 16, 8
 for k in KERNELS:
     c = {n: round(v / cnt, 1) for (kk, n), (v, cnt) in sorted(acc.items()) if kk == k}
     if not c:
@@ -48,7 +59,13 @@ for k in KERNELS:
     d = {}
     if cyc:
         if "SQ_ACTIVE_INST_VALU" in c:
-            d["valu_busy_frac"] = round(4.0 * c["SQ_ACTIVE_INST_VALU"] / (SIMDS * cyc), 3)   # SIMD-cycles issuing VALU / all SIMD-cycles
+            d["valu_busy_frac"] = round(4.0 * c["SQ_ACTIVE_INST_VALU"] / (SIMDS * cyc), 3)   # wave-summed active time: can exceed 1 (docstring)
+        if "SQ_INSTS_VALU" in c:
+            d["valu_issue_frac"] = round(2.0 * c["SQ_INSTS_VALU"] / (SIMDS * cyc), 3)
+        if "SQ_LDS_IDX_ACTIVE" in c:
+            d["lds_busy_frac"] = round(c["SQ_LDS_IDX_ACTIVE"] / (CUS * cyc), 3)
+            if "SQ_LDS_BANK_CONFLICT" in c and c["SQ_LDS_IDX_ACTIVE"]:
+                d["lds_conflict_frac"] = round(c["SQ_LDS_BANK_CONFLICT"] / c["SQ_LDS_IDX_ACTIVE"], 3)
         if "SQ_VALU_MFMA_BUSY_CYCLES" in c:
             d["mfma_busy_frac"] = round(c["SQ_VALU_MFMA_BUSY_CYCLES"] / (SIMDS * cyc), 3)
         if "SQ_WAVE_CYCLES" in c:
