@@ -39,7 +39,8 @@ def assert_grad(a, b, what, tol=GRAD_RTOL, atol_frac=1e-4, budget=1e-4, outlier=
     mx = max(np.abs(b).max(), 1e-30)
     err = np.abs(a - b)
     bad = err > tol * np.abs(b) + atol_frac * mx
-    allowed = max(int(np.ceil(budget * a.size)), 2)   # small tensors: two elements (one pixel on a threshold touches a few splats)
+    # small tensors: two elements (one pixel on a threshold touches a few splats); budget 0: decision-free operators, none
+    allowed = max(int(np.ceil(budget * a.size)), 2) if budget > 0 else 0
     assert bad.sum() <= allowed, (f"{what}: {int(bad.sum())} of {a.size} elements off by more than rtol {tol:g} + "
                                   f"{atol_frac:g} * max (worst {err.max() / mx:.3e} of max)")
     assert err.max() / mx < outlier * tol, f"{what}: outlier {err.max() / mx:.3e} of the tensor maximum (bound {outlier:g} x {tol:g})"
@@ -62,6 +63,8 @@ def oracle_geometry(o, sc, f=0):
 @pytest.mark.parametrize("ortho", [False, True])
 @pytest.mark.parametrize("N,W,H", [(1, 16, 16), (777, 100, 60), (20000, 256, 256)])
 def test_pointwise_ops(gpu, oracle_mod, ortho, N, W, H):
+    """no outlier budget for the gradients: these operators hold no per-pixel decision, and per row they stay far inside
+    the stricter bars of tests/test_gpu_geometry_reference.py (profiles/geometry_reference_gpu.json)"""
     import dptr.gs as gs
     o = oracle_mod
     sc = make_scene(N, W, H, seed=7 + N, ortho=ortho)
@@ -87,9 +90,9 @@ def test_pointwise_ops(gpu, oracle_mod, ortho, N, W, H):
         dx_r = o.project_point_ortho_backward(sc.extr, W, H, d_r, g_uv, g_d)
     else:
         dx_r, di_r, de_r = o.project_point_backward(xyz, sc.intr, sc.extr, W, H, uv_r, d_r, g_uv, g_d)
-        assert_grad(t_intr.grad, di_r, "dL_dintr")
-        assert_grad(t_extr.grad[:3, :4], de_r, "dL_dextr")
-    assert_grad(t_xyz.grad, dx_r, "dL_dxyz", 1e-4)
+        assert_grad(t_intr.grad, di_r, "dL_dintr", budget=0.0)
+        assert_grad(t_extr.grad[:3, :4], de_r, "dL_dextr", budget=0.0)
+    assert_grad(t_xyz.grad, dx_r, "dL_dxyz", 1e-4, budget=0.0)
 
     # ---- cov3d
     vis = d_r.reshape(-1) != 0
@@ -100,7 +103,7 @@ def test_pointwise_ops(gpu, oracle_mod, ortho, N, W, H):
     g_c = rng.normal(size=(N, 6)).astype(np.float32)
     (cov * dev(g_c, gpu)).sum().backward()
     ds_r, dq_r = o.compute_cov3d_backward(sc.scale, sc.rotate, vis, g_c)
-    assert_grad(t_s.grad, ds_r, "dL_dscale", 1e-4); assert_grad(t_q.grad, dq_r, "dL_dquat", 1e-4)
+    assert_grad(t_s.grad, ds_r, "dL_dscale", 1e-4, budget=0.0); assert_grad(t_q.grad, dq_r, "dL_dquat", 1e-4, budget=0.0)
 
     # ---- ewa (same inputs as the oracle: its uv / cov3d)
     t_xyz2 = dev(xyz, gpu).requires_grad_(True); t_cov = dev(cov_r, gpu).requires_grad_(True)
@@ -118,11 +121,11 @@ def test_pointwise_ops(gpu, oracle_mod, ortho, N, W, H):
     (conic * dev(g_k, gpu)).sum().backward()
     dxe_r, dcov_r, dei_r, dee_r = o.ewa_project_backward(xyz, cov_r, sc.intr, sc.extr, rad_r, g_k, W, H, ortho=ortho)
     if same.all():
-        assert_grad(t_cov.grad, dcov_r, "dL_dcov3d", 5e-4)
+        assert_grad(t_cov.grad, dcov_r, "dL_dcov3d", 5e-4, budget=0.0)
         if not ortho:
-            assert_grad(t_xyz2.grad, dxe_r, "ewa dL_dxyz", 5e-4)
-            assert_grad(t_intr2.grad[:2], dei_r[:2], "ewa dL_dintr")
-            assert_grad(t_extr2.grad[:3, :4], dee_r, "ewa dL_dextr")
+            assert_grad(t_xyz2.grad, dxe_r, "ewa dL_dxyz", 5e-4, budget=0.0)
+            assert_grad(t_intr2.grad[:2], dei_r[:2], "ewa dL_dintr", budget=0.0)
+            assert_grad(t_extr2.grad[:3, :4], dee_r, "ewa dL_dextr", budget=0.0)
 
 
 @pytest.mark.parametrize("deg", [0, 1, 2, 3])
