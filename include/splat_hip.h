@@ -204,6 +204,8 @@ int splat_alpha_blending_backward(int P, int C, const float *uv, const float *co
 /* The same two calls with the forward's cull decisions handed to the backward (ABI 17): cull_flags[M] receives one word per
  * sorted entry (byte b = the 4x4 quarters of the tile's 8x8 block b the splat can reach); a backward that gets them walks one
  * survivor list per quarter instead of culling again (narrow rows without |taps|, rows of 16 .. 32 channels).  NULL: as above.
+ * The bits are a SUPERSET of the (entry, quarter) pairs that applied to a pixel in the forward (alpha >= 1/255 and not the
+ * splat that would saturate the pixel); for rows of at most four channels without a bias they are exactly those pairs.
  * Reference: the same operators, src/submodules/dptr/dptr/gs/src/alpha_blending.cu:16-110 (forward), :150-249 (backward). */
 int splat_alpha_blending_forward_flags(int P, int C, const float *uv, const float *conic, const float *opacity,
                                        const float *feature, const float *opacity_bias,
@@ -423,7 +425,10 @@ int splat_alpha_blending_backward_batch(int F, int P, int C, const int32_t *idx_
 /* cull_flags: one 32-bit word per sorted tile entry (frame stride = capacity), byte w != 0 = the forward kept the entry for
  * the tile's 8x8 block w.  The forward writes them when the pointer is given; the backward then reads them instead of repeating the
  * cull (the same decisions: both passes skip exactly the splats that cannot reach alpha >= 1/255 in a block, and the
- * blocks that were saturated).  NULL on either side: that pass culls for itself. */
+ * blocks that were saturated).  Bits 0 .. 3 of byte w are the block's 4x4 quarters: a superset of the (entry, quarter) pairs
+ * that applied to at least one pixel in the forward -- what its geometric cull could not exclude -- and for rows of at most
+ * four channels without a bias exactly those pairs, recorded by the forward's evaluation.  A consumer may rely on nothing else:
+ * a set bit has no geometric meaning of its own.  NULL on either side: that pass culls for itself. */
 /* Gaussian-side backward of a batch of static Gaussians + per-frame offsets under the orthographic camera: sums every
  * Gaussian's pair records over all frames and runs the preprocess backward (projection, EWA, cov3d: linear in the
  * summed dL_duv / dL_dconic because conic and Jacobian do not depend on the frame) once.  Replaces, per batch, F x

@@ -98,9 +98,14 @@ struct BlendArgs {
     int src_c0[SPLAT_MAX_SOURCES], src_cn[SPLAT_MAX_SOURCES];
     const float *src_f[SPLAT_MAX_SOURCES];
     long long src_fs[SPLAT_MAX_SOURCES];
-    // optional [F, cap] words, one per sorted tile entry: byte w != 0 = the forward's cull kept the entry for the tile's
-    // block w (the keep word of tile_cull).  The forward writes them, the strip-walk backward kernels read them instead
-    // of repeating the cull (13 % of their VALU instructions); NULL: every kernel culls for itself.
+    // optional [F, cap] words, one per sorted tile entry: byte w != 0 = the forward kept the entry for the tile's block w,
+    // bits 0 .. 3 of the byte = the block's 4x4 quarters.  The forward writes them, the strip-walk backward kernels read them
+    // instead of repeating the cull (13 % of their VALU instructions); NULL: every kernel culls for itself.
+    // Contract: a SUPERSET of the (entry, quarter) pairs that applied to at least one pixel in the forward (alpha >= 1/255, not
+    // saturating).  The generic and the matrix-core forward write the keep words of tile_cull (what the geometric cull could not
+    // exclude); the lane = pixel forward of rows of at most four channels without a bias writes EXACTLY the applied pairs, which
+    // its evaluation knows.  A pair that applied nowhere adds only zeros in the backward, so any superset gives the
+    // same gradients up to summation order; no consumer may read a geometric meaning into a set bit.
     unsigned int *cull_flags;
     // pair records inside a wider record: floats [rec_off, rec_off + ..) of records rec_stride floats apart (0: the kernel's
     // own stride).  The renderer's row in two passes -- the tap set through the narrow matrix-core kernel, depth + attributes
@@ -701,9 +706,10 @@ blend_fwd_kernel(const BlendArgs B) {
         st.load_ids(A, tid, range.x, pos, batch + 2);  // ids two ahead
         __syncthreads();
         if ((s_done[0] & s_done[1] & s_done[2] & s_done[3]) == 15) break;  // every pixel of the tile is saturated
-        // (the keep words also go to A.cull_flags: what the backward needs of this cull -- a saturated block keeps nothing)
+        // (the keep words also go to A.cull_flags: what the backward needs of this cull -- a saturated block keeps nothing.  BC
+        // publishes them after the evaluation instead, reduced to the (entry, quarter) pairs that applied: see the flush below)
         tile_cull<CH, SB, BIAS, true, !BIAS>(L, tid, nb, (float)(tx * TILE), (float)(ty * TILE), [&](int, int ww) -> unsigned { return 15u & ~(unsigned)s_done[ww]; },
-                                             A.cull_flags ? A.cull_flags + range.x + base : nullptr);
+                                             (!BC && A.cull_flags) ? A.cull_flags + range.x + base : nullptr);
         __syncthreads();
         if (!alld) {
             // one order-preserving survivor list per 4x4 quarter of the wave's block: the 16 lanes of a quarter walk
@@ -717,7 +723,10 @@ blend_fwd_kernel(const BlendArgs B) {
 #pragma unroll
             for (int r = 0; r < SB / WAVE; ++r) {
                 const int e = r * WAVE + lane;
-                const unsigned bits = (L.keep[e] >> (8 * w)) & 0xffu;
+                // BC: the wave takes its byte out of the keep word (nobody else reads it); the evaluation below sets the bits
+                // of the quarters on which the entry APPLIED, and the word goes to A.cull_flags behind the super-batch
+                const unsigned kw = BC ? atomicAnd(&L.keep[e], ~(0xffu << (8 * w))) : L.keep[e];
+                const unsigned bits = (kw >> (8 * w)) & 0xffu;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const bool keep = (bits >> q) & 1u;
@@ -741,16 +750,15 @@ blend_fwd_kernel(const BlendArgs B) {
             const char *recb = reinterpret_cast<const char *>(L.rec);
             const char *cfb = reinterpret_cast<const char *>(L.coef);
             if constexpr (BC) {
-                // list position of the last splat applied in this super-batch, relative to the chunk in hand (the chunk's u is an
-                // inline constant of the select; one subtraction per chunk keeps it relative); far below zero: none yet
-                int lastrel = -(1 << 20);
-                int j0 = 0;
+                // list position of the last splat applied in this super-batch; below zero: none yet
+                int lastpos = -1;
+                const bool publish = A.cull_flags != nullptr;
                 // the monomials are made here, once per super-batch, from an x and y the compiler cannot see through: three registers
                 // less that live through the staging and the cull, where this kernel's register pressure peaks
                 asm volatile("" : "+v"(x), "+v"(y));
                 const float xx = x * x, xy = x * y, yy = y * y;
                 const unsigned int *mine = mylist + (lane & 15);
-                for (; j0 < cntU; j0 += 16, lastrel -= 16) {
+                for (int j0 = 0; j0 < cntU; j0 += 16) {
                     // lane l of the row: entry j0 + l of its quarter's list and that survivor's block (16 different survivors per row)
                     const unsigned off = mine[j0];
                     const float4 c0 = *reinterpret_cast<const float4 *>(cfb + off);        // q0 qx qy qxx
@@ -758,6 +766,8 @@ blend_fwd_kernel(const BlendArgs B) {
                     const float4 c2 = *reinterpret_cast<const float4 *>(cfb + off + 32);   // channels 0 .. 3
                     const float fc[4] = {c2.x, c2.y, c2.z, c2.w};
                     const int rem = cntU - j0;   // evaluations left (even): the wave leaves the chunk after them
+                    // which evaluations of the chunk applied on this pixel: one bit shifted in per evaluation, acc = 2 acc + app
+                    unsigned acc = 0u;
                     // evaluation u: the survivor in lane u of the row.  Same operations in the same order as the lane = pixel loop
                     // below -- fma(qx, x, q0) and fma(x, qx, q0) are the same bits.  EXEC is all ones here (uniform flow, branch-free
                     // compositing), so every lane a row_newbcast names is a live one.
@@ -781,13 +791,15 @@ blend_fwd_kernel(const BlendArgs B) {
                         const float alpha = aok ? a : 0.f;
                         const float nT = T * (1.f - alpha);
                         const bool sat = nT < 0.0001f;
-                        const float wgt = sat ? 0.f : alpha * T;
                         const bool app = aok && !sat;
+                        // the weight alpha T of an applied splat, NEGATED, else + 0: its sign bit is `app`, and a funnel shift moves
+                        // that bit into acc (one instruction, where the select of the last applied u was)
+                        const float wneg = app ? -(alpha * T) : 0.f;
 #pragma unroll
-                        for (int k = 0; k < CH; ++k)   // F[k] += f[k] * wgt (the DPP operand is a register no VALU instruction writes)
-                            asm("v_fmac_f32_dpp %0, %1, %2 row_newbcast:%c3 row_mask:0xf bank_mask:0xf" : "+v"(F[k]) : "v"(fc[k]), "v"(wgt), "n"(u));
+                        for (int k = 0; k < CH; ++k)   // F[k] += (-f[k]) * wneg: the same product (the DPP operand is a register no VALU instruction writes)
+                            asm("v_fmac_f32_dpp %0, -%1, %2 row_newbcast:%c3 row_mask:0xf bank_mask:0xf" : "+v"(F[k]) : "v"(fc[k]), "v"(wneg), "n"(u));
                         T = sat ? -fabsf(T) : nT;
-                        lastrel = app ? u : lastrel;
+                        acc = __builtin_amdgcn_alignbit(acc, __float_as_uint(wneg), 31);   // 2 acc + app
                         if (ENH) {
                             const int id = __builtin_amdgcn_update_dpp(0, __float_as_int(c1.w), 0x150 + u, 0xf, 0xf, true);   // row_newbcast:u
                             if (app && (A.trunc || layer < A.K)) {
@@ -800,11 +812,31 @@ blend_fwd_kernel(const BlendArgs B) {
                     };
 #define FWD_EVAL2(u) eval(std::integral_constant<int, u>{}); eval(std::integral_constant<int, u + 1>{});
 #define FWD_NEXT2(u) if (rem <= u) break; FWD_EVAL2(u)
-                    FWD_EVAL2(0) FWD_NEXT2(2) FWD_NEXT2(4) FWD_NEXT2(6) FWD_NEXT2(8) FWD_NEXT2(10) FWD_NEXT2(12) FWD_NEXT2(14)
+                    do {
+                        FWD_EVAL2(0) FWD_NEXT2(2) FWD_NEXT2(4) FWD_NEXT2(6) FWD_NEXT2(8) FWD_NEXT2(10) FWD_NEXT2(12) FWD_NEXT2(14)
+                    } while (false);
 #undef FWD_NEXT2
 #undef FWD_EVAL2
+                    // evaluation u of the chunk -> bit 15 - u, however early the wave left it (a chunk cut short is the list's last)
+                    acc <<= 16 - imin_(rem, 16);
+                    lastpos = acc ? j0 + 15 - (int)__builtin_ctz(acc) : lastpos;
+                    if (publish) {
+                        // OR over the quarter's 16 pixels (rotations inside the DPP row), then the lane that fetched entry j0 + l
+                        // looks at evaluation l: an entry that applied on some pixel of the quarter gets the quarter's bit
+                        // (lane and bit position from the thread id again, behind a barrier for the optimiser: kept in registers
+                        // through the loop they are the two that do not fit the kernel's 80)
+                        unsigned t = (unsigned)tid;
+                        asm volatile("" : "+v"(t));
+                        const unsigned mybit = 1u << (((t >> 3) & 0x18u) | ((t >> 4) & 3u));   // bit 8 w + quarter
+                        unsigned red = acc;
+                        red |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)red, 0x121, 0xf, 0xf, false);   // row_ror:1
+                        red |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)red, 0x122, 0xf, 0xf, false);   // row_ror:2
+                        red |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)red, 0x124, 0xf, 0xf, false);   // row_ror:4
+                        red |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)red, 0x128, 0xf, 0xf, false);   // row_ror:8
+                        const unsigned ent = off / (unsigned)CSB;   // (the inert pad entry is SB: it never applies, and is kept out)
+                        if (((red << (t & 15u)) & 0x8000u) && ent < (unsigned)SB) atomicOr(&L.keep[ent], mybit);
+                    }
                 }
-                const int lastpos = j0 + lastrel;   // (both exits leave lastrel relative to j0)
                 const int lastoff = (int)mine[imax_(lastpos, 0) - (lane & 15)];
                 last = lastpos >= 0 ? base + lastoff / CSB + 1 : last;
             } else {
@@ -914,6 +946,10 @@ blend_fwd_kernel(const BlendArgs B) {
             }
         }
         __syncthreads();
+        // BC: the super-batch's words as the evaluation left them -- bit 8 w + q: the entry applied on a pixel of quarter q of
+        // block w.  Every evaluated super-batch passes here (the early exit above leaves before its own is culled), and the next
+        // cull rewrites L.keep only behind the next barrier.
+        if (BC && A.cull_flags && tid < nb) A.cull_flags[range.x + base + tid] = L.keep[tid];
     }
     if constexpr (MF) {
         // D -> the lane's own F[]: a quarter at a time through the wave's 16 x 36 floats of the (dead) staging area.  (Every
