@@ -1441,6 +1441,251 @@ __device__ __forceinline__ void row_shr1_add4(float (&R)[4], const float (&rs)[4
         : "v"(rs[0]), "v"(rs[1]), "v"(rs[2]), "v"(rs[3]), "v"(base[0]), "v"(base[1]), "v"(base[2]), "v"(base[3]));
 }
 
+// ------------------------------------------------------------------ building blocks of the strip-walk backward kernels
+// One definition of what blend_bwd_quarter_kernel, blend_bwd_sets_quarter_kernel and blend_bwd_wide_quarter_kernel share.  All
+// are __forceinline__.  LDS arrays are taken by REFERENCE to the array (not as pointers) and the survivor lists through an
+// accessor of the caller: the address arithmetic then folds as it does for the array indexed in place.  The block-level
+// kernels (blend_bwd_mfma_kernel, blend_bwd_sets_kernel) keep their own copies of the tables and of the flag load: with
+// the shared ones their register allocation changes.
+
+// Strip walk: step (G, i) of lane group kk handles pixel q = 16 G + 4 kk + i of the wave's 64 pixels; (qx, qy) is the pixel's
+// place in the wave's pixel set.  The wave owns four 4x4 quarters G = (sx, sy) a pitch of QP pixels apart -- QP = 4: the
+// quarters of ONE 8x8 block (pixel (4 sx + i, 4 sy + kk)), QP = 8: the same quarter of the tile's four blocks (pixel
+// (8 gx + i, 8 gy + kk)).
+template <int QP>
+struct QuarterWalk {
+    static constexpr float CEN = 0.5f * (float)(QP + 3);   // centre of the pixel set (3.5 / 5.5): origin of the raw moments
+    static __device__ __forceinline__ int qx(int q) { return QP * ((q >> 4) & 1) + (q & 3); }
+    static __device__ __forceinline__ int qy(int q) { return QP * (q >> 5) + ((q >> 2) & 3); }
+};
+
+// A operand of the power product, A[m = pixel nl of strip G][k = kk]: monomials 1 x y xx | xy yy 0 0 of the pixel's
+// position relative to the TILE centre ((ox, oy) = the pixel set's origin relative to it) -- with the coefficients of
+// power_coeffs() the two MFMAs of a step are the fma chain power_poly() runs in the forward kernel, bit for bit.
+// Every lane calls it (registers only).
+template <typename Walk>
+__device__ __forceinline__ void strip_phi(int nl, int kk, float ox, float oy, float (&phi1)[4], float (&phi2)[4]) {
+#pragma unroll
+    for (int Gs = 0; Gs < 4; ++Gs) {
+        const int q = 16 * Gs + nl;
+        const float x = (float)Walk::qx(q) + ox, y = (float)Walk::qy(q) + oy;
+        phi1[Gs] = kk == 0 ? 1.f : kk == 1 ? x : kk == 2 ? y : x * x;
+        phi2[Gs] = kk == 0 ? x * y : kk == 1 ? y * y : 0.f;
+    }
+}
+
+// A operand of the moment product of the three-set and wide kernels, s_mom[step][lane group][row & 7] (16 * 32 floats, one
+// table for the four waves: wave w fills steps 4 w .. 4 w + 3; rows 8-15 alias rows 0-7, their products are not used), of the
+// pixel in coordinates about the centre of the wave's pixel set; the combine moves a wave's sums to the tile centre.  Rows
+// 0-3 = 1 x y xx, 4-5 = xy yy.  (The narrow kernel fills its own: without abs taps its rows are 1 x y | xx xy yy.)  All 256
+// threads call it; the caller's __syncthreads() in front of the first step publishes the table.
+template <typename Walk>
+__device__ __forceinline__ void strip_moment_table(float (&s_mom)[16 * 32], int w, int nl, int kk) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int st = 4 * w + r, Gs = st >> 2, is = st & 3;
+        const int q = 16 * Gs + 4 * kk + is;
+        const float x = (float)Walk::qx(q) - Walk::CEN, y = (float)Walk::qy(q) - Walk::CEN;
+        float v = 0.f;
+        if (nl < 4) v = nl == 0 ? 1.f : nl == 1 ? x : nl == 2 ? y : x * x;
+        else if (nl < 6) v = nl == 4 ? x * y : y * y;
+        if (nl < 8) s_mom[32 * st + 8 * kk + nl] = v;
+    }
+}
+
+// The forward's cull word of this thread's entry of the super-batch whose first (deepest) entry sits at list position `topb`
+// of the tile (thread e: entry e; `first` = the tile's first position in the sorted arrays); zero past the front of the list
+// and for threads without an entry.  Callers load one super-batch ahead; cull_flags = BlendArgs::cull_flags, not null.
+template <int SB>
+__device__ __forceinline__ unsigned load_flags(const unsigned int *cull_flags, int tid, int first, int topb) {
+    const int q = topb - tid;
+    return (tid < SB && q >= 0) ? (unsigned)cull_flags[first + q] : 0u;
+}
+
+// Keep word of entry tid from the forward's cull word fl (byte G = block G, bit s = quarter s of the block): byte w = the
+// quarters wave w replays the entry for, zero where the wave's pixels all ended in front of it (top - tid >= s_wmax[w]) and
+// past the super-batch's nb entries.  TRANSPOSE false: wave w owns block w, byte w = the cull word's.  TRANSPOSE true: wave w'
+// owns quarter w' of every block -- byte w' bit G = byte G bit w' of the cull word.  Threads 0 .. SB - 1 write their word, all
+// 256 may call; the caller's __syncthreads() stands between this and build_quarter_lists.
+template <int SB, bool TRANSPOSE, int NKEEP>
+__device__ __forceinline__ void keep_from_quarter_flags(unsigned int (&s_keep)[NKEEP], const int (&s_wmax)[4], int tid, int nb, int top, unsigned fl) {
+    static_assert(NKEEP >= SB, "a keep word per staged entry");
+    if (tid < SB) {
+        unsigned kw = 0u;
+        if (tid < nb) {
+#pragma unroll
+            for (int ww = 0; ww < 4; ++ww) {
+                if (TRANSPOSE) {
+                    const unsigned t4 = (fl >> ww) & 0x01010101u;
+                    const unsigned nib = ((t4 * 0x01020408u) >> 24) & 0xfu;
+                    if (top - tid < s_wmax[ww]) kw |= nib << (8 * ww);
+                } else {
+                    if (top - tid < s_wmax[ww]) kw |= fl & (0xfu << (8 * ww));
+                }
+            }
+        }
+        s_keep[tid] = kw;
+    }
+}
+
+// Inclusive prefix sum over the 64 lanes of a wave of four byte counters packed in one word (no byte may pass 255): row scan
+// by row_shr 1 2 4 8, then the rows' totals by row_bcast 15 / 31.  Every lane of the wave must be active.
+__device__ __forceinline__ unsigned wave_scan_bytes4(unsigned word) {
+    unsigned incl = word;
+    asm volatile("s_nop 1\n\t"
+                 "v_add_u32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_add_u32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_add_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_add_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_add_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_add_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+                 : "+v"(incl));
+    return incl;
+}
+
+// One wave's survivor lists of the staged super-batch, from the keep words (byte w of s_keep[e] = the quarters wave w replays
+// entry e for; words past the super-batch are zero):
+//   * s_pos4 byte w of entry e = its position in wave w's block-level list (the slab row the combine looks up; 255: none),
+//   * list(q, i) (the caller's slot i of the wave's list of quarter q) = the entries of quarter q in staging order (ascending
+//     e = back to front), each entry | row << 8, row = the position in the block-level list; cq[q] = its length.  The four
+//     quarter counts ride in the bytes of one word, so one wave-wide prefix sum serves the four lists.  16 padding entries
+//     follow each list (SB | CAP << 8: the inert record, the slab's zero row), so whole 16-lane steps may read past the end,
+//   * rows 0 .. of the wave's slab (RW floats each) that the lists name start from zero.
+// ROUNDS false: CAP covers every staged entry, p0 and more are not used.  ROUNDS true: the call serves positions p0 .. p0 +
+// CAP - 1 of the block-level list (rows relative to p0), *more tells the caller's next round whether the wave has entries
+// left; s_pos4 is written in the round p0 = 0 (positions saturate at 254: the combine asks for (position - p0) < CAP).
+// Returns the length of the block-level list.  The whole wave calls it, behind a __syncthreads() that follows the keep words;
+// it ends with a release fence and a wave barrier: the wave's own steps may read the lists and add to the rows at once.
+template <int SB, int CAP, int RW, bool ROUNDS, int NKEEP, typename List>
+__device__ __forceinline__ int build_quarter_lists(const unsigned int (&s_keep)[NKEEP], unsigned int (&s_pos4)[NKEEP], List list, float *slab,
+                                                   int w, int lane, int (&cq)[4], int p0 = 0, int *more = nullptr) {
+    static_assert(ROUNDS || CAP >= SB, "one round: a slab row per staged entry");
+    static_assert(NKEEP >= (SB + WAVE - 1) / WAVE * WAVE, "every lane of a pass reads a keep word");
+    unsigned cqw = 0u;   // packed list lengths, byte q = quarter q (at most CAP entries of a round in a list)
+    int cnt = 0;
+#pragma unroll
+    for (int r = 0; r < (SB + WAVE - 1) / WAVE; ++r) {
+        const int e = r * WAVE + lane;
+        unsigned bits = (s_keep[e] >> (8 * w)) & 0xfu;
+        const bool kb = bits != 0u;
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(kb);
+        const int ps = cnt + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        if (!ROUNDS) reinterpret_cast<unsigned char *>(s_pos4)[4 * e + w] = kb ? (unsigned char)ps : (unsigned char)255;
+        else if (p0 == 0) reinterpret_cast<unsigned char *>(s_pos4)[4 * e + w] = kb ? (unsigned char)imin_(ps, 254) : (unsigned char)255;
+        if (ROUNDS) bits = ((unsigned)(ps - p0) < (unsigned)CAP) ? bits : 0u;   // entries of this round
+        const unsigned word = (bits * 0x00204081u) & 0x01010101u;                 // bit q -> byte q
+        const unsigned incl = wave_scan_bytes4(word);
+        const unsigned posw = cqw + incl - word;                                  // packed list positions of this lane's entry
+        const unsigned short ent = (unsigned short)(e | ((ROUNDS ? ps - p0 : ps) << 8));
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if ((bits >> q) & 1u) list(q, (posw >> (8 * q)) & 0xffu) = ent;
+        cqw += (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
+        cnt += __popcll(m);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) cq[q] = (int)((cqw >> (8 * q)) & 0xffu);
+    if (lane < 16) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) list(q, cq[q] + lane) = (unsigned short)(SB | (CAP << 8));   // pad: inert entry, zero row
+    }
+    {   // rows of this round start from zero
+        const int rows = ROUNDS ? imin_(imax_(cnt - p0, 0), CAP) : cnt;
+        float4 *z = reinterpret_cast<float4 *>(slab);
+        for (int c = lane; c < rows * (RW / 4); c += WAVE) z[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (ROUNDS && lane == 0) *more = cnt > p0 + CAP;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    return cnt;
+}
+
+// Staging of the quarter-list kernels with 64-entry super-batches: a QUAD of threads per entry -- thread t <-> entry t >> 2,
+// 16-byte part sp = t & 3 of each of the record's NSEC 64-byte sectors (four lanes per sector: coalesced; of the last sector
+// only parts sp < LAST are loaded, the others keep zero).  One index load and NSEC payload loads per thread and super-batch,
+// no division.  RS: floats between two records of BlendArgs::pack.  Ids run two super-batches ahead, the payload one (see
+// Stager); `pos(e, b)` maps (entry, batch) to the list position or a negative number.  Past the list the quad loads Gaussian
+// 0's record: staged entries >= nb are in no list and the combine skips them.  All 256 threads call both.
+template <int NSEC, int LAST, int RS>
+struct QuadStager {
+    int id_next;       // Gaussian of entry tid >> 2, two super-batches ahead (-1: past the list)
+    float4 v[NSEC];    // parts 4 k + sp of the entry, one super-batch ahead
+
+    __device__ __forceinline__ QuadStager() {
+        if (LAST < 4) v[NSEC - 1] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    template <typename Pos>
+    __device__ __forceinline__ void load_ids(const BlendArgs &A, int tid, int base, Pos pos, int batch) {
+        const int q = pos(tid >> 2, batch);
+        id_next = q >= 0 ? A.idx_sorted[base + q] : -1;
+    }
+    __device__ __forceinline__ void load_payload(const BlendArgs &A, int tid) {
+        const int sp = tid & 3;
+        const float4 *src = reinterpret_cast<const float4 *>(A.pack + (size_t)imax_(id_next, 0) * RS) + sp;
+#pragma unroll
+        for (int k = 0; k < NSEC - 1; ++k) v[k] = src[4 * k];
+        if (LAST == 4 || (LAST > 0 && sp < LAST)) v[NSEC - 1] = src[4 * (NSEC - 1)];
+    }
+};
+
+// The two geometry parts of a staged record, g0 = [u v cA cB] and g1 = [cC o . .], in BOTH lanes that hold one of them: the
+// lanes of a pair (quad_perm [1,0,3,2]) exchange their part; `first` tells which of the two this lane holds.  Every lane of
+// the wave must be active (DPP reads the neighbour's register).
+__device__ __forceinline__ void pair_exchange_geometry(const float4 &mine, bool first, float4 &g0, float4 &g1) {
+    float4 other;
+    other.x = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(mine.x), 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
+    other.y = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(mine.y), 0xB1, 0xf, 0xf, true));
+    other.z = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(mine.z), 0xB1, 0xf, 0xf, true));
+    other.w = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(mine.w), 0xB1, 0xf, 0xf, true));
+    g0 = first ? mine : other;
+    g1 = first ? other : mine;
+}
+
+// dbg_T_front (optional): the transmittance in front of the last replayed splat, of this lane's pixel (px, py) if it lies
+// inside the image; t is the pixel's T_state in LDS (read only where it is stored).
+__device__ __forceinline__ void store_T_front(const BlendArgs &A, int px, int py, const float &t) {
+    if (A.dbg_T_front) {
+        if (px < A.W && py < A.H) A.dbg_T_front[(size_t)A.W * py + px] = t;
+    }
+}
+
+// dL_dout of the wave's 64 pixels (gpix: the slots of this lane's pixel, lanes in strip-walk order) into registers in both MFMA
+// operand layouts, through `stage` (wave-private LDS of at least 32 * CH floats; wave barriers order it), 32 pixels at a time:
+//   hcg[G][j] = A[m = pixel nl of strip G][k = slot 4 j + kk]     (colour dot product)
+//   hft[st][q] = A[m = slot 16 q + nl][k = own pixel of step st]   (feature-gradient product; zero past CH)
+// The whole wave calls it.  The three-set kernel's; the wide kernel keeps the same loop inline: through a function argument its
+// staging stores lose the slab's 16-byte alignment (ds_write_b128 -> ds_write2_b32 at 16 and 32 channels).
+template <int CH, int NK, int NA>
+__device__ __forceinline__ void hoist_dl_dout(float *stage, const float (&gpix)[CH], int lane, float (&hcg)[4][NK], float (&hft)[16][NA]) {
+    const int nl = lane & 15, kk = lane >> 4;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if ((lane >> 5) == h) {
+#pragma unroll
+            for (int k = 0; k < CH; ++k) stage[(lane & 31) * CH + k] = gpix[k];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int G = 2 * h; G < 2 * h + 2; ++G)
+#pragma unroll
+            for (int j = 0; j < NK; ++j) hcg[G][j] = stage[(16 * (G & 1) + nl) * CH + 4 * j + kk];   // pixel 16 (G & 1) + nl of the half
+#pragma unroll
+        for (int st = 8 * h; st < 8 * h + 8; ++st) {
+#pragma unroll
+            for (int q = 0; q < NA; ++q)   // pixel 16 (G & 1) + 4 kk + i of the half
+                hft[st][q] = 16 * q + nl < CH ? stage[(16 * ((st >> 2) & 1) + 4 * kk + (st & 3)) * CH + 16 * q + nl] : 0.f;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 template <int CH, bool ABS, bool EXACT>
 __global__ void __launch_bounds__(256, (MfmaCfg<CH, ABS>::MINW))
 blend_bwd_mfma_kernel(const BlendArgs B) {
@@ -1979,15 +2224,13 @@ blend_bwd_quarter_kernel(const BlendArgs B) {
     const float ox = (float)((w & 1) * 8) - 7.5f, oy = (float)((w >> 1) * 8) - 7.5f;
     const int cn = EXACT ? CH : A.cn;
     const int nl = lane & 15, kk = lane >> 4;
-    // pixel index of the strip walk: q = 16 G + 4 kk + i  <->  quarter G = (sx, sy), pixel (x, y) = (4 sx + i, 4 sy + kk)
-    auto qx = [](int q) { return 4 * ((q >> 4) & 1) + (q & 3); };
-    auto qy = [](int q) { return 4 * (q >> 5) + ((q >> 2) & 3); };
+    using Walk = QuarterWalk<4>;   // the four quarters of the wave's own block; moments about the BLOCK centre
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {   // A operand of the moment product (one table for the four waves): rows 0-3 = 1 x y xx, rows
-                                    // 4-5 = xy yy of the pixel in BLOCK-centred coordinates; the combine moves a wave's sums to the tile centre
+    for (int r = 0; r < 4; ++r) {   // A operand of the moment product (one table for the four waves, see strip_moment_table):
+                                    // inline here for the row layout without abs taps
         const int st = 4 * w + r, Gs = st >> 2, is = st & 3;
         const int q = 16 * Gs + 4 * kk + is;
-        const float x = (float)qx(q) - 3.5f, y = (float)qy(q) - 3.5f;
+        const float x = (float)Walk::qx(q) - Walk::CEN, y = (float)Walk::qy(q) - Walk::CEN;
         float v = 0.f;
         if (ABS) {
             if (nl < 4) v = nl == 0 ? 1.f : nl == 1 ? x : nl == 2 ? y : x * x;
@@ -1999,13 +2242,7 @@ blend_bwd_quarter_kernel(const BlendArgs B) {
         if (nl < 8) s_mom[32 * st + 8 * kk + nl] = v;
     }
     float phi1[4], phi2[4];
-#pragma unroll
-    for (int Gs = 0; Gs < 4; ++Gs) {
-        const int q = 16 * Gs + nl;
-        const float x = (float)qx(q) + ox, y = (float)qy(q) + oy;
-        phi1[Gs] = kk == 0 ? 1.f : kk == 1 ? x : kk == 2 ? y : x * x;
-        phi2[Gs] = kk == 0 ? x * y : kk == 1 ? y * y : 0.f;
-    }
+    strip_phi<Walk>(nl, kk, ox, oy, phi1, phi2);
     const int lx = lane & 7, ly = lane >> 3;                                       // lane <-> pixel (lx, ly) of the block
     const int myq = 16 * ((lx >> 2) + 2 * (ly >> 2)) + 4 * (ly & 3) + (lx & 3);    // its index in the strip walk
     {
@@ -2047,10 +2284,7 @@ blend_bwd_quarter_kernel(const BlendArgs B) {
         for (int ql = n + tid; ql < len; ql += 256) store_rec(slots[ql], z);   // entries nobody replays: zero record
     }
     if (n <= 0) {
-        if (A.dbg_T_front) {
-            const int px = bx + lx, py = by + ly;
-            if (px < A.W && py < A.H) A.dbg_T_front[(size_t)A.W * py + px] = s_pix[w][pixoff(myq) + 6];
-        }
+        store_T_front(A, bx + lx, by + ly, s_pix[w][pixoff(myq) + 6]);
         return;
     }
     float *pixrow = s_pix[w] + kk * KS;            // own pixel of step (G, i): pixrow + G * GS + i * PW
@@ -2074,11 +2308,7 @@ blend_bwd_quarter_kernel(const BlendArgs B) {
     st.load_ids(A, tid, range.x, pos, 0);
     st.load_payload(A, tid);
     st.load_ids(A, tid, range.x, pos, 1);
-    auto load_flags = [&](int topb) -> unsigned {
-        const int q = topb - tid;
-        return (tid < SB && q >= 0) ? (unsigned)A.cull_flags[range.x + q] : 0u;
-    };
-    unsigned fl_next = load_flags(n - 1);
+    unsigned fl_next = load_flags<SB>(A.cull_flags, tid, range.x, n - 1);
 
     int batch = 0;
     for (int top = n - 1; top >= 0; top -= SB, ++batch) {
@@ -2090,12 +2320,8 @@ blend_bwd_quarter_kernel(const BlendArgs B) {
             for (int k = 0; k < Stager<CH, SB>::K; ++k) {
                 const int e = (tid >> 2) + 64 * k;
                 const float4 mine = st.v[k];
-                float4 other;
-                other.x = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(mine.x), 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-                other.y = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(mine.y), 0xB1, 0xf, 0xf, true));
-                other.z = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(mine.z), 0xB1, 0xf, 0xf, true));
-                other.w = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(mine.w), 0xB1, 0xf, 0xf, true));
-                const float4 g0 = p == 0 ? mine : other, g1 = p == 0 ? other : mine;
+                float4 g0, g1;
+                pair_exchange_geometry(mine, p == 0, g0, g1);
                 const PowerCoef pc = power_coeffs(g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, tcx, tcy);
                 if (p == 0) {
                     s_rec[qpart(e, 0)] = mine;
@@ -2108,71 +2334,15 @@ blend_bwd_quarter_kernel(const BlendArgs B) {
             }
         }
         const unsigned fl = fl_next;
-        fl_next = load_flags(top - SB);
-        if (tid < SB) {   // keep word of entry tid: byte w = the quarter bits of the forward's cull, if wave w still needs the entry
-            unsigned kw = 0u;
-            if (tid < nb) {
-#pragma unroll
-                for (int ww = 0; ww < 4; ++ww)
-                    if (top - tid < s_wmax[ww]) kw |= fl & (0xfu << (8 * ww));
-            }
-            s_keep[tid] = kw;
-        }
+        fl_next = load_flags<SB>(A.cull_flags, tid, range.x, top - SB);
+        keep_from_quarter_flags<SB, false>(s_keep, s_wmax, tid, nb, top, fl);
         __syncthreads();
         float *slab = s_acc[w];
         int slot_mine = 0;
         for (int p0 = 0;; p0 += CAP) {   // rounds of CAP positions of the wave's block-level list (one, unless more survive)
-            // ---- this wave's lists: block-level positions (slab rows, the combine's lookup) and one list per quarter
-            // (the four quarter counts ride in the bytes of one word: one wave-wide prefix sum serves the four lists)
-            unsigned cqw = 0u;   // packed list lengths, byte q = quarter q (at most CAP entries of a round in a list)
-            int cnt = 0;
-#pragma unroll
-            for (int r = 0; r < SB / WAVE; ++r) {
-                const int e = r * WAVE + lane;
-                unsigned bits = (s_keep[e] >> (8 * w)) & 0xfu;
-                const bool kb = bits != 0u;
-                const unsigned long long m = __builtin_amdgcn_ballot_w64(kb);
-                const int ps = cnt + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                if (p0 == 0) reinterpret_cast<unsigned char *>(s_pos4)[4 * e + w] = kb ? (unsigned char)imin_(ps, 254) : (unsigned char)255;
-                bits = ((unsigned)(ps - p0) < (unsigned)CAP) ? bits : 0u;       // entries of this round
-                const unsigned word = (bits * 0x00204081u) & 0x01010101u;      // bit q -> byte q
-                unsigned incl = word;
-                asm volatile("s_nop 1\n\t"
-                             "v_add_u32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                             "s_nop 1\n\t"
-                             "v_add_u32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-                             "s_nop 1\n\t"
-                             "v_add_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                             "s_nop 1\n\t"
-                             "v_add_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-                             "s_nop 1\n\t"
-                             "v_add_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-                             "s_nop 1\n\t"
-                             "v_add_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-                             : "+v"(incl));
-                const unsigned posw = cqw + incl - word;                       // packed list positions of this lane's entry
-                const unsigned short ent = (unsigned short)(e | ((ps - p0) << 8));
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if ((bits >> q) & 1u) s_qlist[w][q][(posw >> (8 * q)) & 0xffu] = ent;
-                cqw += (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
-                cnt += __popcll(m);
-            }
             int cq[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) cq[q] = (int)((cqw >> (8 * q)) & 0xffu);
-            if (lane < 16) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) s_qlist[w][q][cq[q] + lane] = (unsigned short)(SB | (CAP << 8));   // pad: inert entry, zero row
-            }
-            {   // rows of this round start from zero
-                const int rows = imin_(imax_(cnt - p0, 0), CAP);
-                float4 *z = reinterpret_cast<float4 *>(slab);
-                for (int c = lane; c < rows * (RW / 4); c += WAVE) z[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            if (lane == 0) s_more[w] = cnt > p0 + CAP;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            build_quarter_lists<SB, CAP, RW, true>(s_keep, s_pos4, [&](int q, int i) -> unsigned short & { return s_qlist[w][q][i]; }, slab, w, lane, cq, p0,
+                                                   &s_more[w]);
 #pragma unroll
             for (int G = 0; G < 4; ++G) {
                 for (int j0 = 0; j0 < cq[G]; j0 += 16) {
@@ -2348,10 +2518,7 @@ blend_bwd_quarter_kernel(const BlendArgs B) {
             if (!more) break;
         }
     }
-    if (A.dbg_T_front) {
-        const int px = bx + lx, py = by + ly;
-        if (px < A.W && py < A.H) A.dbg_T_front[(size_t)A.W * py + px] = s_pix[w][pixoff(myq) + 6];
-    }
+    store_T_front(A, bx + lx, by + ly, s_pix[w][pixoff(myq) + 6]);
 }
 
 // ------------------------------------------------------------------ backward of several feature SETS in ONE pass
@@ -2894,29 +3061,12 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
     const float tcx = (float)(tx * TILE) + 7.5f, tcy = (float)(ty * TILE) + 7.5f;
     const float ox = (float)wx - 7.5f, oy = (float)wy - 7.5f;
     const int nl = lane & 15, kk = lane >> 4;
-    // strip walk: q = 16 G + 4 kk + i  <->  block G = (gx, gy), pixel (8 gx + i, 8 gy + kk) + (wx, wy) of the tile
-    auto qx = [](int q) { return 8 * ((q >> 4) & 1) + (q & 3); };
-    auto qy = [](int q) { return 8 * (q >> 5) + ((q >> 2) & 3); };
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {   // moment operand about the centre of the wave's pixel set: rows 0-3 = 1 x y xx, rows 4-5 = xy yy
-        const int st = 4 * w + r, Gs = st >> 2, is = st & 3;
-        const int q = 16 * Gs + 4 * kk + is;
-        const float x = (float)qx(q) - 5.5f, y = (float)qy(q) - 5.5f;
-        float v = 0.f;
-        if (nl < 4) v = nl == 0 ? 1.f : nl == 1 ? x : nl == 2 ? y : x * x;
-        else if (nl < 6) v = nl == 4 ? x * y : y * y;
-        if (nl < 8) s_mom[32 * st + 8 * kk + nl] = v;
-    }
+    using Walk = QuarterWalk<8>;   // quarter (wx, wy) of the tile's four blocks; moments about the centre of that pixel set
+    strip_moment_table<Walk>(s_mom, w, nl, kk);
     float phi1[4], phi2[4];
-#pragma unroll
-    for (int Gs = 0; Gs < 4; ++Gs) {
-        const int q = 16 * Gs + nl;
-        const float x = (float)qx(q) + ox, y = (float)qy(q) + oy;
-        phi1[Gs] = kk == 0 ? 1.f : kk == 1 ? x : kk == 2 ? y : x * x;
-        phi2[Gs] = kk == 0 ? x * y : kk == 1 ? y * y : 0.f;
-    }
+    strip_phi<Walk>(nl, kk, ox, oy, phi1, phi2);
     const int myq = lane;                              // lane <-> pixel `lane` of the strip walk
-    const int lx = wx + qx(myq), ly = wy + qy(myq);    // its position in the tile
+    const int lx = wx + Walk::qx(myq), ly = wy + Walk::qy(myq);    // its position in the tile
     float *stage = s_acc[w];  // [pixel of the half block (raster)][slot]
     float gpix[CH];
     {
@@ -2989,28 +3139,7 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
     if (SB < 64 && tid < 64) s_keep[tid] = 0u;          // (entries SB .. 63 of the list build: never kept)
     // ---- dL_dout of the wave's pixels into registers in both MFMA operand layouts, 32 pixels (two quarters) at a time
     float hcg[4][NKU], hft[16][NAU];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        if ((lane >> 5) == h) {
-#pragma unroll
-            for (int k = 0; k < CH; ++k) stage[(lane & 31) * CH + k] = gpix[k];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int G = 2 * h; G < 2 * h + 2; ++G)
-#pragma unroll
-            for (int j = 0; j < NKU; ++j)   // A[m = pixel nl of quarter G][k = slot]: pixel 16 (G & 1) + nl of the half (lanes in walk order)
-                hcg[G][j] = stage[(16 * (G & 1) + nl) * CH + 4 * j + kk];
-#pragma unroll
-        for (int st = 8 * h; st < 8 * h + 8; ++st) {
-#pragma unroll
-            for (int q = 0; q < NAU; ++q)  // A[m = slot 16 q + nl][k = own pixel of step st = (G, i)]: pixel 16 (G & 1) + 4 kk + i of the half
-                hft[st][q] = 16 * q + nl < CH ? stage[(16 * ((st >> 2) & 1) + 4 * kk + (st & 3)) * CH + 16 * q + nl] : 0.f;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
+    hoist_dl_dout<CH, NKU, NAU>(stage, gpix, lane, hcg, hft);
     if (lane < RW) s_acc[w][CAP * RW + lane] = 0.f;   // the slab's zero row
     __syncthreads();
     // (one plain store per workgroup and set; the caller adds them up: reproducible, no atomics)
@@ -3038,43 +3167,24 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
     }
 
     auto pos = [n](int e, int b) { return n - 1 - b * SB - e; };
-    // staging: a QUAD per entry -- thread t <-> entry se = t >> 2, 16-byte part sp = t & 3 of each of the record's three 64-byte
-    // sectors (four lanes per sector: coalesced).  One index load and three payload loads per thread and super-batch (of the
-    // third sector only parts 8 and 9, the last feature slots, are used; the cull parameters behind them are not), no
-    // division, and the coefficient block runs ONCE per wave (the generic Stager -- chunk c = t + 256 k, entry c / 12 -- made every
-    // wave run it for each of its three chunks: 230 of the 830 VALU instructions a wave spent per super-batch outside the steps).
+    // staging: a quad per entry (QuadStager).  Of the packed record's third sector only parts 8 and 9, the last feature slots,
+    // are used (the cull parameters behind them are not); the forward's 32-float records have two sectors.  The coefficient
+    // block of the park runs ONCE per wave (the generic Stager -- chunk c = t + 256 k, entry c / 12 -- made every wave run it for
+    // each of its three chunks: 230 of the 830 VALU instructions a wave spent per super-batch outside the steps).
     static_assert(SB <= 64 && RQ == 12, "256 threads = 64 entries x 4 parts (entries SB .. 63 idle); three sectors per record");
     const int se = tid >> 2, sp = tid & 3;
-    int sid_next;              // Gaussian of entry se, two super-batches ahead (-1: past the list)
-    float4 sv0, sv1, sv2 = make_float4(0.f, 0.f, 0.f, 0.f);   // parts sp, 4 + sp, 8 + sp (sp < 2) of entry se, one super-batch ahead
-#define SETSQ_STAGE_IDS(b)                                                        \
-    do {                                                                          \
-        const int q_ = pos(se, (b));                                              \
-        sid_next = q_ >= 0 ? A.idx_sorted[range.x + q_] : -1;                     \
-    } while (0)
-    // (past the list the quad loads Gaussian 0's record: staged entries >= nb are in no list and the combine skips them)
-#define SETSQ_STAGE_PAYLOAD()                                                                                                   \
-    do {                                                                                                                        \
-        const float4 *src_ = reinterpret_cast<const float4 *>(A.pack + (size_t)imax_(sid_next, 0) * (FWDREC ? 32 : Rec<CH>::RS)) + sp; \
-        sv0 = src_[0];                                                                                                          \
-        sv1 = src_[4];                                                                                                          \
-        if (!FWDREC && sp < 2) sv2 = src_[8];                                                                                   \
-    } while (0)
-    SETSQ_STAGE_IDS(0);
-    SETSQ_STAGE_PAYLOAD();
-    SETSQ_STAGE_IDS(1);
-    auto load_flags = [&](int topb) -> unsigned {
-        const int q = topb - tid;
-        return (tid < SB && q >= 0) ? (unsigned)A.cull_flags[range.x + q] : 0u;
-    };
-    unsigned fl_next = load_flags(n - 1);
+    QuadStager<3, FWDREC ? 0 : 2, FWDREC ? 32 : Rec<CH>::RS> st;   // v[k]: part 4 k + sp of entry se (v[2]: sp < 2, packed records only)
+    st.load_ids(A, tid, range.x, pos, 0);
+    st.load_payload(A, tid);
+    st.load_ids(A, tid, range.x, pos, 1);
+    unsigned fl_next = load_flags<SB>(A.cull_flags, tid, range.x, n - 1);
 
     int batch = 0;
     for (int top = n - 1; top >= 0; top -= SB, ++batch) {
         const int nb = imin_(SB, top + 1);
         {   // park: the quad's lanes copy their parts and each leaves ONE of the four operand rows Q[sp] (the two geometry parts
             // sit in lanes 0 / 1 of the quad: broadcast)
-            const float4 mine = sv0;
+            const float4 mine = st.v[0];
             float4 g0, g1;
 #define QB_(v, c) __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), c, 0xf, 0xf, true))
             g0.x = QB_(mine.x, 0x00); g0.y = QB_(mine.y, 0x00); g0.z = QB_(mine.z, 0x00); g0.w = QB_(mine.w, 0x00);   // quad_perm [0,0,0,0]
@@ -3092,12 +3202,12 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
                 if (sp < 2) rb[sp] = mine;
                 else if (sp == 2) { rf[8] = mine.x; rf[16] = mine.y; rf[24] = mine.z; rf[9] = mine.w; }
                 else { rf[10] = mine.x; rf[18] = mine.y; rf[26] = mine.z; rf[34] = mine.w; }
-                rf[11 + sp] = sv1.x; rf[19 + sp] = sv1.y; rf[27 + sp] = sv1.z;   // slots 12 + 4 sp + i at 11 + sp + 8 i
-                if (sp < 3) rf[35 + sp] = sv1.w;                                   // (sp 3: channel 23 is the record's padding -> slot 27 stays zero)
+                rf[11 + sp] = st.v[1].x; rf[19 + sp] = st.v[1].y; rf[27 + sp] = st.v[1].z;   // slots 12 + 4 sp + i at 11 + sp + 8 i
+                if (sp < 3) rf[35 + sp] = st.v[1].w;                                   // (sp 3: channel 23 is the record's padding -> slot 27 stays zero)
             } else {
                 rb[sp] = mine;                                // parts 0 .. 3
-                rb[4 + sp] = sv1;                             // parts 4 .. 7
-                if (sp < 2) rb[8 + sp] = sv2;                 // parts 8, 9
+                rb[4 + sp] = st.v[1];                             // parts 4 .. 7
+                if (sp < 2) rb[8 + sp] = st.v[2];                 // parts 8, 9
             }
             float4 qv;                                    // Q[sp] = (q1 q2 lx ly)[sp]
             qv.x = sp == 0 ? pc.q0 : sp == 1 ? pc.qx : sp == 2 ? pc.qy : pc.qxx;
@@ -3107,22 +3217,13 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
             if (SB == 64 || se < SB) rb[10 + sp] = qv;
         }
         const unsigned fl = fl_next;
-        fl_next = load_flags(top - SB);
-        if (tid < SB) {   // byte w' bit G = quarter w' of block G in the forward's cull flags (byte G bit w')
-            unsigned kw = 0u;
-            if (tid < nb) {
-#pragma unroll
-                for (int ww = 0; ww < 4; ++ww) {
-                    const unsigned t4 = (fl >> ww) & 0x01010101u;
-                    const unsigned nib = ((t4 * 0x01020408u) >> 24) & 0xfu;
-                    if (top - tid < s_wmax[ww]) kw |= nib << (8 * ww);
-                }
-            }
-            s_keep[tid] = kw;
-        }
+        fl_next = load_flags<SB>(A.cull_flags, tid, range.x, top - SB);
+        keep_from_quarter_flags<SB, true>(s_keep, s_wmax, tid, nb, top, fl);
         __syncthreads();
         float *slab = s_acc[w];
-        // ---- this wave's lists (SB = 64: one entry per lane)
+        // ---- this wave's lists (SB = 64: one entry per lane): the one-pass, one-round case of build_quarter_lists, written out
+        // here -- through the shared function the three SMALL instantiations spill one more register (scratch + 4 bytes per lane
+        // at their 168-register budget), whichever way the lists and counts are handed over
         unsigned cqw = 0u;
         int cnt;
         {
@@ -3133,20 +3234,7 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
             const int ps = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
             reinterpret_cast<unsigned char *>(s_pos4)[4 * e + w] = kb ? (unsigned char)ps : (unsigned char)255;
             const unsigned word = (bits * 0x00204081u) & 0x01010101u;
-            unsigned incl = word;
-            asm volatile("s_nop 1\n\t"
-                         "v_add_u32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                         "s_nop 1\n\t"
-                         "v_add_u32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-                         "s_nop 1\n\t"
-                         "v_add_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                         "s_nop 1\n\t"
-                         "v_add_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-                         "s_nop 1\n\t"
-                         "v_add_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-                         "s_nop 1\n\t"
-                         "v_add_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-                         : "+v"(incl));
+            const unsigned incl = wave_scan_bytes4(word);
             const unsigned posw = incl - word;
             const unsigned short ent = (unsigned short)(e | (ps << 8));
 #pragma unroll
@@ -3297,8 +3385,8 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
             }
         }
         const int slot_mine = ce < nb ? slots[top - ce] : 0;   // entry ce of the combine
-        SETSQ_STAGE_PAYLOAD();
-        SETSQ_STAGE_IDS(batch + 2);
+        st.load_payload(A, tid);
+        st.load_ids(A, tid, range.x, pos, batch + 2);
         // the combine's only reads of the staged records, taken BEFORE the barrier: behind it a fast wave may already park the next
         // super-batch over them while a slow one still combines (the combine otherwise reads the slabs and position bytes, which
         // nobody writes before the next super-batch's barrier) -- two barriers per super-batch instead of three
@@ -3456,14 +3544,8 @@ blend_bwd_sets_quarter_kernel(const BlendArgs B) {
             }
         }
     }
-    if (A.dbg_T_front) {
-        const int px = tx * TILE + lx, py = ty * TILE + ly;
-        if (px < A.W && py < A.H) A.dbg_T_front[(size_t)A.W * py + px] = s_state[w][pixoff(myq)];
-    }
+    store_T_front(A, tx * TILE + lx, ty * TILE + ly, s_state[w][pixoff(myq)]);
 }
-
-#undef SETSQ_STAGE_IDS
-#undef SETSQ_STAGE_PAYLOAD
 
 // ------------------------------------------------------------------ wide single-set backward on QUARTER lists
 // The strip walk of blend_bwd_sets_quarter_kernel for ONE feature set of 16 .. 32 channels (the wide instantiations of
@@ -3513,28 +3595,12 @@ blend_bwd_wide_quarter_kernel(const BlendArgs B) {
     const float ox = (float)wx - 7.5f, oy = (float)wy - 7.5f;
     const int cn = EXACT ? CH : A.cn;
     const int nl = lane & 15, kk = lane >> 4;
-    auto qx = [](int q) { return 8 * ((q >> 4) & 1) + (q & 3); };
-    auto qy = [](int q) { return 8 * (q >> 5) + ((q >> 2) & 3); };
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int st = 4 * w + r, Gs = st >> 2, is = st & 3;
-        const int q = 16 * Gs + 4 * kk + is;
-        const float x = (float)qx(q) - 5.5f, y = (float)qy(q) - 5.5f;
-        float v = 0.f;
-        if (nl < 4) v = nl == 0 ? 1.f : nl == 1 ? x : nl == 2 ? y : x * x;
-        else if (nl < 6) v = nl == 4 ? x * y : y * y;
-        if (nl < 8) s_mom[32 * st + 8 * kk + nl] = v;
-    }
+    using Walk = QuarterWalk<8>;
+    strip_moment_table<Walk>(s_mom, w, nl, kk);
     float phi1[4], phi2[4];
-#pragma unroll
-    for (int Gs = 0; Gs < 4; ++Gs) {
-        const int q = 16 * Gs + nl;
-        const float x = (float)qx(q) + ox, y = (float)qy(q) + oy;
-        phi1[Gs] = kk == 0 ? 1.f : kk == 1 ? x : kk == 2 ? y : x * x;
-        phi2[Gs] = kk == 0 ? x * y : kk == 1 ? y * y : 0.f;
-    }
+    strip_phi<Walk>(nl, kk, ox, oy, phi1, phi2);
     const int myq = lane;
-    const int lx = wx + qx(myq), ly = wy + qy(myq);
+    const int lx = wx + Walk::qx(myq), ly = wy + Walk::qy(myq);
     float *stage = s_acc[w];
     float gpix[CH];
     {
@@ -3562,7 +3628,7 @@ blend_bwd_wide_quarter_kernel(const BlendArgs B) {
     if (tid < 2) s_coef[2 * SB + tid] = make_float4(tid == 0 ? -__builtin_inff() : 0.f, 0.f, 0.f, 0.f);   // inert slot: q0 = log2(0)
     float hcg[4][NK], hft[16][NA];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int h = 0; h < 2; ++h) {   // dL_dout into both MFMA operand layouts (see hoist_dl_dout; inline here: the 16-byte staging stores)
         if ((lane >> 5) == h) {
 #pragma unroll
             for (int k = 0; k < CH; ++k) stage[(lane & 31) * CH + k] = gpix[k];
@@ -3605,111 +3671,34 @@ blend_bwd_wide_quarter_kernel(const BlendArgs B) {
         return;
     }
     auto pos = [n](int e, int b) { return n - 1 - b * SB - e; };
-    // staging: a quad per entry (see blend_bwd_sets_quarter_kernel) -- thread t <-> entry se = t >> 2, part sp = t & 3 of each of the
-    // record's NSEC 64-byte sectors: one index load per thread and super-batch, no division, the coefficient block once per wave
-    constexpr int NSEC = RQ / 4;
+    // staging: a quad per entry (QuadStager), every part of the record's RQ / 4 sectors; the coefficient block once per wave
     const int se = tid >> 2, sp = tid & 3;
-    int sid_next;
-    float4 sv[NSEC];
-#define WIDEQ_STAGE_IDS(b)                                                        \
-    do {                                                                          \
-        const int q_ = pos(se, (b));                                              \
-        sid_next = q_ >= 0 ? A.idx_sorted[range.x + q_] : -1;                     \
-    } while (0)
-    // (past the list the quad loads Gaussian 0's record: staged entries >= nb are in no list and the combine skips them)
-#define WIDEQ_STAGE_PAYLOAD()                                                                                                   \
-    do {                                                                                                                        \
-        const float4 *src_ = reinterpret_cast<const float4 *>(A.pack + (size_t)imax_(sid_next, 0) * Rec<CH>::RS) + sp;          \
-        _Pragma("unroll") for (int k_ = 0; k_ < NSEC; ++k_) sv[k_] = src_[4 * k_];                                              \
-    } while (0)
-    WIDEQ_STAGE_IDS(0);
-    WIDEQ_STAGE_PAYLOAD();
-    WIDEQ_STAGE_IDS(1);
-    auto load_flags = [&](int topb) -> unsigned {
-        const int q = topb - tid;
-        return (tid < SB && q >= 0) ? (unsigned)A.cull_flags[range.x + q] : 0u;
-    };
-    unsigned fl_next = load_flags(n - 1);
+    QuadStager<RQ / 4, 4, Rec<CH>::RS> st;
+    st.load_ids(A, tid, range.x, pos, 0);
+    st.load_payload(A, tid);
+    st.load_ids(A, tid, range.x, pos, 1);
+    unsigned fl_next = load_flags<SB>(A.cull_flags, tid, range.x, n - 1);
 
     int batch = 0;
     for (int top = n - 1; top >= 0; top -= SB, ++batch) {
         const int nb = imin_(SB, top + 1);
         {   // park; the lanes holding parts 0 / 1 of an entry exchange them and leave the polynomial's coefficients
-            const float4 mine = sv[0];
-            float4 other;
-            other.x = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(mine.x), 0xB1, 0xf, 0xf, true));
-            other.y = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(mine.y), 0xB1, 0xf, 0xf, true));
-            other.z = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(mine.z), 0xB1, 0xf, 0xf, true));
-            other.w = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(mine.w), 0xB1, 0xf, 0xf, true));
-            const float4 g0 = (sp & 1) == 0 ? mine : other, g1 = (sp & 1) == 0 ? other : mine;   // (lanes 2, 3 of a quad: unused)
+            float4 g0, g1;
+            pair_exchange_geometry(st.v[0], (sp & 1) == 0, g0, g1);   // (lanes 2, 3 of a quad: unused)
             const PowerCoef pc = power_coeffs(g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, tcx, tcy);
             float4 *rb = s_rec + se * RQ + (sp ^ ((se >> 2) & 3));   // part 4 k + sp at 4 k + (sp ^ swizzle)
 #pragma unroll
-            for (int k = 0; k < NSEC; ++k) rb[4 * k] = sv[k];
+            for (int k = 0; k < RQ / 4; ++k) rb[4 * k] = st.v[k];
             if (sp == 0) s_coef[2 * se] = make_float4(pc.q0, pc.qx, pc.qy, pc.qxx);
             else if (sp == 1) s_coef[2 * se + 1] = make_float4(pc.qxy, pc.qyy, 0.f, 0.f);
         }
         const unsigned fl = fl_next;
-        fl_next = load_flags(top - SB);
-        if (tid < SB) {   // byte w' bit G = quarter w' of block G in the forward's cull flags (byte G bit w')
-            unsigned kw = 0u;
-            if (tid < nb) {
-#pragma unroll
-                for (int ww = 0; ww < 4; ++ww) {
-                    const unsigned t4 = (fl >> ww) & 0x01010101u;
-                    const unsigned nib = ((t4 * 0x01020408u) >> 24) & 0xfu;
-                    if (top - tid < s_wmax[ww]) kw |= nib << (8 * ww);
-                }
-            }
-            s_keep[tid] = kw;
-        }
+        fl_next = load_flags<SB>(A.cull_flags, tid, range.x, top - SB);
+        keep_from_quarter_flags<SB, true>(s_keep, s_wmax, tid, nb, top, fl);
         __syncthreads();
         float *slab = s_acc[w];
-        unsigned cqw = 0u;
-        int cnt;
-        {
-            const int e = lane;
-            const unsigned bits = (s_keep[e] >> (8 * w)) & 0xfu;
-            const bool kb = bits != 0u;
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(kb);
-            const int ps = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-            reinterpret_cast<unsigned char *>(s_pos4)[4 * e + w] = kb ? (unsigned char)ps : (unsigned char)255;
-            const unsigned word = (bits * 0x00204081u) & 0x01010101u;
-            unsigned incl = word;
-            asm volatile("s_nop 1\n\t"
-                         "v_add_u32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                         "s_nop 1\n\t"
-                         "v_add_u32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-                         "s_nop 1\n\t"
-                         "v_add_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                         "s_nop 1\n\t"
-                         "v_add_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-                         "s_nop 1\n\t"
-                         "v_add_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-                         "s_nop 1\n\t"
-                         "v_add_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-                         : "+v"(incl));
-            const unsigned posw = incl - word;
-            const unsigned short ent = (unsigned short)(e | (ps << 8));
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if ((bits >> q) & 1u) s_qlist[w][q][(posw >> (8 * q)) & 0xffu] = ent;
-            cqw = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
-            cnt = __popcll(m);
-        }
         int cq[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) cq[q] = (int)((cqw >> (8 * q)) & 0xffu);
-        if (lane < 16) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) s_qlist[w][q][cq[q] + lane] = (unsigned short)(SB | (CAP << 8));
-        }
-        {
-            float4 *z = reinterpret_cast<float4 *>(slab);
-            for (int c = lane; c < cnt * (RW / 4); c += WAVE) z[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        build_quarter_lists<SB, CAP, RW, false>(s_keep, s_pos4, [&](int q, int i) -> unsigned short & { return s_qlist[w][q][i]; }, slab, w, lane, cq);
 #pragma unroll
         for (int G = 0; G < 4; ++G) {
             for (int j0 = 0; j0 < cq[G]; j0 += 16) {
@@ -3806,8 +3795,8 @@ blend_bwd_wide_quarter_kernel(const BlendArgs B) {
             }
         }
         const int slot_mine = ce < nb ? slots[top - ce] : 0;
-        WIDEQ_STAGE_PAYLOAD();
-        WIDEQ_STAGE_IDS(batch + 2);
+        st.load_payload(A, tid);
+        st.load_ids(A, tid, range.x, pos, batch + 2);
         // the combine's reads of the staged records, in front of its barrier: behind it a fast wave may already park the next
         // super-batch (two barriers per super-batch, see blend_bwd_sets_quarter_kernel)
         float4 cg0 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -3877,9 +3866,6 @@ blend_bwd_wide_quarter_kernel(const BlendArgs B) {
         if (px < A.W && py < A.H) A.dbg_T_front[(size_t)A.W * py + px] = s_state[w][pixoff(myq)];
     }
 }
-#undef WIDEQ_STAGE_IDS
-#undef WIDEQ_STAGE_PAYLOAD
-
 // ------------------------------------------------------------------ backward, atomic mode (foreign idx_sorted)
 // Same tile structure; every wave reduces its partials and lane 63 issues one hardware float atomic
 // per (wave, splat, component).  Gradient outputs must be zero-initialised.
