@@ -793,6 +793,34 @@ int splat_track_loss_grad(int F, int H, int W, int C, const float *track, const 
                           float scale, float *grad, const int64_t *grad_strides, int accumulate, float *per_frame,
                           float *loss_slot, int32_t *counts, void *scratch, splat_stream_t stream);
 
+/* ---- median-normalised depth loss: the trainer's depth term depth_loss_dpt(depth, gt_depth) (src/trainer_fragGS.py:589-601,
+ *      src/loss.py:184-207, weight = None).  Frame f is the plane [H, W] at img + f * strides[0] of an [F, 1, H, W] view given by
+ *      four ELEMENT strides (strides[1] is not used; read in place: a channel slice of a wider row works).  Per frame, n = H W:
+ *        t_p = torch.median(p): the LOWER median, rank (n - 1) / 2 ascending;  s_p = (1 / n) sum |p_i - t_p|;  t_g, s_g likewise;
+ *        d_i = (p_i - t_p) / s_p - (g_i - t_g) / s_g;   loss_f = (1 / n) sum d_i^2
+ *      and the gradient is autograd's of that expression, the paths through t_p and s_p included, the median's gradient spread
+ *      evenly over the m pixels equal to it:  with a_i = 2 d_i / n, A = sum a_i, B = sum a_i (p_i - t_p), sg_i = sign(p_i - t_p),
+ *      S = sum sg_i:   dL/dp_j = a_j / s_p - B sg_j / (n s_p^2) + [p_j == t_p] / m * (-A / s_p + B S / (n s_p^2)).
+ *      The selection is exact (radix select on sign-flipped 32-bit keys, -0 counted as +0, floats of both signs).  A NaN in a
+ *      frame's p or g makes that frame's loss and every pixel of its gradient NaN and leaves the other frames alone; a constant
+ *      image (s = 0) is not special-cased (IEEE division: inf / NaN, as in the reference; no epsilon).
+ *      splat_depth_stats: stats [F, 2] = (t, s) of every frame of img -- for ground-truth depth, which is fixed per video frame.
+ *      splat_depth_dpt_loss_grad: gt_stats (optional, [F, 2] as written by splat_depth_stats: the gt rows are then not selected
+ *      again; same bits as without).  Outputs (each optional): grad (own strides, must not overlap the inputs) = scale / F * the
+ *      gradient above, written in full or, accumulate != 0, added; per_frame [F] = loss_f; *loss_slot += mean_f loss_f;
+ *      stats_out [F, 4] = t_p, s_p, t_g, s_g; ties_out int32 [F] = m.
+ *      Many workgroups per frame (one per 4096 pixels and row); launches: one memset of the counters, four digit passes (LDS
+ *      histograms flushed with INTEGER atomics), |p - t| partials + m + S, the d partials, the gradient (+ one for the slot).
+ *      Float sums are per-workgroup partials added in a fixed order: no float atomics, bit-reproducible; no host synchronisation,
+ *      n and every rank stay on the device.  H W <= 2^31 - 1, F <= 2^24.  Scratch: splat_depth_dpt_scratch_bytes(F, H, W). ---- */
+size_t splat_depth_dpt_scratch_bytes(int F, int H, int W);      /* 0: invalid sizes */
+int splat_depth_stats(int F, int H, int W, const float *img, const int64_t *strides, float *stats, void *scratch,
+                      splat_stream_t stream);
+int splat_depth_dpt_loss_grad(int F, int H, int W, const float *pred, const int64_t *pred_strides, const float *gt,
+                              const int64_t *gt_strides, const float *gt_stats, float scale, float *grad,
+                              const int64_t *grad_strides, int accumulate, float *per_frame, float *loss_slot, float *stats_out,
+                              int32_t *ties_out, void *scratch, splat_stream_t stream);
+
 #define SPLAT_ADAM_MAX_SEGMENTS 16
 int splat_adam_step(int64_t n, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int nseg,
                     const int64_t *seg_end_host, const float *seg_lr_host, float beta1, float beta2, float eps,

@@ -58,6 +58,7 @@ SYMBOLS = [
     "splat_profile_enable", "splat_profile_reset", "splat_profile_read",
     "splat_ssim_scratch_bytes", "splat_ssim_forward", "splat_ssim_backward", "splat_dssim_l1_loss_grad",
     "splat_track_loss_scratch_bytes", "splat_track_loss_grad",
+    "splat_depth_dpt_scratch_bytes", "splat_depth_stats", "splat_depth_dpt_loss_grad",
 ]
 
 
@@ -113,6 +114,10 @@ def lib() -> ctypes.CDLL:
         L.splat_track_loss_scratch_bytes.restype = ctypes.c_size_t
         L.splat_track_loss_scratch_bytes.argtypes = [i, ctypes.c_int64]
         L.splat_track_loss_grad.argtypes = [i, i, i, i, p, s4, p, p, p, ctypes.c_int64, p, f, f, p, s4, i, p, p, p, p, p]
+        L.splat_depth_dpt_scratch_bytes.restype = ctypes.c_size_t
+        L.splat_depth_dpt_scratch_bytes.argtypes = [i, i, i]
+        L.splat_depth_stats.argtypes = [i, i, i, p, s4, p, p, p]
+        L.splat_depth_dpt_loss_grad.argtypes = [i, i, i, p, s4, p, s4, p, f, p, s4, i, p, p, p, p, p, p]
         if L.splat_abi_version() != ABI_VERSION:
             raise SplatError("libsplat_hip.so ABI version mismatch; rebuild it")
         _lib = L

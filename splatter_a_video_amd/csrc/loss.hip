@@ -768,3 +768,540 @@ extern "C" int splat_track_loss_grad(int F, int H, int W, int C, const float *tr
     }
     return SPLAT_OK;
 }
+
+// ==================================================================================================================================
+// Median-normalised depth loss: the trainer's depth_loss_dpt (src/loss.py:184-207, src/trainer_fragGS.py:589-601).  A "row" is one
+// image of n = H W pixels: rows 0 .. F-1 are the frames of pred, rows F .. 2F-1 those of gt (absent when the caller hands in
+// gt's statistics).  One workgroup = DPT_CH consecutive pixels of one row; the grid is (chunks, rows).  Launches:
+//   0.     one memset of the rows' histograms and integer counters
+//   1.-4.  digit pass d = 0 .. 3 of the radix select of rank (n - 1) / 2 on sign-flipped keys: every workgroup first finds the
+//          bins of the digits already counted (one wave, a prefix scan over 256 counters per digit), then counts digit d of the
+//          keys that match them in per-wave LDS histograms and flushes those with integer atomics; pass 0 also counts NaNs
+//   5.     t from the four histograms; per workgroup the partial of sum |p - t|, and m = #{p == t}, #{p > t}, #{p < t}
+//          (integer atomics)
+//   6.     s = the partials added in chunk order / n; per workgroup the partials of sum d^2, sum d, sum d (p - t_p)
+//   7.     those added in chunk order -> loss_f, A, B; the gradient, elementwise
+//   8.     the slot: the per-frame losses added in frame order
+// Partials are doubles in a fixed slot; every reader adds them in the same order: no float atomics, bit-reproducible.  What a
+// launch reads of another's output crosses a kernel boundary, never a fence inside a launch.
+namespace {
+
+constexpr int DPT_THREADS = 256;
+constexpr int DPT_PER = 16;                        // pixels per thread: four float4 groups
+constexpr int DPT_CH = DPT_THREADS * DPT_PER;      // pixels per workgroup
+constexpr int DPT_MAX_ROWS_Y = 65535;
+
+struct DptImg {
+    const float *p;
+    long long s0, s2, s3;
+    int lin;                  // a frame's pixels are contiguous in raster order
+};
+
+struct DptArgs {
+    int F, W, rows;           // rows: F (pred only: gt's statistics are given) or 2 F
+    unsigned n;
+    int nchunks;
+    DptImg im[2];             // rows < F, rows >= F
+    const float *gt_stats;    // [F, 2] or null
+    unsigned *hist;           // [2F][4][256]
+    unsigned *cnt;            // [2F][4]: NaNs, == t, > t, < t
+    float *tval;              // [2F]
+    double *part_abs;         // [2F][nchunks]
+    double *part_d;           // [F][nchunks][3]
+    float *lossf;             // [F]
+    float gscale;
+    float *grad;
+    long long g0, g2, g3;
+    int glin, accumulate;
+    float *per_frame, *stats_out;
+    int32_t *ties_out;
+    float *stats;             // splat_depth_stats: [rows, 2]
+};
+
+// ordered key of a float: ascending as the values, -0 = +0
+__device__ __forceinline__ unsigned dpt_key(float v) {
+    unsigned u = __float_as_uint(v);
+    if (u == 0x80000000u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float dpt_unkey(unsigned k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+__device__ __forceinline__ const float *dpt_row(const DptArgs &A, int row, int &which) {
+    which = row >= A.F;
+    const DptImg &im = A.im[which];
+    return im.p + (long long)(which ? row - A.F : row) * im.s0;
+}
+
+// element offset of pixel i of a plane
+__device__ __forceinline__ long long dpt_off(int lin, long long s2, long long s3, unsigned W, unsigned i) {
+    if (lin) return (long long)i;
+    const unsigned y = i / W, x = i - y * W;
+    return (long long)y * s2 + (long long)x * s3;
+}
+
+// this thread's DPT_PER pixels of the chunk that starts at c0: v[4 k + j] = pixel c0 + (k * DPT_THREADS + tid) * 4 + j (where < n)
+__device__ __forceinline__ unsigned dpt_idx(unsigned c0, int k, int tid) { return c0 + (unsigned)(k * DPT_THREADS + tid) * 4u; }
+
+__device__ __forceinline__ void dpt_load(const float *base, const DptImg &im, unsigned W, unsigned c0, unsigned n, int tid,
+                                         float (&v)[DPT_PER]) {
+    const bool vec = im.lin && (((uintptr_t)base & 15) == 0);
+#pragma unroll
+    for (int k = 0; k < DPT_PER / 4; ++k) {
+        const unsigned i = dpt_idx(c0, k, tid);
+        if (vec && i < n && n - i >= 4u) {
+            const float4 q = *(const float4 *)(base + i);
+            v[4 * k] = q.x; v[4 * k + 1] = q.y; v[4 * k + 2] = q.z; v[4 * k + 3] = q.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                // (i + j < n written without overflow: i may be within 4 of 2^32)
+                const bool ok = i < n && (unsigned)j < n - i;
+                v[4 * k + j] = ok ? base[dpt_off(im.lin, im.s2, im.s3, W, i + j)] : 0.f;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ bool dpt_valid(unsigned c0, int k, int j, int tid, unsigned n) {
+    const unsigned i = dpt_idx(c0, k, tid);
+    return i < n && (unsigned)j < n - i;
+}
+
+// one wave: the bin of the 256 counters h that holds rank kk (0-based) and the count below that bin; the same in every lane
+__device__ __forceinline__ void dpt_scan(const unsigned *h, unsigned kk, unsigned &bin, unsigned &below) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const uint4 q = *(const uint4 *)(h + 4 * lane);
+    const unsigned s = (q.x + q.y) + (q.z + q.w);
+    unsigned incl = s;
+#pragma unroll
+    for (int o = 1; o < WAVE; o <<= 1) {
+        const unsigned t = __shfl_up(incl, o);
+        if (lane >= o) incl += t;
+    }
+    const unsigned excl = incl - s;
+    unsigned b = 4 * lane, bl = excl;
+    const bool hit = excl <= kk && kk < incl;
+    if (hit) {
+        if (bl + q.x <= kk) { bl += q.x; ++b;
+            if (bl + q.y <= kk) { bl += q.y; ++b;
+                if (bl + q.z <= kk) { bl += q.z; ++b; } } }
+    }
+    const unsigned long long m = __ballot(hit);
+    const int src = m ? __ffsll((long long)m) - 1 : 0;      // (a row's counters always hold its rank; 0 keeps the reads in range)
+    bin = __shfl(b, src);
+    below = __shfl(bl, src);
+    if (!m) { bin = 0; below = 0; }
+}
+
+// one wave: the key bits fixed by digits 0 .. D-1 of a row's select (every lane gets the same)
+__device__ __forceinline__ unsigned dpt_prefix(const unsigned *hist_row, unsigned n, int D) {
+    unsigned prefix = 0, kk = (n - 1u) / 2u;
+    for (int d = 0; d < D; ++d) {
+        unsigned bin, below;
+        dpt_scan(hist_row + 256 * d, kk, bin, below);
+        prefix |= bin << (24 - 8 * d);
+        kk -= below;
+    }
+    return prefix;
+}
+
+// one wave: the chunk partials part[k * stride], k < nchunks, added in a fixed order (lane l takes k = l, l + 64, ...; then a
+// butterfly, which gives every lane the same bits)
+__device__ __forceinline__ double dpt_sum_partials(const double *part, int nchunks, int stride) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    double s = 0.0;
+    for (int k = lane; k < nchunks; k += WAVE) s += part[(long long)k * stride];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    return s;
+}
+
+// workgroup sum of a double in a fixed order; the total in every thread
+__device__ __forceinline__ double dpt_block_sum(double v, double *red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x / WAVE] = v;
+    __syncthreads();
+    const double t = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return t;
+}
+
+template <int DIGIT>
+__global__ void __launch_bounds__(DPT_THREADS) dpt_hist_kernel(DptArgs A) {
+    __shared__ __attribute__((aligned(16))) unsigned hist[DPT_THREADS / WAVE][256];
+    __shared__ unsigned sh_prefix;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
+    const unsigned c0 = blockIdx.x * (unsigned)DPT_CH;
+    constexpr unsigned pmask = DIGIT == 0 ? 0u : 0xffffffffu << (32 - 8 * DIGIT);
+    constexpr int shift = 24 - 8 * DIGIT;
+    for (int row = blockIdx.y; row < A.rows; row += gridDim.y) {
+        int which;
+        const float *base = dpt_row(A, row, which);
+#pragma unroll
+        for (int w = 0; w < DPT_THREADS / WAVE; ++w) hist[w][tid] = 0;
+        if (DIGIT > 0 && wv == 0) {
+            const unsigned p = dpt_prefix(A.hist + (long long)row * 1024, A.n, DIGIT);
+            if (lane == 0) sh_prefix = p;
+        }
+        __syncthreads();
+        const unsigned prefix = DIGIT > 0 ? sh_prefix : 0u;
+        float v[DPT_PER];
+        dpt_load(base, A.im[which], (unsigned)A.W, c0, A.n, tid, v);
+        unsigned cur = 0, run = 0, nnan = 0;      // runs of one bin (a plateau) go to LDS as one add
+#pragma unroll
+        for (int e = 0; e < DPT_PER; ++e) {
+            if (!dpt_valid(c0, e >> 2, e & 3, tid, A.n)) continue;
+            const unsigned key = dpt_key(v[e]);
+            if (DIGIT == 0) nnan += v[e] != v[e];
+            if ((key & pmask) != prefix) continue;
+            const unsigned b = (key >> shift) & 255u;
+            if (run && b != cur) { atomicAdd(&hist[wv][cur], run); run = 0; }
+            cur = b;
+            ++run;
+        }
+        if (run) atomicAdd(&hist[wv][cur], run);
+        __syncthreads();
+        {
+            const unsigned tot = (hist[0][tid] + hist[1][tid]) + (hist[2][tid] + hist[3][tid]);
+            if (tot) atomicAdd(A.hist + (long long)row * 1024 + 256 * DIGIT + tid, tot);
+        }
+        if (DIGIT == 0) {
+            nnan = wave_sum_u(nnan);
+            if (lane == 0 && nnan) atomicAdd(A.cnt + 4ll * row, nnan);
+        }
+        __syncthreads();
+    }
+}
+
+// launch 5: t of every row, the chunk's partial of sum |p - t|, the counts of p == t, p > t, p < t
+__global__ void __launch_bounds__(DPT_THREADS) dpt_absdev_kernel(DptArgs A) {
+    __shared__ unsigned sh_prefix;
+    __shared__ double red[DPT_THREADS / WAVE];
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
+    const unsigned c0 = blockIdx.x * (unsigned)DPT_CH;
+    for (int row = blockIdx.y; row < A.rows; row += gridDim.y) {
+        int which;
+        const float *base = dpt_row(A, row, which);
+        if (wv == 0) {
+            const unsigned p = dpt_prefix(A.hist + (long long)row * 1024, A.n, 4);
+            if (lane == 0) sh_prefix = p;
+        }
+        __syncthreads();
+        const float t = A.cnt[4ll * row] ? __builtin_nanf("") : dpt_unkey(sh_prefix);
+        float v[DPT_PER];
+        dpt_load(base, A.im[which], (unsigned)A.W, c0, A.n, tid, v);
+        float acc = 0.f;
+        unsigned eq = 0, gt = 0, lt = 0;
+#pragma unroll
+        for (int e = 0; e < DPT_PER; ++e) {
+            if (!dpt_valid(c0, e >> 2, e & 3, tid, A.n)) continue;
+            acc += fabsf(v[e] - t);
+            eq += v[e] == t;
+            gt += v[e] > t;
+            lt += v[e] < t;
+        }
+        const double tot = dpt_block_sum((double)acc, red);
+        eq = wave_sum_u(eq);
+        gt = wave_sum_u(gt);
+        lt = wave_sum_u(lt);
+        if (lane == 0) {
+            if (eq) atomicAdd(A.cnt + 4ll * row + 1, eq);
+            if (gt) atomicAdd(A.cnt + 4ll * row + 2, gt);
+            if (lt) atomicAdd(A.cnt + 4ll * row + 3, lt);
+        }
+        if (tid == 0) {
+            A.part_abs[(long long)row * A.nchunks + blockIdx.x] = tot;
+            if (blockIdx.x == 0) A.tval[row] = t;
+        }
+        __syncthreads();
+    }
+}
+
+// s of a row from its chunk partials (one wave; the same bits wherever it is called)
+__device__ __forceinline__ float dpt_scale_of(const DptArgs &A, int row) {
+    return (float)(dpt_sum_partials(A.part_abs + (long long)row * A.nchunks, A.nchunks, 1) / (double)A.n);
+}
+
+// splat_depth_stats: (t, s) of every row
+__global__ void __launch_bounds__(WAVE) dpt_stats_kernel(DptArgs A) {
+    for (int row = blockIdx.x; row < A.rows; row += gridDim.x) {
+        const float s = dpt_scale_of(A, row);
+        if (threadIdx.x == 0) {
+            A.stats[2ll * row] = A.tval[row];
+            A.stats[2ll * row + 1] = s;
+        }
+    }
+}
+
+struct DptNorm {
+    float tp, sp, tg, sg;
+};
+
+// one wave: the four statistics of frame f
+__device__ __forceinline__ DptNorm dpt_norm(const DptArgs &A, int f) {
+    DptNorm N;
+    N.tp = A.tval[f];
+    N.sp = dpt_scale_of(A, f);
+    if (A.gt_stats) {
+        N.tg = A.gt_stats[2ll * f];
+        N.sg = A.gt_stats[2ll * f + 1];
+    } else {
+        N.tg = A.tval[A.F + f];
+        N.sg = dpt_scale_of(A, A.F + f);
+    }
+    return N;
+}
+
+// launch 6: the chunk's partials of sum d^2, sum d, sum d (p - t_p)
+__global__ void __launch_bounds__(DPT_THREADS) dpt_d_kernel(DptArgs A) {
+    __shared__ DptNorm shN;
+    __shared__ double red[DPT_THREADS / WAVE];
+    const int tid = threadIdx.x, wv = tid / WAVE;
+    const unsigned c0 = blockIdx.x * (unsigned)DPT_CH;
+    for (int f = blockIdx.y; f < A.F; f += gridDim.y) {
+        if (wv == 0) {
+            const DptNorm N = dpt_norm(A, f);
+            if (tid == 0) shN = N;
+        }
+        __syncthreads();
+        const DptNorm N = shN;
+        float p[DPT_PER], g[DPT_PER];
+        dpt_load(A.im[0].p + (long long)f * A.im[0].s0, A.im[0], (unsigned)A.W, c0, A.n, tid, p);
+        dpt_load(A.im[1].p + (long long)f * A.im[1].s0, A.im[1], (unsigned)A.W, c0, A.n, tid, g);
+        float a2 = 0.f, a1 = 0.f, ab = 0.f;
+#pragma unroll
+        for (int e = 0; e < DPT_PER; ++e) {
+            if (!dpt_valid(c0, e >> 2, e & 3, tid, A.n)) continue;
+            const float dp = p[e] - N.tp;
+            const float d = dp / N.sp - (g[e] - N.tg) / N.sg;
+            a2 += d * d;
+            a1 += d;
+            ab += d * dp;
+        }
+        const double s2 = dpt_block_sum((double)a2, red);
+        const double s1 = dpt_block_sum((double)a1, red);
+        const double sb = dpt_block_sum((double)ab, red);
+        if (tid == 0) {
+            double *o = A.part_d + 3 * ((long long)f * A.nchunks + blockIdx.x);
+            o[0] = s2; o[1] = s1; o[2] = sb;
+        }
+        __syncthreads();
+    }
+}
+
+// launch 7: loss_f, A, B from the chunk partials; the frame's outputs (chunk 0); the gradient of the chunk's pixels (grad given)
+__global__ void __launch_bounds__(DPT_THREADS) dpt_grad_kernel(DptArgs A) {
+    __shared__ DptNorm shN;
+    __shared__ float shc[3];          // 2 / n, B / (n s_p^2), the tie pixels' extra term
+    const int tid = threadIdx.x, wv = tid / WAVE;
+    const unsigned c0 = blockIdx.x * (unsigned)DPT_CH;
+    for (int f = blockIdx.y; f < A.F; f += gridDim.y) {
+        if (wv == 0) {
+            const DptNorm N = dpt_norm(A, f);
+            const double *pd = A.part_d + 3ll * f * A.nchunks;
+            const double n = (double)A.n;
+            const double sum2 = dpt_sum_partials(pd, A.nchunks, 3);
+            const double Asum = 2.0 / n * dpt_sum_partials(pd + 1, A.nchunks, 3);
+            const double Bsum = 2.0 / n * dpt_sum_partials(pd + 2, A.nchunks, 3);
+            if (tid == 0) {
+                const unsigned m = A.cnt[4ll * f + 1];
+                const double S = (double)A.cnt[4ll * f + 2] - (double)A.cnt[4ll * f + 3];
+                const double sp = (double)N.sp;
+                const double c1 = Bsum / (n * sp * sp);
+                shN = N;
+                shc[0] = (float)(2.0 / n);
+                shc[1] = (float)c1;
+                shc[2] = (float)((-Asum / sp + c1 * S) / (double)m);
+                if (blockIdx.x == 0) {
+                    const float loss = (float)(sum2 / n);
+                    A.lossf[f] = loss;
+                    if (A.per_frame) A.per_frame[f] = loss;
+                    if (A.stats_out) {
+                        float *o = A.stats_out + 4ll * f;
+                        o[0] = N.tp; o[1] = N.sp; o[2] = N.tg; o[3] = N.sg;
+                    }
+                    if (A.ties_out) A.ties_out[f] = (int32_t)m;
+                }
+            }
+        }
+        __syncthreads();
+        if (A.grad) {
+            const DptNorm N = shN;
+            const float c2n = shc[0], c1 = shc[1], tie = shc[2], gs = A.gscale;
+            float p[DPT_PER], g[DPT_PER];
+            dpt_load(A.im[0].p + (long long)f * A.im[0].s0, A.im[0], (unsigned)A.W, c0, A.n, tid, p);
+            dpt_load(A.im[1].p + (long long)f * A.im[1].s0, A.im[1], (unsigned)A.W, c0, A.n, tid, g);
+            float *gb = A.grad + (long long)f * A.g0;
+            const bool vec = A.glin && (((uintptr_t)gb & 15) == 0);
+#pragma unroll
+            for (int k = 0; k < DPT_PER / 4; ++k) {
+                float o[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float pe = p[4 * k + j];
+                    const float dp = pe - N.tp;
+                    const float d = dp / N.sp - (g[4 * k + j] - N.tg) / N.sg;
+                    float r = (d * c2n) / N.sp;
+                    r -= pe > N.tp ? c1 : (pe < N.tp ? -c1 : 0.f);
+                    if (pe == N.tp) r += tie;
+                    o[j] = gs * r;
+                }
+                const unsigned i = dpt_idx(c0, k, tid);
+                if (vec && i < A.n && A.n - i >= 4u) {
+                    float4 *dst = (float4 *)(gb + i);
+                    float4 q = make_float4(o[0], o[1], o[2], o[3]);
+                    if (A.accumulate) {
+                        const float4 old = *dst;
+                        q.x += old.x; q.y += old.y; q.z += old.z; q.w += old.w;
+                    }
+                    *dst = q;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (!dpt_valid(c0, k, j, tid, A.n)) continue;
+                        float *dst = gb + dpt_off(A.glin, A.g2, A.g3, (unsigned)A.W, i + j);
+                        *dst = A.accumulate ? *dst + o[j] : o[j];
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+int dpt_lin(int H, int W, const int64_t *s) { return (W == 1 || s[3] == 1) && (H == 1 || s[2] == W); }
+
+size_t dpt_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+bool dpt_sizes_ok(int F, int H, int W) {
+    return F >= 1 && H >= 1 && W >= 1 && (long long)H * W <= 0x7fffffffLL && F <= (1 << 24);
+}
+
+// scratch: [hist | cnt] (zeroed together), tval, part_abs, part_d, lossf -- always sized for 2 F rows
+struct DptScratch {
+    size_t hist, cnt, zero_bytes, tval, part_abs, part_d, lossf, total;
+    int nchunks;
+};
+
+DptScratch dpt_scratch(int F, int H, int W) {
+    DptScratch S;
+    const size_t R = 2 * (size_t)F, n = (size_t)H * W;
+    S.nchunks = (int)((n + DPT_CH - 1) / DPT_CH);
+    size_t o = 0;
+    S.hist = o; o += R * 1024 * sizeof(unsigned);
+    S.cnt = o; o += R * 4 * sizeof(unsigned);
+    S.zero_bytes = o;
+    o = dpt_align(o);
+    S.tval = o; o = dpt_align(o + R * sizeof(float));
+    S.part_abs = o; o = dpt_align(o + R * S.nchunks * sizeof(double));
+    S.part_d = o; o = dpt_align(o + (size_t)F * S.nchunks * 3 * sizeof(double));
+    S.lossf = o; o = dpt_align(o + (size_t)F * sizeof(float));
+    S.total = o;
+    return S;
+}
+
+void dpt_bind(DptArgs &A, const DptScratch &S, void *scratch) {
+    char *b = (char *)scratch;
+    A.hist = (unsigned *)(b + S.hist);
+    A.cnt = (unsigned *)(b + S.cnt);
+    A.tval = (float *)(b + S.tval);
+    A.part_abs = (double *)(b + S.part_abs);
+    A.part_d = (double *)(b + S.part_d);
+    A.lossf = (float *)(b + S.lossf);
+    A.nchunks = S.nchunks;
+}
+
+DptImg dpt_img(int H, int W, const float *p, const int64_t *s) {
+    DptImg I;
+    I.p = p; I.s0 = s[0]; I.s2 = s[2]; I.s3 = s[3];
+    I.lin = dpt_lin(H, W, s);
+    return I;
+}
+
+// launches 0 - 5 on A.rows rows
+int dpt_select_rows(const DptArgs &A, const DptScratch &S, void *scratch, hipStream_t s) {
+    SPLAT_CHECK_HIP(hipMemsetAsync(scratch, 0, S.zero_bytes, s));
+    const dim3 grid((unsigned)A.nchunks, (unsigned)std::min(A.rows, DPT_MAX_ROWS_Y)), block(DPT_THREADS);
+    SPLAT_LAUNCH("depth_dpt_hist", dpt_hist_kernel<0>, grid, block, 0, s, A);
+    SPLAT_LAUNCH("depth_dpt_hist", dpt_hist_kernel<1>, grid, block, 0, s, A);
+    SPLAT_LAUNCH("depth_dpt_hist", dpt_hist_kernel<2>, grid, block, 0, s, A);
+    SPLAT_LAUNCH("depth_dpt_hist", dpt_hist_kernel<3>, grid, block, 0, s, A);
+    SPLAT_LAUNCH("depth_dpt_absdev", dpt_absdev_kernel, grid, block, 0, s, A);
+    SPLAT_POST_LAUNCH();
+    return SPLAT_OK;
+}
+
+}  // namespace
+
+extern "C" size_t splat_depth_dpt_scratch_bytes(int F, int H, int W) {
+    if (!dpt_sizes_ok(F, H, W)) return 0;
+    return dpt_scratch(F, H, W).total;
+}
+
+extern "C" int splat_depth_stats(int F, int H, int W, const float *img, const int64_t *strides, float *stats, void *scratch,
+                                 splat_stream_t stream) {
+    SPLAT_CHECK_ARG(F >= 1 && H >= 1 && W >= 1, "bad sizes (F, H, W >= 1)");
+    SPLAT_CHECK_ARG(dpt_sizes_ok(F, H, W), "sizes too large (H W <= 2^31 - 1, F <= 2^24)");
+    SPLAT_CHECK_ARG(img && strides && stats && scratch, "null pointer");
+    for (int k = 0; k < 4; ++k) SPLAT_CHECK_ARG(strides[k] >= 0, "strides must be >= 0");
+    const hipStream_t s = (hipStream_t)stream;
+    const DptScratch S = dpt_scratch(F, H, W);
+    DptArgs A;
+    memset(&A, 0, sizeof(A));
+    A.F = F; A.W = W; A.rows = F; A.n = (unsigned)((long long)H * W);
+    A.im[0] = A.im[1] = dpt_img(H, W, img, strides);
+    A.stats = stats;
+    dpt_bind(A, S, scratch);
+    const int rc = dpt_select_rows(A, S, scratch, s);
+    if (rc) return rc;
+    SPLAT_LAUNCH("depth_dpt_stats", dpt_stats_kernel, dim3((unsigned)std::min(F, DPT_MAX_ROWS_Y)), dim3(WAVE), 0, s, A);
+    SPLAT_POST_LAUNCH();
+    return SPLAT_OK;
+}
+
+extern "C" int splat_depth_dpt_loss_grad(int F, int H, int W, const float *pred, const int64_t *pred_strides, const float *gt,
+                                         const int64_t *gt_strides, const float *gt_stats, float scale, float *grad,
+                                         const int64_t *grad_strides, int accumulate, float *per_frame, float *loss_slot,
+                                         float *stats_out, int32_t *ties_out, void *scratch, splat_stream_t stream) {
+    SPLAT_CHECK_ARG(F >= 1 && H >= 1 && W >= 1, "bad sizes (F, H, W >= 1)");
+    SPLAT_CHECK_ARG(dpt_sizes_ok(F, H, W), "sizes too large (H W <= 2^31 - 1, F <= 2^24)");
+    SPLAT_CHECK_ARG(pred && pred_strides && gt && gt_strides && scratch, "null pointer");
+    for (int k = 0; k < 4; ++k) SPLAT_CHECK_ARG(pred_strides[k] >= 0 && gt_strides[k] >= 0, "strides must be >= 0");
+    if (grad) {
+        SPLAT_CHECK_ARG(grad_strides, "null pointer (grad_strides)");
+        for (int k = 0; k < 4; ++k) SPLAT_CHECK_ARG(grad_strides[k] >= 0, "strides must be >= 0");
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    const DptScratch S = dpt_scratch(F, H, W);
+    DptArgs A;
+    memset(&A, 0, sizeof(A));
+    A.F = F; A.W = W; A.rows = gt_stats ? F : 2 * F; A.n = (unsigned)((long long)H * W);
+    A.im[0] = dpt_img(H, W, pred, pred_strides);
+    A.im[1] = dpt_img(H, W, gt, gt_strides);
+    A.gt_stats = gt_stats;
+    A.gscale = scale / (float)F;
+    A.grad = grad;
+    if (grad) {
+        A.g0 = grad_strides[0]; A.g2 = grad_strides[2]; A.g3 = grad_strides[3];
+        A.glin = dpt_lin(H, W, grad_strides);
+    }
+    A.accumulate = accumulate ? 1 : 0;
+    A.per_frame = per_frame; A.stats_out = stats_out; A.ties_out = ties_out;
+    dpt_bind(A, S, scratch);
+    const int rc = dpt_select_rows(A, S, scratch, s);
+    if (rc) return rc;
+    const unsigned gy = (unsigned)std::min(F, DPT_MAX_ROWS_Y);
+    SPLAT_LAUNCH("depth_dpt_d", dpt_d_kernel, dim3((unsigned)A.nchunks, gy), dim3(DPT_THREADS), 0, s, A);
+    // without a gradient image only the frames' outputs are left: one workgroup per frame
+    SPLAT_LAUNCH("depth_dpt_grad", dpt_grad_kernel, dim3(grad ? (unsigned)A.nchunks : 1u, gy), dim3(DPT_THREADS), 0, s, A);
+    SPLAT_POST_LAUNCH();
+    if (loss_slot) {
+        SPLAT_LAUNCH("depth_dpt_slot", track_loss_slot_kernel, dim3(1), dim3(WAVE), 0, s, F, (const float *)A.lossf, loss_slot);
+        SPLAT_POST_LAUNCH();
+    }
+    return SPLAT_OK;
+}

@@ -4,6 +4,7 @@
 the channel is dim -3, so the trainer's literal call ``ssim(pred.reshape(-1, h, w, 3), ...)`` (src/trainer_fragGS.py:576) slides
 the window over (x, colour) planes, one per image row, and gives the trainer's number.  Inputs are read in place through their
 strides (no copy).  ``dssim_l1`` is the trainer's RGB objective ``(1 - lam) * l1 + lam * (1 - ssim)`` (:575-578) in one launch.
+``track_loss`` is its optical-flow term (:528-569) and ``depth_loss_dpt`` its median-normalised depth term (:589-601).
 There is no CPU fallback.
 """
 from __future__ import annotations
@@ -214,3 +215,113 @@ def track_loss(track_image: torch.Tensor, targets, frame_weights: torch.Tensor, 
     gradient comes from the same launch."""
     _check(track_image, "track_image")
     return _TrackLoss.apply(track_image, targets, frame_weights, float(quantile))
+
+
+# ------------------------------------------------------------------------------------- the median-normalised depth loss
+DEPTH_CHUNK = 4096          # pixels one workgroup of the depth kernels handles (DPT_CH of csrc/loss.hip)
+
+
+def _depth_frames(t: torch.Tensor, name: str) -> torch.Tensor:
+    """the [F, 1, H, W] view the depth kernels read: an [F, 1, H, W] tensor as it is; any other shape is ONE frame of numel
+    pixels (the reference's semantics: the trainer passes [H, W, 1]), viewed as [1, 1, rows, cols] in place where its strides
+    allow a 2-D view (else copied)"""
+    _check(t, name)
+    if t.dim() == 4 and t.shape[1] == 1:
+        return t
+    s = t.squeeze()
+    if s.dim() > 2:
+        try:
+            s = s.view(-1, s.shape[-1])
+        except RuntimeError:
+            s = s.reshape(-1, s.shape[-1])
+    while s.dim() < 2:
+        s = s.unsqueeze(0)
+    return s[None, None]
+
+
+def _depth_scratch(F: int, H: int, W: int, dev) -> torch.Tensor:
+    nbytes = L.lib().splat_depth_dpt_scratch_bytes(F, H, W)
+    if nbytes == 0:
+        raise ValueError(f"depth loss: unsupported sizes (F = {F}, H = {H}, W = {W}; H W <= 2^31 - 1, F <= 2^24)")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+
+
+def _depth_out(t, name: str, n: int, dev, dtype=torch.float32) -> None:
+    if t is None:
+        return
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of {n} elements on the image's device")
+
+
+def depth_stats(img: torch.Tensor) -> torch.Tensor:
+    """[F, 2] = (lower median, mean absolute deviation from it) of every frame of ``img`` [F, 1, H, W] (any strides; any other
+    shape: one frame) -- splat_depth_stats.  For ground-truth depth, which is fixed per video frame: compute once, hand it to
+    ``depth_dpt_loss_grad`` / the training step as ``gt_stats``."""
+    v = _depth_frames(img.detach(), "img")
+    F, _, H, W = v.shape
+    out = torch.empty(F, 2, dtype=torch.float32, device=v.device)
+    L.check(L.lib().splat_depth_stats(F, H, W, L.ptr(v), _strides(v), L.ptr(out), L.ptr(_depth_scratch(F, H, W, v.device)),
+                                      L.stream()))
+    return out
+
+
+def depth_dpt_loss_grad(pred: torch.Tensor, gt: torch.Tensor, scale: float = 1.0, grad: torch.Tensor = None,
+                        accumulate: bool = False, per_frame: torch.Tensor = None, loss_slot: torch.Tensor = None,
+                        gt_stats: torch.Tensor = None, stats: torch.Tensor = None, ties: torch.Tensor = None) -> None:
+    """splat_depth_dpt_loss_grad (include/splat_hip.h) on depth frames ``pred``, ``gt`` [F, 1, H, W] (any strides, read in
+    place).  Each output is optional: ``grad`` (pred's shape, own strides) = scale * d(mean_f loss_f) / d pred, written in full
+    or (accumulate) added; ``per_frame`` [F] = loss_f; ``loss_slot`` (1 element) += mean_f loss_f; ``stats`` [F, 4] = t_p, s_p,
+    t_g, s_g; ``ties`` int32 [F] = the number of pixels equal to the median.  ``gt_stats`` [F, 2]: ``depth_stats(gt)``, cached."""
+    _check(pred, "pred")
+    _check(gt, "gt")
+    if pred.dim() != 4 or pred.shape[1] != 1 or gt.shape != pred.shape:
+        raise ValueError(f"pred and gt must both be [F, 1, H, W], got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    F, _, H, W = pred.shape
+    dev = pred.device
+    if grad is not None:
+        _check(grad, "grad")
+        if grad.shape != pred.shape:
+            raise ValueError(f"grad {tuple(grad.shape)} must have pred's shape {tuple(pred.shape)}")
+    _depth_out(per_frame, "per_frame", F, dev)
+    _depth_out(loss_slot, "loss_slot", 1, dev)
+    _depth_out(gt_stats, "gt_stats", 2 * F, dev)
+    _depth_out(stats, "stats", 4 * F, dev)
+    _depth_out(ties, "ties", F, dev, torch.int32)
+    L.check(L.lib().splat_depth_dpt_loss_grad(F, H, W, L.ptr(pred), _strides(pred), L.ptr(gt), _strides(gt), L.ptr(gt_stats),
+                                              L.cf(scale), L.ptr(grad), _strides(grad) if grad is not None else None,
+                                              1 if accumulate else 0, L.ptr(per_frame), L.ptr(loss_slot), L.ptr(stats),
+                                              L.ptr(ties), L.ptr(_depth_scratch(F, H, W, dev)), L.stream()))
+
+
+class _DepthDPT(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt):
+        loss = torch.zeros(1, dtype=torch.float32, device=pred.device)
+        grad = torch.empty(pred.shape, dtype=torch.float32, device=pred.device) if ctx.needs_input_grad[0] else None
+        depth_dpt_loss_grad(pred.detach(), gt, 1.0, grad, loss_slot=loss)
+        ctx.save_for_backward(grad)
+        return loss[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None
+
+
+def depth_loss_dpt(pred_depth: torch.Tensor, gt_depth: torch.Tensor, weight=None) -> torch.Tensor:
+    """the reference's ``depth_loss_dpt(pred_depth, gt_depth)`` (src/loss.py:184-207; the trainer's depth term,
+    src/trainer_fragGS.py:600): the mean squared difference of the two images after each is shifted by its median and scaled by
+    its mean absolute deviation from it.  A tensor of any shape is one frame of numel pixels (the trainer passes [H, W, 1]);
+    [F, 1, H, W] gives the mean of the F frames' losses.  Strided views are read in place.  Differentiable w.r.t. pred_depth
+    (once), the paths through the median and the scale included; the gradient comes from the same launches.  gt_depth is ground
+    truth: no gradient reaches it.  ``weight`` (which the trainer never passes) is not implemented."""
+    if weight is not None:
+        raise NotImplementedError("depth_loss_dpt: the optional weight map is not implemented (the trainer never passes it)")
+    _check(pred_depth, "pred_depth")
+    _check(gt_depth, "gt_depth")
+    if gt_depth.requires_grad:
+        raise ValueError("depth_loss_dpt: gt_depth is ground truth; detach it (no gradient w.r.t. gt_depth is computed)")
+    if pred_depth.shape != gt_depth.shape:
+        raise ValueError(f"depth_loss_dpt: shapes differ: {tuple(pred_depth.shape)} vs {tuple(gt_depth.shape)}")
+    return _DepthDPT.apply(_depth_frames(pred_depth, "pred_depth"), _depth_frames(gt_depth, "gt_depth"))

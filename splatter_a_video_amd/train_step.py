@@ -18,6 +18,8 @@ K = 5 nearest neighbours + the ARAP energy of the pair (:671-675; src/geometry_u
         splat_l1_loss_grad (the fused_l1=False path)
         LossWeights.track > 0: the 2-D track loss on track_gs (gt["tracks"]) from splat_track_loss_grad; the attribute L1
         covers the A attribute channels only (the fused_l1=False path)
+        LossWeights.depth_dpt > 0: the trainer's depth term depth_loss_dpt (median-normalised) from splat_depth_dpt_loss_grad,
+        on top of (depth > 0) or instead of (depth = 0) the depth L1 (the fused_l1=False path)
     three-set tile backward + Gaussian-side walk        (autograd of render_dynamic_sets)        row a10
         track_gs' per-frame gradient lands next to the ARAP gradient of position(ids2)
     both position gradients -> spline segments          splat_dynamic_positions_batch_backward
@@ -48,7 +50,7 @@ from .dynamics import (GAUSSIAN_MAJOR, SEGMENT_MAJOR, FrameClock, frame_table, p
 from .frames import FrameBatch
 from .gs.fused_ops import compute_sh_into
 from .gs.point_ops import project_point_ortho
-from .losses import dssim_l1_grad, planes, track_loss_grad
+from .losses import depth_dpt_loss_grad, dssim_l1_grad, planes, track_loss_grad
 from .optim import FlatAdam, OwnerShardedAdam, PatternLR
 from .parallel import (FlatGradBucket, OwnerShards, PositionExchangePlan, Zero1Shards, exchange_frames, gather_times, owner_gather,
                        owner_reduce, reduce_densify_batch)
@@ -80,6 +82,8 @@ class DensifyConfig:
 
 @dataclass
 class LossWeights:
+    """weights of the step's loss terms.  The defaults are L1 terms on the three images; the reference trainer's configuration
+    is ``LossWeights(dssim=0.2, track=2.0, depth=0.0, depth_dpt=1.0)``: its depth term is depth_loss_dpt, not an L1."""
     rgb: float = 1.0
     depth: float = 1.0
     attr: float = 1.0
@@ -95,6 +99,14 @@ class LossWeights:
     # channels, and the step takes the unfused L1 path (fused_l1 does not apply)
     track: float = 0.0
     track_quantile: float = 0.98       # masked_l1_loss(..., quantile=0.98): the worst 2 % of the residuals are trimmed
+    # weight of the reference's depth term depth_loss_dpt(depth, gt_depth) (src/trainer_fragGS.py:589-601, src/loss.py:184-207):
+    # the mean squared difference after each image is shifted by its median and scaled by its mean absolute deviation from it,
+    # the mean over the step's local frames.  0: no such term (the step's code path and bits before the term existed).  > 0: the
+    # depth image's gradient is depth * the L1's (skipped at depth = 0) + depth_dpt * this term's (splat_depth_dpt_loss_grad),
+    # gt["depth_stats"] (optional: losses.depth_stats(gt["depth"]), cached) saves selecting the ground truth's median again,
+    # and the step takes the unfused L1 path (fused_l1 does not apply).  The reference trainer puts NO L1 on depth:
+    # LossWeights(dssim=0.2, track=2.0, depth=0.0, depth_dpt=1.0) is its loss, term for term
+    depth_dpt: float = 0.0
 
 
 class _Phases:
@@ -264,6 +276,22 @@ class TrainingStep:
         that mean (unweighted) added to ``slot`` (one launch: splat_track_loss_grad)"""
         track_loss_grad(pred.detach(), tracks, weights, self.w.track_quantile, self.w.track, grad, loss_slot=slot)
 
+    def _depth_loss_grad(self, pred: Tensor, gt: Dict[str, Tensor], sums: Tensor, slot: Tensor) -> Tensor:
+        """(depth_dpt > 0) the depth image's gradient [F, 1, H, W]: depth * the L1's gradient (depth > 0; its sum of |.| added to
+        sums[1]) + depth_dpt * the gradient of the mean over the local frames of depth_loss_dpt(pred_f, gt_f); that mean
+        (unweighted) added to ``slot`` (splat_depth_dpt_loss_grad; gt["depth_stats"], when given, are the cached statistics of
+        the ground-truth frames)"""
+        F, c, H, W = pred.shape
+        target = gt["depth"]
+        if tuple(target.shape) != (F, c, H, W):
+            raise ValueError(f"ground truth must be [{F}, {c}, {H}, {W}]")
+        l1 = self.w.depth != 0
+        g = (self._l1(pred, target, self.w.depth, sums[1:2]) if l1
+             else torch.empty(F, c, H, W, dtype=torch.float32, device=pred.device))
+        depth_dpt_loss_grad(pred.detach(), target, self.w.depth_dpt, g, accumulate=l1, loss_slot=slot,
+                            gt_stats=gt.get("depth_stats"))
+        return g
+
     def _attr_l1(self, pred: Tensor, target: Tensor, grad: Tensor, loss_slot: Tensor) -> None:
         """(track > 0) the attribute L1 over channels 3.. of the attribute set: grad[:, 3:] = attr * the gradient of their mean
         |pred - target| over the local frames, the sum of |.| added to ``loss_slot``; one splat_l1_loss_grad per frame (a frame's
@@ -288,8 +316,9 @@ class TrainingStep:
         """one gradient step on the pairs (times1[f], times2[f]); ``gt``: rgb [F,3,H,W], depth [F,1,H,W], attr [F,3+A,H,W] of
         the frames times1 (attr: track_gs of the pair in its first three channels); with LossWeights.track > 0 also
         tracks: the ``tracks.TrackTargets`` of the F pairs, in pair order (attr's first three channels are then not supervised by
-        the L1).  Returns device scalars (no host sync): the L1 sums of the three images, the ARAP energies (and the track
-        loss).  The order of the pairs inside a step does not change the result;
+        the L1); with LossWeights.depth_dpt > 0 optionally depth_stats [F, 2]: ``losses.depth_stats`` of gt["depth"].  Returns
+        device scalars (no host sync): the L1 sums of the three images, the ARAP energies (and the track loss; "depth_dpt": the
+        mean over the frames of the median-normalised depth loss).  The order of the pairs inside a step does not change the result;
         sorted by times1 the Gaussian-side backward shares its projection / EWA chain between consecutive frames of one spline
         segment."""
         if len(times1) != self.F or len(times2) != self.F:
@@ -342,7 +371,8 @@ class TrainingStep:
                                           grad_sink=sink)
         ph.mark("render_forward")
         dssim = self.w.dssim > 0
-        if self.fused_l1 and not dssim and not track and L.get_option("bwd_quarters"):
+        dpt = self.w.depth_dpt > 0
+        if self.fused_l1 and not dssim and not track and not dpt and L.get_option("bwd_quarters"):
             # the L1 terms' gradient images are never materialised: the tile kernel derives them from the forward's output row and
             # the ground-truth frames where it hoists the image gradient (splat_alpha_blending_backward_batch_sets_l1)
             fsums = torch.empty(F, self.fb.T, 3, dtype=torch.float32, device=self.dev)      # per tile: every entry is written
@@ -351,7 +381,7 @@ class TrainingStep:
             torch.autograd.backward(list(out[:3]), self.fb.l1_placeholders([3, 1, self.C - 4]))
             sums = fsums.sum((0, 1))
         else:
-            sums = torch.zeros(5 if track else (4 if dssim else 3), dtype=torch.float32, device=self.dev)
+            sums = torch.zeros(6 if dpt else (5 if track else (4 if dssim else 3)), dtype=torch.float32, device=self.dev)
             g_rgb = (self._rgb_loss_grad(out[0], gt["rgb"], sums) if dssim else self._l1(out[0], gt["rgb"], self.w.rgb, sums[0:1]))
             if track:
                 # the track channels: the 2-D track loss alone; the attribute channels: their L1
@@ -361,7 +391,9 @@ class TrainingStep:
                 self._attr_l1(out[2], gt["attr"], g_attr, sums[2:3])
             else:
                 g_attr = self._l1(out[2], gt["attr"], self.w.attr, sums[2:3])
-            grads = [g_rgb, self._l1(out[1], gt["depth"], self.w.depth, sums[1:2]), g_attr]
+            g_depth = (self._depth_loss_grad(out[1], gt, sums, sums[5:6]) if dpt
+                       else self._l1(out[1], gt["depth"], self.w.depth, sums[1:2]))
+            grads = [g_rgb, g_depth, g_attr]
             ph.mark("loss")
             torch.autograd.backward(list(out[:3]), grads)
         # ---- both position gradients of every pair (ARAP on ids1 and ids2, track_gs on ids2) reach the spline segments
@@ -406,6 +438,8 @@ class TrainingStep:
             A = self.C - 7
             self.last["l1_attr"] = sums[2] / (F * A * hw) if A > 0 else sums[2]      # A = 0: no attribute term (0)
             self.last["track"] = sums[4]
+        if dpt:
+            self.last["depth_dpt"] = sums[5]
         if self.timing:
             self._marks = ph
         return self.last
@@ -486,6 +520,8 @@ class TrainingStep:
         tot = self.w.rgb * rgb + self.w.depth * l["l1_depth"] + self.w.attr * l["l1_attr"] + self.w.arap * l["arap"]
         if "track" in l:
             tot = tot + self.w.track * l["track"]
+        if "depth_dpt" in l:
+            tot = tot + self.w.depth_dpt * l["depth_dpt"]
         return float(tot)
 
     # ------------------------------------------------------------------ structure
