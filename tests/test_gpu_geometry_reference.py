@@ -8,8 +8,8 @@ tests/test_geometry_ref_cpu.py proves attainable with the float32 C oracle.
 
 Covered: the individual operators, the fused preprocess operators forward and backward (offset, gradient sinks), the
 dynamic evaluation, and the per-Gaussian buffers FrameBatch fills in its forward pass.  The batch's Gaussian-side BACKWARD
-reads per-pair partials from the compositor; it is out of scope here and stays covered by the batch-equals-operators
-tests (tests/test_gpu_frames.py, tests/test_gpu_frames_oracle.py)."""
+reads per-pair records from the compositor: tests/test_gpu_gauss_backward_reference.py calls those kernels on their own,
+with records built by the test, against the same float64 twin and bars."""
 import numpy as np
 import pytest
 import torch
