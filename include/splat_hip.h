@@ -821,6 +821,32 @@ int splat_depth_dpt_loss_grad(int F, int H, int W, const float *pred, const int6
                               const int64_t *grad_strides, int accumulate, float *per_frame, float *loss_slot, float *stats_out,
                               int32_t *ties_out, void *scratch, splat_stream_t stream);
 
+/* ---- point tracking: compositing at sparse sub-pixel points, and the feature rows of a tracking query (csrc/query.hip).
+ *      splat_alpha_blending_points_forward: out [Q, C] = F.grid_sample(alpha_blending(...)[None], grid, mode = "bilinear",
+ *      padding_mode = "zeros", align_corners = True) at Q points, without the dense image.  points [Q, 2] = (ix, iy) are
+ *      grid_sample's UN-NORMALISED sample coordinates: ix is the continuous column index, an integer lands on a stored pixel.
+ *      Corners (x0, y0) = floor, x0 + 1, y0 + 1 in the order nw, ne, sw, se with weights (x1 - ix)(y1 - iy), ...; a corner outside
+ *      [0, W-1] x [0, H-1] contributes nothing (tested in float before any conversion: 1e9 and non-finite points give a row of
+ *      zeros).  Every corner pixel walks its tile's list (tile_range over idx_sorted, as splat_bin_sort leaves them) with the
+ *      forward's decisions bit for bit: the exponent arithmetic is shared (csrc/blend_power.h), alpha = min(0.99, o exp(power)),
+ *      skipped below 1/255, the splat that would take T below 1e-4 ends the pixel unapplied.  feature is [P, C] row-major, any
+ *      C >= 1.  corner_T / corner_ncontrib (each optional, [Q, 4]): final transmittance and 1-based list position of the last
+ *      applied splat of every corner pixel -- the forward's final_T / ncontrib there; 0 for a corner outside.  Q = 0, P = 0
+ *      (the other inputs may then be NULL) and empty tiles are valid: an in-image corner without splats has T = 1.  One workgroup
+ *      per query, one launch per 256 channels; no atomics: bit-reproducible.  Forward only.
+ *      splat_track_flow_rows: rows [P, T, 3] (Gaussian-major: the feature [P, 3 T] of the call above), rows[n, t] =
+ *      (u_t - u_ref, v_t - v_ref, depth_t) with (u_t, v_t, depth_t) the orthographic project_point of get_position at the t-th
+ *      time of tab (a device table of T 64-byte frame entries, as splat_dynamic_positions_batch_forward takes it) and uv_ref [P, 2]
+ *      the projection of the query frame.  A point culled at t (nearest / extent, as the operator culls) has uv_t = depth_t = 0;
+ *      nearest = extent = 0 switches culling off. ---- */
+int splat_alpha_blending_points_forward(int P, int C, const float *uv, const float *conic, const float *opacity,
+                                        const float *feature, const int32_t *idx_sorted, const int32_t *tile_range, float bg,
+                                        int W, int H, int Q, const float *points, float *out, float *corner_T,
+                                        int32_t *corner_ncontrib, splat_stream_t stream);
+int splat_track_flow_rows(int T, int P, int I, const void *tab, const float *position, const float *cubic, int cubic_layout,
+                          const float *extr, int W, int H, float nearest, float extent, const float *uv_ref, float *rows,
+                          splat_stream_t stream);
+
 #define SPLAT_ADAM_MAX_SEGMENTS 16
 int splat_adam_step(int64_t n, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int nseg,
                     const int64_t *seg_end_host, const float *seg_lr_host, float beta1, float beta2, float eps,

@@ -59,6 +59,7 @@ SYMBOLS = [
     "splat_ssim_scratch_bytes", "splat_ssim_forward", "splat_ssim_backward", "splat_dssim_l1_loss_grad",
     "splat_track_loss_scratch_bytes", "splat_track_loss_grad",
     "splat_depth_dpt_scratch_bytes", "splat_depth_stats", "splat_depth_dpt_loss_grad",
+    "splat_alpha_blending_points_forward", "splat_track_flow_rows",
 ]
 
 
@@ -118,6 +119,8 @@ def lib() -> ctypes.CDLL:
         L.splat_depth_dpt_scratch_bytes.argtypes = [i, i, i]
         L.splat_depth_stats.argtypes = [i, i, i, p, s4, p, p, p]
         L.splat_depth_dpt_loss_grad.argtypes = [i, i, i, p, s4, p, s4, p, f, p, s4, i, p, p, p, p, p, p]
+        L.splat_alpha_blending_points_forward.argtypes = [i, i, p, p, p, p, p, p, f, i, i, i, p, p, p, p, p]
+        L.splat_track_flow_rows.argtypes = [i, i, i, p, p, p, i, p, i, i, f, f, p, p, p]
         if L.splat_abi_version() != ABI_VERSION:
             raise SplatError("libsplat_hip.so ABI version mismatch; rebuild it")
         _lib = L

@@ -1,0 +1,277 @@
+// Point tracking: compositing at sparse sub-pixel query points, and the feature rows of a tracking query.
+// Reference semantics: F.grid_sample(alpha_blending(...)[None], grid, mode="bilinear", padding_mode="zeros",
+// align_corners=True) as draw_pixel_trajectory and get_correspondences_and_occlusion_masks_for_pixels_core use it
+// (src/trainer_fragGS.py:1483-1566, :1644-1677) -- without the dense image: only the four bilinear corner pixels of every
+// query walk their tile lists.
+//
+// MI355X design:
+//   * one 256-thread workgroup per query = four waves, wave w = corner w (nw, ne, sw, se).  A corner outside the image
+//     walks nothing.
+//   * the alpha of a list entry does not depend on the transmittance: 64 entries are evaluated at once, lane = entry
+//     (gather of uv / conic / opacity by id, power_coeffs + power_poly + exp2_guard of blend_power.h: the forward's bits).
+//   * the transmittance chain T <- T (1 - alpha) is the forward's, in list order, over the entries that passed alpha >= 1/255
+//     only (ballot), on wave-uniform values read out of the lanes; an applied entry leaves its weight alpha T in its lane.
+//   * then lanes are CHANNELS: the applied entries' feature rows are read one coalesced row per entry (four rows in flight)
+//     and accumulated F[c] += f[id, c] w in list order, ceil(cn / 64) <= NA accumulators per lane; rows wider than 64 NA
+//     channels take one launch per chunk.
+//   * the four corner values (F + T bg) meet in LDS and are combined nw, ne, sw, se with the bilinear weights.  No
+//     atomics anywhere: results are bit-reproducible.
+#include "blend_power.h"
+#include "dynamics_dev.h"
+#include "pointwise_dev.h"
+
+namespace {
+
+constexpr int PT_NA_MAX = 4;                  // accumulators per lane: channel chunks of at most 256
+constexpr int PT_CHUNK = 64 * PT_NA_MAX;
+
+struct PointsArgs {
+    int P, C, c0, cn;
+    const float2 *uv;
+    const float *conic, *opacity, *feature;
+    const int *idx_sorted;
+    const int2 *tile_range;
+    float bg;
+    int W, H, gx;
+    const float2 *points;
+    float *out;       // [Q, C]
+    float *corner_T;  // [Q, 4] or NULL
+    int *corner_n;    // [Q, 4] or NULL
+};
+
+__device__ __forceinline__ float lane_f(float v, int j) {
+    return __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(v), j));
+}
+
+template <int NA>
+__global__ void __launch_bounds__(256) points_fwd_kernel(const PointsArgs A) {
+    __shared__ float s_val[4][64 * NA];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave = corner: uniform, so the walk below branches on scalars
+    const size_t q = blockIdx.x;
+    const float2 pt = A.points[q];
+    // corner w of the query: the in / out test in float, before any conversion to int (1e9, inf and NaN are simply outside)
+    const float x0f = floorf(pt.x), y0f = floorf(pt.y);
+    const float cxf = x0f + (float)(w & 1), cyf = y0f + (float)(w >> 1);
+    const bool in = cxf >= 0.f && cxf <= (float)(A.W - 1) && cyf >= 0.f && cyf <= (float)(A.H - 1);
+
+    float T = 1.f;
+    int last = 0;
+    float F[NA];
+#pragma unroll
+    for (int k = 0; k < NA; ++k) F[k] = 0.f;
+
+    if (in) {
+        const int px = (int)cxf, py = (int)cyf;
+        const int tx = px / TILE, ty = py / TILE;
+        int2 range = make_int2(0, 0);
+        if (A.P > 0) range = A.tile_range[ty * A.gx + tx];
+        const int n = imax_(range.y - range.x, 0);
+        // pixel relative to the tile centre and its monomials (exact in f32), the tile centre as the forward forms it
+        const float x = (float)(px - tx * TILE) - 7.5f, y = (float)(py - ty * TILE) - 7.5f;
+        const float xx = x * x, xy = x * y, yy = y * y;
+        const float tcx = (float)(tx * TILE) + 7.5f, tcy = (float)(ty * TILE) + 7.5f;
+        bool done = false;
+        for (int base = 0; base < n && !done; base += WAVE) {
+            // ---- lane = entry: its alpha on this pixel
+            const int e = base + lane;
+            int id = 0;
+            float alpha = 0.f;
+            bool aok = false;
+            if (e < n) {
+                id = A.idx_sorted[range.x + e];
+                if ((unsigned)id < (unsigned)A.P) {   // (an id outside the set is skipped, never dereferenced)
+                    const float2 c = A.uv[id];
+                    const float cA = A.conic[3 * (size_t)id], cB = A.conic[3 * (size_t)id + 1], cC = A.conic[3 * (size_t)id + 2];
+                    const PowerCoef k = power_coeffs(c.x, c.y, cA, cB, cC, A.opacity[id], tcx, tcy);
+                    const float pw = power_poly(make_float4(k.q0, k.qx, k.qy, k.qxx), make_float4(k.qxy, k.qyy, 0.f, 0.f), x, y, xx, xy, yy);
+                    bool pw_ok;
+                    const float a = fminf(0.99f, exp2_guard(pw, pw_ok));
+                    aok = pw_ok && !(a < (1.0f / 255.0f));
+                    alpha = aok ? a : 0.f;
+                } else {
+                    id = 0;
+                }
+            }
+            // ---- the transmittance chain over the entries that touch the pixel, in list order (wave-uniform values)
+            unsigned long long cand = __ballot(aok), applied = 0ull;
+            float wv = 0.f;   // lane j: weight alpha T of entry base + j, if it applied
+            while (cand) {
+                const int j = (int)__builtin_ctzll(cand);
+                cand &= cand - 1ull;
+                const float a = lane_f(alpha, j);
+                const float nT = T * (1.f - a);
+                if (nT < 0.0001f) {   // the splat that would take T below 1e-4 ends the pixel, unapplied
+                    done = true;
+                    break;
+                }
+                const float wgt = a * T;
+                wv = lane == j ? wgt : wv;
+                T = nT;
+                last = base + j + 1;
+                applied |= 1ull << j;
+            }
+            // ---- lane = channel: the applied entries' rows, four in flight, accumulated in list order
+            const float *fbase = A.feature + A.c0 + lane;
+            while (__popcll(applied) >= 4) {
+                int jj[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    jj[u] = (int)__builtin_ctzll(applied);
+                    applied &= applied - 1ull;
+                }
+                float f[4][NA], wg[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float *row = fbase + (size_t)__builtin_amdgcn_readlane(id, jj[u]) * (size_t)A.C;
+                    wg[u] = lane_f(wv, jj[u]);
+#pragma unroll
+                    for (int k = 0; k < NA; ++k) f[u][k] = (lane + 64 * k < A.cn) ? row[64 * k] : 0.f;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int k = 0; k < NA; ++k) F[k] = __builtin_fmaf(f[u][k], wg[u], F[k]);
+            }
+            while (applied) {
+                const int j = (int)__builtin_ctzll(applied);
+                applied &= applied - 1ull;
+                const float *row = fbase + (size_t)__builtin_amdgcn_readlane(id, j) * (size_t)A.C;
+                const float wg = lane_f(wv, j);
+#pragma unroll
+                for (int k = 0; k < NA; ++k) {
+                    const float f = (lane + 64 * k < A.cn) ? row[64 * k] : 0.f;
+                    F[k] = __builtin_fmaf(f, wg, F[k]);
+                }
+            }
+        }
+        if (lane == 0) {
+            if (A.corner_T) A.corner_T[q * 4 + w] = T;
+            if (A.corner_n) A.corner_n[q * 4 + w] = last;
+        }
+    } else if (lane == 0) {
+        if (A.corner_T) A.corner_T[q * 4 + w] = 0.f;
+        if (A.corner_n) A.corner_n[q * 4 + w] = 0;
+    }
+    // ---- the four corners meet: value = F + T bg, combined nw, ne, sw, se with the bilinear weights
+#pragma unroll
+    for (int k = 0; k < NA; ++k) s_val[w][64 * k + lane] = F[k] + T * A.bg;
+    __syncthreads();
+    const float x1f = x0f + 1.f, y1f = y0f + 1.f;
+    const float wx[2] = {x1f - pt.x, pt.x - x0f}, wy[2] = {y1f - pt.y, pt.y - y0f};
+    bool cin[4];
+    float cw[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float cx = x0f + (float)(k & 1), cy = y0f + (float)(k >> 1);
+        cin[k] = cx >= 0.f && cx <= (float)(A.W - 1) && cy >= 0.f && cy <= (float)(A.H - 1);
+        cw[k] = wx[k & 1] * wy[k >> 1];
+    }
+    for (int c = tid; c < A.cn; c += 256) {
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (cin[k]) acc += s_val[k][c] * cw[k];   // a corner outside the image contributes nothing
+        A.out[q * (size_t)A.C + A.c0 + c] = acc;
+    }
+}
+
+template <int NA>
+int launch_points(const PointsArgs &A, int Q, hipStream_t s) {
+    SPLAT_LAUNCH("blend_points", points_fwd_kernel<NA>, dim3((unsigned)Q), dim3(256), 0, s, A);
+    SPLAT_POST_LAUNCH();
+    return SPLAT_OK;
+}
+
+// rows[n, t] = (u_t - u_ref, v_t - v_ref, depth_t) of Gaussian n at the t-th time of the table: get_position(t) (the segment
+// polynomial of dynamic_eval_fwd_kernel) through the orthographic project_point.  One thread per (n, t): consecutive threads
+// write consecutive 12-byte entries of a Gaussian's row.
+__global__ void __launch_bounds__(DYN_BLOCK) track_flow_rows_kernel(int T, int P, int I, int layout, const DynTab *__restrict__ tab,
+                                                                    const float *__restrict__ position, const float *__restrict__ cubic,
+                                                                    const float *__restrict__ extr, int W, int H, float nearest,
+                                                                    float extent, int no_cull, const float2 *__restrict__ uv_ref,
+                                                                    float *__restrict__ rows) {
+    const size_t i = (size_t)blockIdx.x * DYN_BLOCK + threadIdx.x;
+    if (i >= (size_t)P * (size_t)T) return;
+    const size_t n = i / (size_t)T;
+    const int t = (int)(i - n * (size_t)T);
+    const int seg = imin_(imax_(tab[t].seg, 0), I - 1);   // (a segment outside the table is clamped, never dereferenced)
+    const CubicAddr ca = cubic_addr(layout, P, I, seg);
+    const float d = tab[t].d;
+    float p3[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float *c = cubic + ca.seg_off + n * ca.stride_n + j;
+        const size_t row = ca.stride_k;
+        const float c0 = c[0], c1 = c[row], c2 = c[2 * row], c3 = c[3 * row];
+        float p = c3 + c2 * d;
+        p = p + c1 * (d * d);
+        p = p + c0 * (d * d * d);
+        p3[j] = p + position[n * 3 + j];
+    }
+    Cam cam;
+    load_cam(nullptr, extr, cam);
+    float u, v, dep;
+    const bool cull = project_ortho_pt(cam, p3[0], p3[1], p3[2], W, H, nearest, extent, u, v, dep) && !no_cull;
+    u = cull ? 0.f : u; v = cull ? 0.f : v; dep = cull ? 0.f : dep;
+    const float2 r = uv_ref[n];
+    float *o = rows + i * 3;
+    o[0] = u - r.x;
+    o[1] = v - r.y;
+    o[2] = dep;
+}
+
+}  // namespace
+
+extern "C" int splat_alpha_blending_points_forward(int P, int C, const float *uv, const float *conic, const float *opacity,
+                                                   const float *feature, const int32_t *idx_sorted, const int32_t *tile_range,
+                                                   float bg, int W, int H, int Q, const float *points, float *out,
+                                                   float *corner_T, int32_t *corner_ncontrib, splat_stream_t stream) {
+    SPLAT_CHECK_ARG(P >= 0 && C >= 1 && W > 0 && H > 0 && Q >= 0, "bad sizes (P, Q >= 0, C, W, H >= 1)");
+    SPLAT_CHECK_ARG(W <= (1 << 24) && H <= (1 << 24), "sizes too large (W, H <= 2^24: pixel indices are compared in float32)");
+    if (Q == 0) return SPLAT_OK;
+    SPLAT_CHECK_ARG(points && out, "null pointer (points / out)");
+    // idx_sorted may be NULL when no Gaussian touches any tile (every tile range is empty, nothing dereferences it)
+    SPLAT_CHECK_ARG(P == 0 || (uv && conic && opacity && feature && tile_range), "null pointer");
+    PointsArgs A;
+    memset(&A, 0, sizeof(A));
+    A.P = P; A.C = C;
+    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
+    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
+    A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
+    A.points = (const float2 *)points;
+    A.out = out;
+    for (int c0 = 0; c0 < C; c0 += PT_CHUNK) {
+        A.c0 = c0;
+        A.cn = C - c0 > PT_CHUNK ? PT_CHUNK : C - c0;
+        A.corner_T = c0 == 0 ? corner_T : nullptr;   // every chunk walks the same lists: the first one reports them
+        A.corner_n = c0 == 0 ? corner_ncontrib : nullptr;
+        int rc;
+        switch ((A.cn + 63) / 64) {
+            case 1: rc = launch_points<1>(A, Q, (hipStream_t)stream); break;
+            case 2: rc = launch_points<2>(A, Q, (hipStream_t)stream); break;
+            case 3: rc = launch_points<3>(A, Q, (hipStream_t)stream); break;
+            default: rc = launch_points<4>(A, Q, (hipStream_t)stream); break;
+        }
+        if (rc != SPLAT_OK) return rc;
+    }
+    return SPLAT_OK;
+}
+
+extern "C" int splat_track_flow_rows(int T, int P, int I, const void *tab, const float *position, const float *cubic,
+                                     int cubic_layout, const float *extr, int W, int H, float nearest, float extent,
+                                     const float *uv_ref, float *rows, splat_stream_t stream) {
+    SPLAT_CHECK_ARG(T >= 0 && P >= 0 && I >= 1 && W > 0 && H > 0, "bad sizes (T, P >= 0, I, W, H >= 1)");
+    SPLAT_CHECK_ARG(cubic_layout == SPLAT_CUBIC_GAUSSIAN_MAJOR || cubic_layout == SPLAT_CUBIC_SEGMENT_MAJOR, "unknown cubic_layout");
+    SPLAT_CHECK_ARG(nearest == nearest && extent == extent, "nearest / extent must not be NaN");
+    if (T == 0 || P == 0) return SPLAT_OK;
+    SPLAT_CHECK_ARG(tab && position && cubic && extr && uv_ref && rows, "null pointer");
+    const size_t total = (size_t)P * (size_t)T;
+    SPLAT_CHECK_ARG((total + DYN_BLOCK - 1) / DYN_BLOCK <= 0x7fffffffull, "sizes too large");
+    const int no_cull = (nearest == 0.f && extent == 0.f) ? 1 : 0;   // nearest = extent = 0: culling switched off
+    SPLAT_LAUNCH("track_flow_rows", track_flow_rows_kernel, dim3((unsigned)((total + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0,
+                 (hipStream_t)stream, T, P, I, cubic_layout, (const DynTab *)tab, position, cubic, extr, W, H, nearest, extent, no_cull,
+                 (const float2 *)uv_ref, rows);
+    SPLAT_POST_LAUNCH();
+    return SPLAT_OK;
+}

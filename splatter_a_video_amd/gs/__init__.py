@@ -4,8 +4,8 @@ through the top-level ``dptr`` shim package of this repository."""
 from .point_ops import (compute_cov3d, compute_sh, compute_sh_free, ewa_project, ewa_project_ortho, project_point,
                         project_point_ortho)
 from .fused_ops import compute_sh_into, preprocess_ortho, preprocess_persp
-from .raster_ops import (SortStatus, alpha_blending, alpha_blending_shared, alpha_blending_enhanced, alpha_blending_with_bias, rasterization,
-                         rasterization_ortho, sort_gaussian, sort_gaussian_capped)
+from .raster_ops import (SortStatus, alpha_blending, alpha_blending_points, alpha_blending_shared, alpha_blending_enhanced,
+                         alpha_blending_with_bias, rasterization, rasterization_ortho, sort_gaussian, sort_gaussian_capped)
 
 __all__ = [
     "project_point",
@@ -29,4 +29,6 @@ __all__ = [
     "sort_gaussian_capped",
     "SortStatus",
     "rasterization_ortho",
+    # compositing at sparse sub-pixel points (point tracking: splatter_a_video_amd.tracking)
+    "alpha_blending_points",
 ]

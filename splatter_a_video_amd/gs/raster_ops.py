@@ -369,6 +369,57 @@ def alpha_blending_with_bias(uv: Tensor, conic: Tensor, opacity: Tensor, feature
                              abs_ndc, 0, False)
 
 
+# ------------------------------------------------------------------ compositing at sparse sub-pixel points (forward only)
+def alpha_blending_points(uv: Tensor, conic: Tensor, opacity: Tensor, feature: Tensor, idx_sorted: Tensor, tile_range: Tensor,
+                          bg: float, W: int, H: int, points: Tensor, return_corners: bool = False):
+    """``F.grid_sample(alpha_blending(uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H)[None], grid,
+    mode="bilinear", padding_mode="zeros", align_corners=True)`` at ``points`` [Q, 2] without the dense image: [Q, C].
+
+    ``points[:, 0]`` = ix, the continuous column index, ``points[:, 1]`` = iy (grid_sample's un-normalised sample coordinates:
+    an integer lands on a stored pixel).  Only the four bilinear corner pixels of every point walk their tile lists, with the
+    dense forward's decisions bit for bit; a corner outside the image contributes nothing, a point far outside or not finite
+    gives a row of zeros.  ``feature`` [P, C] may be any width (one coalesced row read per applied splat).
+    ``return_corners``: also ``corner_T`` [Q, 4] float32 and ``corner_ncontrib`` [Q, 4] int32, the dense forward's final
+    transmittance and ncontrib at the corner pixels nw, ne, sw, se (0 for a corner outside).
+    Forward only: an input that requires grad raises ``ValueError``."""
+    named = (("uv", uv), ("conic", conic), ("opacity", opacity), ("feature", feature), ("points", points))
+    for name, t in named:
+        if isinstance(t, Tensor) and t.requires_grad:
+            raise ValueError(f"alpha_blending_points is forward only: {name} requires grad (detach it or use torch.no_grad())")
+    uv = L.need(uv, "uv")
+    conic = L.need(conic, "conic")
+    opacity = L.need(opacity, "opacity")
+    feature = L.need(feature, "feature")
+    idx_sorted = L.need(idx_sorted, "idx_sorted", torch.int32)
+    tile_range = L.need(tile_range, "tile_range", torch.int32)
+    points = L.need(points, "points")
+    W, H = int(W), int(H)
+    if W < 1 or H < 1:
+        raise ValueError("W and H must be >= 1")
+    if feature.dim() != 2:
+        raise ValueError("feature must have shape [P, C]")
+    P, C = feature.shape
+    if C < 1:
+        raise ValueError("feature needs at least one channel")
+    if uv.numel() != 2 * P or conic.numel() != 3 * P or opacity.numel() != P:
+        raise ValueError("uv [P,2] / conic [P,3] / opacity [P] / feature [P,C] must agree on P")
+    if tile_range.numel() != 2 * _num_tiles(W, H):
+        raise ValueError("tile_range must have shape [ceil(W/16)*ceil(H/16), 2]")
+    if points.dim() != 2 or points.shape[1] != 2:
+        raise ValueError("points must have shape [Q, 2] = (ix, iy)")
+    Q = points.shape[0]
+    dev = feature.device
+    out = torch.empty(Q, C, dtype=torch.float32, device=dev)
+    corner_T = torch.empty(Q, 4, dtype=torch.float32, device=dev) if return_corners else None
+    corner_n = torch.empty(Q, 4, dtype=torch.int32, device=dev) if return_corners else None
+    L.check(L.lib().splat_alpha_blending_points_forward(
+        L.ci(P), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(idx_sorted), L.ptr(tile_range), L.cf(bg),
+        L.ci(W), L.ci(H), L.ci(Q), L.ptr(points), L.ptr(out), L.ptr(corner_T), L.ptr(corner_n), L.stream()))
+    if return_corners:
+        return out, corner_T, corner_n
+    return out
+
+
 _BG_CHANNELS = {}
 
 

@@ -1,0 +1,173 @@
+"""gs.alpha_blending_points (csrc/query.hip) against the dense route: the existing alpha_blending image sampled by the float64
+reference of tests/track_query_ref.py, and the raw splat_alpha_blending_forward's final_T / ncontrib at the corner pixels.
+
+Tolerance of the sampled values: 1e-5 (1 + S) + 1e-4 |ref| with S = the same sample of a dense render of |feature| -- the project's
+image tolerance (atol 1e-5 + rtol 1e-4), the absolute part scaled by the magnitude of what is summed.  corner_T and
+corner_ncontrib are compared bit for bit.  Points sit on eighths, so the bilinear weights are exact in float32."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import dptr.gs as gs
+import track_query_ref as R
+from splatter_a_video_amd import _lib as L
+from splatter_a_video_amd.synth import make_scene
+
+pytestmark = pytest.mark.gpu
+
+SCENES = {"1500_100x60": (1500, 100, 60, 11, False), "64_32x32": (64, 32, 32, 12, False), "left_half_128x64": (1600, 128, 64, 13, True)}
+
+
+def _t(a, dtype=np.float32):
+    return torch.tensor(np.ascontiguousarray(a, dtype=dtype), device="cuda")
+
+
+@functools.lru_cache(maxsize=None)
+def _scene(name):
+    """geometry of a seeded scene, sorted once: (uv, conic, opacity, idx_sorted, tile_range, N, W, H)"""
+    N, W, H, seed, left = SCENES[name]
+    sc = make_scene(N, W, H, seed=seed)
+    keep = sc.xyz[:, 0] < -0.3 if left else np.ones(N, bool)      # left: nothing reaches the right tile columns
+    xyz, scale, rot, op = sc.xyz[keep], sc.scale[keep], sc.rotate[keep], sc.opacity[keep]
+    uv, depth, conic, radius, tiles = gs.preprocess_ortho(_t(xyz), _t(scale), _t(rot), _t(sc.extr), W, H, nearest=0.01)
+    idx, tr = gs.sort_gaussian(uv, depth, W, H, radius, tiles)
+    if left:
+        trn = tr.cpu().numpy().reshape(-1, 2)
+        gx = (W + 15) // 16
+        assert (trn[:, 1] - trn[:, 0]).reshape(-1, gx)[:, gx - 2:].max() == 0, "the right tile columns must be empty"
+    return uv, conic, _t(op), idx, tr, int(keep.sum()), W, H
+
+
+def _query_points(W, H, seed):
+    """64 points on eighths: every place the kernel can go wrong"""
+    rng = np.random.default_rng(seed)
+    nan, inf = float("nan"), float("inf")
+    pts = [[0, 0], [3, 5], [W - 2, 1], [17, H - 2],                                       # integer pixels
+           [15.5, 15.5], [15, 16], [16, 15], [15.5, 16], [16, 16], [15.875, 15.125], [31.5, 15.5],   # straddling tile corners
+           [W - 1, H - 1], [W - 1, 0], [0, H - 1], [W - 1.5, H - 1.5], [W - 1, H - 1.25],          # the last pixel
+           [-0.5, 3], [W - 0.5, 5.25], [3.5, -0.125], [7.25, H - 0.125],                  # two corners outside
+           [-0.25, -0.25], [W - 0.5, H - 0.5], [-0.75, H - 0.5], [W - 0.125, -0.875],     # three corners outside
+           [-1, 2], [W, 3], [2, H], [-5, -5], [W + 2.5, H + 1], [-1.125, -3],             # fully outside
+           [1e9, 1e9], [1e9, 2], [-1e9, 3], [4, -1e9], [3e38, 1],                          # far outside
+           [nan, 3], [3, nan], [nan, nan], [inf, 2], [2, -inf],                           # not finite
+           [W - 8.5, H // 2 + 0.25], [W - 20.125, 3.5]]                                   # (left-half scene: an empty tile)
+    extra = np.round(rng.uniform(0, [W - 1, H - 1], size=(64 - len(pts), 2)) * 8) / 8     # eighths
+    pts = np.concatenate([np.asarray(pts, np.float64), extra]).astype(np.float32)
+    assert pts.shape == (64, 2)
+    return pts
+
+
+def _dense(geom, feat, bg):
+    """(image [C,H,W], final_T [H,W], ncontrib [H,W]): the existing operator, and the raw forward for the two per-pixel maps"""
+    uv, conic, op, idx, tr, N, W, H = geom
+    C = feat.shape[1]
+    img = gs.alpha_blending(uv, conic, op, feat, idx, tr, bg, W, H)
+    lib = L.lib()
+    out = torch.empty(C, H, W, device="cuda"); fT = torch.empty(H, W, device="cuda")
+    nc = torch.empty(H, W, dtype=torch.int32, device="cuda")
+    pack = torch.empty(max(N, 1) * lib.splat_blend_pack_floats(C), device="cuda")
+    L.check(lib.splat_alpha_blending_forward(
+        L.ci(N), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(op), L.ptr(feat), L.ptr(None), L.ptr(idx), L.ptr(tr), L.cf(bg),
+        L.ptr(None), L.ci(W), L.ci(H), L.ci(0), L.ci(0), L.ptr(out), L.ptr(fT), L.ptr(nc), L.ptr(None), L.ptr(pack), L.stream()))
+    assert torch.equal(out, img)
+    return img.cpu().numpy(), fT.cpu().numpy(), nc.cpu().numpy()
+
+
+def _check(geom, feat, bg, pts):
+    uv, conic, op, idx, tr, N, W, H = geom
+    img, fT, nc = _dense(geom, feat, bg)
+    mag = gs.alpha_blending(uv, conic, op, feat.abs(), idx, tr, abs(bg), W, H).cpu().numpy()
+    p = _t(pts)
+    out, cT, cn = gs.alpha_blending_points(uv, conic, op, feat, idx, tr, bg, W, H, p, return_corners=True)
+    junk = torch.empty(1234567, device="cuda")                       # (shifts the allocator)
+    out2, cT2, cn2 = gs.alpha_blending_points(uv, conic, op, feat, idx, tr, bg, W, H, p, return_corners=True)
+    only = gs.alpha_blending_points(uv, conic, op, feat, idx, tr, bg, W, H, p)
+    del junk
+    # 3. run to run, bit for bit (NaN-free outputs: equal means equal)
+    assert torch.equal(out, out2) and torch.equal(cT, cT2) and torch.equal(cn, cn2) and torch.equal(out, only)
+    # 1. the forward's decisions at the corner pixels, bit for bit; nothing at a corner outside
+    xi, yi, inside = R.corner_pixels(pts, W, H)
+    want_T = np.where(inside, fT[yi, xi], np.float32(0))
+    want_n = np.where(inside, nc[yi, xi], 0)
+    assert np.array_equal(cT.cpu().numpy().view(np.uint32), want_T.astype(np.float32).view(np.uint32))
+    assert np.array_equal(cn.cpu().numpy(), want_n.astype(np.int32))
+    # 2. the sampled values
+    ref, S = R.sample_points(img, pts), R.sample_points(mag, pts)
+    got = out.cpu().numpy().astype(np.float64)
+    assert got.shape == (pts.shape[0], feat.shape[1]) and np.isfinite(got).all()
+    tol = 1e-5 * (1 + S) + 1e-4 * np.abs(ref)
+    err = np.abs(got - ref)
+    print(f"C={feat.shape[1]} bg={bg}: max err {err.max():.3e}, max err / tol {np.max(err / tol):.3f}, max |ref| {np.abs(ref).max():.3f}")
+    assert (err <= tol).all(), f"{int((err > tol).sum())} values off, worst {np.max(err / tol):.2f} x the tolerance"
+    assert (got[~inside.any(1)] == 0).all() and (~inside.any(1)).sum() >= 15      # fully outside: rows of zeros
+    return inside
+
+
+@pytest.mark.parametrize("bg", [0.0, 1.0])
+@pytest.mark.parametrize("C", [1, 3, 64, 65, 150])
+@pytest.mark.parametrize("scene", list(SCENES))
+def test_points_match_the_dense_route(scene, C, bg):
+    geom = _scene(scene)
+    N, W, H = geom[5:]
+    rng = np.random.default_rng(1000 * C + len(scene))
+    feat = _t(rng.uniform(-1, 1, size=(N, C)))
+    pts = _query_points(W, H, seed=C)
+    inside = _check(geom, feat, bg, pts)
+    assert inside.all(1).sum() >= 25 and (inside.any(1) & ~inside.all(1)).sum() >= 8
+
+
+def test_rows_wider_than_one_launch_and_an_empty_tile_reads_the_background():
+    """C = 300: two launches (256 + 44 channels); on the left-half scene a point in an empty tile is bg times its in-image weights"""
+    geom = _scene("left_half_128x64")
+    uv, conic, op, idx, tr, N, W, H = geom
+    rng = np.random.default_rng(5)
+    feat = _t(rng.uniform(-1, 1, size=(N, 300)))
+    pts = _query_points(W, H, seed=300)
+    _check(geom, feat, 1.0, pts)
+    empty = _t([[W - 8.5, H // 2 + 0.25], [W - 0.5, 20], [W - 3, H - 0.25]])
+    out, cT, cn = gs.alpha_blending_points(uv, conic, op, feat, idx, tr, 0.75, W, H, empty, return_corners=True)
+    want = np.array([0.75, 0.75 * 0.5, 0.75 * 0.25], np.float32)
+    assert np.array_equal(out.cpu().numpy(), np.repeat(want[:, None], 300, 1))
+    assert cn.abs().max().item() == 0
+    assert cT.cpu().numpy().tolist() == [[1, 1, 1, 1], [1, 0, 1, 0], [1, 1, 0, 0]]
+
+
+def test_no_queries_and_no_gaussians_are_valid():
+    geom = _scene("64_32x32")
+    uv, conic, op, idx, tr, N, W, H = geom
+    feat = torch.ones(N, 5, device="cuda")
+    out, cT, cn = gs.alpha_blending_points(uv, conic, op, feat, idx, tr, 0.5, W, H, torch.empty(0, 2, device="cuda"), return_corners=True)
+    assert out.shape == (0, 5) and cT.shape == (0, 4) and cn.shape == (0, 4) and cn.dtype == torch.int32
+    # P = 0: every in-image corner has T = 1 and the value is bg times the in-image weights
+    z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device="cuda")
+    pts = _query_points(W, H, seed=0)
+    out, cT, cn = gs.alpha_blending_points(z(0, 2), z(0, 3), z(0, 1), z(0, 4), z(0, dt=torch.int32), z(4, 2, dt=torch.int32), 0.5, W, H,
+                                           _t(pts), return_corners=True)
+    ref = R.sample_points(np.full((4, H, W), 0.5), pts)
+    assert np.abs(out.cpu().numpy() - ref).max() <= 1e-6
+    _, _, inside = R.corner_pixels(pts, W, H)
+    assert np.array_equal(cT.cpu().numpy(), inside.astype(np.float32)) and cn.abs().max().item() == 0
+    # an empty list with Gaussians present (nothing sorted into any tile)
+    out2 = gs.alpha_blending_points(uv, conic, op, feat[:, :4].contiguous(), z(0, dt=torch.int32), z(4, 2, dt=torch.int32), 0.5, W, H, _t(pts))
+    assert torch.equal(out2, out)
+
+
+def test_shape_and_dtype_checks():
+    geom = _scene("64_32x32")
+    uv, conic, op, idx, tr, N, W, H = geom
+    feat = torch.ones(N, 2, device="cuda")
+    pts = torch.zeros(3, 2, device="cuda")
+    with pytest.raises(ValueError):
+        gs.alpha_blending_points(uv, conic, op, feat, idx, tr, 0.0, W, H, torch.zeros(3, 3, device="cuda"))
+    with pytest.raises(ValueError):
+        gs.alpha_blending_points(uv, conic, op, feat[:-1], idx, tr, 0.0, W, H, pts)
+    with pytest.raises(ValueError):
+        gs.alpha_blending_points(uv, conic, op, feat, idx, tr[:-1], 0.0, W, H, pts)
+    with pytest.raises(ValueError):
+        gs.alpha_blending_points(uv, conic, op, feat, idx.long(), tr, 0.0, W, H, pts)
+    with pytest.raises(ValueError):
+        gs.alpha_blending_points(uv, conic, op, feat.double(), idx, tr, 0.0, W, H, pts)
+    with pytest.raises(ValueError, match="forward only"):
+        gs.alpha_blending_points(uv, conic, op, feat.clone().requires_grad_(True), idx, tr, 0.0, W, H, pts)
