@@ -833,7 +833,23 @@ int splat_depth_dpt_loss_grad(int F, int H, int W, const float *pred, const int6
  *      C >= 1.  corner_T / corner_ncontrib (each optional, [Q, 4]): final transmittance and 1-based list position of the last
  *      applied splat of every corner pixel -- the forward's final_T / ncontrib there; 0 for a corner outside.  Q = 0, P = 0
  *      (the other inputs may then be NULL) and empty tiles are valid: an in-image corner without splats has T = 1.  One workgroup
- *      per query, one launch per 256 channels; no atomics: bit-reproducible.  Forward only.
+ *      per query, one launch per 256 channels; no atomics: bit-reproducible.
+ *      splat_alpha_blending_points_forward_live: the same call for a caller that only needs the corners that carry weight (the
+ *      forward of the backward below): an in-image corner whose bilinear weight is zero is not walked and reports corner_T = 0,
+ *      corner_ncontrib = 0 like a corner outside.  out has the same bits for finite features (the corner added 0 * value); a
+ *      query on an integer pixel walks one list instead of four.
+ *      splat_alpha_blending_points_backward: the gradient of that expression w.r.t. uv, conic, opacity and feature (not w.r.t.
+ *      points).  Corner pixel k of query q receives dL_dpix[c] = w_k(q) dL_dout[q, c] with the forward's weights and in / out
+ *      tests (a corner outside the image, a non-finite or far-outside point: nothing) and replays its tile list back to front
+ *      from corner_T / corner_ncontrib [Q, 4] as either forward above returned them: the entries applied are those with list position
+ *      < corner_ncontrib whose recomputed alpha (csrc/blend_power.h) passes the forward's test; T is replayed by division, the
+ *      bg term is included and the 0.99 clamp is not masked, as in splat_alpha_blending_backward.  There are no ndc / abs_ndc
+ *      taps.  dL_dout is [Q, C].  The outputs dL_duv [P, 2], dL_dconic [P, 3], dL_dopacity [P], dL_dfeature [P, C] are ADDED
+ *      into caller-zeroed buffers; each may be NULL (dL_dopacity == NULL: the reference's opacity.detach()).  Q = 0, P = 0 and
+ *      empty tiles are valid; an id outside [0, P) is skipped.  One workgroup per query, wave = corner, one launch per 256
+ *      channels (the chunks' geometry gradients add).  DETERMINISM: many queries hit one Gaussian, so the sums are float
+ *      atomics and not bit-reproducible; with splat_set_deterministic(1) the entry returns SPLAT_E_ARG (no backward of this
+ *      library uses float atomics under that flag) -- take the dense route there.
  *      splat_track_flow_rows: rows [P, T, 3] (Gaussian-major: the feature [P, 3 T] of the call above), rows[n, t] =
  *      (u_t - u_ref, v_t - v_ref, depth_t) with (u_t, v_t, depth_t) the orthographic project_point of get_position at the t-th
  *      time of tab (a device table of T 64-byte frame entries, as splat_dynamic_positions_batch_forward takes it) and uv_ref [P, 2]
@@ -843,6 +859,15 @@ int splat_alpha_blending_points_forward(int P, int C, const float *uv, const flo
                                         const float *feature, const int32_t *idx_sorted, const int32_t *tile_range, float bg,
                                         int W, int H, int Q, const float *points, float *out, float *corner_T,
                                         int32_t *corner_ncontrib, splat_stream_t stream);
+int splat_alpha_blending_points_forward_live(int P, int C, const float *uv, const float *conic, const float *opacity,
+                                             const float *feature, const int32_t *idx_sorted, const int32_t *tile_range, float bg,
+                                             int W, int H, int Q, const float *points, float *out, float *corner_T,
+                                             int32_t *corner_ncontrib, splat_stream_t stream);
+int splat_alpha_blending_points_backward(int P, int C, const float *uv, const float *conic, const float *opacity,
+                                         const float *feature, const int32_t *idx_sorted, const int32_t *tile_range, float bg,
+                                         int W, int H, int Q, const float *points, const float *corner_T,
+                                         const int32_t *corner_ncontrib, const float *dL_dout, float *dL_duv, float *dL_dconic,
+                                         float *dL_dopacity, float *dL_dfeature, splat_stream_t stream);
 int splat_track_flow_rows(int T, int P, int I, const void *tab, const float *position, const float *cubic, int cubic_layout,
                           const float *extr, int W, int H, float nearest, float extent, const float *uv_ref, float *rows,
                           splat_stream_t stream);

@@ -59,7 +59,7 @@ SYMBOLS = [
     "splat_ssim_scratch_bytes", "splat_ssim_forward", "splat_ssim_backward", "splat_dssim_l1_loss_grad",
     "splat_track_loss_scratch_bytes", "splat_track_loss_grad",
     "splat_depth_dpt_scratch_bytes", "splat_depth_stats", "splat_depth_dpt_loss_grad",
-    "splat_alpha_blending_points_forward", "splat_track_flow_rows",
+    "splat_alpha_blending_points_forward", "splat_alpha_blending_points_forward_live", "splat_alpha_blending_points_backward", "splat_track_flow_rows",
 ]
 
 
@@ -120,6 +120,8 @@ def lib() -> ctypes.CDLL:
         L.splat_depth_stats.argtypes = [i, i, i, p, s4, p, p, p]
         L.splat_depth_dpt_loss_grad.argtypes = [i, i, i, p, s4, p, s4, p, f, p, s4, i, p, p, p, p, p, p]
         L.splat_alpha_blending_points_forward.argtypes = [i, i, p, p, p, p, p, p, f, i, i, i, p, p, p, p, p]
+        L.splat_alpha_blending_points_forward_live.argtypes = L.splat_alpha_blending_points_forward.argtypes
+        L.splat_alpha_blending_points_backward.argtypes = [i, i, p, p, p, p, p, p, f, i, i, i, p, p, p, p, p, p, p, p, p]
         L.splat_track_flow_rows.argtypes = [i, i, i, p, p, p, i, p, i, i, f, f, p, p, p]
         if L.splat_abi_version() != ABI_VERSION:
             raise SplatError("libsplat_hip.so ABI version mismatch; rebuild it")

@@ -15,7 +15,8 @@
 //     and accumulated F[c] += f[id, c] w in list order, ceil(cn / 64) <= NA accumulators per lane; rows wider than 64 NA
 //     channels take one launch per chunk.
 //   * the four corner values (F + T bg) meet in LDS and are combined nw, ne, sw, se with the bilinear weights.  No
-//     atomics anywhere: results are bit-reproducible.
+//     atomics anywhere in the forward: results are bit-reproducible.
+//   * the backward (points_bwd_kernel below) replays every corner's list back to front and adds with float atomics.
 #include "blend_power.h"
 #include "dynamics_dev.h"
 #include "pointwise_dev.h"
@@ -43,7 +44,10 @@ __device__ __forceinline__ float lane_f(float v, int j) {
     return __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(v), j));
 }
 
-template <int NA>
+// LIVE: an in-image corner whose bilinear weight is zero is not walked either (it reports T = 0, ncontrib = 0 like a corner
+// outside and adds 0 * bg = 0: the same value bits for finite features) -- the differentiable route's forward, whose backward
+// replays only the corners that carry weight; an integer query pixel then walks one list instead of four.
+template <int NA, bool LIVE>
 __global__ void __launch_bounds__(256) points_fwd_kernel(const PointsArgs A) {
     __shared__ float s_val[4][64 * NA];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -53,7 +57,11 @@ __global__ void __launch_bounds__(256) points_fwd_kernel(const PointsArgs A) {
     // corner w of the query: the in / out test in float, before any conversion to int (1e9, inf and NaN are simply outside)
     const float x0f = floorf(pt.x), y0f = floorf(pt.y);
     const float cxf = x0f + (float)(w & 1), cyf = y0f + (float)(w >> 1);
-    const bool in = cxf >= 0.f && cxf <= (float)(A.W - 1) && cyf >= 0.f && cyf <= (float)(A.H - 1);
+    bool in = cxf >= 0.f && cxf <= (float)(A.W - 1) && cyf >= 0.f && cyf <= (float)(A.H - 1);
+    if (LIVE) {   // (the weight as the combine below forms it; pt is finite where `in` holds)
+        const float wxl = (w & 1) ? pt.x - x0f : (x0f + 1.f) - pt.x, wyl = (w >> 1) ? pt.y - y0f : (y0f + 1.f) - pt.y;
+        in = in && wxl * wyl != 0.f;
+    }
 
     float T = 1.f;
     int last = 0;
@@ -177,8 +185,196 @@ __global__ void __launch_bounds__(256) points_fwd_kernel(const PointsArgs A) {
 }
 
 template <int NA>
-int launch_points(const PointsArgs &A, int Q, hipStream_t s) {
-    SPLAT_LAUNCH("blend_points", points_fwd_kernel<NA>, dim3((unsigned)Q), dim3(256), 0, s, A);
+int launch_points(const PointsArgs &A, int Q, bool live, hipStream_t s) {
+    if (live) SPLAT_LAUNCH("blend_points", (points_fwd_kernel<NA, true>), dim3((unsigned)Q), dim3(256), 0, s, A);
+    else SPLAT_LAUNCH("blend_points", (points_fwd_kernel<NA, false>), dim3((unsigned)Q), dim3(256), 0, s, A);
+    SPLAT_POST_LAUNCH();
+    return SPLAT_OK;
+}
+
+// the launches of the validated forward: one per 256 channels
+int points_forward_chunks(int P, int C, const float *uv, const float *conic, const float *opacity, const float *feature,
+                          const int32_t *idx_sorted, const int32_t *tile_range, float bg, int W, int H, int Q, const float *points,
+                          float *out, float *corner_T, int32_t *corner_ncontrib, bool live, hipStream_t stream) {
+    PointsArgs A;
+    memset(&A, 0, sizeof(A));
+    A.P = P; A.C = C;
+    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
+    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
+    A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
+    A.points = (const float2 *)points;
+    A.out = out;
+    for (int c0 = 0; c0 < C; c0 += PT_CHUNK) {
+        A.c0 = c0;
+        A.cn = C - c0 > PT_CHUNK ? PT_CHUNK : C - c0;
+        A.corner_T = c0 == 0 ? corner_T : nullptr;   // every chunk walks the same lists: the first one reports them
+        A.corner_n = c0 == 0 ? corner_ncontrib : nullptr;
+        int rc;
+        switch ((A.cn + 63) / 64) {
+            case 1: rc = launch_points<1>(A, Q, live, stream); break;
+            case 2: rc = launch_points<2>(A, Q, live, stream); break;
+            case 3: rc = launch_points<3>(A, Q, live, stream); break;
+            default: rc = launch_points<4>(A, Q, live, stream); break;
+        }
+        if (rc != SPLAT_OK) return rc;
+    }
+    return SPLAT_OK;
+}
+
+// ---- backward of the sparse compositing: the gradient of grid_sample(alpha_blending(...)) w.r.t. uv, conic, opacity, feature.
+// Corner pixel k of query q receives dL_dpix[c] = w_k(q) dL_dout[q, c] and replays its list back to front from the forward's
+// corner_T / corner_ncontrib (the dense backward's per-pixel replay, replay_one of blend.hip: T by division, the bg term, the
+// 0.99 clamp not masked).  Wave = corner as in the forward; a corner outside the image or with zero weight exits at once.
+//   * lane = entry: 64 entries' alphas at once with the forward's arithmetic; applied = position < ncontrib and alpha >= 1/255.
+//   * lane = channel: the applied entries back to front, four feature rows in flight; acc_c and g_c in registers, the dot
+//     sum_c (f_c - acc_c) g_c by one DPP wave reduction, alpha T g_c added to dL_dfeature[id, c] with one coalesced row of float
+//     atomics; the entry's dL_dalpha stays in the entry's lane.
+//   * lane = entry again: the uv / conic / opacity atomics of the block issue from up to 64 lanes at once.
+// Many queries hit one Gaussian: float atomics, outputs ADDED (the host entry refuses deterministic mode).
+struct PointsBwdArgs {
+    int P, C, c0, cn;
+    const float2 *uv;
+    const float *conic, *opacity, *feature;
+    const int *idx_sorted;
+    const int2 *tile_range;
+    float bg;
+    int W, H, gx;
+    const float2 *points;
+    const float *corner_T;   // [Q, 4]
+    const int *corner_n;     // [Q, 4]
+    const float *dL_dout;    // [Q, C]
+    float *dL_duv, *dL_dconic, *dL_dopacity, *dL_dfeature;   // each may be NULL
+};
+
+template <int NA>
+__global__ void __launch_bounds__(256) points_bwd_kernel(const PointsBwdArgs A) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave = corner
+    const size_t q = blockIdx.x;
+    const float2 ptv = A.points[q];
+    const float ptx = lane_f(ptv.x, 0), pty = lane_f(ptv.y, 0);   // (uniform: the exits below are scalar branches)
+    // the forward's corner, in / out test and bilinear weight
+    const float x0f = floorf(ptx), y0f = floorf(pty);
+    const float cxf = x0f + (float)(w & 1), cyf = y0f + (float)(w >> 1);
+    const bool in = cxf >= 0.f && cxf <= (float)(A.W - 1) && cyf >= 0.f && cyf <= (float)(A.H - 1);
+    if (!in) return;
+    const float x1f = x0f + 1.f, y1f = y0f + 1.f;
+    const float cw = ((w & 1) ? ptx - x0f : x1f - ptx) * ((w >> 1) ? pty - y0f : y1f - pty);
+    if (cw == 0.f) return;
+    const int px = (int)cxf, py = (int)cyf;
+    const int tx = px / TILE, ty = py / TILE;
+    const int2 range = A.tile_range[ty * A.gx + tx];
+    const int n = imax_(range.y - range.x, 0);
+    const int last = imin_(__builtin_amdgcn_readfirstlane(A.corner_n[q * 4 + w]), n);   // (never past the list)
+    if (last <= 0) return;   // nothing applied: no Gaussian saw this corner
+    const float Tf = lane_f(A.corner_T[q * 4 + w], 0);
+    const float pxf = (float)px, pyf = (float)py;
+    const float x = (float)(px - tx * TILE) - 7.5f, y = (float)(py - ty * TILE) - 7.5f;
+    const float xx = x * x, xy = x * y, yy = y * y;
+    const float tcx = (float)(tx * TILE) + 7.5f, tcy = (float)(ty * TILE) + 7.5f;
+
+    float g[NA], acc[NA];
+    float gsum = 0.f;
+#pragma unroll
+    for (int k = 0; k < NA; ++k) {
+        g[k] = (lane + 64 * k < A.cn) ? cw * A.dL_dout[q * (size_t)A.C + A.c0 + lane + 64 * k] : 0.f;
+        acc[k] = 0.f;
+        gsum += g[k];
+    }
+    const float bgdot = A.bg * wave_sum_bcast(gsum);
+    float T = Tf;
+    const float *fbase = A.feature + A.c0 + lane;
+    float *dfbase = A.dL_dfeature ? A.dL_dfeature + A.c0 + lane : nullptr;
+
+    for (int base = ((last - 1) / WAVE) * WAVE; base >= 0; base -= WAVE) {
+        // ---- lane = entry: its alpha on this pixel (the forward's bits)
+        const int e = base + lane;
+        int id = 0;
+        float alpha = 0.f, araw = 0.f, ux = 0.f, uy = 0.f, cA = 0.f, cB = 0.f, cC = 0.f, o = 1.f;
+        bool aok = false;
+        if (e < last) {
+            id = A.idx_sorted[range.x + e];
+            if ((unsigned)id < (unsigned)A.P) {   // (an id outside the set is skipped, never dereferenced)
+                const float2 c = A.uv[id];
+                ux = c.x; uy = c.y;
+                cA = A.conic[3 * (size_t)id]; cB = A.conic[3 * (size_t)id + 1]; cC = A.conic[3 * (size_t)id + 2];
+                o = A.opacity[id];
+                const PowerCoef k = power_coeffs(ux, uy, cA, cB, cC, o, tcx, tcy);
+                const float pw = power_poly(make_float4(k.q0, k.qx, k.qy, k.qxx), make_float4(k.qxy, k.qyy, 0.f, 0.f), x, y, xx, xy, yy);
+                bool pw_ok;
+                araw = exp2_guard(pw, pw_ok);
+                const float a = fminf(0.99f, araw);
+                aok = pw_ok && !(a < (1.0f / 255.0f));
+                alpha = aok ? a : 0.f;
+            } else {
+                id = 0;
+            }
+        }
+        // ---- lane = channel: the applied entries back to front, four rows in flight
+        unsigned long long ap = __ballot(aok);
+        float dLa_v = 0.f;   // lane j: dL_dalpha of entry base + j, if it applied
+        while (ap) {
+            int jj[4];
+            float f[4][NA];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                jj[u] = ap ? 63 - (int)__builtin_clzll(ap) : -1;
+                if (jj[u] >= 0) {
+                    ap &= ~(1ull << jj[u]);
+                    const float *row = fbase + (size_t)__builtin_amdgcn_readlane(id, jj[u]) * (size_t)A.C;
+#pragma unroll
+                    for (int k = 0; k < NA; ++k) f[u][k] = (lane + 64 * k < A.cn) ? row[64 * k] : 0.f;
+                } else {
+#pragma unroll
+                    for (int k = 0; k < NA; ++k) f[u][k] = 0.f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (jj[u] < 0) break;
+                const int j = jj[u];
+                const float a = lane_f(alpha, j);
+                const float r1a = __builtin_amdgcn_rcpf(1.f - a);
+                T = T * r1a;   // the transmittance in front of the entry
+                const float wgt = a * T;
+                float part = 0.f;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) part += (f[u][k] - acc[k]) * g[k];
+                float dLa = wave_sum_bcast(part) * T;
+                dLa += (-Tf * r1a) * bgdot;
+                dLa_v = lane == j ? dLa : dLa_v;
+                if (dfbase) {
+                    float *drow = dfbase + (size_t)__builtin_amdgcn_readlane(id, j) * (size_t)A.C;
+#pragma unroll
+                    for (int k = 0; k < NA; ++k)
+                        if (lane + 64 * k < A.cn) atomic_add_f32(drow + 64 * k, wgt * g[k]);
+                }
+#pragma unroll
+                for (int k = 0; k < NA; ++k) acc[k] = a * f[u][k] + (1.f - a) * acc[k];
+            }
+        }
+        // ---- lane = entry: the geometry gradients of the block's applied entries (replay_one's expressions)
+        if (aok) {
+            const float dx = ux - pxf, dy = uy - pyf;
+            const float G = araw * __builtin_amdgcn_rcpf(o);
+            const float dLG = o * dLa_v;
+            if (A.dL_duv) {
+                atomic_add_f32(A.dL_duv + 2 * (size_t)id, dLG * (-G * dx * cA - G * dy * cB));
+                atomic_add_f32(A.dL_duv + 2 * (size_t)id + 1, dLG * (-G * dy * cC - G * dx * cB));
+            }
+            if (A.dL_dconic) {
+                atomic_add_f32(A.dL_dconic + 3 * (size_t)id, -0.5f * G * dx * dx * dLG);
+                atomic_add_f32(A.dL_dconic + 3 * (size_t)id + 1, -G * dx * dy * dLG);
+                atomic_add_f32(A.dL_dconic + 3 * (size_t)id + 2, -0.5f * G * dy * dy * dLG);
+            }
+            if (A.dL_dopacity) atomic_add_f32(A.dL_dopacity + id, G * dLa_v);
+        }
+    }
+}
+
+template <int NA>
+int launch_points_bwd(const PointsBwdArgs &A, int Q, hipStream_t s) {
+    SPLAT_LAUNCH("blend_points_bwd", points_bwd_kernel<NA>, dim3((unsigned)Q), dim3(256), 0, s, A);
     SPLAT_POST_LAUNCH();
     return SPLAT_OK;
 }
@@ -233,25 +429,59 @@ extern "C" int splat_alpha_blending_points_forward(int P, int C, const float *uv
     SPLAT_CHECK_ARG(points && out, "null pointer (points / out)");
     // idx_sorted may be NULL when no Gaussian touches any tile (every tile range is empty, nothing dereferences it)
     SPLAT_CHECK_ARG(P == 0 || (uv && conic && opacity && feature && tile_range), "null pointer");
-    PointsArgs A;
+    return points_forward_chunks(P, C, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, Q, points, out, corner_T,
+                                 corner_ncontrib, false, (hipStream_t)stream);
+}
+
+extern "C" int splat_alpha_blending_points_forward_live(int P, int C, const float *uv, const float *conic, const float *opacity,
+                                                        const float *feature, const int32_t *idx_sorted, const int32_t *tile_range,
+                                                        float bg, int W, int H, int Q, const float *points, float *out,
+                                                        float *corner_T, int32_t *corner_ncontrib, splat_stream_t stream) {
+    SPLAT_CHECK_ARG(P >= 0 && C >= 1 && W > 0 && H > 0 && Q >= 0, "bad sizes (P, Q >= 0, C, W, H >= 1)");
+    SPLAT_CHECK_ARG(W <= (1 << 24) && H <= (1 << 24), "sizes too large (W, H <= 2^24: pixel indices are compared in float32)");
+    if (Q == 0) return SPLAT_OK;
+    SPLAT_CHECK_ARG(points && out, "null pointer (points / out)");
+    SPLAT_CHECK_ARG(P == 0 || (uv && conic && opacity && feature && tile_range), "null pointer");
+    return points_forward_chunks(P, C, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, Q, points, out, corner_T,
+                                 corner_ncontrib, true, (hipStream_t)stream);
+}
+
+extern "C" int splat_alpha_blending_points_backward(int P, int C, const float *uv, const float *conic, const float *opacity,
+                                                    const float *feature, const int32_t *idx_sorted, const int32_t *tile_range,
+                                                    float bg, int W, int H, int Q, const float *points, const float *corner_T,
+                                                    const int32_t *corner_ncontrib, const float *dL_dout, float *dL_duv,
+                                                    float *dL_dconic, float *dL_dopacity, float *dL_dfeature, splat_stream_t stream) {
+    SPLAT_CHECK_ARG(P >= 0 && C >= 1 && W > 0 && H > 0 && Q >= 0, "bad sizes (P, Q >= 0, C, W, H >= 1)");
+    SPLAT_CHECK_ARG(W <= (1 << 24) && H <= (1 << 24), "sizes too large (W, H <= 2^24: pixel indices are compared in float32)");
+    if (Q == 0) return SPLAT_OK;
+    SPLAT_CHECK_ARG(points && corner_T && corner_ncontrib && dL_dout, "null pointer (points / corner_T / corner_ncontrib / dL_dout)");
+    // idx_sorted may be NULL when no Gaussian touches any tile (every tile range is empty, nothing dereferences it)
+    SPLAT_CHECK_ARG(P == 0 || (uv && conic && opacity && feature && tile_range), "null pointer");
+    if (P == 0 || !(dL_duv || dL_dconic || dL_dopacity || dL_dfeature)) return SPLAT_OK;   // nothing to add to
+    if (splat_deterministic()) {   // refused before any launch
+        splat_set_error("%s: deterministic mode: the backward of the sparse compositing adds with float atomics (many queries hit "
+                        "one Gaussian); use the dense alpha_blending route", __func__);
+        return SPLAT_E_ARG;
+    }
+    PointsBwdArgs A;
     memset(&A, 0, sizeof(A));
     A.P = P; A.C = C;
     A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
     A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
     A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
-    A.points = (const float2 *)points;
-    A.out = out;
+    A.points = (const float2 *)points; A.corner_T = corner_T; A.corner_n = corner_ncontrib; A.dL_dout = dL_dout;
+    A.dL_dfeature = dL_dfeature;
     for (int c0 = 0; c0 < C; c0 += PT_CHUNK) {
         A.c0 = c0;
         A.cn = C - c0 > PT_CHUNK ? PT_CHUNK : C - c0;
-        A.corner_T = c0 == 0 ? corner_T : nullptr;   // every chunk walks the same lists: the first one reports them
-        A.corner_n = c0 == 0 ? corner_ncontrib : nullptr;
+        // every chunk adds its share of the geometry gradients: dL_dalpha is linear in the channels
+        A.dL_duv = dL_duv; A.dL_dconic = dL_dconic; A.dL_dopacity = dL_dopacity;
         int rc;
         switch ((A.cn + 63) / 64) {
-            case 1: rc = launch_points<1>(A, Q, (hipStream_t)stream); break;
-            case 2: rc = launch_points<2>(A, Q, (hipStream_t)stream); break;
-            case 3: rc = launch_points<3>(A, Q, (hipStream_t)stream); break;
-            default: rc = launch_points<4>(A, Q, (hipStream_t)stream); break;
+            case 1: rc = launch_points_bwd<1>(A, Q, (hipStream_t)stream); break;
+            case 2: rc = launch_points_bwd<2>(A, Q, (hipStream_t)stream); break;
+            case 3: rc = launch_points_bwd<3>(A, Q, (hipStream_t)stream); break;
+            default: rc = launch_points_bwd<4>(A, Q, (hipStream_t)stream); break;
         }
         if (rc != SPLAT_OK) return rc;
     }

@@ -369,23 +369,9 @@ def alpha_blending_with_bias(uv: Tensor, conic: Tensor, opacity: Tensor, feature
                              abs_ndc, 0, False)
 
 
-# ------------------------------------------------------------------ compositing at sparse sub-pixel points (forward only)
-def alpha_blending_points(uv: Tensor, conic: Tensor, opacity: Tensor, feature: Tensor, idx_sorted: Tensor, tile_range: Tensor,
-                          bg: float, W: int, H: int, points: Tensor, return_corners: bool = False):
-    """``F.grid_sample(alpha_blending(uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H)[None], grid,
-    mode="bilinear", padding_mode="zeros", align_corners=True)`` at ``points`` [Q, 2] without the dense image: [Q, C].
-
-    ``points[:, 0]`` = ix, the continuous column index, ``points[:, 1]`` = iy (grid_sample's un-normalised sample coordinates:
-    an integer lands on a stored pixel).  Only the four bilinear corner pixels of every point walk their tile lists, with the
-    dense forward's decisions bit for bit; a corner outside the image contributes nothing, a point far outside or not finite
-    gives a row of zeros.  ``feature`` [P, C] may be any width (one coalesced row read per applied splat).
-    ``return_corners``: also ``corner_T`` [Q, 4] float32 and ``corner_ncontrib`` [Q, 4] int32, the dense forward's final
-    transmittance and ncontrib at the corner pixels nw, ne, sw, se (0 for a corner outside).
-    Forward only: an input that requires grad raises ``ValueError``."""
-    named = (("uv", uv), ("conic", conic), ("opacity", opacity), ("feature", feature), ("points", points))
-    for name, t in named:
-        if isinstance(t, Tensor) and t.requires_grad:
-            raise ValueError(f"alpha_blending_points is forward only: {name} requires grad (detach it or use torch.no_grad())")
+# ------------------------------------------------------------------ compositing at sparse sub-pixel points
+def _points_inputs(uv, conic, opacity, feature, idx_sorted, tile_range, W, H, points):
+    """device / dtype / shape gate of alpha_blending_points: the contiguous tensors and (P, C, Q, W, H)"""
     uv = L.need(uv, "uv")
     conic = L.need(conic, "conic")
     opacity = L.need(opacity, "opacity")
@@ -407,14 +393,88 @@ def alpha_blending_points(uv: Tensor, conic: Tensor, opacity: Tensor, feature: T
         raise ValueError("tile_range must have shape [ceil(W/16)*ceil(H/16), 2]")
     if points.dim() != 2 or points.shape[1] != 2:
         raise ValueError("points must have shape [Q, 2] = (ix, iy)")
-    Q = points.shape[0]
+    return (uv, conic, opacity, feature, idx_sorted, tile_range, points), (P, C, points.shape[0], W, H)
+
+
+def _points_forward(tensors, sizes, bg, corners: bool, live: bool = False):
+    """``live``: corners of zero bilinear weight are not walked (their corner maps read 0); the values are the same"""
+    uv, conic, opacity, feature, idx_sorted, tile_range, points = tensors
+    P, C, Q, W, H = sizes
     dev = feature.device
     out = torch.empty(Q, C, dtype=torch.float32, device=dev)
-    corner_T = torch.empty(Q, 4, dtype=torch.float32, device=dev) if return_corners else None
-    corner_n = torch.empty(Q, 4, dtype=torch.int32, device=dev) if return_corners else None
-    L.check(L.lib().splat_alpha_blending_points_forward(
+    corner_T = torch.empty(Q, 4, dtype=torch.float32, device=dev) if corners else None
+    corner_n = torch.empty(Q, 4, dtype=torch.int32, device=dev) if corners else None
+    fwd = L.lib().splat_alpha_blending_points_forward_live if live else L.lib().splat_alpha_blending_points_forward
+    L.check(fwd(
         L.ci(P), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(idx_sorted), L.ptr(tile_range), L.cf(bg),
         L.ci(W), L.ci(H), L.ci(Q), L.ptr(points), L.ptr(out), L.ptr(corner_T), L.ptr(corner_n), L.stream()))
+    return out, corner_T, corner_n
+
+
+class _BlendPoints(torch.autograd.Function):
+    """inputs: uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, points, live; outputs: out, corner_T,
+    corner_ncontrib.  ``live``: nobody but the backward reads the corner maps, and it replays only the corners that carry
+    weight -- the forward walks only those (an integer query pixel: one list instead of four)."""
+
+    @staticmethod
+    def forward(ctx, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, points, live):
+        tensors, sizes = _points_inputs(uv, conic, opacity, feature, idx_sorted, tile_range, W, H, points)
+        out, corner_T, corner_n = _points_forward(tensors, sizes, bg, True, live)
+        ctx.save_for_backward(*tensors, corner_T, corner_n)
+        ctx.sizes, ctx.bg = sizes, float(bg)
+        ctx.shapes = (uv.shape, conic.shape, opacity.shape, feature.shape)
+        ctx.mark_non_differentiable(corner_T, corner_n)
+        return out, corner_T, corner_n
+
+    @staticmethod
+    def backward(ctx, g_out, _g_T, _g_n):
+        uv, conic, opacity, feature, idx_sorted, tile_range, points, corner_T, corner_n = ctx.saved_tensors
+        P, C, Q, W, H = ctx.sizes
+        g_out = L.need(g_out, "grad of out")
+        dev = feature.device
+        # the kernel ADDS into zeroed buffers; a gradient nobody asked for is a NULL pointer (opacity: the reference's detach)
+        grads = [torch.zeros(shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[k] else None
+                 for k, shape in enumerate(ctx.shapes)]
+        L.check(L.lib().splat_alpha_blending_points_backward(
+            L.ci(P), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(idx_sorted), L.ptr(tile_range),
+            L.cf(ctx.bg), L.ci(W), L.ci(H), L.ci(Q), L.ptr(points), L.ptr(corner_T), L.ptr(corner_n), L.ptr(g_out),
+            L.ptr(grads[0]), L.ptr(grads[1]), L.ptr(grads[2]), L.ptr(grads[3]), L.stream()))
+        return grads[0], grads[1], grads[2], grads[3], None, None, None, None, None, None, None
+
+
+def alpha_blending_points(uv: Tensor, conic: Tensor, opacity: Tensor, feature: Tensor, idx_sorted: Tensor, tile_range: Tensor,
+                          bg: float, W: int, H: int, points: Tensor, return_corners: bool = False, differentiable: bool = False):
+    """``F.grid_sample(alpha_blending(uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H)[None], grid,
+    mode="bilinear", padding_mode="zeros", align_corners=True)`` at ``points`` [Q, 2] without the dense image: [Q, C].
+
+    ``points[:, 0]`` = ix, the continuous column index, ``points[:, 1]`` = iy (grid_sample's un-normalised sample coordinates:
+    an integer lands on a stored pixel).  Only the four bilinear corner pixels of every point walk their tile lists, with the
+    dense forward's decisions bit for bit; a corner outside the image contributes nothing, a point far outside or not finite
+    gives a row of zeros.  ``feature`` [P, C] may be any width (one coalesced row read per applied splat).
+    ``return_corners``: also ``corner_T`` [Q, 4] float32 and ``corner_ncontrib`` [Q, 4] int32, the dense forward's final
+    transmittance and ncontrib at the corner pixels nw, ne, sw, se (0 for a corner outside).
+    ``differentiable=False`` (the default) is forward only: an input that requires grad raises ``ValueError``.
+    ``differentiable=True``: the result carries the gradient of that expression w.r.t. ``uv``, ``conic``, ``opacity`` and
+    ``feature`` (each only where it requires grad; a detached opacity is the reference's ``opacity.detach()``), every corner
+    pixel replaying its list back to front (splat_alpha_blending_points_backward); without ``return_corners`` the forward
+    does not walk a corner of zero bilinear weight either (same values; an integer pixel walks one list).  Its sums are float atomics: in
+    deterministic mode (``splat_set_deterministic(1)``) the backward raises.  There is no gradient w.r.t. ``points``: a
+    ``points`` that requires grad raises ``ValueError``."""
+    if differentiable:
+        if isinstance(points, Tensor) and points.requires_grad:
+            raise ValueError("alpha_blending_points: no gradient w.r.t. points is computed (detach points)")
+        out, corner_T, corner_n = _BlendPoints.apply(uv, conic, opacity, feature, idx_sorted, tile_range, float(bg), W, H, points,
+                                                     not return_corners)
+        if return_corners:
+            return out, corner_T, corner_n
+        return out
+    named = (("uv", uv), ("conic", conic), ("opacity", opacity), ("feature", feature), ("points", points))
+    for name, t in named:
+        if isinstance(t, Tensor) and t.requires_grad:
+            raise ValueError(f"alpha_blending_points is forward only: {name} requires grad (detach it, use torch.no_grad() or "
+                             "pass differentiable=True)")
+    tensors, sizes = _points_inputs(uv, conic, opacity, feature, idx_sorted, tile_range, W, H, points)
+    out, corner_T, corner_n = _points_forward(tensors, sizes, bg, return_corners)
     if return_corners:
         return out, corner_T, corner_n
     return out

@@ -217,6 +217,35 @@ def track_loss(track_image: torch.Tensor, targets, frame_weights: torch.Tensor, 
     return _TrackLoss.apply(track_image, targets, frame_weights, float(quantile))
 
 
+def track_loss_sparse(uv: torch.Tensor, conic: torch.Tensor, opacity: torch.Tensor, track_gs: torch.Tensor,
+                      idx_sorted: torch.Tensor, tile_range: torch.Tensor, W: int, H: int, targets, frame_weights: torch.Tensor,
+                      quantile: float = 0.98, bg: float = 0.0) -> torch.Tensor:
+    """``track_loss`` of ONE frame pair without the dense track image: ``track_gs`` [P, C >= 2] (its first three channels at
+    most) is composited at the integer query pixels of ``targets`` only (``gs.alpha_blending_points(differentiable=True)``),
+    the [Q, C'] result is scattered into a zero [1, C', H, W] image and handed to ``track_loss`` -- which reads nothing but
+    those pixels, so value and gradients are the dense route's ``track_loss(alpha_blending(...)[None, :3], ...)``.
+    ``opacity`` is detached, as the reference does for its attribute blend.  Differentiable w.r.t. ``uv``, ``conic`` and
+    ``track_gs``; the backward adds with float atomics (it raises in deterministic mode)."""
+    from .gs.raster_ops import alpha_blending_points
+    if targets.F != 1:
+        raise ValueError(f"track_loss_sparse takes the targets of one frame pair, got {targets.F}")
+    W, H = int(W), int(H)
+    if (targets.H, targets.W) != (H, W):
+        raise ValueError(f"track targets of a {targets.W} x {targets.H} image for W, H = {W}, {H}")
+    _check(track_gs, "track_gs")
+    if track_gs.dim() != 2 or track_gs.shape[1] < 2:
+        raise ValueError(f"track_gs must be [P, C >= 2], got {tuple(track_gs.shape)}")
+    if targets.device != track_gs.device:
+        raise ValueError(f"track targets live on {targets.device}, track_gs on {track_gs.device}")
+    feat = track_gs[:, :3]
+    C = feat.shape[1]
+    pix = targets.pixels.long()
+    points = torch.stack([pix % W, pix // W], dim=1).to(torch.float32)       # integer pixels: one corner of weight 1
+    vals = alpha_blending_points(uv, conic, opacity.detach(), feat, idx_sorted, tile_range, bg, W, H, points, differentiable=True)
+    image = torch.zeros(C, H * W, dtype=torch.float32, device=track_gs.device).index_copy(1, pix, vals.t())
+    return track_loss(image.view(1, C, H, W), targets, frame_weights, quantile)
+
+
 # ------------------------------------------------------------------------------------- the median-normalised depth loss
 DEPTH_CHUNK = 4096          # pixels one workgroup of the depth kernels handles (DPT_CH of csrc/loss.hip)
 
