@@ -792,6 +792,15 @@ int splat_track_loss_grad(int F, int H, int W, int C, const float *track, const 
                           const int32_t *pixels, const float *targets, int64_t Q, const float *frame_weights, float quantile,
                           float scale, float *grad, const int64_t *grad_strides, int accumulate, float *per_frame,
                           float *loss_slot, int32_t *counts, void *scratch, splat_stream_t stream);
+/* ... on PER-QUERY predictions: values [Q, C] (row i = the prediction of query i, in target order: what
+ * splat_alpha_blending_points_forward_batch returns at the query pixels) instead of an image, grad [Q, C] (optional) written in
+ * full: zeros outside the selected set and in channels >= 2.  pixels keep their role: they decide which queries are malformed,
+ * exactly as above.  Same kernels and arithmetic -- only the two address computations differ -- so per_frame, *loss_slot, counts
+ * and the gradient rows are bit-equal to splat_track_loss_grad on an image holding those values at the query pixels. */
+int splat_track_loss_grad_points(int F, int H, int W, int C, const float *values, const int64_t *offsets, const int32_t *pixels,
+                                 const float *targets, int64_t Q, const float *frame_weights, float quantile, float scale,
+                                 float *grad, float *per_frame, float *loss_slot, int32_t *counts, void *scratch,
+                                 splat_stream_t stream);
 
 /* ---- median-normalised depth loss: the trainer's depth term depth_loss_dpt(depth, gt_depth) (src/trainer_fragGS.py:589-601,
  *      src/loss.py:184-207, weight = None).  Frame f is the plane [H, W] at img + f * strides[0] of an [F, 1, H, W] view given by
@@ -850,6 +859,24 @@ int splat_depth_dpt_loss_grad(int F, int H, int W, const float *pred, const int6
  *      channels (the chunks' geometry gradients add).  DETERMINISM: many queries hit one Gaussian, so the sums are float
  *      atomics and not bit-reproducible; with splat_set_deterministic(1) the entry returns SPLAT_E_ARG (no backward of this
  *      library uses float atomics under that flag) -- take the dense route there.
+ *      splat_alpha_blending_points_forward_batch: the _forward_live walk for the queries of F frames of a frame batch in one
+ *      launch per 256 channels.  The batch's buffers as they are: uv [F, P, 2], conic [F, P, 3], opacity and feature with a frame
+ *      stride in floats (0: [P] / [P, C] shared by the frames, else one block per frame), idx_sorted [F, capacity], tile_range
+ *      [F, T, 2] relative to the frame's segment.  The queries are CSR: offsets (device int64 [F + 1]), points [Q, 2] with the
+ *      single-frame semantics (non-finite and far-outside points included); the frame of a query is found on the device.  A query
+ *      that no frame owns (malformed offsets) writes zeros and dereferences nothing.  out [Q, C], corner_T / corner_ncontrib
+ *      [Q, 4] (optional).  Q = 0, P = 0, a frame without queries and empty tiles are valid.  No atomics: bit-reproducible, and
+ *      bit-equal to the single-frame entry on every frame's slices.
+ *      splat_alpha_blending_points_backward_batch: the backward of that call.  The GEOMETRY gradients go into the frame batch's
+ *      pair records (pair_records, record_stride floats apart, `capacity` records per frame; NULL: none): an applied entry at
+ *      list position e of frame f adds dL_duv (2), dL_dconic (3) and, unless detach_opacity, dL_dopacity (1) with float atomics to
+ *      the leading floats ux uy ca cb cc o of the record at slot slot_sorted[f, range.x + e] of frame f -- the record the tile
+ *      backward wrote for that (Gaussian, tile) pair; the Gaussian-side walk sums a Gaussian's records.  The FEATURE gradients
+ *      are added to dL_dfeature with a frame stride (0: the sum over the frames into [P, C]; else each frame's own block; NULL:
+ *      none).  The entry RELIES ON: corner_T / corner_ncontrib of the batch forward on the same buffers; the tile backward of the
+ *      same forward having run before it on the stream (every variant writes EVERY record of a frame's used slots: the combined
+ *      record of the entries it replays, a zero record for the others); the Gaussian-side backward running after it.
+ *      DETERMINISM: float atomics; with splat_set_deterministic(1) the entry returns SPLAT_E_ARG before any launch.
  *      splat_track_flow_rows: rows [P, T, 3] (Gaussian-major: the feature [P, 3 T] of the call above), rows[n, t] =
  *      (u_t - u_ref, v_t - v_ref, depth_t) with (u_t, v_t, depth_t) the orthographic project_point of get_position at the t-th
  *      time of tab (a device table of T 64-byte frame entries, as splat_dynamic_positions_batch_forward takes it) and uv_ref [P, 2]
@@ -868,6 +895,19 @@ int splat_alpha_blending_points_backward(int P, int C, const float *uv, const fl
                                          int W, int H, int Q, const float *points, const float *corner_T,
                                          const int32_t *corner_ncontrib, const float *dL_dout, float *dL_duv, float *dL_dconic,
                                          float *dL_dopacity, float *dL_dfeature, splat_stream_t stream);
+int splat_alpha_blending_points_forward_batch(int F, int P, int C, const float *uv, const float *conic, const float *opacity,
+                                              int64_t opacity_frame_stride, const float *feature, int64_t feature_frame_stride,
+                                              const int32_t *idx_sorted, const int32_t *tile_range, int64_t capacity, float bg,
+                                              int W, int H, int64_t Q, const int64_t *offsets, const float *points, float *out,
+                                              float *corner_T, int32_t *corner_ncontrib, splat_stream_t stream);
+int splat_alpha_blending_points_backward_batch(int F, int P, int C, const float *uv, const float *conic, const float *opacity,
+                                               int64_t opacity_frame_stride, const float *feature, int64_t feature_frame_stride,
+                                               const int32_t *idx_sorted, const int32_t *tile_range, int64_t capacity, float bg,
+                                               int W, int H, int64_t Q, const int64_t *offsets, const float *points,
+                                               const float *corner_T, const int32_t *corner_ncontrib, const float *dL_dout,
+                                               const int32_t *slot_sorted, float *pair_records, int record_stride,
+                                               int detach_opacity, float *dL_dfeature, int64_t dfeature_frame_stride,
+                                               splat_stream_t stream);
 int splat_track_flow_rows(int T, int P, int I, const void *tab, const float *position, const float *cubic, int cubic_layout,
                           const float *extr, int W, int H, float nearest, float extent, const float *uv_ref, float *rows,
                           splat_stream_t stream);

@@ -60,6 +60,7 @@ SYMBOLS = [
     "splat_track_loss_scratch_bytes", "splat_track_loss_grad",
     "splat_depth_dpt_scratch_bytes", "splat_depth_stats", "splat_depth_dpt_loss_grad",
     "splat_alpha_blending_points_forward", "splat_alpha_blending_points_forward_live", "splat_alpha_blending_points_backward", "splat_track_flow_rows",
+    "splat_alpha_blending_points_forward_batch", "splat_alpha_blending_points_backward_batch", "splat_track_loss_grad_points",
 ]
 
 
@@ -123,6 +124,11 @@ def lib() -> ctypes.CDLL:
         L.splat_alpha_blending_points_forward_live.argtypes = L.splat_alpha_blending_points_forward.argtypes
         L.splat_alpha_blending_points_backward.argtypes = [i, i, p, p, p, p, p, p, f, i, i, i, p, p, p, p, p, p, p, p, p]
         L.splat_track_flow_rows.argtypes = [i, i, i, p, p, p, i, p, i, i, f, f, p, p, p]
+        i64 = ctypes.c_int64
+        L.splat_alpha_blending_points_forward_batch.argtypes = [i, i, i, p, p, p, i64, p, i64, p, p, i64, f, i, i, i64, p, p, p, p, p, p]
+        L.splat_alpha_blending_points_backward_batch.argtypes = [i, i, i, p, p, p, i64, p, i64, p, p, i64, f, i, i, i64, p, p, p, p, p,
+                                                                 p, p, i, i, p, i64, p]
+        L.splat_track_loss_grad_points.argtypes = [i, i, i, i, p, p, p, p, i64, p, f, f, p, p, p, p, p, p]
         if L.splat_abi_version() != ABI_VERSION:
             raise SplatError("libsplat_hip.so ABI version mismatch; rebuild it")
         _lib = L

@@ -176,11 +176,15 @@ __device__ __forceinline__ bool cull_test(float u, float v, float a, float b, fl
 // One record per (tile, splat) pair at its Gaussian-major slot: r[] = [ux uy ca cb cc o | ax ay (ABS) | bias (BIAS) |
 // CH feature terms] -- written by the tile kernels of blend.hip, summed per Gaussian by pair_reduce (blend.hip) or by
 // the frame-batch Gaussian-side backward (preprocess.hip).
+// Both record layouts (GradLayout below and the SETS record) BEGIN with the same geometry fields, at these float indices: the
+// tile kernels of blend.hip write them, the Gaussian-side walks read them, and the frame-batched sparse compositing backward
+// (query.hip) adds its share into them.
+enum { REC_UX = 0, REC_UY = 1, REC_CA = 2, REC_CB = 3, REC_CC = 4, REC_O = 5, REC_GEOM = 6 };
 template <bool ABS, bool BIAS>
 struct GradLayout {
-    static constexpr int NG = 6 + (ABS ? 2 : 0) + (BIAS ? 1 : 0);
-    static constexpr int I_ABS = 6;
-    static constexpr int I_BIAS = 6 + (ABS ? 2 : 0);
+    static constexpr int NG = REC_GEOM + (ABS ? 2 : 0) + (BIAS ? 1 : 0);
+    static constexpr int I_ABS = REC_GEOM;
+    static constexpr int I_BIAS = REC_GEOM + (ABS ? 2 : 0);
 };
 // stride of a pair record in floats: the used floats rounded up to whole 16-byte chunks (a Gaussian's records are
 // contiguous and streamed with float4 loads; padding every record to a 64-byte sector cost 30 % more traffic)
@@ -190,6 +194,7 @@ struct GradLayout {
 // start on a chunk boundary (the tile kernel stores them as float4, the Gaussian-side walk reads whole chunks anyway; for the
 // renderer's 23 channels the stride stays PAIR_STRIDE(12 + 23) = 36 floats)
 constexpr int SETS_NG = 12;
+static_assert(REC_O + 1 == REC_GEOM && REC_GEOM <= SETS_NG, "ux uy ca cb cc o lead both record layouts");
 // Workgroups are handed to the 8 XCDs round-robin by linear block id, and every XCD has its own L2.  Neighbouring
 // tiles gather largely the same packed records (a splat touches ~4 tiles), so runs of XCD_RUN consecutive tiles
 // of the row-major order go to the same XCD (its consecutive blocks, i.e. roughly concurrently resident), and the runs

@@ -488,7 +488,9 @@ __device__ __forceinline__ float trk_one_minus_sigmoid(float x) {
 }
 
 // query e of frame f (whose queries start at o0): false when invisible or malformed (pixel out of range, or not above the
-// previous query's); else its residual parts and weight
+// previous query's); else its residual parts and weight.  PTS (splat_track_loss_grad_points): the prediction is row e of a value
+// table [Q, C] (is[0] = C, is[1] = 1) instead of the image's pixel -- the only difference, the pixel still decides `malformed`
+template <bool PTS>
 __device__ __forceinline__ bool trk_point(const TrackArgs &A, int f, long long o0, long long e, float w, float &dx, float &dy,
                                           float &r, float &c, int &py, int &px) {
 #pragma clang fp contract(off)
@@ -499,7 +501,7 @@ __device__ __forceinline__ bool trk_point(const TrackArgs &A, int f, long long o
     if (!(trk_one_minus_sigmoid(t.z) * conf > 0.5f)) return false;
     py = p / A.W;
     px = p - py * A.W;
-    const float *b = A.img + (long long)f * A.is[0] + (long long)py * A.is[2] + (long long)px * A.is[3];
+    const float *b = PTS ? A.img + e * A.is[0] : A.img + (long long)f * A.is[0] + (long long)py * A.is[2] + (long long)px * A.is[3];
     const float X = ((b[0] + 1.f) * (float)A.W) / 2.f;
     const float Y = ((b[A.is[1]] + 1.f) * (float)A.H) / 2.f;
     dx = X - t.x;
@@ -521,6 +523,7 @@ __device__ __forceinline__ unsigned wave_min_u(unsigned v) {
     return v;
 }
 
+template <bool PTS>
 __global__ void __launch_bounds__(TRK_THREADS) track_loss_kernel(TrackArgs A) {
 #pragma clang fp contract(off)
     __shared__ unsigned hist[256];
@@ -541,7 +544,7 @@ __global__ void __launch_bounds__(TRK_THREADS) track_loss_kernel(TrackArgs A) {
         float dx, dy, r, c;
         int py, px;
         unsigned key = TRK_NONE;
-        if (trk_point(A, f, o0, e, w, dx, dy, r, c, py, px)) {
+        if (trk_point<PTS>(A, f, o0, e, w, dx, dy, r, c, py, px)) {
             key = __float_as_uint(r);
             ++nloc;
             nnan += key > 0x7f800000u;
@@ -678,9 +681,9 @@ __global__ void __launch_bounds__(TRK_THREADS) track_loss_kernel(TrackArgs A) {
     for (long long e = o0 + tid; e < o1; e += TRK_THREADS) {
         float dx, dy, r, c;
         int py, px;
-        if (!trk_point(A, f, o0, e, w, dx, dy, r, c, py, px) || !(r <= thr)) continue;
+        if (!trk_point<PTS>(A, f, o0, e, w, dx, dy, r, c, py, px) || !(r <= thr)) continue;
         const float g = base * c;
-        float *gp = A.grad + (long long)f * A.gs[0] + (long long)py * A.gs[2] + (long long)px * A.gs[3];
+        float *gp = PTS ? A.grad + e * A.gs[0] : A.grad + (long long)f * A.gs[0] + (long long)py * A.gs[2] + (long long)px * A.gs[3];
         gp[0] += dx > 0.f ? g * hx : (dx < 0.f ? -(g * hx) : 0.f);
         gp[A.gs[1]] += dy > 0.f ? g * hy : (dy < 0.f ? -(g * hy) : 0.f);
     }
@@ -760,7 +763,55 @@ extern "C" int splat_track_loss_grad(int F, int H, int W, int C, const float *tr
                      C, H, W, (int)planes);
         SPLAT_POST_LAUNCH();
     }
-    SPLAT_LAUNCH("track_loss", track_loss_kernel, dim3(F), dim3(TRK_THREADS), 0, s, A);
+    SPLAT_LAUNCH("track_loss", track_loss_kernel<false>, dim3(F), dim3(TRK_THREADS), 0, s, A);
+    SPLAT_POST_LAUNCH();
+    if (loss_slot) {
+        SPLAT_LAUNCH("track_loss_slot", track_loss_slot_kernel, dim3(1), dim3(WAVE), 0, s, F, (const float *)A.part, loss_slot);
+        SPLAT_POST_LAUNCH();
+    }
+    return SPLAT_OK;
+}
+
+// The same loss on PER-QUERY values: row i of values [Q, C] is the prediction of query i (what the sparse compositing returns at
+// the query pixels, in target order), grad [Q, C] its gradient.  Same kernels, same contraction-off residual arithmetic: only
+// the two address computations differ, so losses, counts and gradient rows are bit-equal to splat_track_loss_grad on an image
+// that holds those values at the query pixels.
+extern "C" int splat_track_loss_grad_points(int F, int H, int W, int C, const float *values, const int64_t *offsets,
+                                            const int32_t *pixels, const float *targets, int64_t Q, const float *frame_weights,
+                                            float quantile, float scale, float *grad, float *per_frame, float *loss_slot,
+                                            int32_t *counts, void *scratch, splat_stream_t stream) {
+    SPLAT_CHECK_ARG(F >= 1 && H >= 1 && W >= 1 && C >= 2 && Q >= 0, "bad sizes (F, H, W >= 1, C >= 2, Q >= 0)");
+    SPLAT_CHECK_ARG((long long)H * W <= 0x7fffffffLL && Q <= 0x7fffffffLL && F <= (1 << 24) && (long long)Q * C <= 0x7fffffffLL,
+                    "sizes too large");
+    SPLAT_CHECK_ARG(quantile >= 0.f && quantile <= 1.f, "quantile must be in [0, 1]");
+    SPLAT_CHECK_ARG(offsets && frame_weights && scratch, "null pointer");
+    SPLAT_CHECK_ARG(Q == 0 || (values && pixels && targets), "null pointer (values / pixels / targets)");
+    SPLAT_CHECK_ARG(((uintptr_t)targets & 15) == 0, "targets must be 16-byte aligned [Q, 4] float32");
+    const hipStream_t s = (hipStream_t)stream;
+    TrackArgs A;
+    memset(&A, 0, sizeof(A));
+    A.H = H; A.W = W;
+    A.img = values;
+    A.is[0] = C; A.is[1] = 1;
+    A.offsets = offsets; A.pixels = pixels; A.targets = (const float4 *)targets; A.Q = Q;
+    A.fw = frame_weights;
+    A.q = quantile;
+    A.gscale = scale / (float)F;
+    A.grad = Q > 0 ? grad : nullptr;
+    A.gs[0] = C; A.gs[1] = 1;
+    A.per_frame = per_frame;
+    A.counts = counts;
+    A.keys = (unsigned *)scratch;
+    A.part = (float *)((char *)scratch + trk_align((size_t)Q * sizeof(unsigned)));
+    if (A.grad) {   // written in full: zeros outside the selected set and in channels >= 2
+        const long long n = (long long)Q * C;
+        long long bx = (n + 255) / 256;
+        if (bx > 1024) bx = 1024;
+        SPLAT_LAUNCH("track_grad_zero", track_grad_zero_kernel, dim3((unsigned)bx, 1u), dim3(256), 0, s, grad, 0ll, 0ll, 0ll, 1ll, 1, 1,
+                     (int)n, 1);
+        SPLAT_POST_LAUNCH();
+    }
+    SPLAT_LAUNCH("track_loss", track_loss_kernel<true>, dim3(F), dim3(TRK_THREADS), 0, s, A);
     SPLAT_POST_LAUNCH();
     if (loss_slot) {
         SPLAT_LAUNCH("track_loss_slot", track_loss_slot_kernel, dim3(1), dim3(WAVE), 0, s, F, (const float *)A.part, loss_slot);

@@ -17,6 +17,9 @@
 //   * the four corner values (F + T bg) meet in LDS and are combined nw, ne, sw, se with the bilinear weights.  No
 //     atomics anywhere in the forward: results are bit-reproducible.
 //   * the backward (points_bwd_kernel below) replays every corner's list back to front and adds with float atomics.
+//   * the frame-batched entries (BATCH instantiations of the same two kernels) take the queries of F frames in CSR form: the
+//     frame of a query comes from `offsets` on the device (F is a few dozen: a scalar scan), the FrameBatch buffers are read
+//     through their frame strides, and the backward adds its geometry gradients into the frame batch's pair records.
 #include "blend_power.h"
 #include "dynamics_dev.h"
 #include "pointwise_dev.h"
@@ -44,15 +47,64 @@ __device__ __forceinline__ float lane_f(float v, int j) {
     return __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(v), j));
 }
 
+// The frame-batched view (BATCH kernels): the queries offsets[f] .. offsets[f + 1] belong to frame f, whose buffers lie
+// f * stride behind the batch's base pointers (uv [F,P,2], conic [F,P,3], idx_sorted / slot_sorted [F,cap], tile_range [F,T,2];
+// opacity, feature and dL_dfeature with their own frame strides, 0 = shared by the frames).
+struct PointsBatch {
+    int F, T;
+    const long long *offsets;   // device int64 [F + 1]
+    long long Q, cap, opacity_fs, feature_fs, dfeature_fs;
+    // backward: the geometry gradients go into the pair records of the frame batch (record of frame f, slot s at
+    // rec + (f * cap + s) * rec_stride floats; fields REC_UX .. REC_O of common.h)
+    const int *slot_sorted;
+    float *rec;
+    int rec_stride, detach_opacity;
+};
+
+// frame of query q: the first f with 0 <= offsets[f] <= q < offsets[f + 1] <= Q, or -1 (malformed offsets: nobody owns q).
+// Uniform per workgroup: scalar loads.
+__device__ __forceinline__ int points_frame_of(const PointsBatch &B, long long q) {
+    int f = -1;
+    for (int i = B.F - 1; i >= 0; --i) {
+        const long long o0 = B.offsets[i], o1 = B.offsets[i + 1];
+        if (0 <= o0 && o0 <= q && q < o1 && o1 <= B.Q) f = i;
+    }
+    return f;
+}
+
+template <typename Args>
+__device__ __forceinline__ void points_frame_view(Args &A, const PointsBatch &B, int f) {
+    const size_t fz = (size_t)f;
+    A.uv += fz * (size_t)A.P;
+    A.conic += fz * 3 * (size_t)A.P;
+    A.opacity += fz * (size_t)B.opacity_fs;
+    A.feature += fz * (size_t)B.feature_fs;
+    if (A.idx_sorted) A.idx_sorted += fz * (size_t)B.cap;
+    A.tile_range += fz * (size_t)B.T;
+}
+
 // LIVE: an in-image corner whose bilinear weight is zero is not walked either (it reports T = 0, ncontrib = 0 like a corner
 // outside and adds 0 * bg = 0: the same value bits for finite features) -- the differentiable route's forward, whose backward
 // replays only the corners that carry weight; an integer query pixel then walks one list instead of four.
-template <int NA, bool LIVE>
-__global__ void __launch_bounds__(256) points_fwd_kernel(const PointsArgs A) {
+template <int NA, bool LIVE, bool BATCH>
+__global__ void __launch_bounds__(256) points_fwd_kernel(const PointsArgs A0, const PointsBatch B) {
     __shared__ float s_val[4][64 * NA];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave = corner: uniform, so the walk below branches on scalars
     const size_t q = blockIdx.x;
+    PointsArgs A = A0;
+    if (BATCH) {
+        const int f = points_frame_of(B, (long long)q);
+        if (f < 0) {   // a query no frame owns: a row of zeros, nothing dereferenced (uniform: the whole workgroup leaves)
+            for (int c = tid; c < A.cn; c += 256) A.out[q * (size_t)A.C + A.c0 + c] = 0.f;
+            if (tid < 4) {
+                if (A.corner_T) A.corner_T[q * 4 + tid] = 0.f;
+                if (A.corner_n) A.corner_n[q * 4 + tid] = 0;
+            }
+            return;
+        }
+        if (A.P > 0) points_frame_view(A, B, f);
+    }
     const float2 pt = A.points[q];
     // corner w of the query: the in / out test in float, before any conversion to int (1e9, inf and NaN are simply outside)
     const float x0f = floorf(pt.x), y0f = floorf(pt.y);
@@ -185,9 +237,12 @@ __global__ void __launch_bounds__(256) points_fwd_kernel(const PointsArgs A) {
 }
 
 template <int NA>
-int launch_points(const PointsArgs &A, int Q, bool live, hipStream_t s) {
-    if (live) SPLAT_LAUNCH("blend_points", (points_fwd_kernel<NA, true>), dim3((unsigned)Q), dim3(256), 0, s, A);
-    else SPLAT_LAUNCH("blend_points", (points_fwd_kernel<NA, false>), dim3((unsigned)Q), dim3(256), 0, s, A);
+int launch_points(const PointsArgs &A, int Q, bool live, hipStream_t s, const PointsBatch *batch = nullptr) {
+    PointsBatch B;
+    memset(&B, 0, sizeof(B));
+    if (batch) SPLAT_LAUNCH("blend_points", (points_fwd_kernel<NA, true, true>), dim3((unsigned)Q), dim3(256), 0, s, A, *batch);
+    else if (live) SPLAT_LAUNCH("blend_points", (points_fwd_kernel<NA, true, false>), dim3((unsigned)Q), dim3(256), 0, s, A, B);
+    else SPLAT_LAUNCH("blend_points", (points_fwd_kernel<NA, false, false>), dim3((unsigned)Q), dim3(256), 0, s, A, B);
     SPLAT_POST_LAUNCH();
     return SPLAT_OK;
 }
@@ -195,7 +250,8 @@ int launch_points(const PointsArgs &A, int Q, bool live, hipStream_t s) {
 // the launches of the validated forward: one per 256 channels
 int points_forward_chunks(int P, int C, const float *uv, const float *conic, const float *opacity, const float *feature,
                           const int32_t *idx_sorted, const int32_t *tile_range, float bg, int W, int H, int Q, const float *points,
-                          float *out, float *corner_T, int32_t *corner_ncontrib, bool live, hipStream_t stream) {
+                          float *out, float *corner_T, int32_t *corner_ncontrib, bool live, hipStream_t stream,
+                          const PointsBatch *batch = nullptr) {
     PointsArgs A;
     memset(&A, 0, sizeof(A));
     A.P = P; A.C = C;
@@ -211,10 +267,10 @@ int points_forward_chunks(int P, int C, const float *uv, const float *conic, con
         A.corner_n = c0 == 0 ? corner_ncontrib : nullptr;
         int rc;
         switch ((A.cn + 63) / 64) {
-            case 1: rc = launch_points<1>(A, Q, live, stream); break;
-            case 2: rc = launch_points<2>(A, Q, live, stream); break;
-            case 3: rc = launch_points<3>(A, Q, live, stream); break;
-            default: rc = launch_points<4>(A, Q, live, stream); break;
+            case 1: rc = launch_points<1>(A, Q, live, stream, batch); break;
+            case 2: rc = launch_points<2>(A, Q, live, stream, batch); break;
+            case 3: rc = launch_points<3>(A, Q, live, stream, batch); break;
+            default: rc = launch_points<4>(A, Q, live, stream, batch); break;
         }
         if (rc != SPLAT_OK) return rc;
     }
@@ -246,11 +302,27 @@ struct PointsBwdArgs {
     float *dL_duv, *dL_dconic, *dL_dopacity, *dL_dfeature;   // each may be NULL
 };
 
-template <int NA>
-__global__ void __launch_bounds__(256) points_bwd_kernel(const PointsBwdArgs A) {
+// BATCH: the queries of F frames (PointsBatch).  The geometry gradients of an applied entry at list position e of frame f are
+// added to the pair record at slot slot_sorted[f, range.x + e] of that frame -- the record the tile backward of the same forward
+// wrote for this (Gaussian, tile) pair, which the Gaussian-side walk sums per Gaussian afterwards.
+template <int NA, bool BATCH>
+__global__ void __launch_bounds__(256) points_bwd_kernel(const PointsBwdArgs A0, const PointsBatch B) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave = corner
     const size_t q = blockIdx.x;
+    PointsBwdArgs A = A0;
+    const int *slots = nullptr;   // BATCH: the frame's slot_sorted
+    float *recs = nullptr;        //        and its pair records
+    if (BATCH) {
+        const int f = points_frame_of(B, (long long)q);
+        if (f < 0) return;        // a query no frame owns
+        points_frame_view(A, B, f);
+        if (A.dL_dfeature) A.dL_dfeature += (size_t)f * (size_t)B.dfeature_fs;
+        if (B.rec) {
+            slots = B.slot_sorted + (size_t)f * (size_t)B.cap;
+            recs = B.rec + (size_t)f * (size_t)B.cap * (size_t)B.rec_stride;
+        }
+    }
     const float2 ptv = A.points[q];
     const float ptx = lane_f(ptv.x, 0), pty = lane_f(ptv.y, 0);   // (uniform: the exits below are scalar branches)
     // the forward's corner, in / out test and bilinear weight
@@ -358,23 +430,41 @@ __global__ void __launch_bounds__(256) points_bwd_kernel(const PointsBwdArgs A) 
             const float dx = ux - pxf, dy = uy - pyf;
             const float G = araw * __builtin_amdgcn_rcpf(o);
             const float dLG = o * dLa_v;
-            if (A.dL_duv) {
-                atomic_add_f32(A.dL_duv + 2 * (size_t)id, dLG * (-G * dx * cA - G * dy * cB));
-                atomic_add_f32(A.dL_duv + 2 * (size_t)id + 1, dLG * (-G * dy * cC - G * dx * cB));
+            if (BATCH) {
+                if (recs) {
+                    const int slot = slots[range.x + e];
+                    if (slot >= 0 && (long long)slot < B.cap) {   // (a slot outside the frame's records is skipped, never written)
+                        float *r = recs + (size_t)slot * (size_t)B.rec_stride;
+                        atomic_add_f32(r + REC_UX, dLG * (-G * dx * cA - G * dy * cB));
+                        atomic_add_f32(r + REC_UY, dLG * (-G * dy * cC - G * dx * cB));
+                        atomic_add_f32(r + REC_CA, -0.5f * G * dx * dx * dLG);
+                        atomic_add_f32(r + REC_CB, -G * dx * dy * dLG);
+                        atomic_add_f32(r + REC_CC, -0.5f * G * dy * dy * dLG);
+                        if (!B.detach_opacity) atomic_add_f32(r + REC_O, G * dLa_v);
+                    }
+                }
+            } else {
+                if (A.dL_duv) {
+                    atomic_add_f32(A.dL_duv + 2 * (size_t)id, dLG * (-G * dx * cA - G * dy * cB));
+                    atomic_add_f32(A.dL_duv + 2 * (size_t)id + 1, dLG * (-G * dy * cC - G * dx * cB));
+                }
+                if (A.dL_dconic) {
+                    atomic_add_f32(A.dL_dconic + 3 * (size_t)id, -0.5f * G * dx * dx * dLG);
+                    atomic_add_f32(A.dL_dconic + 3 * (size_t)id + 1, -G * dx * dy * dLG);
+                    atomic_add_f32(A.dL_dconic + 3 * (size_t)id + 2, -0.5f * G * dy * dy * dLG);
+                }
+                if (A.dL_dopacity) atomic_add_f32(A.dL_dopacity + id, G * dLa_v);
             }
-            if (A.dL_dconic) {
-                atomic_add_f32(A.dL_dconic + 3 * (size_t)id, -0.5f * G * dx * dx * dLG);
-                atomic_add_f32(A.dL_dconic + 3 * (size_t)id + 1, -G * dx * dy * dLG);
-                atomic_add_f32(A.dL_dconic + 3 * (size_t)id + 2, -0.5f * G * dy * dy * dLG);
-            }
-            if (A.dL_dopacity) atomic_add_f32(A.dL_dopacity + id, G * dLa_v);
         }
     }
 }
 
 template <int NA>
-int launch_points_bwd(const PointsBwdArgs &A, int Q, hipStream_t s) {
-    SPLAT_LAUNCH("blend_points_bwd", points_bwd_kernel<NA>, dim3((unsigned)Q), dim3(256), 0, s, A);
+int launch_points_bwd(const PointsBwdArgs &A, int Q, hipStream_t s, const PointsBatch *batch = nullptr) {
+    PointsBatch B;
+    memset(&B, 0, sizeof(B));
+    if (batch) SPLAT_LAUNCH("blend_points_bwd", (points_bwd_kernel<NA, true>), dim3((unsigned)Q), dim3(256), 0, s, A, *batch);
+    else SPLAT_LAUNCH("blend_points_bwd", (points_bwd_kernel<NA, false>), dim3((unsigned)Q), dim3(256), 0, s, A, B);
     SPLAT_POST_LAUNCH();
     return SPLAT_OK;
 }
@@ -484,6 +574,103 @@ extern "C" int splat_alpha_blending_points_backward(int P, int C, const float *u
             default: rc = launch_points_bwd<4>(A, Q, (hipStream_t)stream); break;
         }
         if (rc != SPLAT_OK) return rc;
+    }
+    return SPLAT_OK;
+}
+
+// ---- the frame-batched entries: the queries of F frames of a FrameBatch in one launch per 256-channel chunk
+namespace {
+int points_batch_check(const char *fn, int F, int P, int C, int W, int H, int64_t Q, int64_t capacity, int64_t opacity_fs,
+                       int64_t feature_fs) {
+    if (!(F >= 1 && P >= 0 && C >= 1 && W > 0 && H > 0 && Q >= 0 && capacity >= 0 && opacity_fs >= 0 && feature_fs >= 0)) {
+        splat_set_error("%s: bad sizes (F, C, W, H >= 1; P, Q, capacity, frame strides >= 0)", fn);
+        return SPLAT_E_ARG;
+    }
+    if (!(W <= (1 << 24) && H <= (1 << 24) && Q <= 0x7fffffffLL && F <= (1 << 16))) {
+        splat_set_error("%s: sizes too large (W, H <= 2^24: pixel indices are compared in float32; Q < 2^31, F <= 2^16)", fn);
+        return SPLAT_E_ARG;
+    }
+    return SPLAT_OK;
+}
+}  // namespace
+
+extern "C" int splat_alpha_blending_points_forward_batch(int F, int P, int C, const float *uv, const float *conic,
+                                                         const float *opacity, int64_t opacity_frame_stride, const float *feature,
+                                                         int64_t feature_frame_stride, const int32_t *idx_sorted,
+                                                         const int32_t *tile_range, int64_t capacity, float bg, int W, int H,
+                                                         int64_t Q, const int64_t *offsets, const float *points, float *out,
+                                                         float *corner_T, int32_t *corner_ncontrib, splat_stream_t stream) {
+    const int rc = points_batch_check(__func__, F, P, C, W, H, Q, capacity, opacity_frame_stride, feature_frame_stride);
+    if (rc != SPLAT_OK) return rc;
+    if (Q == 0) return SPLAT_OK;
+    SPLAT_CHECK_ARG(points && out && offsets, "null pointer (points / out / offsets)");
+    // idx_sorted may be NULL when no Gaussian touches any tile (every tile range is empty, nothing dereferences it)
+    SPLAT_CHECK_ARG(P == 0 || (uv && conic && opacity && feature && tile_range), "null pointer");
+    PointsBatch B;
+    memset(&B, 0, sizeof(B));
+    B.F = F; B.T = ((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
+    B.offsets = (const long long *)offsets; B.Q = Q; B.cap = capacity;
+    B.opacity_fs = opacity_frame_stride; B.feature_fs = feature_frame_stride;
+    return points_forward_chunks(P, C, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, (int)Q, points, out, corner_T,
+                                 corner_ncontrib, true, (hipStream_t)stream, &B);
+}
+
+// RELIES ON: (1) corner_T / corner_ncontrib of splat_alpha_blending_points_forward_batch on the same buffers; (2) the tile
+// backward of the SAME forward (splat_alpha_blending_backward_batch_sets* / _batch) has run on this stream and has WRITTEN every
+// record of every frame's used slots -- each variant stores the combined record of the entries it replays and a zero record for
+// the entries nobody replays, so this entry only ever adds to initialised floats; (3) the Gaussian-side backward
+// (splat_frames_gauss_backward_*), which sums a Gaussian's records, runs after it.
+extern "C" int splat_alpha_blending_points_backward_batch(int F, int P, int C, const float *uv, const float *conic,
+                                                          const float *opacity, int64_t opacity_frame_stride, const float *feature,
+                                                          int64_t feature_frame_stride, const int32_t *idx_sorted,
+                                                          const int32_t *tile_range, int64_t capacity, float bg, int W, int H,
+                                                          int64_t Q, const int64_t *offsets, const float *points,
+                                                          const float *corner_T, const int32_t *corner_ncontrib,
+                                                          const float *dL_dout, const int32_t *slot_sorted, float *pair_records,
+                                                          int record_stride, int detach_opacity, float *dL_dfeature,
+                                                          int64_t dfeature_frame_stride, splat_stream_t stream) {
+    const int rc = points_batch_check(__func__, F, P, C, W, H, Q, capacity, opacity_frame_stride, feature_frame_stride);
+    if (rc != SPLAT_OK) return rc;
+    SPLAT_CHECK_ARG(dfeature_frame_stride >= 0, "bad sizes (dL_dfeature frame stride >= 0)");
+    SPLAT_CHECK_ARG(!pair_records || (record_stride >= REC_GEOM && record_stride % 4 == 0 && capacity >= 1),
+                    "bad sizes (pair records: a stride of whole 16-byte chunks >= 8 floats, capacity >= 1)");
+    if (Q == 0) return SPLAT_OK;
+    SPLAT_CHECK_ARG(points && offsets && corner_T && corner_ncontrib && dL_dout,
+                    "null pointer (points / offsets / corner_T / corner_ncontrib / dL_dout)");
+    SPLAT_CHECK_ARG(P == 0 || (uv && conic && opacity && feature && tile_range), "null pointer");
+    SPLAT_CHECK_ARG(!pair_records || slot_sorted, "null pointer (slot_sorted goes with pair_records)");
+    if (P == 0 || !(pair_records || dL_dfeature)) return SPLAT_OK;   // nothing to add to
+    SPLAT_CHECK_ARG(idx_sorted, "null pointer (idx_sorted)");
+    if (splat_deterministic()) {   // refused before any launch
+        splat_set_error("%s: deterministic mode: the backward of the sparse compositing adds with float atomics (many queries hit "
+                        "one Gaussian); render the set densely instead", __func__);
+        return SPLAT_E_ARG;
+    }
+    PointsBatch B;
+    memset(&B, 0, sizeof(B));
+    B.F = F; B.T = ((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
+    B.offsets = (const long long *)offsets; B.Q = Q; B.cap = capacity;
+    B.opacity_fs = opacity_frame_stride; B.feature_fs = feature_frame_stride; B.dfeature_fs = dfeature_frame_stride;
+    B.slot_sorted = slot_sorted; B.rec = pair_records; B.rec_stride = record_stride; B.detach_opacity = detach_opacity ? 1 : 0;
+    PointsBwdArgs A;
+    memset(&A, 0, sizeof(A));
+    A.P = P; A.C = C;
+    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
+    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
+    A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
+    A.points = (const float2 *)points; A.corner_T = corner_T; A.corner_n = corner_ncontrib; A.dL_dout = dL_dout;
+    A.dL_dfeature = dL_dfeature;
+    for (int c0 = 0; c0 < C; c0 += PT_CHUNK) {
+        A.c0 = c0;
+        A.cn = C - c0 > PT_CHUNK ? PT_CHUNK : C - c0;
+        int r;   // every chunk adds its share of the geometry gradients: dL_dalpha is linear in the channels
+        switch ((A.cn + 63) / 64) {
+            case 1: r = launch_points_bwd<1>(A, (int)Q, (hipStream_t)stream, &B); break;
+            case 2: r = launch_points_bwd<2>(A, (int)Q, (hipStream_t)stream, &B); break;
+            case 3: r = launch_points_bwd<3>(A, (int)Q, (hipStream_t)stream, &B); break;
+            default: r = launch_points_bwd<4>(A, (int)Q, (hipStream_t)stream, &B); break;
+        }
+        if (r != SPLAT_OK) return r;
     }
     return SPLAT_OK;
 }

@@ -414,7 +414,7 @@ class FrameBatch:
     def render_dynamic_sets(self, clock, times, extr: Tensor, sets, *, position: Tensor, pos_cubic_node: Tensor,
                             rotation: Tensor, rot_poly_feat: Tensor, rot_fourier_feat: Tensor, opacity: Tensor, scaling: Tensor,
                             cubic_layout: int = 1, K: int = 0, nearest: float = 0.01, extent: float = 1.3,
-                            grad_sink: Optional[Dict[str, Tensor]] = None):
+                            grad_sink: Optional[Dict[str, Tensor]] = None, points: Optional[dict] = None):
         """The reference's real training frame, for all frames of the batch: its dynamic Gaussians (``render_dynamic``)
         through the three blends of ``render_iter`` (``render_sets``: same ``sets`` list, same return value).  The sets must
         fit the one-pass backward (one set per routing group, <= 4 / 4 / 20 channels).
@@ -426,7 +426,16 @@ class FrameBatch:
         tensor's gradient is the sum over the frames, a per-frame tensor gets every frame's own.  ``grad_sink["feature:k"]``
         (k = position of the tensor in the flattened list of all sets' tensors) receives that gradient by ADDITION instead of
         autograd.  Any one-pass plan takes lists / per-frame tensors: the renderer's own plan (rgb 3 | depth 1 | 19 attribute
-        channels) stages the forward's records in the tile kernel, other plans repack them in one launch."""
+        channels) stages the forward's records in the tile kernel, other plans repack them in one launch.
+
+        ``points``: one more feature set composited at SPARSE points only, outside the row (its channels do not count towards
+        ``C``): a dict ``feature`` ([P, c] shared or [F, P, c] per frame), ``points`` [Q, 2] (float (ix, iy), the semantics of
+        ``gs.alpha_blending_points``), ``offsets`` (device int64 [F + 1]: the queries offsets[f] .. offsets[f + 1] belong to frame
+        f, as ``tracks.TrackTargets`` holds them), ``bg``, ``detach_opacity``.  The call then returns one more tensor [Q, c]
+        behind the images and in front of ``gs_idx``, an output of the same autograd node: its gradient enters the batch's pair
+        records between the tile backward and the Gaussian-side backward (float atomics: it raises in deterministic mode); the
+        feature's gradient is ADDED to ``grad_sink["points"]`` (the feature's shape) when given, else returned through autograd.
+        Not differentiable w.r.t. the points.  A ``None`` gradient of the sparse output launches nothing."""
         tab = self.frame_table(clock, times)
         meta, parts, feats = _parse_sets(sets, self.F, self.P)
         widths = [1 if m[0] == "depth" else m[0] for m in meta]
@@ -437,7 +446,10 @@ class FrameBatch:
             raise ValueError("render_dynamic_sets needs sets that fit the one-pass backward: one set per routing group "
                              "(taps / live opacity / detached opacity) of at most 4 / 4 / 20 channels")
         fsink = {k: v for k, v in (grad_sink or {}).items() if k.startswith("feature:")}
-        psink = {k: v for k, v in (grad_sink or {}).items() if not k.startswith("feature:")}
+        psink = {k: v for k, v in (grad_sink or {}).items() if not k.startswith("feature:") and k != "points"}
+        pts = _parse_points(points, (grad_sink or {}).get("points"), self.F, self.P)
+        if pts is None and "points" in (grad_sink or {}):
+            raise ValueError('grad_sink["points"] belongs to the sparse set: pass points=...')
         sink = check_sink(psink, {"position": position, "pos_cubic_node": pos_cubic_node, "rotation": rotation,
                                   "opacity": opacity, "scaling": scaling})
         for k, buf in fsink.items():
@@ -447,7 +459,8 @@ class FrameBatch:
                 raise ValueError(f"grad_sink[{k!r}] must be a float32 GPU buffer of the feature tensor's shape with dense rows")
         return _RenderDynamicSets.apply(position, pos_cubic_node, rotation, opacity, scaling, rot_poly_feat, rot_fourier_feat, extr,
                                         tab, self, int(clock.interval_num), int(cubic_layout), meta, int(K), float(nearest),
-                                        float(extent), sink, parts, fsink or None, *feats)
+                                        float(extent), sink, parts, fsink or None, pts,
+                                        *(list(feats) + ([pts["feature"]] if pts is not None else [])))
 
     # ------------------------------------------------------------------ several feature sets of one geometry (row a1)
     def render_sets(self, xyz: Tensor, scales: Tensor, uquats: Tensor, opacity: Tensor, sets, offsets: Optional[Tensor],
@@ -550,12 +563,15 @@ class _RenderDynamic(torch.autograd.Function):
 
 
 class _RenderDynamicSets(torch.autograd.Function):
-    N_FIXED = 19      # arguments in front of the feature tensors
+    N_FIXED = 20      # arguments in front of the feature tensors
 
     @staticmethod
     def forward(ctx, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr, tab, fb, I, layout, meta, K,
-                nearest, extent, sink, parts, fsink, *feats):
+                nearest, extent, sink, parts, fsink, pts, *feats):
         P, F = fb.P, fb.F
+        pfeat = None
+        if pts is not None:       # the sparse set's feature rides behind the sets' tensors
+            feats, pfeat = feats[:-1], feats[-1]
         position = _points(position, "position", 3)
         rotation = _points(rotation, "rotation", 4)
         scaling = _points(scaling, "scaling", 3)
@@ -589,6 +605,13 @@ class _RenderDynamicSets(torch.autograd.Function):
         ctx.fb, ctx.meta, ctx.sink, ctx.geo = fb, meta, sink, (I, layout)
         ctx.parts, ctx.fsink, ctx.sources = parts, (fsink or {}), sources
         ctx.opa_t = opa_t
+        ctx.pts = None
+        sparse = ()
+        if pts is not None:
+            pfeat = _source_tensor(pfeat, pts["per_frame"], F, P)
+            sparse = (_points_forward(fb, pts, pfeat, opa_t),)
+            ctx.pts = pts
+            feats = tuple(feats) + (pfeat,)
         ctx.save_for_backward(position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr_c, tab, *feats)
         ctx.set_materialize_grads(False)
         imgs, c0 = [], 0
@@ -598,7 +621,7 @@ class _RenderDynamicSets(torch.autograd.Function):
             c0 += w
         if gs_idx is not None:
             ctx.mark_non_differentiable(gs_idx)
-        return tuple(imgs) + (gs_idx,)
+        return tuple(imgs) + sparse + (gs_idx,)
 
     @staticmethod
     def backward(ctx, *grads):
@@ -612,6 +635,22 @@ class _RenderDynamicSets(torch.autograd.Function):
         F, P, W, H, C, cap = fb.F, fb.P, fb.W, fb.H, fb.C, fb.capacity
         dev = fb.dev
         widths = ctx.blend["widths"]
+        pts, pfeat, g_pts, d_pts = ctx.pts, None, None, ()
+        if pts is not None:
+            feats, pfeat = feats[:-1], feats[-1]
+            g_pts = grads[len(meta)]
+            d_pts = (None,)
+
+        def sparse_backward(rec):
+            # the sparse set's gradient: into the pair records the tile backward has just written, before the Gaussian-side walk
+            if g_pts is None:
+                return (None,) if pts is not None else ()
+            want = ctx.needs_input_grad[NF + len(feats)] or pts["sink"] is not None
+            buf, ret = pts["sink"], None
+            if want and buf is None:
+                buf = ret = torch.zeros(pfeat.shape, dtype=torch.float32, device=dev)
+            _points_backward(fb, pts, pfeat, ctx.opa_t, g_pts, rec, buf if want else None)
+            return (ret,)
         like = {"position": position, "pos_cubic_node": cubic, "rotation": rotation, "opacity": opacity, "scaling": scaling}
         bufs = {k: (sink[k] if k in sink else torch.zeros_like(v)) for k, v in like.items()}
         c0s, cns, bgs, depth_ch, tap_set = _one_pass_plan(meta, widths, C)
@@ -621,6 +660,7 @@ class _RenderDynamicSets(torch.autograd.Function):
         if ctx.sources:
             # the row by SOURCES: a shared tensor's gradient is the sum over the frames, a per-frame tensor gets every frame's own
             rec = _blend_sets_backward_one_pass(fb, meta, ctx.blend, grads[:len(meta)], ctx.opa_t, 0, want_abs)
+            d_pts = sparse_backward(rec)
             table = (L.FeatureSource * L.MAX_SOURCES)()
             dfe, n, fi, c0 = [], 0, 0, 0
             for si, ((w, _, _, _), pp) in enumerate(zip(meta, ctx.parts)):
@@ -651,7 +691,7 @@ class _RenderDynamicSets(torch.autograd.Function):
                 table, L.ci(depth_ch), L.ptr(fb.tap if has_tap else None),
                 L.ptr(fb.abs_tap if (has_tap and want_abs) else None), L.ptr(fb.radii_max if has_tap else None), st))
             ret = tuple(None if k in sink else bufs[k] for k in like)
-            return ret + (None,) * (NF - 5) + tuple(dfe)
+            return ret + (None,) * (NF - 5) + tuple(dfe) + d_pts
         group_of = _set_groups(meta)
         fi, dfe, dfs, strides = 0, [], [None, None, None], [0, 0, 0]
         for si, (w, _, _, _) in enumerate(meta):
@@ -663,6 +703,7 @@ class _RenderDynamicSets(torch.autograd.Function):
             dfs[group_of[si]], strides[group_of[si]] = dfeat, int(feats[fi].shape[1])
             fi += 1
         rec = _blend_sets_backward_one_pass(fb, meta, ctx.blend, grads[:len(meta)], ctx.opa_t, 0, want_abs)
+        d_pts = sparse_backward(rec)
         i3 = ctypes.c_int32 * 3
         p3 = (ctypes.c_void_p * 3)(*[0 if d is None else d.data_ptr() for d in dfs])
         L.check(lib.splat_frames_gauss_backward_dynamic_sets(
@@ -673,7 +714,65 @@ class _RenderDynamicSets(torch.autograd.Function):
             L.ci(depth_ch), L.ptr(fb.tap if has_tap else None), L.ptr(fb.abs_tap if (has_tap and want_abs) else None),
             L.ptr(fb.radii_max if has_tap else None), st))
         ret = tuple(None if k in sink else bufs[k] for k in like)
-        return ret + (None,) * (NF - 5) + tuple(dfe)
+        return ret + (None,) * (NF - 5) + tuple(dfe) + d_pts
+
+
+def _parse_points(points, sink, F, P):
+    """the sparse set of ``render_dynamic_sets``: None, or its checked description (feature, points [Q,2], offsets [F+1], bg,
+    detach_opacity, per_frame, the feature's gradient sink or None); nothing here reads device memory"""
+    if points is None:
+        return None
+    unknown = set(points) - {"feature", "points", "offsets", "bg", "detach_opacity"}
+    if unknown:
+        raise ValueError(f"points: unknown keys {sorted(unknown)}")
+    f, xy, off = points.get("feature"), points.get("points"), points.get("offsets")
+    if not isinstance(f, Tensor) or f.dim() not in (2, 3) or f.shape[-2] != P or (f.dim() == 3 and f.shape[0] != F) \
+            or f.shape[-1] < 1 or f.dtype != torch.float32 or not f.is_cuda:
+        raise ValueError(f"points['feature'] must be a float32 GPU tensor [P={P}, c] or [F={F}, P, c]")
+    if not isinstance(xy, Tensor) or xy.dim() != 2 or xy.shape[1] != 2:
+        raise ValueError("points['points'] must be [Q, 2] (ix, iy)")
+    if xy.requires_grad:
+        raise ValueError("the sparse set is not differentiable w.r.t. its points")
+    if not isinstance(off, Tensor) or off.dtype != torch.int64 or tuple(off.shape) != (F + 1,) or not off.is_cuda:
+        raise ValueError(f"points['offsets'] must be a device int64 tensor [F + 1 = {F + 1}]")
+    if sink is not None and (tuple(sink.shape) != tuple(f.shape) or sink.dtype != torch.float32 or not sink.is_cuda
+                             or sink.stride(-1) != 1 or sink.stride(-2) != sink.shape[-1]):
+        raise ValueError('grad_sink["points"] must be a float32 GPU buffer of the sparse feature\'s shape with dense rows')
+    return dict(feature=f, points=L.need(xy.detach(), "points"), offsets=L.need(off, "offsets", torch.int64),
+                bg=float(points.get("bg", 0.0)), detach_opacity=bool(points.get("detach_opacity", False)),
+                per_frame=f.dim() == 3, sink=sink)
+
+
+def _points_forward(fb, pts, pfeat, opacity):
+    """the sparse set at its points (splat_alpha_blending_points_forward_batch on the batch's buffers): [Q, c]; the corners'
+    final transmittance / last applied position stay in ``pts`` for the backward"""
+    Q, c = int(pts["points"].shape[0]), int(pfeat.shape[-1])
+    out = torch.empty(Q, c, dtype=torch.float32, device=fb.dev)
+    pts["corner_T"] = torch.empty(Q, 4, dtype=torch.float32, device=fb.dev)
+    pts["corner_n"] = torch.empty(Q, 4, dtype=torch.int32, device=fb.dev)
+    L.check(L.lib().splat_alpha_blending_points_forward_batch(
+        L.ci(fb.F), L.ci(fb.P), L.ci(c), L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), ctypes.c_int64(0), L.ptr(pfeat),
+        ctypes.c_int64(int(pfeat.stride(0)) if pts["per_frame"] else 0), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range),
+        ctypes.c_int64(fb.capacity), L.cf(pts["bg"]), L.ci(fb.W), L.ci(fb.H), ctypes.c_int64(Q), L.ptr(pts["offsets"]),
+        L.ptr(pts["points"]), L.ptr(out), L.ptr(pts["corner_T"]), L.ptr(pts["corner_n"]), L.stream()))
+    return out
+
+
+def _points_backward(fb, pts, pfeat, opacity, g, rec, d_feature):
+    """splat_alpha_blending_points_backward_batch: the sparse set's geometry gradients into the SETS pair records ``rec`` the tile
+    backward has written, its feature gradient added to ``d_feature`` (the feature's shape; None: not wanted)"""
+    Q, c = int(pts["points"].shape[0]), int(pfeat.shape[-1])
+    g = L.need(g, "gradient of the sparse output")
+    if tuple(g.shape) != (Q, c):
+        raise ValueError(f"the gradient of the sparse output must be [{Q}, {c}]")
+    dfs = 0 if d_feature is None or not pts["per_frame"] else int(d_feature.stride(0))
+    L.check(L.lib().splat_alpha_blending_points_backward_batch(
+        L.ci(fb.F), L.ci(fb.P), L.ci(c), L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), ctypes.c_int64(0), L.ptr(pfeat),
+        ctypes.c_int64(int(pfeat.stride(0)) if pts["per_frame"] else 0), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range),
+        ctypes.c_int64(fb.capacity), L.cf(pts["bg"]), L.ci(fb.W), L.ci(fb.H), ctypes.c_int64(Q), L.ptr(pts["offsets"]),
+        L.ptr(pts["points"]), L.ptr(pts["corner_T"]), L.ptr(pts["corner_n"]), L.ptr(g), L.ptr(fb.slot_sorted), L.ptr(rec),
+        L.ci(int(L.lib().splat_blend_sets_pair_stride(fb.C))), L.ci(1 if pts["detach_opacity"] else 0), L.ptr(d_feature),
+        ctypes.c_int64(dfs), L.stream()))
 
 
 def _parse_sets(sets, F, P):

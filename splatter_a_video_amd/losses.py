@@ -189,6 +189,49 @@ def track_loss_grad(track: torch.Tensor, targets, frame_weights: torch.Tensor, q
                                       L.ptr(per_frame), L.ptr(loss_slot), L.ptr(counts), L.ptr(scratch), L.stream()))
 
 
+def track_loss_points_grad(values: torch.Tensor, targets, frame_weights: torch.Tensor, quantile: float = 0.98, scale: float = 1.0,
+                           grad: torch.Tensor = None, per_frame: torch.Tensor = None, loss_slot: torch.Tensor = None,
+                           counts: torch.Tensor = None) -> None:
+    """``track_loss_grad`` on PER-QUERY predictions (splat_track_loss_grad_points): ``values`` [Q, C >= 2], row i = the prediction
+    of query i of ``targets`` (``tracks.TrackTargets`` of F pairs) in target order -- what
+    ``FrameBatch.render_dynamic_sets(points=...)`` returns at the integer query pixels -- instead of a track image.  ``grad``
+    [Q, C] = scale * d(mean_f loss_f) / d values, written in full (zeros outside the selected set and in channels >= 2); the
+    other outputs as in ``track_loss_grad``.  Losses, counts and gradient rows are bit-equal to ``track_loss_grad`` on an image
+    that holds the values at the query pixels; no image is filled or read."""
+    _check(values, "values")
+    if values.dim() != 2 or values.shape[1] < 2 or values.shape[0] != targets.Q or not values.is_contiguous():
+        raise ValueError(f"values must be a contiguous [Q = {targets.Q}, C >= 2] tensor, got {tuple(values.shape)}")
+    Q, C = values.shape
+    F, H, W = targets.F, targets.H, targets.W
+    if targets.device != values.device:
+        raise ValueError(f"track targets live on {targets.device}, the values on {values.device}")
+    if not 0.0 <= float(quantile) <= 1.0:
+        raise ValueError(f"quantile must be in [0, 1], got {quantile}")
+    fw = frame_weights
+    if not isinstance(fw, torch.Tensor) or fw.numel() != F:
+        raise ValueError(f"frame_weights must be a tensor of {F} weights")
+    fw = fw.to(device=values.device, dtype=torch.float32).reshape(F).contiguous()
+    if grad is not None:
+        _check(grad, "grad")
+        if grad.shape != values.shape or not grad.is_contiguous():
+            raise ValueError(f"grad {tuple(grad.shape)} must be contiguous with the values' shape {tuple(values.shape)}")
+    for t, name, n in ((per_frame, "per_frame", F), (loss_slot, "loss_slot", 1)):
+        if t is not None and (_check(t, name).numel() != n or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous float32 tensor of {n} elements")
+    if counts is not None and (counts.dtype != torch.int32 or counts.numel() != 2 * F or not counts.is_contiguous()
+                               or counts.device != values.device):
+        raise ValueError(f"counts must be a contiguous int32 [{F}, 2] tensor on the values' device")
+    lib = L.lib()
+    nbytes = lib.splat_track_loss_scratch_bytes(F, Q)
+    if nbytes == 0:
+        raise ValueError(f"track loss: unsupported sizes (F = {F}, Q = {Q})")
+    scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=values.device)
+    L.check(lib.splat_track_loss_grad_points(F, H, W, C, L.ptr(values), L.ptr(targets.offsets), L.ptr(targets.pixels),
+                                             L.ptr(targets.targets), ctypes.c_int64(Q), L.ptr(fw), L.cf(quantile), L.cf(scale),
+                                             L.ptr(grad), L.ptr(per_frame), L.ptr(loss_slot), L.ptr(counts), L.ptr(scratch),
+                                             L.stream()))
+
+
 class _TrackLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, track, targets, frame_weights, quantile):

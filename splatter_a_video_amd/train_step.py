@@ -50,7 +50,7 @@ from .dynamics import (GAUSSIAN_MAJOR, SEGMENT_MAJOR, FrameClock, frame_table, p
 from .frames import FrameBatch
 from .gs.fused_ops import compute_sh_into
 from .gs.point_ops import project_point_ortho
-from .losses import depth_dpt_loss_grad, dssim_l1_grad, planes, track_loss_grad
+from .losses import depth_dpt_loss_grad, dssim_l1_grad, planes, track_loss_grad, track_loss_points_grad
 from .optim import FlatAdam, OwnerShardedAdam, PatternLR
 from .parallel import (FlatGradBucket, OwnerShards, PositionExchangePlan, Zero1Shards, exchange_frames, gather_times, owner_gather,
                        owner_reduce, reduce_densify_batch)
@@ -134,14 +134,19 @@ class TrainingStep:
     ``params``: per-Gaussian tensors on the GPU -- position [N,3], pos_cubic_node [N, 4*I*3] (the reference's layout; stored
     segment-major), rotation [N,4], rot_poly_feat [N,4,4], rot_fourier_feat [N,8,4], opacity [N,1] (logit), scaling [N,3]
     (log), shs [N,16,3], attrs [N,A] (the render attributes behind track_gs; 3 + 1 + 3 + A = the composited row, A = 16 for
-    the renderer's own 23-channel plan).  At set-up (and after every densification) the Gaussians are put in Morton order of their
+    the renderer's own 23-channel plan).  ``sparse_track=True`` (needs LossWeights.track > 0 and attr == 0; default False: the
+    step as it was, bit for bit): the attribute set leaves the frame batch (C = 4: rgb + depth) and the track term runs on
+    track_gs composited at the query pixels of gt["tracks"] only; gt["attr"] is not read, the attributes keep a zero gradient,
+    last["l1_attr"] is a zero scalar, and step() raises in deterministic mode (float atomics).  Only the render part changes:
+    the owner-sharded / ZeRO-1 / position-exchange schedules are untouched by construction.  At set-up (and after every densification) the Gaussians are put in Morton order of their
     screen positions (``spatial_order=False``: kept as given); ``initial_order`` maps the rows here to the caller's."""
 
     def __init__(self, params: Dict[str, Tensor], clock: FrameClock, W: int, H: int, frames_per_step: int, extr: Tensor,
                  lr: Optional[Dict[str, float]] = None, weights: Optional[LossWeights] = None,
                  densify: Optional[DensifyConfig] = None, K: int = 20, knn_K: int = 5, arap_samples: int = 512,
                  bg: float = 0.0, sample_seed: Optional[int] = None, timing: bool = False, owner_sharded: bool = False,
-                 spatial_order: bool = True, zero1: bool = False, fused_l1: bool = True, exchange_positions: bool = False):
+                 spatial_order: bool = True, zero1: bool = False, fused_l1: bool = True, exchange_positions: bool = False,
+                 sparse_track: bool = False):
         self.clock, self.W, self.H, self.F = clock, int(W), int(H), int(frames_per_step)
         self.extr = extr
         self.dev = params["position"].device
@@ -149,6 +154,21 @@ class TrainingStep:
         self.w = weights or LossWeights()
         if self.w.dssim > 0:
             planes(torch.empty(0, 3, 1, 1), self.w.ssim_layout)      # validates the layout name
+        # SPARSE TRACK TERM: the reference supervises nothing of the attribute set but track_gs, and that only at the
+        # TAPIR query pixels.  With sparse_track the frame batch composites rgb + depth alone (C = 4 instead of 3 + 1 + 3 + A) and
+        # track_gs is composited at the query pixels only (FrameBatch.render_dynamic_sets(points=...)); its gradient enters the
+        # batch's pair records before the Gaussian-side backward.  Only the render part of the step changes: the owner-sharded /
+        # ZeRO-1 / position-exchange schedules see the same flat bucket and the same g_pairs and are untouched.  The attributes
+        # stay in the bucket with a zero gradient, as the dense step with attr = 0 leaves them.  The sparse backward adds with
+        # float atomics: step() raises in deterministic mode.
+        self.sparse_track = bool(sparse_track)
+        if self.sparse_track:
+            if not self.w.track > 0:
+                raise ValueError("sparse_track=True replaces the dense track image by compositing at the query pixels: it needs "
+                                 "LossWeights.track > 0 (without a track term there is nothing to composite)")
+            if self.w.attr != 0:
+                raise ValueError("sparse_track=True does not render the attribute images, so they cannot be supervised: it needs "
+                                 "LossWeights.attr == 0 (the reference trainer's configuration)")
         self.cfg = densify or DensifyConfig()
         self.K, self.knn_K, self.S, self.bg = int(K), int(knn_K), int(arap_samples), float(bg)
         self.timing = timing
@@ -216,7 +236,7 @@ class TrainingStep:
                     dst[a:b].copy_(src.reshape(-1))
             self.opt.load_moments(full[0], full[1])
         A = self.p["attrs"].shape[1]
-        self.C = 3 + 1 + 3 + A
+        self.C = 4 if self.sparse_track else 3 + 1 + 3 + A
         self.fb = FrameBatch(self.F, N, self.W, self.H, self.C, self.dev, want_abs=False)
         self.dstate = D.DensifyState(N, self.dev)
         self.dirs = torch.zeros(N, 3, device=self.dev)
@@ -323,6 +343,9 @@ class TrainingStep:
         segment."""
         if len(times1) != self.F or len(times2) != self.F:
             raise ValueError(f"the step takes {self.F} frame pairs")
+        if self.sparse_track and L.deterministic():      # before anything touches the bucket
+            raise L.SplatError("TrainingStep(sparse_track=True): deterministic mode is set and the sparse track term's backward adds "
+                               "with float atomics; build the step with sparse_track=False")
         track = self.w.track > 0
         if track:
             tt = gt.get("tracks")
@@ -359,20 +382,40 @@ class TrainingStep:
         # ---- the frame: dynamic Gaussians through the three blends, track_gs = position(ids2) read in place
         times = list(times1)
         tab1 = self.fb.frame_table(self.clock, times)
-        sets = [dict(feature=rgb, bg=self.bg, taps=True), dict(feature="depth", bg=1.0),
-                dict(feature=[self.pairs[:, 1], p["attrs"]], bg=0.0, detach_opacity=True)]
+        sets = [dict(feature=rgb, bg=self.bg, taps=True), dict(feature="depth", bg=1.0)]
         sink = {k: g[k] for k in ("pos_cubic_node", "rotation", "opacity", "scaling")}
-        sink["feature:1"] = self.g_pairs[:, 1]          # track_gs' gradient: next to the ARAP gradient of position(ids2)
-        sink["feature:2"] = g["attrs"]
+        sparse = None
+        if self.sparse_track:
+            # track_gs at the integer query pixels only: one corner of weight 1 per query, the gradient next to ARAP's
+            tt = gt["tracks"]
+            pix = tt.pixels.long()
+            sparse = dict(feature=self.pairs[:, 1], points=torch.stack([pix % self.W, pix // self.W], dim=1).to(torch.float32),
+                          offsets=tt.offsets, bg=0.0, detach_opacity=True)
+            sink["points"] = self.g_pairs[:, 1]
+        else:
+            sets.append(dict(feature=[self.pairs[:, 1], p["attrs"]], bg=0.0, detach_opacity=True))
+            sink["feature:1"] = self.g_pairs[:, 1]          # track_gs' gradient: next to the ARAP gradient of position(ids2)
+            sink["feature:2"] = g["attrs"]
         out = self.fb.render_dynamic_sets(self.clock, times, self.extr, sets, position=fz["position"],
                                           pos_cubic_node=p["pos_cubic_node"], rotation=p["rotation"],
                                           rot_poly_feat=fz["rot_poly_feat"], rot_fourier_feat=fz["rot_fourier_feat"],
                                           opacity=p["opacity"], scaling=p["scaling"], cubic_layout=SEGMENT_MAJOR, K=self.K,
-                                          grad_sink=sink)
+                                          grad_sink=sink, points=sparse)
         ph.mark("render_forward")
         dssim = self.w.dssim > 0
         dpt = self.w.depth_dpt > 0
-        if self.fused_l1 and not dssim and not track and not dpt and L.get_option("bwd_quarters"):
+        if self.sparse_track:
+            sums = torch.zeros(6, dtype=torch.float32, device=self.dev)      # (l1_rgb, l1_depth, 0 = l1_attr, ssim, track, depth_dpt)
+            g_rgb = (self._rgb_loss_grad(out[0], gt["rgb"], sums) if dssim else self._l1(out[0], gt["rgb"], self.w.rgb, sums[0:1]))
+            wts = _upload(frame_weights(times1, times2, self.clock.num_frames), self.dev)
+            g_pts = torch.empty_like(out[2])
+            track_loss_points_grad(out[2].detach(), gt["tracks"], wts, self.w.track_quantile, self.w.track, g_pts,
+                                   loss_slot=sums[4:5])
+            g_depth = (self._depth_loss_grad(out[1], gt, sums, sums[5:6]) if dpt
+                       else self._l1(out[1], gt["depth"], self.w.depth, sums[1:2]))
+            ph.mark("loss")
+            torch.autograd.backward(list(out[:3]), [g_rgb, g_depth, g_pts])
+        elif self.fused_l1 and not dssim and not track and not dpt and L.get_option("bwd_quarters"):
             # the L1 terms' gradient images are never materialised: the tile kernel derives them from the forward's output row and
             # the ground-truth frames where it hoists the image gradient (splat_alpha_blending_backward_batch_sets_l1)
             fsums = torch.empty(F, self.fb.T, 3, dtype=torch.float32, device=self.dev)      # per tile: every entry is written
@@ -431,10 +474,13 @@ class TrainingStep:
         self.iteration += 1
         hw = self.W * self.H
         self.last = {"l1_rgb": sums[0] / (F * 3 * hw), "l1_depth": sums[1] / (F * hw),
-                     "l1_attr": sums[2] / (F * (self.C - 4) * hw), "arap": arap.mean()}
+                     "l1_attr": sums[2] / (F * max(self.C - 4, 1) * hw), "arap": arap.mean()}
         if dssim:
             self.last["ssim_rgb"] = sums[3] / (F * 3 * hw)
-        if track:
+        if track and self.sparse_track:
+            self.last["l1_attr"] = sums[2]            # the attribute images are not rendered: a zero device scalar
+            self.last["track"] = sums[4]
+        elif track:
             A = self.C - 7
             self.last["l1_attr"] = sums[2] / (F * A * hw) if A > 0 else sums[2]      # A = 0: no attribute term (0)
             self.last["track"] = sums[4]
