@@ -877,6 +877,33 @@ int splat_depth_dpt_loss_grad(int F, int H, int W, const float *pred, const int6
  *      same forward having run before it on the stream (every variant writes EVERY record of a frame's used slots: the combined
  *      record of the entries it replays, a zero record for the others); the Gaussian-side backward running after it.
  *      DETERMINISM: float atomics; with splat_set_deterministic(1) the entry returns SPLAT_E_ARG before any launch.
+ *      splat_alpha_blending_points_backward_ordered / _batch_ordered: the same two gradients WITHOUT a float atomic -- for the
+ *      same inputs every float they write has the same bits on every run, on any stream, with the deterministic flag on or off
+ *      (they never refuse it).  They take the arguments of the two entries above plus the PAIR MAP of the sort that made
+ *      idx_sorted (goff_incl [P] / [F, P], slot_sorted [capacity] / [F, capacity] of splat_bin_sort / its batch form; the single-
+ *      frame entry also takes `capacity`, the length of idx_sorted and slot_sorted) and a caller-owned scratch.  A NULL pair map
+ *      returns SPLAT_E_ARG before any launch; Q = 0, P = 0 and "nothing to add to" return SPLAT_OK like the atomic entries.  The
+ *      (frame, tile) owns the work: each (Gaussian, tile) pair has exactly one slot, so the wave that owns a tile is the only
+ *      writer of its slots and adds with plain loads and stores.  THE ORDER of every sum:
+ *        - within a (frame, tile): its live corners (inside the image, bilinear weight != 0, corner_ncontrib > 0) in ascending
+ *          (query index, corner nw / ne / sw / se); within a corner the applied entries back to front;
+ *        - channel chunks (256 channels) ascending, every chunk adding its share of the geometry terms;
+ *        - per Gaussian: its pair slots goff_incl[i - 1] .. goff_incl[i] ascending, summed from 0;
+ *        - for a feature shared by the frames (dfeature_frame_stride = 0): frames ascending, one running sum;
+ *        - that sum is then ADDED to the caller's value.
+ *      Integer atomics only count the live corners per tile and hand out places in a tile's corner list; the list is reordered
+ *      by rank of the unique keys 4 q + k afterwards, so nothing depends on arrival order.  Single frame: geometry and feature
+ *      terms go to slot records [capacity, S], S = (6 + C) rounded up to 4 floats, in the scratch, and a Gaussian-side pass ADDS
+ *      each Gaussian's sum to dL_duv / dL_dconic / dL_dopacity / dL_dfeature (each may be NULL).  Batch: the geometry terms are
+ *      added into pair_records exactly where the atomic batch entry adds them (same RELIES ON, detach_opacity honoured); the
+ *      feature terms go to slot records [F, capacity, S], S = C rounded up to 4 floats, in the scratch, and the Gaussian-side pass
+ *      ADDS into dL_dfeature with its frame stride.  Slots and ids outside their ranges are skipped, never dereferenced.
+ *      Scratch: the *_scratch_bytes query of the entry (0: invalid sizes) =
+ *        16 * ceil((2 NT + 1 + 12 Q) / 4) + 4 * R bytes, NT = tiles (batch: F * tiles), tiles = ceil(W / 16) ceil(H / 16),
+ *        R = capacity * S (batch: F * capacity * S) floats of slot records;
+ *      the library allocates nothing, the entry initialises what it reads (two memsets), a NULL or too small scratch returns
+ *      SPLAT_E_ARG before any launch.  Q <= 2^29, NT <= 2^30.  One wave walks a tile's corners one after the other: cheap for
+ *      a handful of corners per tile (integer query pixels), serial for thousands of corners in one tile.
  *      splat_track_flow_rows: rows [P, T, 3] (Gaussian-major: the feature [P, 3 T] of the call above), rows[n, t] =
  *      (u_t - u_ref, v_t - v_ref, depth_t) with (u_t, v_t, depth_t) the orthographic project_point of get_position at the t-th
  *      time of tab (a device table of T 64-byte frame entries, as splat_dynamic_positions_batch_forward takes it) and uv_ref [P, 2]
@@ -908,6 +935,25 @@ int splat_alpha_blending_points_backward_batch(int F, int P, int C, const float 
                                                const int32_t *slot_sorted, float *pair_records, int record_stride,
                                                int detach_opacity, float *dL_dfeature, int64_t dfeature_frame_stride,
                                                splat_stream_t stream);
+size_t splat_alpha_blending_points_backward_ordered_scratch_bytes(int C, int W, int H, int Q, int64_t capacity);
+int splat_alpha_blending_points_backward_ordered(int P, int C, const float *uv, const float *conic, const float *opacity,
+                                                 const float *feature, const int32_t *idx_sorted, const int32_t *tile_range,
+                                                 int64_t capacity, float bg, int W, int H, int Q, const float *points,
+                                                 const float *corner_T, const int32_t *corner_ncontrib, const float *dL_dout,
+                                                 float *dL_duv, float *dL_dconic, float *dL_dopacity, float *dL_dfeature,
+                                                 const int32_t *goff_incl, const int32_t *slot_sorted, void *scratch,
+                                                 size_t scratch_bytes, splat_stream_t stream);
+size_t splat_alpha_blending_points_backward_batch_ordered_scratch_bytes(int F, int C, int W, int H, int64_t Q, int64_t capacity);
+int splat_alpha_blending_points_backward_batch_ordered(int F, int P, int C, const float *uv, const float *conic,
+                                                       const float *opacity, int64_t opacity_frame_stride, const float *feature,
+                                                       int64_t feature_frame_stride, const int32_t *idx_sorted,
+                                                       const int32_t *tile_range, int64_t capacity, float bg, int W, int H, int64_t Q,
+                                                       const int64_t *offsets, const float *points, const float *corner_T,
+                                                       const int32_t *corner_ncontrib, const float *dL_dout,
+                                                       const int32_t *slot_sorted, float *pair_records, int record_stride,
+                                                       int detach_opacity, float *dL_dfeature, int64_t dfeature_frame_stride,
+                                                       const int32_t *goff_incl, void *scratch, size_t scratch_bytes,
+                                                       splat_stream_t stream);
 int splat_track_flow_rows(int T, int P, int I, const void *tab, const float *position, const float *cubic, int cubic_layout,
                           const float *extr, int W, int H, float nearest, float extent, const float *uv_ref, float *rows,
                           splat_stream_t stream);

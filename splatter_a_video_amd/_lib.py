@@ -61,6 +61,8 @@ SYMBOLS = [
     "splat_depth_dpt_scratch_bytes", "splat_depth_stats", "splat_depth_dpt_loss_grad",
     "splat_alpha_blending_points_forward", "splat_alpha_blending_points_forward_live", "splat_alpha_blending_points_backward", "splat_track_flow_rows",
     "splat_alpha_blending_points_forward_batch", "splat_alpha_blending_points_backward_batch", "splat_track_loss_grad_points",
+    "splat_alpha_blending_points_backward_ordered", "splat_alpha_blending_points_backward_ordered_scratch_bytes",
+    "splat_alpha_blending_points_backward_batch_ordered", "splat_alpha_blending_points_backward_batch_ordered_scratch_bytes",
 ]
 
 
@@ -129,6 +131,14 @@ def lib() -> ctypes.CDLL:
         L.splat_alpha_blending_points_backward_batch.argtypes = [i, i, i, p, p, p, i64, p, i64, p, p, i64, f, i, i, i64, p, p, p, p, p,
                                                                  p, p, i, i, p, i64, p]
         L.splat_track_loss_grad_points.argtypes = [i, i, i, i, p, p, p, p, i64, p, f, f, p, p, p, p, p, p]
+        L.splat_alpha_blending_points_backward_ordered_scratch_bytes.restype = ctypes.c_size_t
+        L.splat_alpha_blending_points_backward_ordered_scratch_bytes.argtypes = [i, i, i, i, i64]
+        L.splat_alpha_blending_points_backward_ordered.argtypes = [i, i, p, p, p, p, p, p, i64, f, i, i, i, p, p, p, p, p, p, p, p,
+                                                                   p, p, p, ctypes.c_size_t, p]
+        L.splat_alpha_blending_points_backward_batch_ordered_scratch_bytes.restype = ctypes.c_size_t
+        L.splat_alpha_blending_points_backward_batch_ordered_scratch_bytes.argtypes = [i, i, i, i, i64, i64]
+        L.splat_alpha_blending_points_backward_batch_ordered.argtypes = (
+            L.splat_alpha_blending_points_backward_batch.argtypes[:-1] + [p, p, ctypes.c_size_t, p])
         if L.splat_abi_version() != ABI_VERSION:
             raise SplatError("libsplat_hip.so ABI version mismatch; rebuild it")
         _lib = L

@@ -469,6 +469,351 @@ int launch_points_bwd(const PointsBwdArgs &A, int Q, hipStream_t s, const Points
     return SPLAT_OK;
 }
 
+// ---- the ORDERED backward: the same gradient without a float atomic, every sum in a fixed order.
+// The atomic kernel above is one workgroup per query; here the (frame, tile) owns the work.  Every corner of a tile replays the
+// same list, and every (Gaussian, tile) pair of that list has exactly one slot (slot_sorted of the pair map): the wave that owns
+// a tile is the only writer of its slots and adds with plain loads and stores.
+//   1. points_ord_corners_kernel<.., false>: thread = query; its LIVE corners (in the image, bilinear weight != 0,
+//      corner_ncontrib > 0: the tests of points_bwd_kernel) are counted per (frame, tile) with an INTEGER atomic (a count does
+//      not depend on the arrival order);
+//   2. points_ord_scan_kernel: exclusive scan of the counts (one workgroup);
+//   3. points_ord_corners_kernel<.., true>: the corners' keys 4 q + k go into their tile's segment through an integer cursor,
+//      in arrival order -- and points_ord_rank_kernel REORDERS every segment: the keys of a segment are unique, the rank of a
+//      key among them is its place (thread = corner, one pass over its segment);
+//   4. points_bwd_ordered_kernel: wave = (frame, tile) with corners (the others exit at once); it walks its corners in ascending
+//      (q, k) and replays each with the machinery of points_bwd_kernel (lane = entry for 64 alphas, the applied entries back to
+//      front with lane = channel, lane = entry for the geometry terms).  Every atomic_add_f32 of that kernel is here a load, an
+//      add and a store BY THE SAME LANE on the same address (lane = channel for a feature column, lane = list position mod 64
+//      for an entry's geometry terms), so program order fixes the sum: corners ascending, within a corner the entries back to
+//      front.  Channel chunks are launches on one stream: ascending.
+//   5. points_ord_gauss_kernel: thread = (Gaussian, column); sums the Gaussian's slots in ascending slot order (frames
+//      ascending where the frames share the destination) from 0 and ADDS the sum to the caller's buffer.
+struct PointsOrd {
+    int NT;                         // F * T (frame, tile) owners
+    int *seg;                       // [NT + 1]: the corners of every tile, then their exclusive scan (seg[NT] = all live corners)
+    int *cursor;                    // [NT]
+    int *tmp_key, *tmp_tile;        // [4 Q]: the corners in arrival order
+    int *sorted;                    // [4 Q]: every tile's keys 4 q + k ascending
+    // where an applied entry with slot s of frame f adds: geometry at geo + f geo_fs + s geo_stride + REC_*, feature column c at
+    // fsc + f fsc_fs + s fsc_stride + c (fsc already points at the first feature column); either may be NULL
+    float *geo, *fsc;
+    long long geo_stride, geo_fs, fsc_stride, fsc_fs;
+};
+
+// corner k of a query at pt: the tile of a live corner, else -1
+__device__ __forceinline__ int points_live_corner_tile(const PointsBwdArgs &A, size_t q, float2 pt, int k) {
+    const float x0f = floorf(pt.x), y0f = floorf(pt.y);
+    const float cxf = x0f + (float)(k & 1), cyf = y0f + (float)(k >> 1);
+    const bool in = cxf >= 0.f && cxf <= (float)(A.W - 1) && cyf >= 0.f && cyf <= (float)(A.H - 1);
+    if (!in) return -1;
+    const float x1f = x0f + 1.f, y1f = y0f + 1.f;
+    const float cw = ((k & 1) ? pt.x - x0f : x1f - pt.x) * ((k >> 1) ? pt.y - y0f : y1f - pt.y);
+    if (cw == 0.f) return -1;
+    if (A.corner_n[q * 4 + k] <= 0) return -1;
+    return ((int)cyf / TILE) * A.gx + (int)cxf / TILE;
+}
+
+template <bool BATCH, bool FILL>
+__global__ void __launch_bounds__(256) points_ord_corners_kernel(const PointsBwdArgs A, const PointsBatch B, const PointsOrd O) {
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= B.Q) return;
+    int f = 0;
+    if (BATCH) {
+        f = points_frame_of(B, q);
+        if (f < 0) return;   // a query no frame owns
+    }
+    const float2 pt = A.points[q];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int tile = points_live_corner_tile(A, (size_t)q, pt, k);
+        if (tile < 0) continue;
+        const int t = f * B.T + tile;
+        if (!FILL) {
+            atomicAdd(O.seg + t, 1);
+        } else {   // (arrival order: points_ord_rank_kernel reorders the segment)
+            const int pos = O.seg[t] + atomicAdd(O.cursor + t, 1);
+            O.tmp_key[pos] = (int)(4 * q + k);
+            O.tmp_tile[pos] = t;
+        }
+    }
+}
+
+// seg[0 .. n) -> its exclusive scan in place, seg[n] = the total.  One workgroup: n = F T is some ten thousand.
+__global__ void __launch_bounds__(1024) points_ord_scan_kernel(int *seg, int n) {
+    __shared__ int s[1024];
+    const int tid = threadIdx.x;
+    const int per = (n + 1023) / 1024;
+    const long long b = (long long)tid * per;
+    const long long e = b + per < n ? b + per : n;
+    int sum = 0;
+    for (long long i = b; i < e; ++i) sum += seg[i];
+    s[tid] = sum;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const int v = tid >= o ? s[tid - o] : 0;
+        __syncthreads();
+        s[tid] += v;
+        __syncthreads();
+    }
+    int run = s[tid] - sum;
+    for (long long i = b; i < e; ++i) {
+        const int c = seg[i];
+        seg[i] = run;
+        run += c;
+    }
+    if (tid == 1023) seg[n] = s[1023];
+}
+
+// thread = corner in arrival order: its rank among the (unique) keys of its tile's segment is its place
+__global__ void __launch_bounds__(256) points_ord_rank_kernel(const PointsOrd O) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= O.seg[O.NT]) return;
+    const int t = O.tmp_tile[i], key = O.tmp_key[i];
+    const int s0 = O.seg[t], s1 = O.seg[t + 1];
+    int r = 0;
+    for (int j = s0; j < s1; ++j) r += O.tmp_key[j] < key ? 1 : 0;
+    O.sorted[s0 + r] = key;
+}
+
+template <int NA>
+__global__ void __launch_bounds__(256) points_bwd_ordered_kernel(const PointsBwdArgs A0, const PointsBatch B, const PointsOrd O) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const long long gw = (long long)blockIdx.x * 4 + (tid >> 6);
+    if (gw >= O.NT) return;
+    const int t = __builtin_amdgcn_readfirstlane((int)gw);   // wave = (frame, tile): everything below branches on scalars
+    const int s0 = __builtin_amdgcn_readfirstlane(O.seg[t]), s1 = __builtin_amdgcn_readfirstlane(O.seg[t + 1]);
+    if (s0 >= s1) return;   // a tile without live corners
+    const int f = t / B.T, tile = t - f * B.T;
+    PointsBwdArgs A = A0;
+    points_frame_view(A, B, f);
+    const int *slots = B.slot_sorted + (size_t)f * (size_t)B.cap;
+    float *geo = O.geo ? O.geo + (size_t)f * (size_t)O.geo_fs : nullptr;
+    float *dfbase = O.fsc ? O.fsc + (size_t)f * (size_t)O.fsc_fs + A.c0 + lane : nullptr;
+    const int2 range = A.tile_range[tile];
+    // (a list that leaves the frame's segment is cut short, never read)
+    long long nn = (long long)range.y - (long long)range.x;
+    nn = nn > B.cap - (long long)range.x ? B.cap - (long long)range.x : nn;
+    const int n = range.x < 0 || nn < 0 ? 0 : (int)nn;
+    const int tx = tile % A.gx, ty = tile / A.gx;
+    const float tcx = (float)(tx * TILE) + 7.5f, tcy = (float)(ty * TILE) + 7.5f;
+    const float *fbase = A.feature + A.c0 + lane;
+
+    for (int ci = s0; ci < s1; ++ci) {   // the tile's live corners in ascending (q, k)
+        const int key = __builtin_amdgcn_readfirstlane(O.sorted[ci]);
+        const size_t q = (size_t)(key >> 2);
+        const int w = key & 3;
+        const float2 ptv = A.points[q];
+        const float ptx = lane_f(ptv.x, 0), pty = lane_f(ptv.y, 0);
+        // the forward's corner and bilinear weight (the corner is live: inside the image, cw != 0)
+        const float x0f = floorf(ptx), y0f = floorf(pty);
+        const float cxf = x0f + (float)(w & 1), cyf = y0f + (float)(w >> 1);
+        const float x1f = x0f + 1.f, y1f = y0f + 1.f;
+        const float cw = ((w & 1) ? ptx - x0f : x1f - ptx) * ((w >> 1) ? pty - y0f : y1f - pty);
+        const int px = (int)cxf, py = (int)cyf;
+        const int last = imin_(__builtin_amdgcn_readfirstlane(A.corner_n[q * 4 + w]), n);   // (never past the list)
+        if (last <= 0) continue;
+        const float Tf = lane_f(A.corner_T[q * 4 + w], 0);
+        const float pxf = (float)px, pyf = (float)py;
+        const float x = (float)(px - tx * TILE) - 7.5f, y = (float)(py - ty * TILE) - 7.5f;
+        const float xx = x * x, xy = x * y, yy = y * y;
+
+        float g[NA], acc[NA];
+        float gsum = 0.f;
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            g[k] = (lane + 64 * k < A.cn) ? cw * A.dL_dout[q * (size_t)A.C + A.c0 + lane + 64 * k] : 0.f;
+            acc[k] = 0.f;
+            gsum += g[k];
+        }
+        const float bgdot = A.bg * wave_sum_bcast(gsum);
+        float T = Tf;
+
+        for (int base = ((last - 1) / WAVE) * WAVE; base >= 0; base -= WAVE) {
+            // ---- lane = entry: its alpha on this pixel (the forward's bits) and its slot
+            const int e = base + lane;
+            int id = 0, slot = -1;
+            float alpha = 0.f, araw = 0.f, ux = 0.f, uy = 0.f, cA = 0.f, cB = 0.f, cC = 0.f, o = 1.f;
+            bool aok = false;
+            if (e < last) {
+                id = A.idx_sorted[range.x + e];
+                if ((unsigned)id < (unsigned)A.P) {   // (an id outside the set is skipped, never dereferenced)
+                    const float2 c = A.uv[id];
+                    ux = c.x; uy = c.y;
+                    cA = A.conic[3 * (size_t)id]; cB = A.conic[3 * (size_t)id + 1]; cC = A.conic[3 * (size_t)id + 2];
+                    o = A.opacity[id];
+                    const PowerCoef k = power_coeffs(ux, uy, cA, cB, cC, o, tcx, tcy);
+                    const float pw = power_poly(make_float4(k.q0, k.qx, k.qy, k.qxx), make_float4(k.qxy, k.qyy, 0.f, 0.f), x, y, xx, xy, yy);
+                    bool pw_ok;
+                    araw = exp2_guard(pw, pw_ok);
+                    const float a = fminf(0.99f, araw);
+                    aok = pw_ok && !(a < (1.0f / 255.0f));
+                    alpha = aok ? a : 0.f;
+                    const int s = slots[range.x + e];
+                    slot = (s >= 0 && (long long)s < B.cap) ? s : -1;   // (a slot outside the frame's records is skipped, never written)
+                } else {
+                    id = 0;
+                }
+            }
+            // ---- lane = channel: the applied entries back to front, four rows in flight
+            unsigned long long ap = __ballot(aok);
+            float dLa_v = 0.f;   // lane j: dL_dalpha of entry base + j, if it applied
+            while (ap) {
+                int jj[4];
+                float fr[4][NA], dr[4][NA];   // feature rows and the slots' running feature sums (distinct entries of a list have
+                float *drow[4];               //   distinct slots: the four rows do not alias)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    jj[u] = ap ? 63 - (int)__builtin_clzll(ap) : -1;
+                    drow[u] = nullptr;
+#pragma unroll
+                    for (int k = 0; k < NA; ++k) fr[u][k] = dr[u][k] = 0.f;
+                    if (jj[u] >= 0) {
+                        ap &= ~(1ull << jj[u]);
+                        const float *row = fbase + (size_t)__builtin_amdgcn_readlane(id, jj[u]) * (size_t)A.C;
+#pragma unroll
+                        for (int k = 0; k < NA; ++k) fr[u][k] = (lane + 64 * k < A.cn) ? row[64 * k] : 0.f;
+                        const int sj = __builtin_amdgcn_readlane(slot, jj[u]);
+                        if (dfbase && sj >= 0) {
+                            drow[u] = dfbase + (size_t)sj * (size_t)O.fsc_stride;
+#pragma unroll
+                            for (int k = 0; k < NA; ++k) dr[u][k] = (lane + 64 * k < A.cn) ? drow[u][64 * k] : 0.f;
+                        }
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (jj[u] < 0) break;
+                    const int j = jj[u];
+                    const float a = lane_f(alpha, j);
+                    const float r1a = __builtin_amdgcn_rcpf(1.f - a);
+                    T = T * r1a;   // the transmittance in front of the entry
+                    const float wgt = a * T;
+                    float part = 0.f;
+#pragma unroll
+                    for (int k = 0; k < NA; ++k) part += (fr[u][k] - acc[k]) * g[k];
+                    float dLa = wave_sum_bcast(part) * T;
+                    dLa += (-Tf * r1a) * bgdot;
+                    dLa_v = lane == j ? dLa : dLa_v;
+                    if (drow[u]) {   // this lane is the only writer of its column of the slot: loaded above, add, store
+#pragma unroll
+                        for (int k = 0; k < NA; ++k)
+                            if (lane + 64 * k < A.cn) drow[u][64 * k] = dr[u][k] + wgt * g[k];
+                    }
+#pragma unroll
+                    for (int k = 0; k < NA; ++k) acc[k] = a * fr[u][k] + (1.f - a) * acc[k];
+                }
+            }
+            // ---- lane = entry: the geometry terms of the block's applied entries (replay_one's expressions); list position e is
+            //      this lane's in every corner of the tile, and its slot is nobody else's
+            if (aok && geo && slot >= 0) {
+                const float dx = ux - pxf, dy = uy - pyf;
+                const float G = araw * __builtin_amdgcn_rcpf(o);
+                const float dLG = o * dLa_v;
+                float *r = geo + (size_t)slot * (size_t)O.geo_stride;
+                r[REC_UX] = r[REC_UX] + dLG * (-G * dx * cA - G * dy * cB);
+                r[REC_UY] = r[REC_UY] + dLG * (-G * dy * cC - G * dx * cB);
+                r[REC_CA] = r[REC_CA] + -0.5f * G * dx * dx * dLG;
+                r[REC_CB] = r[REC_CB] + -G * dx * dy * dLG;
+                r[REC_CC] = r[REC_CC] + -0.5f * G * dy * dy * dLG;
+                if (!B.detach_opacity) r[REC_O] = r[REC_O] + G * dLa_v;
+            }
+        }
+    }
+}
+
+// thread = (Gaussian i, column j of the slot records at `sc`, `stride` floats apart, `fs` floats per frame): the sum of the
+// Gaussian's slots [goff_incl[f, i - 1], goff_incl[f, i]) in ascending order from 0, frames ascending, ADDED to its destination.
+// geom: columns 0 .. 5 are ux uy ca cb cc o (-> dL_duv, dL_dconic, dL_dopacity), the feature columns follow; else all columns
+// are feature columns.  dfeat_fs != 0: every frame's feature sum goes to its own block.
+__global__ void __launch_bounds__(256) points_ord_gauss_kernel(int F, int P, int ncol, const float *sc, long long stride, long long fs,
+                                                               long long cap, const int *goff, int geom, float *duv, float *dconic,
+                                                               float *dopac, float *dfeat, int C, long long dfeat_fs) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)P * (size_t)ncol) return;
+    const size_t i = idx / (size_t)ncol;
+    const int j = (int)(idx - i * (size_t)ncol);
+    const bool isgeo = geom && j < REC_GEOM;
+    float *dst = nullptr;
+    if (isgeo) {
+        if (j < 2) dst = duv ? duv + 2 * i + j : nullptr;
+        else if (j < 5) dst = dconic ? dconic + 3 * i + (j - 2) : nullptr;
+        else dst = dopac ? dopac + i : nullptr;
+    } else {
+        dst = dfeat ? dfeat + i * (size_t)C + (j - (geom ? REC_GEOM : 0)) : nullptr;
+    }
+    if (!dst) return;
+    const bool per_frame = !isgeo && dfeat_fs != 0;
+    float sum = 0.f;
+    for (int f = 0; f < F; ++f) {
+        const int *g = goff + (size_t)f * (size_t)P;
+        long long a = i ? g[i - 1] : 0, b = g[i];
+        a = a < 0 ? 0 : a;
+        b = b > cap ? cap : b;   // (slots past the capacity do not exist)
+        const float *col = sc + (size_t)f * (size_t)fs + j;
+        for (long long s = a; s < b; ++s) sum += col[(size_t)s * (size_t)stride];
+        if (per_frame) {
+            dst[(size_t)f * (size_t)dfeat_fs] += sum;
+            sum = 0.f;
+        }
+    }
+    if (!per_frame) *dst += sum;
+}
+
+struct OrdLayout {
+    size_t seg, cursor, tmp_key, tmp_tile, sorted, rec, total;   // byte offsets into the scratch
+};
+
+// [seg NT + 1 | cursor NT | three int arrays of 4 Q] rounded up to 16 bytes, then `rec_floats` floats of slot records
+bool points_ord_layout(long long NT, long long Q, double rec_floats, OrdLayout &L) {
+    if (NT < 1 || Q < 0 || !(rec_floats >= 0.0 && rec_floats < 4.0e18 / 4.0)) return false;
+    const size_t nt = (size_t)NT, q4 = 4 * (size_t)Q;
+    L.seg = 0;
+    L.cursor = 4 * (nt + 1);
+    L.tmp_key = L.cursor + 4 * nt;
+    L.tmp_tile = L.tmp_key + 4 * q4;
+    L.sorted = L.tmp_tile + 4 * q4;
+    L.rec = (L.sorted + 4 * q4 + 15) & ~(size_t)15;
+    L.total = L.rec + 4 * (size_t)rec_floats;
+    return true;
+}
+
+// the launches of a validated ordered backward.  A / B as the atomic entries fill them (single frame: F = 1, no offsets).
+int points_ordered_run(PointsBwdArgs A, const PointsBatch &B, PointsOrd O, bool batch, const OrdLayout &L, char *scratch,
+                       size_t rec_bytes_to_zero, hipStream_t s) {
+    const int Q = (int)B.Q;
+    O.seg = (int *)(scratch + L.seg); O.cursor = (int *)(scratch + L.cursor);
+    O.tmp_key = (int *)(scratch + L.tmp_key); O.tmp_tile = (int *)(scratch + L.tmp_tile); O.sorted = (int *)(scratch + L.sorted);
+    {
+        ProfiledLaunch pl_("blend_points_ord_zero", s);
+        SPLAT_CHECK_HIP(hipMemsetAsync(scratch, 0, L.tmp_key, s));   // counts and cursors
+        if (rec_bytes_to_zero) SPLAT_CHECK_HIP(hipMemsetAsync(scratch + L.rec, 0, rec_bytes_to_zero, s));   // the slot records
+    }
+    const dim3 qgrid((unsigned)(((size_t)Q + 255) / 256)), cgrid((unsigned)((4 * (size_t)Q + 255) / 256));
+    if (batch) SPLAT_LAUNCH("blend_points_ord_lists", (points_ord_corners_kernel<true, false>), qgrid, dim3(256), 0, s, A, B, O);
+    else SPLAT_LAUNCH("blend_points_ord_lists", (points_ord_corners_kernel<false, false>), qgrid, dim3(256), 0, s, A, B, O);
+    SPLAT_POST_LAUNCH();
+    SPLAT_LAUNCH("blend_points_ord_lists", points_ord_scan_kernel, dim3(1), dim3(1024), 0, s, O.seg, O.NT);
+    SPLAT_POST_LAUNCH();
+    if (batch) SPLAT_LAUNCH("blend_points_ord_lists", (points_ord_corners_kernel<true, true>), qgrid, dim3(256), 0, s, A, B, O);
+    else SPLAT_LAUNCH("blend_points_ord_lists", (points_ord_corners_kernel<false, true>), qgrid, dim3(256), 0, s, A, B, O);
+    SPLAT_POST_LAUNCH();
+    SPLAT_LAUNCH("blend_points_ord_lists", points_ord_rank_kernel, cgrid, dim3(256), 0, s, O);
+    SPLAT_POST_LAUNCH();
+    const dim3 tgrid((unsigned)(((size_t)O.NT + 3) / 4));
+    for (int c0 = 0; c0 < A.C; c0 += PT_CHUNK) {   // every chunk adds its share of the geometry terms: dL_dalpha is linear in the channels
+        A.c0 = c0;
+        A.cn = A.C - c0 > PT_CHUNK ? PT_CHUNK : A.C - c0;
+        switch ((A.cn + 63) / 64) {
+            case 1: SPLAT_LAUNCH("blend_points_bwd_ord", points_bwd_ordered_kernel<1>, tgrid, dim3(256), 0, s, A, B, O); break;
+            case 2: SPLAT_LAUNCH("blend_points_bwd_ord", points_bwd_ordered_kernel<2>, tgrid, dim3(256), 0, s, A, B, O); break;
+            case 3: SPLAT_LAUNCH("blend_points_bwd_ord", points_bwd_ordered_kernel<3>, tgrid, dim3(256), 0, s, A, B, O); break;
+            default: SPLAT_LAUNCH("blend_points_bwd_ord", points_bwd_ordered_kernel<4>, tgrid, dim3(256), 0, s, A, B, O); break;
+        }
+        SPLAT_POST_LAUNCH();
+    }
+    return SPLAT_OK;
+}
+
 // rows[n, t] = (u_t - u_ref, v_t - v_ref, depth_t) of Gaussian n at the t-th time of the table: get_position(t) (the segment
 // polynomial of dynamic_eval_fwd_kernel) through the orthographic project_point.  One thread per (n, t): consecutive threads
 // write consecutive 12-byte entries of a Gaussian's row.
@@ -673,6 +1018,150 @@ extern "C" int splat_alpha_blending_points_backward_batch(int F, int P, int C, c
         if (r != SPLAT_OK) return r;
     }
     return SPLAT_OK;
+}
+
+// ---- the ordered entries: no float atomic, run with the deterministic flag on or off
+namespace {
+constexpr long long ORD_MAX_Q = 1ll << 29;    // a corner's key 4 q + k is an int32
+constexpr long long ORD_MAX_NT = 1ll << 30;   // (frame, tile) owners
+
+long long points_num_tiles(int W, int H) { return (long long)((W + TILE - 1) / TILE) * (long long)((H + TILE - 1) / TILE); }
+
+int points_ord_gauss(int F, int P, int ncol, const float *sc, long long stride, long long fs, long long cap, const int32_t *goff,
+                     int geom, float *duv, float *dconic, float *dopac, float *dfeat, int C, long long dfeat_fs, hipStream_t s) {
+    const size_t total = (size_t)P * (size_t)ncol;
+    SPLAT_LAUNCH("blend_points_ord_gauss", points_ord_gauss_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, F, P, ncol,
+                 sc, stride, fs, cap, goff, geom, duv, dconic, dopac, dfeat, C, dfeat_fs);
+    SPLAT_POST_LAUNCH();
+    return SPLAT_OK;
+}
+}  // namespace
+
+extern "C" size_t splat_alpha_blending_points_backward_ordered_scratch_bytes(int C, int W, int H, int Q, int64_t capacity) {
+    if (!(C >= 1 && W > 0 && H > 0 && Q >= 0 && capacity >= 0)) return 0;
+    if (!(W <= (1 << 24) && H <= (1 << 24) && Q <= ORD_MAX_Q && points_num_tiles(W, H) <= ORD_MAX_NT)) return 0;
+    OrdLayout L;
+    if (!points_ord_layout(points_num_tiles(W, H), Q, (double)capacity * (double)PAIR_STRIDE(REC_GEOM + (long long)C), L)) return 0;
+    return L.total;
+}
+
+extern "C" size_t splat_alpha_blending_points_backward_batch_ordered_scratch_bytes(int F, int C, int W, int H, int64_t Q,
+                                                                                   int64_t capacity) {
+    if (!(F >= 1 && C >= 1 && W > 0 && H > 0 && Q >= 0 && capacity >= 0)) return 0;
+    if (!(W <= (1 << 24) && H <= (1 << 24) && Q <= ORD_MAX_Q && F <= (1 << 16) && (long long)F * points_num_tiles(W, H) <= ORD_MAX_NT))
+        return 0;
+    OrdLayout L;
+    if (!points_ord_layout((long long)F * points_num_tiles(W, H), Q, (double)F * (double)capacity * (double)PAIR_STRIDE((long long)C), L))
+        return 0;
+    return L.total;
+}
+
+extern "C" int splat_alpha_blending_points_backward_ordered(int P, int C, const float *uv, const float *conic, const float *opacity,
+                                                            const float *feature, const int32_t *idx_sorted,
+                                                            const int32_t *tile_range, int64_t capacity, float bg, int W, int H, int Q,
+                                                            const float *points, const float *corner_T,
+                                                            const int32_t *corner_ncontrib, const float *dL_dout, float *dL_duv,
+                                                            float *dL_dconic, float *dL_dopacity, float *dL_dfeature,
+                                                            const int32_t *goff_incl, const int32_t *slot_sorted, void *scratch,
+                                                            size_t scratch_bytes, splat_stream_t stream) {
+    SPLAT_CHECK_ARG(P >= 0 && C >= 1 && W > 0 && H > 0 && Q >= 0 && capacity >= 0, "bad sizes (P, Q, capacity >= 0, C, W, H >= 1)");
+    SPLAT_CHECK_ARG(W <= (1 << 24) && H <= (1 << 24) && Q <= ORD_MAX_Q && points_num_tiles(W, H) <= ORD_MAX_NT,
+                    "sizes too large (W, H <= 2^24: pixel indices are compared in float32; Q <= 2^29, tiles <= 2^30)");
+    if (Q == 0) return SPLAT_OK;
+    SPLAT_CHECK_ARG(points && corner_T && corner_ncontrib && dL_dout, "null pointer (points / corner_T / corner_ncontrib / dL_dout)");
+    SPLAT_CHECK_ARG(P == 0 || (uv && conic && opacity && feature && tile_range), "null pointer");
+    if (P == 0 || !(dL_duv || dL_dconic || dL_dopacity || dL_dfeature)) return SPLAT_OK;   // nothing to add to
+    SPLAT_CHECK_ARG(goff_incl && slot_sorted, "the ordered backward needs this library's pair map (goff_incl, slot_sorted of "
+                                              "splat_bin_sort for THIS idx_sorted); a foreign idx_sorted has none");
+    SPLAT_CHECK_ARG(idx_sorted, "null pointer (idx_sorted)");
+    const size_t need = splat_alpha_blending_points_backward_ordered_scratch_bytes(C, W, H, Q, capacity);
+    SPLAT_CHECK_ARG(need != 0, "sizes too large (scratch)");
+    SPLAT_CHECK_ARG(scratch && scratch_bytes >= need,
+                    "scratch missing or too small (splat_alpha_blending_points_backward_ordered_scratch_bytes)");
+    if (capacity == 0) return SPLAT_OK;   // no pair, no slot: every list is empty
+    const int T = (int)points_num_tiles(W, H);
+    const int S = PAIR_STRIDE(REC_GEOM + C);
+    OrdLayout L;
+    points_ord_layout(T, Q, (double)capacity * (double)S, L);
+    PointsBatch B;
+    memset(&B, 0, sizeof(B));
+    B.F = 1; B.T = T; B.Q = Q; B.cap = capacity; B.slot_sorted = slot_sorted;
+    PointsBwdArgs A;
+    memset(&A, 0, sizeof(A));
+    A.P = P; A.C = C;
+    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
+    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
+    A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
+    A.points = (const float2 *)points; A.corner_T = corner_T; A.corner_n = corner_ncontrib; A.dL_dout = dL_dout;
+    float *rec = (float *)((char *)scratch + L.rec);
+    PointsOrd O;
+    memset(&O, 0, sizeof(O));
+    O.NT = T;
+    if (dL_duv || dL_dconic || dL_dopacity) { O.geo = rec; O.geo_stride = S; }
+    if (dL_dfeature) { O.fsc = rec + REC_GEOM; O.fsc_stride = S; }
+    int rc = points_ordered_run(A, B, O, false, L, (char *)scratch, (size_t)capacity * (size_t)S * 4, (hipStream_t)stream);
+    if (rc != SPLAT_OK) return rc;
+    return points_ord_gauss(1, P, REC_GEOM + C, rec, S, 0, capacity, goff_incl, 1, dL_duv, dL_dconic, dL_dopacity, dL_dfeature, C, 0,
+                            (hipStream_t)stream);
+}
+
+// RELIES ON what splat_alpha_blending_points_backward_batch relies on (corner maps of the batch forward, the tile backward of the
+// same forward before it, the Gaussian-side backward after it).
+extern "C" int splat_alpha_blending_points_backward_batch_ordered(
+    int F, int P, int C, const float *uv, const float *conic, const float *opacity, int64_t opacity_frame_stride, const float *feature,
+    int64_t feature_frame_stride, const int32_t *idx_sorted, const int32_t *tile_range, int64_t capacity, float bg, int W, int H,
+    int64_t Q, const int64_t *offsets, const float *points, const float *corner_T, const int32_t *corner_ncontrib,
+    const float *dL_dout, const int32_t *slot_sorted, float *pair_records, int record_stride, int detach_opacity, float *dL_dfeature,
+    int64_t dfeature_frame_stride, const int32_t *goff_incl, void *scratch, size_t scratch_bytes, splat_stream_t stream) {
+    const int rc = points_batch_check(__func__, F, P, C, W, H, Q, capacity, opacity_frame_stride, feature_frame_stride);
+    if (rc != SPLAT_OK) return rc;
+    SPLAT_CHECK_ARG(Q <= ORD_MAX_Q && (long long)F * points_num_tiles(W, H) <= ORD_MAX_NT,
+                    "sizes too large (Q <= 2^29, F * tiles <= 2^30)");
+    SPLAT_CHECK_ARG(dfeature_frame_stride >= 0, "bad sizes (dL_dfeature frame stride >= 0)");
+    SPLAT_CHECK_ARG(!pair_records || (record_stride >= REC_GEOM && record_stride % 4 == 0 && capacity >= 1),
+                    "bad sizes (pair records: a stride of whole 16-byte chunks >= 8 floats, capacity >= 1)");
+    if (Q == 0) return SPLAT_OK;
+    SPLAT_CHECK_ARG(points && offsets && corner_T && corner_ncontrib && dL_dout,
+                    "null pointer (points / offsets / corner_T / corner_ncontrib / dL_dout)");
+    SPLAT_CHECK_ARG(P == 0 || (uv && conic && opacity && feature && tile_range), "null pointer");
+    if (P == 0 || !(pair_records || dL_dfeature)) return SPLAT_OK;   // nothing to add to
+    SPLAT_CHECK_ARG(goff_incl && slot_sorted, "the ordered backward needs the frame batch's pair map (goff_incl [F, P], slot_sorted "
+                                              "[F, capacity] of splat_bin_sort_batch for THIS idx_sorted)");
+    SPLAT_CHECK_ARG(idx_sorted, "null pointer (idx_sorted)");
+    const size_t need = splat_alpha_blending_points_backward_batch_ordered_scratch_bytes(F, C, W, H, Q, capacity);
+    SPLAT_CHECK_ARG(need != 0, "sizes too large (scratch)");
+    SPLAT_CHECK_ARG(scratch && scratch_bytes >= need,
+                    "scratch missing or too small (splat_alpha_blending_points_backward_batch_ordered_scratch_bytes)");
+    if (capacity == 0) return SPLAT_OK;   // no pair, no slot: every list is empty
+    const int T = (int)points_num_tiles(W, H);
+    const int S = PAIR_STRIDE(C);
+    OrdLayout L;
+    points_ord_layout((long long)F * T, Q, (double)F * (double)capacity * (double)S, L);
+    PointsBatch B;
+    memset(&B, 0, sizeof(B));
+    B.F = F; B.T = T;
+    B.offsets = (const long long *)offsets; B.Q = Q; B.cap = capacity;
+    B.opacity_fs = opacity_frame_stride; B.feature_fs = feature_frame_stride; B.dfeature_fs = dfeature_frame_stride;
+    B.slot_sorted = slot_sorted; B.rec = pair_records; B.rec_stride = record_stride; B.detach_opacity = detach_opacity ? 1 : 0;
+    PointsBwdArgs A;
+    memset(&A, 0, sizeof(A));
+    A.P = P; A.C = C;
+    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
+    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
+    A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
+    A.points = (const float2 *)points; A.corner_T = corner_T; A.corner_n = corner_ncontrib; A.dL_dout = dL_dout;
+    float *rec = (float *)((char *)scratch + L.rec);
+    PointsOrd O;
+    memset(&O, 0, sizeof(O));
+    O.NT = F * T;
+    if (pair_records) { O.geo = pair_records; O.geo_stride = record_stride; O.geo_fs = (long long)capacity * record_stride; }
+    if (dL_dfeature) { O.fsc = rec; O.fsc_stride = S; O.fsc_fs = (long long)capacity * S; }
+    const size_t zero = dL_dfeature ? (size_t)F * (size_t)capacity * (size_t)S * 4 : 0;
+    int r = points_ordered_run(A, B, O, true, L, (char *)scratch, zero, (hipStream_t)stream);
+    if (r != SPLAT_OK) return r;
+    if (!dL_dfeature) return SPLAT_OK;
+    return points_ord_gauss(F, P, C, rec, S, (long long)capacity * S, capacity, goff_incl, 0, nullptr, nullptr, nullptr, dL_dfeature, C,
+                            dfeature_frame_stride, (hipStream_t)stream);
 }
 
 extern "C" int splat_track_flow_rows(int T, int P, int I, const void *tab, const float *position, const float *cubic,

@@ -433,8 +433,9 @@ class FrameBatch:
         ``gs.alpha_blending_points``), ``offsets`` (device int64 [F + 1]: the queries offsets[f] .. offsets[f + 1] belong to frame
         f, as ``tracks.TrackTargets`` holds them), ``bg``, ``detach_opacity``.  The call then returns one more tensor [Q, c]
         behind the images and in front of ``gs_idx``, an output of the same autograd node: its gradient enters the batch's pair
-        records between the tile backward and the Gaussian-side backward (float atomics: it raises in deterministic mode); the
-        feature's gradient is ADDED to ``grad_sink["points"]`` (the feature's shape) when given, else returned through autograd.
+        records between the tile backward and the Gaussian-side backward (float atomics: it raises in deterministic mode;
+        ``ordered=True`` in the dict takes splat_alpha_blending_points_backward_batch_ordered instead: no float atomic, a fixed
+        order of every sum, bit-reproducible and allowed in deterministic mode); the feature's gradient is ADDED to ``grad_sink["points"]`` (the feature's shape) when given, else returned through autograd.
         Not differentiable w.r.t. the points.  A ``None`` gradient of the sparse output launches nothing."""
         tab = self.frame_table(clock, times)
         meta, parts, feats = _parse_sets(sets, self.F, self.P)
@@ -722,7 +723,7 @@ def _parse_points(points, sink, F, P):
     detach_opacity, per_frame, the feature's gradient sink or None); nothing here reads device memory"""
     if points is None:
         return None
-    unknown = set(points) - {"feature", "points", "offsets", "bg", "detach_opacity"}
+    unknown = set(points) - {"feature", "points", "offsets", "bg", "detach_opacity", "ordered"}
     if unknown:
         raise ValueError(f"points: unknown keys {sorted(unknown)}")
     f, xy, off = points.get("feature"), points.get("points"), points.get("offsets")
@@ -740,7 +741,7 @@ def _parse_points(points, sink, F, P):
         raise ValueError('grad_sink["points"] must be a float32 GPU buffer of the sparse feature\'s shape with dense rows')
     return dict(feature=f, points=L.need(xy.detach(), "points"), offsets=L.need(off, "offsets", torch.int64),
                 bg=float(points.get("bg", 0.0)), detach_opacity=bool(points.get("detach_opacity", False)),
-                per_frame=f.dim() == 3, sink=sink)
+                ordered=bool(points.get("ordered", False)), per_frame=f.dim() == 3, sink=sink)
 
 
 def _points_forward(fb, pts, pfeat, opacity):
@@ -766,6 +767,21 @@ def _points_backward(fb, pts, pfeat, opacity, g, rec, d_feature):
     if tuple(g.shape) != (Q, c):
         raise ValueError(f"the gradient of the sparse output must be [{Q}, {c}]")
     dfs = 0 if d_feature is None or not pts["per_frame"] else int(d_feature.stride(0))
+    if pts["ordered"]:
+        # no float atomic, every sum in a fixed order (runs in deterministic mode too): the batch's pair map and a pooled scratch
+        need = int(L.lib().splat_alpha_blending_points_backward_batch_ordered_scratch_bytes(
+            L.ci(fb.F), L.ci(c), L.ci(fb.W), L.ci(fb.H), ctypes.c_int64(Q), ctypes.c_int64(fb.capacity)))
+        if need == 0:
+            raise ValueError("the ordered sparse backward: sizes too large")
+        scratch = fb._set_buffer(("points", "ordered"), (need + 3) // 4)
+        L.check(L.lib().splat_alpha_blending_points_backward_batch_ordered(
+            L.ci(fb.F), L.ci(fb.P), L.ci(c), L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), ctypes.c_int64(0), L.ptr(pfeat),
+            ctypes.c_int64(int(pfeat.stride(0)) if pts["per_frame"] else 0), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range),
+            ctypes.c_int64(fb.capacity), L.cf(pts["bg"]), L.ci(fb.W), L.ci(fb.H), ctypes.c_int64(Q), L.ptr(pts["offsets"]),
+            L.ptr(pts["points"]), L.ptr(pts["corner_T"]), L.ptr(pts["corner_n"]), L.ptr(g), L.ptr(fb.slot_sorted), L.ptr(rec),
+            L.ci(int(L.lib().splat_blend_sets_pair_stride(fb.C))), L.ci(1 if pts["detach_opacity"] else 0), L.ptr(d_feature),
+            ctypes.c_int64(dfs), L.ptr(fb.goff), L.ptr(scratch), ctypes.c_size_t(scratch.numel() * 4), L.stream()))
+        return
     L.check(L.lib().splat_alpha_blending_points_backward_batch(
         L.ci(fb.F), L.ci(fb.P), L.ci(c), L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), ctypes.c_int64(0), L.ptr(pfeat),
         ctypes.c_int64(int(pfeat.stride(0)) if pts["per_frame"] else 0), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range),

@@ -417,9 +417,10 @@ class _BlendPoints(torch.autograd.Function):
     weight -- the forward walks only those (an integer query pixel: one list instead of four)."""
 
     @staticmethod
-    def forward(ctx, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, points, live):
+    def forward(ctx, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, points, live, pairmap=None):
         tensors, sizes = _points_inputs(uv, conic, opacity, feature, idx_sorted, tile_range, W, H, points)
         out, corner_T, corner_n = _points_forward(tensors, sizes, bg, True, live)
+        ctx.pairmap = pairmap   # ordered=True: the sort's pair map, found and validated before anything ran
         ctx.save_for_backward(*tensors, corner_T, corner_n)
         ctx.sizes, ctx.bg = sizes, float(bg)
         ctx.shapes = (uv.shape, conic.shape, opacity.shape, feature.shape)
@@ -435,15 +436,30 @@ class _BlendPoints(torch.autograd.Function):
         # the kernel ADDS into zeroed buffers; a gradient nobody asked for is a NULL pointer (opacity: the reference's detach)
         grads = [torch.zeros(shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[k] else None
                  for k, shape in enumerate(ctx.shapes)]
-        L.check(L.lib().splat_alpha_blending_points_backward(
-            L.ci(P), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(idx_sorted), L.ptr(tile_range),
-            L.cf(ctx.bg), L.ci(W), L.ci(H), L.ci(Q), L.ptr(points), L.ptr(corner_T), L.ptr(corner_n), L.ptr(g_out),
-            L.ptr(grads[0]), L.ptr(grads[1]), L.ptr(grads[2]), L.ptr(grads[3]), L.stream()))
-        return grads[0], grads[1], grads[2], grads[3], None, None, None, None, None, None, None
+        pm = ctx.pairmap
+        if pm is not None:   # the ordered route: no float atomic, every sum in a fixed order
+            cap = int(pm.slot_sorted.numel())
+            need = int(L.lib().splat_alpha_blending_points_backward_ordered_scratch_bytes(
+                L.ci(C), L.ci(W), L.ci(H), L.ci(Q), ctypes.c_int64(cap)))
+            if need == 0:
+                raise ValueError("alpha_blending_points(ordered=True): sizes too large")
+            scratch = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
+            L.check(L.lib().splat_alpha_blending_points_backward_ordered(
+                L.ci(P), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(idx_sorted), L.ptr(tile_range),
+                ctypes.c_int64(cap), L.cf(ctx.bg), L.ci(W), L.ci(H), L.ci(Q), L.ptr(points), L.ptr(corner_T), L.ptr(corner_n),
+                L.ptr(g_out), L.ptr(grads[0]), L.ptr(grads[1]), L.ptr(grads[2]), L.ptr(grads[3]), L.ptr(pm.goff),
+                L.ptr(pm.slot_sorted), L.ptr(scratch), ctypes.c_size_t(scratch.numel() * 4), L.stream()))
+        else:
+            L.check(L.lib().splat_alpha_blending_points_backward(
+                L.ci(P), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(idx_sorted), L.ptr(tile_range),
+                L.cf(ctx.bg), L.ci(W), L.ci(H), L.ci(Q), L.ptr(points), L.ptr(corner_T), L.ptr(corner_n), L.ptr(g_out),
+                L.ptr(grads[0]), L.ptr(grads[1]), L.ptr(grads[2]), L.ptr(grads[3]), L.stream()))
+        return grads[0], grads[1], grads[2], grads[3], None, None, None, None, None, None, None, None
 
 
 def alpha_blending_points(uv: Tensor, conic: Tensor, opacity: Tensor, feature: Tensor, idx_sorted: Tensor, tile_range: Tensor,
-                          bg: float, W: int, H: int, points: Tensor, return_corners: bool = False, differentiable: bool = False):
+                          bg: float, W: int, H: int, points: Tensor, return_corners: bool = False, differentiable: bool = False,
+                          ordered: bool = False):
     """``F.grid_sample(alpha_blending(uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H)[None], grid,
     mode="bilinear", padding_mode="zeros", align_corners=True)`` at ``points`` [Q, 2] without the dense image: [Q, C].
 
@@ -459,12 +475,28 @@ def alpha_blending_points(uv: Tensor, conic: Tensor, opacity: Tensor, feature: T
     pixel replaying its list back to front (splat_alpha_blending_points_backward); without ``return_corners`` the forward
     does not walk a corner of zero bilinear weight either (same values; an integer pixel walks one list).  Its sums are float atomics: in
     deterministic mode (``splat_set_deterministic(1)``) the backward raises.  There is no gradient w.r.t. ``points``: a
-    ``points`` that requires grad raises ``ValueError``."""
+    ``points`` that requires grad raises ``ValueError``.
+    ``ordered=True`` (needs ``differentiable=True``): the backward is splat_alpha_blending_points_backward_ordered -- the same
+    gradient without a float atomic, every sum in a fixed order (the tile owns its corners, ascending (query, corner); a
+    Gaussian's pair slots ascending), bit-reproducible run to run and allowed in deterministic mode.  It needs the pair map of
+    this package's ``sort_gaussian`` for ``idx_sorted``; an index list without one (a foreign tensor, a ``.clone()``) raises
+    ``ValueError`` here, in the forward."""
+    if ordered and not differentiable:
+        raise ValueError("alpha_blending_points: ordered=True selects a backward; it needs differentiable=True")
     if differentiable:
         if isinstance(points, Tensor) and points.requires_grad:
             raise ValueError("alpha_blending_points: no gradient w.r.t. points is computed (detach points)")
+        pm = None
+        if ordered:
+            if not (isinstance(feature, Tensor) and feature.dim() == 2 and isinstance(idx_sorted, Tensor) and isinstance(tile_range, Tensor)):
+                raise ValueError("alpha_blending_points: feature must have shape [P, C]; idx_sorted / tile_range must be tensors")
+            pm = _PAIRMAPS.get(idx_sorted.data_ptr())   # (not _find_pairmap's warning: a missing map is an error here)
+            if pm is None:
+                raise ValueError("alpha_blending_points(ordered=True) needs the pair map of this package's sort_gaussian for "
+                                 "idx_sorted (a foreign or copied index list has none)")
+            pm = _find_pairmap(idx_sorted, tile_range, int(feature.shape[0]), pm)
         out, corner_T, corner_n = _BlendPoints.apply(uv, conic, opacity, feature, idx_sorted, tile_range, float(bg), W, H, points,
-                                                     not return_corners)
+                                                     not return_corners, pm)
         if return_corners:
             return out, corner_T, corner_n
         return out

@@ -262,13 +262,14 @@ def track_loss(track_image: torch.Tensor, targets, frame_weights: torch.Tensor, 
 
 def track_loss_sparse(uv: torch.Tensor, conic: torch.Tensor, opacity: torch.Tensor, track_gs: torch.Tensor,
                       idx_sorted: torch.Tensor, tile_range: torch.Tensor, W: int, H: int, targets, frame_weights: torch.Tensor,
-                      quantile: float = 0.98, bg: float = 0.0) -> torch.Tensor:
+                      quantile: float = 0.98, bg: float = 0.0, ordered: bool = False) -> torch.Tensor:
     """``track_loss`` of ONE frame pair without the dense track image: ``track_gs`` [P, C >= 2] (its first three channels at
     most) is composited at the integer query pixels of ``targets`` only (``gs.alpha_blending_points(differentiable=True)``),
     the [Q, C'] result is scattered into a zero [1, C', H, W] image and handed to ``track_loss`` -- which reads nothing but
     those pixels, so value and gradients are the dense route's ``track_loss(alpha_blending(...)[None, :3], ...)``.
     ``opacity`` is detached, as the reference does for its attribute blend.  Differentiable w.r.t. ``uv``, ``conic`` and
-    ``track_gs``; the backward adds with float atomics (it raises in deterministic mode)."""
+    ``track_gs``; the backward adds with float atomics (it raises in deterministic mode) unless ``ordered=True``, which is
+    passed on to ``gs.alpha_blending_points`` (no float atomic, a fixed order of every sum; needs the sort's pair map)."""
     from .gs.raster_ops import alpha_blending_points
     if targets.F != 1:
         raise ValueError(f"track_loss_sparse takes the targets of one frame pair, got {targets.F}")
@@ -284,7 +285,8 @@ def track_loss_sparse(uv: torch.Tensor, conic: torch.Tensor, opacity: torch.Tens
     C = feat.shape[1]
     pix = targets.pixels.long()
     points = torch.stack([pix % W, pix // W], dim=1).to(torch.float32)       # integer pixels: one corner of weight 1
-    vals = alpha_blending_points(uv, conic, opacity.detach(), feat, idx_sorted, tile_range, bg, W, H, points, differentiable=True)
+    vals = alpha_blending_points(uv, conic, opacity.detach(), feat, idx_sorted, tile_range, bg, W, H, points, differentiable=True,
+                                 ordered=ordered)
     image = torch.zeros(C, H * W, dtype=torch.float32, device=track_gs.device).index_copy(1, pix, vals.t())
     return track_loss(image.view(1, C, H, W), targets, frame_weights, quantile)
 

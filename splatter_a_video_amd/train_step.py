@@ -137,7 +137,10 @@ class TrainingStep:
     the renderer's own 23-channel plan).  ``sparse_track=True`` (needs LossWeights.track > 0 and attr == 0; default False: the
     step as it was, bit for bit): the attribute set leaves the frame batch (C = 4: rgb + depth) and the track term runs on
     track_gs composited at the query pixels of gt["tracks"] only; gt["attr"] is not read, the attributes keep a zero gradient,
-    last["l1_attr"] is a zero scalar, and step() raises in deterministic mode (float atomics).  Only the render part changes:
+    last["l1_attr"] is a zero scalar, and step() raises in deterministic mode (float atomics) -- unless ``ordered_track=True``
+    (needs sparse_track=True; default False): the sparse set's backward then takes the ordered entry
+    (splat_alpha_blending_points_backward_batch_ordered: no float atomic, every sum in a fixed order), the step runs under the
+    deterministic flag and its gradients are bit-reproducible.  Only the render part changes:
     the owner-sharded / ZeRO-1 / position-exchange schedules are untouched by construction.  At set-up (and after every densification) the Gaussians are put in Morton order of their
     screen positions (``spatial_order=False``: kept as given); ``initial_order`` maps the rows here to the caller's."""
 
@@ -146,7 +149,7 @@ class TrainingStep:
                  densify: Optional[DensifyConfig] = None, K: int = 20, knn_K: int = 5, arap_samples: int = 512,
                  bg: float = 0.0, sample_seed: Optional[int] = None, timing: bool = False, owner_sharded: bool = False,
                  spatial_order: bool = True, zero1: bool = False, fused_l1: bool = True, exchange_positions: bool = False,
-                 sparse_track: bool = False):
+                 sparse_track: bool = False, ordered_track: bool = False):
         self.clock, self.W, self.H, self.F = clock, int(W), int(H), int(frames_per_step)
         self.extr = extr
         self.dev = params["position"].device
@@ -160,8 +163,11 @@ class TrainingStep:
         # batch's pair records before the Gaussian-side backward.  Only the render part of the step changes: the owner-sharded /
         # ZeRO-1 / position-exchange schedules see the same flat bucket and the same g_pairs and are untouched.  The attributes
         # stay in the bucket with a zero gradient, as the dense step with attr = 0 leaves them.  The sparse backward adds with
-        # float atomics: step() raises in deterministic mode.
+        # float atomics: step() raises in deterministic mode -- ordered_track=True takes the ordered entry instead.
         self.sparse_track = bool(sparse_track)
+        self.ordered_track = bool(ordered_track)
+        if self.ordered_track and not self.sparse_track:
+            raise ValueError("ordered_track=True orders the sums of the sparse track term's backward: it needs sparse_track=True")
         if self.sparse_track:
             if not self.w.track > 0:
                 raise ValueError("sparse_track=True replaces the dense track image by compositing at the query pixels: it needs "
@@ -343,7 +349,7 @@ class TrainingStep:
         segment."""
         if len(times1) != self.F or len(times2) != self.F:
             raise ValueError(f"the step takes {self.F} frame pairs")
-        if self.sparse_track and L.deterministic():      # before anything touches the bucket
+        if self.sparse_track and not self.ordered_track and L.deterministic():      # before anything touches the bucket
             raise L.SplatError("TrainingStep(sparse_track=True): deterministic mode is set and the sparse track term's backward adds "
                                "with float atomics; build the step with sparse_track=False")
         track = self.w.track > 0
@@ -390,7 +396,7 @@ class TrainingStep:
             tt = gt["tracks"]
             pix = tt.pixels.long()
             sparse = dict(feature=self.pairs[:, 1], points=torch.stack([pix % self.W, pix // self.W], dim=1).to(torch.float32),
-                          offsets=tt.offsets, bg=0.0, detach_opacity=True)
+                          offsets=tt.offsets, bg=0.0, detach_opacity=True, ordered=self.ordered_track)
             sink["points"] = self.g_pairs[:, 1]
         else:
             sets.append(dict(feature=[self.pairs[:, 1], p["attrs"]], bg=0.0, detach_opacity=True))

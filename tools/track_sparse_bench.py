@@ -5,6 +5,10 @@ feature composited and back-propagated for Q unique integer query pixels, Q = 10
            step takes today: the whole image is composited and replayed, the loss reads Q pixels of it)
   sparse   gs.alpha_blending_points(differentiable=True) forward + backward (splat_alpha_blending_points_forward / _backward):
            only the query pixels walk their tile lists
+  ordered  the same with ordered=True (splat_alpha_blending_points_backward_ordered): no float atomic, the tile owns its corners
+
+--crowded K adds one case per K: K sub-pixel queries inside a 48 x 48 pixel window (nine tiles), where one wave of the ordered
+backward walks hundreds of corners one after the other (no dense leg's gradient image there: the dense leg is skipped).
 
 Both return the gradients w.r.t. uv, conic and the feature; the opacity is detached, as the reference does for this blend.  The
 two routes are timed in alternating rounds in one process with device events around a window of consecutive forward + backward
@@ -34,6 +38,7 @@ ap.add_argument("--rounds", type=int, default=10)
 ap.add_argument("--calls", type=int, default=20, help="forward + backward calls inside one timed window")
 ap.add_argument("--gaussians", type=int, default=300000)
 ap.add_argument("--queries", type=int, nargs="+", default=[1024, 4096, 16384])
+ap.add_argument("--crowded", type=int, nargs="*", default=[4096])
 ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "points_backward_bench.json"))
 args = ap.parse_args()
 if not torch.cuda.is_available():
@@ -52,11 +57,15 @@ uv, conic, feat = (x.detach().clone().requires_grad_(True) for x in (uv0, conic0
 leaves = (uv, conic, feat)
 
 
-def case(Q):
-    pix = torch.tensor(np.sort(rng.choice(W * H, size=Q, replace=False)), device=dev)
-    points = torch.stack([pix % W, pix // W], 1).to(torch.float32)
+def case(Q, crowded=False):
     g = torch.tensor(rng.normal(size=(Q, C)).astype(np.float32), device=dev)
-    gimg = torch.zeros(C, H * W, device=dev).index_copy(1, pix, g.t().contiguous()).view(C, H, W)
+    if crowded:
+        points = torch.tensor((np.array([400.0, 224.0]) + rng.uniform(0, 48, size=(Q, 2))).astype(np.float32), device=dev)
+        gimg = None
+    else:
+        pix = torch.tensor(np.sort(rng.choice(W * H, size=Q, replace=False)), device=dev)
+        points = torch.stack([pix % W, pix // W], 1).to(torch.float32)
+        gimg = torch.zeros(C, H * W, device=dev).index_copy(1, pix, g.t().contiguous()).view(C, H, W)
 
     def dense():
         img = gs.alpha_blending(uv, conic, opacity, feat, idx, tr, 0.0, W, H)
@@ -66,7 +75,11 @@ def case(Q):
         out = gs.alpha_blending_points(uv, conic, opacity, feat, idx, tr, 0.0, W, H, points, differentiable=True)
         return torch.autograd.grad(out, leaves, g)
 
-    return dense, sparse
+    def ordered():
+        out = gs.alpha_blending_points(uv, conic, opacity, feat, idx, tr, 0.0, W, H, points, differentiable=True, ordered=True)
+        return torch.autograd.grad(out, leaves, g)
+
+    return (None if crowded else dense), sparse, ordered
 
 
 def timed(fn, calls):
@@ -92,36 +105,50 @@ def grad_ratio(got, ref):
 
 stat = lambda v: {"median_ms": float(np.median(v)), "min_ms": float(np.min(v)), "max_ms": float(np.max(v)), "rounds": len(v)}
 cases = []
-for Q in args.queries:
-    dense, sparse = case(Q)
-    for _ in range(3):      # warm up every shape of the timed window
-        a, b = dense(), sparse()
-    torch.cuda.synchronize()
-    ratio = grad_ratio(b, a)
-    ms = {"dense": [], "sparse": []}
-    for _ in range(args.rounds):
-        ms["dense"].append(timed(dense, args.calls))
-        ms["sparse"].append(timed(sparse, args.calls))
-    L.profile_enable(True)      # per-kernel events: a pass of its own (the brackets cost host time)
+def kernels(fn, names, reps=5):
+    """per-kernel events: a pass of its own (the brackets cost host time)"""
+    L.profile_enable(True)
     L.profile_reset()
-    reps = 5
     for _ in range(reps):
-        sparse()
+        fn()
     torch.cuda.synchronize()
     kern = {}
-    for name in ("blend_points_bwd", "blend_points"):       # (prefix match: the second holds both kernels)
+    for name in names:       # (prefix match: "blend_points" holds every kernel of the route)
         total, launches = L.profile_read(name)
         kern[name] = {"ms_per_call": total / reps, "launches_per_call": launches / reps}
     L.profile_enable(False)
-    rec = {"queries": Q, "dense_alpha_blending_fwd_bwd": stat(ms["dense"]), "sparse_points_fwd_bwd": stat(ms["sparse"]),
-           "dense_over_sparse_median": float(np.median(ms["dense"]) / np.median(ms["sparse"])),
-           "sparse_kernels": kern, "gradient_error_over_bound": ratio}
+    return kern
+
+
+for Q, crowded in [(q, False) for q in args.queries] + [(q, True) for q in args.crowded]:
+    dense, sparse, ordered = case(Q, crowded)
+    for _ in range(3):      # warm up every shape of the timed window
+        a, b, c = (dense() if dense else None), sparse(), ordered()
+    torch.cuda.synchronize()
+    ms = {"dense": [], "sparse": [], "ordered": []}
+    for _ in range(args.rounds):
+        if dense:
+            ms["dense"].append(timed(dense, args.calls))
+        ms["sparse"].append(timed(sparse, args.calls))
+        ms["ordered"].append(timed(ordered, args.calls))
+    bits = all(torch.equal(x, y) for x, y in zip(c, ordered()))
+    rec = {"queries": Q, "crowded_into_48x48_pixels": crowded, "sparse_points_fwd_bwd": stat(ms["sparse"]),
+           "ordered_points_fwd_bwd": stat(ms["ordered"]),
+           "ordered_over_sparse_median": float(np.median(ms["ordered"]) / np.median(ms["sparse"])),
+           "sparse_kernels": kernels(sparse, ("blend_points_bwd", "blend_points")),
+           "ordered_kernels": kernels(ordered, ("blend_points_bwd_ord", "blend_points_ord_lists", "blend_points_ord_zero",
+                                                "blend_points_ord_gauss", "blend_points")),
+           "ordered_bit_equal_run_to_run": bits, "ordered_gradient_error_over_bound_vs_sparse": grad_ratio(c, b)}
+    if dense:
+        rec.update({"dense_alpha_blending_fwd_bwd": stat(ms["dense"]),
+                    "dense_over_sparse_median": float(np.median(ms["dense"]) / np.median(ms["sparse"])),
+                    "gradient_error_over_bound": grad_ratio(b, a)})
     print(json.dumps(rec), flush=True)
     cases.append(rec)
 
 rec = {"bench": "points_backward", **stamp(), "device": torch.cuda.get_device_name(0), "gaussians": N, "W": W, "H": H, "channels": C,
        "cases": cases, "calls_per_window": args.calls,
-       "timing": "device events around a window of consecutive forward + backward calls + synchronise, ms per call; windows of the two "
+       "timing": "device events around a window of consecutive forward + backward calls + synchronise, ms per call; windows of the "
                  "routes alternate in one process after 3 warm-up calls of each at every Q; kernel times from the library's own "
                  "per-kernel events in a pass of their own, not a tracer",
        "gradient_error_over_bound": "largest |sparse - dense| / (2 (2e-3 |dense| + 1e-4 max |dense|)) over uv, conic and feature"}

@@ -7,6 +7,9 @@ pair at the default stride 20).
            replayed for every pixel; the loss reads three of the 19 attribute-set channels at the query pixels
   sparse   TrainingStep(sparse_track=True): rgb + depth in the row (C = 4), track_gs composited at the query pixels only, its
            gradient added to the frame batch's pair records before the Gaussian-side backward
+  ordered  TrainingStep(sparse_track=True, ordered_track=True): the sparse step with the ordered backward (no float atomic)
+  dense_det / ordered_det   the dense and the ordered sparse step with splat_set_deterministic(1) set around their windows: what
+           deterministic training pays for either (the unordered sparse step refuses the flag)
 
 Both legs start from the same perturbed parameters and take the same pairs and targets.  They are timed in alternating rounds
 in one process: host clock around a window of consecutive steps with a synchronise on both sides (ms per step; median, minimum
@@ -84,32 +87,40 @@ del truth
 weights = TS.LossWeights(dssim=0.2, track=2.0, depth=0.0, depth_dpt=1.0, attr=0.0)
 lr = {k: 1e-6 for k in TS.REFERENCE_LR}      # small rates keep the scene's statistics put over the run
 legs = {name: TS.TrainingStep(start, clock, W, H, F, extr, lr=lr, densify=TS.DensifyConfig(cameras_extent=5.0), K=20, weights=weights,
-                              sparse_track=sparse, sample_seed=3)
-        for name, sparse in (("dense", False), ("sparse", True))}
+                              sparse_track=sparse, ordered_track=ordered, sample_seed=3)
+        for name, sparse, ordered in (("dense", False, False), ("sparse", True, False), ("ordered", True, True),
+                                      ("dense_det", False, False), ("ordered_det", True, True))}
+FLAG = {name: name.endswith("_det") for name in legs}      # the deterministic flag is set around these legs' steps only
 
 
-def window(st, steps):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        st.step(t1, t2, gt)
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / steps * 1e3
+def window(name, steps):
+    st = legs[name]
+    L.set_deterministic(FLAG[name])
+    try:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            st.step(t1, t2, gt)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / steps * 1e3
+    finally:
+        L.set_deterministic(False)
 
 
-for st in legs.values():
-    window(st, args.warmup)
+for name, st in legs.items():
+    window(name, args.warmup)
     st.fb.check()
 ms = {name: [] for name in legs}
 for _ in range(args.rounds):
-    for name, st in legs.items():
-        ms[name].append(window(st, args.steps))
+    for name in legs:
+        ms[name].append(window(name, args.steps))
 stat = lambda v: {"median_ms": round(float(np.median(v)), 3), "min_ms": round(float(np.min(v)), 3), "max_ms": round(float(np.max(v)), 3),
                   "rounds": len(v)}
 rec = {"bench": "train_step_sparse_track", **stamp(), "build_id": L.build_id(), "device": torch.cuda.get_device_name(0),
        "gaussians": N, "W": W, "H": H, "pairs": F, "attributes": A, "queries_per_pair": queries_per_pair,
        "loss_weights": "dssim=0.2, track=2.0, depth=0.0, depth_dpt=1.0, attr=0.0", "steps_per_window": args.steps}
 for name, st in legs.items():
+    L.set_deterministic(FLAG[name])
     st.timing = True
     st.step(t1, t2, gt)
     phases = {k: round(v, 3) for k, v in st.phases().items()}
@@ -122,15 +133,20 @@ for name, st in legs.items():
     torch.cuda.synchronize()
     L.profile_enable(False)
     kern = {}
-    for k in ("blend_fwd", "blend_points_bwd", "blend_points", "blend_pack", "blend_bwd", "gauss_bwd", "track_loss", "track_grad_zero"):
+    for k in ("blend_fwd", "blend_points_bwd", "blend_points_bwd_ord", "blend_points_ord_lists", "blend_points_ord_zero",
+              "blend_points_ord_gauss", "blend_points", "blend_pack", "blend_bwd", "gauss_bwd", "track_loss", "track_grad_zero"):
         t_ms, cnt = L.profile_read(k)      # (prefix match: "blend_points" holds both sparse kernels)
         if cnt:
             kern[k] = {"us_per_step": round(t_ms * 1e3, 1), "launches": cnt}
     L.profile_reset()
+    L.set_deterministic(False)
     rec[name] = {"ms_per_step": stat(ms[name]), "phases_ms": phases, "kernels_us_per_step": kern, "channels_in_the_row": st.fb.C,
                  "track_loss": float(st.last["track"]), "loss": st.loss()}
-rec["dense_over_sparse_median"] = round(rec["dense"]["ms_per_step"]["median_ms"] / rec["sparse"]["ms_per_step"]["median_ms"], 4)
-rec["timing"] = ("host clock around a window of consecutive steps, synchronise on both sides, ms per step; windows of the two legs "
+med = lambda name: rec[name]["ms_per_step"]["median_ms"]
+rec["dense_over_sparse_median"] = round(med("dense") / med("sparse"), 4)
+rec["ordered_over_sparse_median"] = round(med("ordered") / med("sparse"), 4)
+rec["deterministic_dense_over_ordered_median"] = round(med("dense_det") / med("ordered_det"), 4)
+rec["timing"] = ("host clock around a window of consecutive steps, synchronise on both sides, ms per step; windows of the legs "
                  "alternate in one process after warm-up steps of each; phases from device events of one more step per leg; one run "
                  "on a shared machine is a single sample")
 print(json.dumps(rec))
