@@ -2114,6 +2114,16 @@ __device__ __forceinline__ void fmac_row_lane(int n, float &acc, float src, floa
 #undef ROW_CASE
     }
 }
+// acc = (src of lane n of the lane's own row) * w: the first term of such a sum, without an accumulator zeroed first.  x * y and
+// fma(x, y, +0) differ in the sign of a zero product alone, and no sum that follows keeps it: the terms behind it add to it, and
+// what receives the sum adds it to a value that is +0 or not zero.
+__device__ __forceinline__ void mul_row_lane(int n, float &acc, float src, float w) {
+    switch (n) {
+#define ROW_CASE(N) case N: asm("v_mul_f32_dpp %0, %1, %2 row_newbcast:" #N " row_mask:0xf bank_mask:0xf" : "=&v"(acc) : "v"(src), "v"(w)); break;
+        ROW_LANES(ROW_CASE)
+#undef ROW_CASE
+    }
+}
 __device__ __forceinline__ int row_lane(int n, int v) {
     switch (n) {
 #define ROW_CASE(N) case N: return __builtin_amdgcn_update_dpp(0, v, 0x150 + N, 0xf, 0xf, true);
@@ -2132,7 +2142,9 @@ struct QuarterCfg {
     // super-batch of 128 entries keeps 59 rows per wave on average (39 before): 64 rows -> 80 (137 -> 132 us per frame; 45 KB of
     // LDS = three workgroups per CU, which the compiler answers with 155 registers; 112 rows = two: 167 us)
     static constexpr int CAP = 80;
-    static constexpr int MINW = 4;  // __launch_bounds__ min waves per SIMD
+    // __launch_bounds__ min waves per SIMD = the workgroups per CU that the LDS allows: four with 12-float slab rows, three with the
+    // 16-float rows of the abs taps (45 KB)
+    static constexpr int MINW = ABS ? 3 : 4;
     static constexpr int NG = GradLayout<ABS, false>::NG, NC = NG + CH, NCP = PAIR_STRIDE(NC);
     // slab row.  ABS: [M0 Mx My Mxx | Mxy Myy ax ay | f0 f1 f2 . of lane groups 0 + 2 | of lane groups 1 + 3], two float4 per lane
     // group 0 / 1.  Without the abs taps (round 6): 12 floats, THREE per lane group -- [M0 Mx My | Mxx Mxy Myy | f of groups 0 + 2 | f
@@ -2294,6 +2306,13 @@ blend_bwd_quarter_kernel(const BlendArgs B) {
                                                    &s_more[w]);
 #pragma unroll
             for (int G = 0; G < 4; ++G) {
+                // the strip's A operands that are the same in every step -- dL_dout of the colour product (floats 0-3 of a pixel row are
+                // written once, in front of the first barrier) and the moment table's four rows -- are read here, not per step: three
+                // LDS instructions and two waits for a value just asked for less in every step
+                const float cgA = pixcol[G * GS + kch];
+                float momA[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) momA[i] = momrow[32 * (4 * G + i)];
                 for (int j0 = 0; j0 < cq[G]; j0 += 16) {
                     const unsigned le = s_qlist[w][G][j0 + nl];
                     const int e = le & 0xffu, row = le >> 8;
@@ -2313,14 +2332,12 @@ blend_bwd_quarter_kernel(const BlendArgs B) {
                     }
                     float s_ax = 0.f, s_ay = 0.f;
                     f32x4 d_mom = {0.f, 0.f, 0.f, 0.f};
-                    float dfv[CH];
-#pragma unroll
-                    for (int c = 0; c < CH; ++c) dfv[c] = 0.f;
+                    float dfv[CH];   // (starts with the product of pixel 0: mul_row_lane)
                     asm volatile("" ::: "memory");
                     f32x4 pw = {0.f, 0.f, 0.f, 0.f}, cgv = {0.f, 0.f, 0.f, 0.f};
                     pw = __builtin_amdgcn_mfma_f32_16x16x4f32(phi1[G], bq1, pw, 0, 0, 0);
                     pw = __builtin_amdgcn_mfma_f32_16x16x4f32(phi2[G], bq2, pw, 0, 0, 0);
-                    cgv = __builtin_amdgcn_mfma_f32_16x16x4f32(pixcol[G * GS + kch], bf, cgv, 0, 0, 0);
+                    cgv = __builtin_amdgcn_mfma_f32_16x16x4f32(cgA, bf, cgv, 0, 0, 0);
                     float cg[4], araw[4], a[4], r1a[4], rp[4], Ts4[4], Rs4[4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
@@ -2358,14 +2375,16 @@ blend_bwd_quarter_kernel(const BlendArgs B) {
                     for (int i = 0; i < 4; ++i) {
                         const float dLa = T[i] * cg[i] - R[i] * r1a[i];
                         const float dLp = araw[i] * dLa;
-                        d_mom = __builtin_amdgcn_mfma_f32_16x16x4f32(momrow[32 * (4 * G + i)], dLp, d_mom, 0, 0, 0);
+                        d_mom = __builtin_amdgcn_mfma_f32_16x16x4f32(momA[i], dLp, d_mom, 0, 0, 0);
                         if (ABS) {
                             s_ax += fabsf(dLp * lx4[i]);
                             s_ay += fabsf(dLp * ly4[i]);
                         }
 #pragma unroll
-                        for (int c = 0; c < CH; ++c)   // dfv[c] = fma(g_c of the step's pixel, wgt[i], dfv[c]); gpix is written once, before the loops
-                            fmac_row_lane(4 * G + i, dfv[c], gpix[c], wgt[i]);
+                        for (int c = 0; c < CH; ++c) {   // dfv[c] = fma(g_c of the step's pixel, wgt[i], dfv[c]); gpix is written once, before the loops
+                            if (i == 0) mul_row_lane(4 * G, dfv[c], gpix[c], wgt[0]);
+                            else fmac_row_lane(4 * G + i, dfv[c], gpix[c], wgt[i]);
+                        }
                     }
                     // ---- step epilogue: raw sums into the survivor's row (this wave's quarters run one after the other: plain
                     //      read-add-write; lane group kk owns floats 4 kk .. 4 kk + 3 of the row)
