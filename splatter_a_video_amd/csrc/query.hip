@@ -16,10 +16,18 @@
 //     channels take one launch per chunk.
 //   * the four corner values (F + T bg) meet in LDS and are combined nw, ne, sw, se with the bilinear weights.  No
 //     atomics anywhere in the forward: results are bit-reproducible.
-//   * the backward (points_bwd_kernel below) replays every corner's list back to front and adds with float atomics.
-//   * the frame-batched entries (BATCH instantiations of the same two kernels) take the queries of F frames in CSR form: the
-//     frame of a query comes from `offsets` on the device (F is a few dozen: a scalar scan), the FrameBatch buffers are read
-//     through their frame strides, and the backward adds its geometry gradients into the frame batch's pair records.
+//   * every kernel takes its corner from points_corner and a list entry's alpha from points_entry: the forward and the
+//     backward's replay decide with the same bits because they run the same code; the backward kernels take the six geometry
+//     terms from points_geo_terms.
+//   * the backward replays every corner's list back to front: points_bwd_kernel adds with float atomics (per-Gaussian buffers,
+//     or the frame batch's pair records in its BATCH instantiation), points_bwd_ordered_kernel with plain load / add / store
+//     into slot records that one wave owns.  The two replay loops are still written out twice: hipcc picks which product of
+//     acc = a f + (1 - a) acc it fuses per loop shape, so a shared loop changes the gradient's bits.
+//   * the frame-batched entries (BATCH instantiations of the forward and the atomic backward) take the queries of F frames in
+//     CSR form: the frame of a query comes from `offsets` on the device (F is a few dozen: a scalar scan) and the FrameBatch
+//     buffers are read through their frame strides.
+#include <type_traits>
+
 #include "blend_power.h"
 #include "dynamics_dev.h"
 #include "pointwise_dev.h"
@@ -29,7 +37,8 @@ namespace {
 constexpr int PT_NA_MAX = 4;                  // accumulators per lane: channel chunks of at most 256
 constexpr int PT_CHUNK = 64 * PT_NA_MAX;
 
-struct PointsArgs {
+// what the forward and the backward kernels both read
+struct PointsGeo {
     int P, C, c0, cn;
     const float2 *uv;
     const float *conic, *opacity, *feature;
@@ -38,9 +47,19 @@ struct PointsArgs {
     float bg;
     int W, H, gx;
     const float2 *points;
+};
+
+struct PointsArgs : PointsGeo {
     float *out;       // [Q, C]
     float *corner_T;  // [Q, 4] or NULL
     int *corner_n;    // [Q, 4] or NULL
+};
+
+struct PointsBwdArgs : PointsGeo {
+    const float *corner_T;   // [Q, 4]
+    const int *corner_n;     // [Q, 4]
+    const float *dL_dout;    // [Q, C]
+    float *dL_duv, *dL_dconic, *dL_dopacity, *dL_dfeature;   // each may be NULL
 };
 
 __device__ __forceinline__ float lane_f(float v, int j) {
@@ -72,8 +91,7 @@ __device__ __forceinline__ int points_frame_of(const PointsBatch &B, long long q
     return f;
 }
 
-template <typename Args>
-__device__ __forceinline__ void points_frame_view(Args &A, const PointsBatch &B, int f) {
+__device__ __forceinline__ void points_frame_view(PointsGeo &A, const PointsBatch &B, int f) {
     const size_t fz = (size_t)f;
     A.uv += fz * (size_t)A.P;
     A.conic += fz * 3 * (size_t)A.P;
@@ -81,6 +99,84 @@ __device__ __forceinline__ void points_frame_view(Args &A, const PointsBatch &B,
     A.feature += fz * (size_t)B.feature_fs;
     if (A.idx_sorted) A.idx_sorted += fz * (size_t)B.cap;
     A.tile_range += fz * (size_t)B.T;
+}
+
+// Corner k (nw, ne, sw, se) of the query at pt.  `in`: the in / out test in float, before any conversion to int (1e9, inf and
+// NaN are simply outside); cw: its bilinear weight (pt is finite where `in` holds).  Where `in` holds: the corner's pixel and
+// tile, the pixel relative to the tile centre with its monomials (exact in f32), and the tile centre as the dense forward forms it.
+struct PointsCorner {
+    bool in;
+    float cw;
+    int px, py, tx, ty;
+    float x, y, xx, xy, yy, tcx, tcy;
+};
+
+__device__ __forceinline__ PointsCorner points_corner(float2 pt, int k, int W, int H) {
+    PointsCorner K;
+    const float x0f = floorf(pt.x), y0f = floorf(pt.y);
+    const float cxf = x0f + (float)(k & 1), cyf = y0f + (float)(k >> 1);
+    K.in = cxf >= 0.f && cxf <= (float)(W - 1) && cyf >= 0.f && cyf <= (float)(H - 1);
+    K.cw = ((k & 1) ? pt.x - x0f : (x0f + 1.f) - pt.x) * ((k >> 1) ? pt.y - y0f : (y0f + 1.f) - pt.y);
+    K.px = (int)cxf; K.py = (int)cyf;
+    K.tx = K.px / TILE; K.ty = K.py / TILE;
+    K.x = (float)(K.px - K.tx * TILE) - 7.5f; K.y = (float)(K.py - K.ty * TILE) - 7.5f;
+    K.xx = K.x * K.x; K.xy = K.x * K.y; K.yy = K.y * K.y;
+    K.tcx = (float)(K.tx * TILE) + 7.5f; K.tcy = (float)(K.ty * TILE) + 7.5f;
+    return K;
+}
+
+// lane = entry: entry e of the list that starts at idx_sorted[first] (n entries count) on corner K -- its alpha with the dense
+// forward's arithmetic, and what the backward needs besides: the unclamped araw and the gathered operands.
+struct PointsEntry {
+    int id;        // -1 unless e < n and the id lies inside the set (an id outside is skipped, never dereferenced)
+    int slot;      // slots[first + e] of such an entry where the caller passes `slots` (issued with the gathers), else -1
+    float alpha, araw, ux, uy, cA, cB, cC, o;
+};
+
+__device__ __forceinline__ bool points_entry(const PointsGeo &A, const PointsCorner &K, int first, int e, int n, PointsEntry &E,
+                                             const int *slots = nullptr) {
+    bool aok = false;
+    E = {-1, -1, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f};
+    if (e < n) {
+        const int id = A.idx_sorted[first + e];
+        if ((unsigned)id < (unsigned)A.P) {
+            E.id = id;
+            const float2 c = A.uv[id];
+            E.ux = c.x; E.uy = c.y;
+            E.cA = A.conic[3 * (size_t)id]; E.cB = A.conic[3 * (size_t)id + 1]; E.cC = A.conic[3 * (size_t)id + 2];
+            E.o = A.opacity[id];
+            if (slots) E.slot = slots[first + e];
+            const PowerCoef k = power_coeffs(E.ux, E.uy, E.cA, E.cB, E.cC, E.o, K.tcx, K.tcy);
+            const float pw = power_poly(make_float4(k.q0, k.qx, k.qy, k.qxx), make_float4(k.qxy, k.qyy, 0.f, 0.f), K.x, K.y, K.xx, K.xy, K.yy);
+            bool pw_ok;
+            E.araw = exp2_guard(pw, pw_ok);
+            const float a = fminf(0.99f, E.araw);
+            aok = pw_ok && !(a < (1.0f / 255.0f));
+            E.alpha = aok ? a : 0.f;
+        }
+    }
+    return aok;
+}
+
+// The six geometry terms of an applied entry on the corner pixel (pxf, pyf), dLa = its dL_dalpha (replay_one's expressions), as
+// products a[i] * b[i] for the fields i = REC_UX .. REC_O.  The ONE copy: the backward kernels only add.  A caller forms the
+// product where it adds, so that an atomic adds the rounded product and a load / add / store may fuse it, as they always did.
+struct PointsGeoTerms {
+    float a[REC_GEOM], b[REC_GEOM];
+};
+
+__device__ __forceinline__ PointsGeoTerms points_geo_terms(const PointsEntry &E, float pxf, float pyf, float dLa) {
+    const float dx = E.ux - pxf, dy = E.uy - pyf;
+    const float G = E.araw * __builtin_amdgcn_rcpf(E.o);
+    const float dLG = E.o * dLa;
+    PointsGeoTerms t;
+    t.a[REC_UX] = dLG; t.b[REC_UX] = -G * dx * E.cA - G * dy * E.cB;
+    t.a[REC_UY] = dLG; t.b[REC_UY] = -G * dy * E.cC - G * dx * E.cB;
+    t.a[REC_CA] = -0.5f * G * dx * dx; t.b[REC_CA] = dLG;
+    t.a[REC_CB] = -G * dx * dy; t.b[REC_CB] = dLG;
+    t.a[REC_CC] = -0.5f * G * dy * dy; t.b[REC_CC] = dLG;
+    t.a[REC_O] = G; t.b[REC_O] = dLa;
+    return t;
 }
 
 // LIVE: an in-image corner whose bilinear weight is zero is not walked either (it reports T = 0, ncontrib = 0 like a corner
@@ -106,14 +202,8 @@ __global__ void __launch_bounds__(256) points_fwd_kernel(const PointsArgs A0, co
         if (A.P > 0) points_frame_view(A, B, f);
     }
     const float2 pt = A.points[q];
-    // corner w of the query: the in / out test in float, before any conversion to int (1e9, inf and NaN are simply outside)
-    const float x0f = floorf(pt.x), y0f = floorf(pt.y);
-    const float cxf = x0f + (float)(w & 1), cyf = y0f + (float)(w >> 1);
-    bool in = cxf >= 0.f && cxf <= (float)(A.W - 1) && cyf >= 0.f && cyf <= (float)(A.H - 1);
-    if (LIVE) {   // (the weight as the combine below forms it; pt is finite where `in` holds)
-        const float wxl = (w & 1) ? pt.x - x0f : (x0f + 1.f) - pt.x, wyl = (w >> 1) ? pt.y - y0f : (y0f + 1.f) - pt.y;
-        in = in && wxl * wyl != 0.f;
-    }
+    const PointsCorner K = points_corner(pt, w, A.W, A.H);
+    const bool in = K.in && (!LIVE || K.cw != 0.f);
 
     float T = 1.f;
     int last = 0;
@@ -122,44 +212,21 @@ __global__ void __launch_bounds__(256) points_fwd_kernel(const PointsArgs A0, co
     for (int k = 0; k < NA; ++k) F[k] = 0.f;
 
     if (in) {
-        const int px = (int)cxf, py = (int)cyf;
-        const int tx = px / TILE, ty = py / TILE;
         int2 range = make_int2(0, 0);
-        if (A.P > 0) range = A.tile_range[ty * A.gx + tx];
+        if (A.P > 0) range = A.tile_range[K.ty * A.gx + K.tx];
         const int n = imax_(range.y - range.x, 0);
-        // pixel relative to the tile centre and its monomials (exact in f32), the tile centre as the forward forms it
-        const float x = (float)(px - tx * TILE) - 7.5f, y = (float)(py - ty * TILE) - 7.5f;
-        const float xx = x * x, xy = x * y, yy = y * y;
-        const float tcx = (float)(tx * TILE) + 7.5f, tcy = (float)(ty * TILE) + 7.5f;
         bool done = false;
         for (int base = 0; base < n && !done; base += WAVE) {
             // ---- lane = entry: its alpha on this pixel
-            const int e = base + lane;
-            int id = 0;
-            float alpha = 0.f;
-            bool aok = false;
-            if (e < n) {
-                id = A.idx_sorted[range.x + e];
-                if ((unsigned)id < (unsigned)A.P) {   // (an id outside the set is skipped, never dereferenced)
-                    const float2 c = A.uv[id];
-                    const float cA = A.conic[3 * (size_t)id], cB = A.conic[3 * (size_t)id + 1], cC = A.conic[3 * (size_t)id + 2];
-                    const PowerCoef k = power_coeffs(c.x, c.y, cA, cB, cC, A.opacity[id], tcx, tcy);
-                    const float pw = power_poly(make_float4(k.q0, k.qx, k.qy, k.qxx), make_float4(k.qxy, k.qyy, 0.f, 0.f), x, y, xx, xy, yy);
-                    bool pw_ok;
-                    const float a = fminf(0.99f, exp2_guard(pw, pw_ok));
-                    aok = pw_ok && !(a < (1.0f / 255.0f));
-                    alpha = aok ? a : 0.f;
-                } else {
-                    id = 0;
-                }
-            }
+            PointsEntry E;
+            const bool aok = points_entry(A, K, range.x, base + lane, n, E);
             // ---- the transmittance chain over the entries that touch the pixel, in list order (wave-uniform values)
             unsigned long long cand = __ballot(aok), applied = 0ull;
             float wv = 0.f;   // lane j: weight alpha T of entry base + j, if it applied
             while (cand) {
                 const int j = (int)__builtin_ctzll(cand);
                 cand &= cand - 1ull;
-                const float a = lane_f(alpha, j);
+                const float a = lane_f(E.alpha, j);
                 const float nT = T * (1.f - a);
                 if (nT < 0.0001f) {   // the splat that would take T below 1e-4 ends the pixel, unapplied
                     done = true;
@@ -183,7 +250,7 @@ __global__ void __launch_bounds__(256) points_fwd_kernel(const PointsArgs A0, co
                 float f[4][NA], wg[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    const float *row = fbase + (size_t)__builtin_amdgcn_readlane(id, jj[u]) * (size_t)A.C;
+                    const float *row = fbase + (size_t)__builtin_amdgcn_readlane(E.id, jj[u]) * (size_t)A.C;
                     wg[u] = lane_f(wv, jj[u]);
 #pragma unroll
                     for (int k = 0; k < NA; ++k) f[u][k] = (lane + 64 * k < A.cn) ? row[64 * k] : 0.f;
@@ -196,7 +263,7 @@ __global__ void __launch_bounds__(256) points_fwd_kernel(const PointsArgs A0, co
             while (applied) {
                 const int j = (int)__builtin_ctzll(applied);
                 applied &= applied - 1ull;
-                const float *row = fbase + (size_t)__builtin_amdgcn_readlane(id, j) * (size_t)A.C;
+                const float *row = fbase + (size_t)__builtin_amdgcn_readlane(E.id, j) * (size_t)A.C;
                 const float wg = lane_f(wv, j);
 #pragma unroll
                 for (int k = 0; k < NA; ++k) {
@@ -217,15 +284,13 @@ __global__ void __launch_bounds__(256) points_fwd_kernel(const PointsArgs A0, co
 #pragma unroll
     for (int k = 0; k < NA; ++k) s_val[w][64 * k + lane] = F[k] + T * A.bg;
     __syncthreads();
-    const float x1f = x0f + 1.f, y1f = y0f + 1.f;
-    const float wx[2] = {x1f - pt.x, pt.x - x0f}, wy[2] = {y1f - pt.y, pt.y - y0f};
     bool cin[4];
     float cw[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const float cx = x0f + (float)(k & 1), cy = y0f + (float)(k >> 1);
-        cin[k] = cx >= 0.f && cx <= (float)(A.W - 1) && cy >= 0.f && cy <= (float)(A.H - 1);
-        cw[k] = wx[k & 1] * wy[k >> 1];
+        const PointsCorner Kk = points_corner(pt, k, A.W, A.H);
+        cin[k] = Kk.in;
+        cw[k] = Kk.cw;
     }
     for (int c = tid; c < A.cn; c += 256) {
         float acc = 0.f;
@@ -236,45 +301,86 @@ __global__ void __launch_bounds__(256) points_fwd_kernel(const PointsArgs A0, co
     }
 }
 
-template <int NA>
-int launch_points(const PointsArgs &A, int Q, bool live, hipStream_t s, const PointsBatch *batch = nullptr) {
-    PointsBatch B;
-    memset(&B, 0, sizeof(B));
-    if (batch) SPLAT_LAUNCH("blend_points", (points_fwd_kernel<NA, true, true>), dim3((unsigned)Q), dim3(256), 0, s, A, *batch);
-    else if (live) SPLAT_LAUNCH("blend_points", (points_fwd_kernel<NA, true, false>), dim3((unsigned)Q), dim3(256), 0, s, A, B);
-    else SPLAT_LAUNCH("blend_points", (points_fwd_kernel<NA, false, false>), dim3((unsigned)Q), dim3(256), 0, s, A, B);
-    SPLAT_POST_LAUNCH();
-    return SPLAT_OK;
-}
+// ---- host side: what the entries below share
+// SPLAT_CHECK_ARG inside a helper: the message names the entry `fn`
+#define PT_CHECK(fn, cond, msg)                    \
+    do {                                           \
+        if (!(cond)) {                             \
+            splat_set_error("%s: %s", fn, msg);    \
+            return SPLAT_E_ARG;                    \
+        }                                          \
+    } while (0)
 
-// the launches of the validated forward: one per 256 channels
-int points_forward_chunks(int P, int C, const float *uv, const float *conic, const float *opacity, const float *feature,
-                          const int32_t *idx_sorted, const int32_t *tile_range, float bg, int W, int H, int Q, const float *points,
-                          float *out, float *corner_T, int32_t *corner_ncontrib, bool live, hipStream_t stream,
-                          const PointsBatch *batch = nullptr) {
-    PointsArgs A;
+long long points_num_tiles(int W, int H) { return (long long)((W + TILE - 1) / TILE) * (long long)((H + TILE - 1) / TILE); }
+
+template <typename Args>
+Args points_args(int P, int C, const float *uv, const float *conic, const float *opacity, const float *feature,
+                 const int32_t *idx_sorted, const int32_t *tile_range, float bg, int W, int H, const float *points) {
+    Args A;
     memset(&A, 0, sizeof(A));
     A.P = P; A.C = C;
     A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
     A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
     A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
     A.points = (const float2 *)points;
-    A.out = out;
-    for (int c0 = 0; c0 < C; c0 += PT_CHUNK) {
+    return A;
+}
+
+PointsBatch points_batch(int F, int W, int H, const int64_t *offsets, int64_t Q, int64_t capacity, int64_t opacity_fs,
+                         int64_t feature_fs) {
+    PointsBatch B;
+    memset(&B, 0, sizeof(B));
+    B.F = F; B.T = (int)points_num_tiles(W, H);
+    B.offsets = (const long long *)offsets; B.Q = Q; B.cap = capacity;
+    B.opacity_fs = opacity_fs; B.feature_fs = feature_fs;
+    return B;
+}
+
+// One launch per 256 channels: launch(A, std::integral_constant<int, NA>) starts the NA = ceil(cn / 64) instantiation of a kernel
+// family on the chunk A.c0 .. A.c0 + A.cn.  Launches on one stream: the chunks run in ascending order.
+template <typename Args, typename Launch>
+int points_chunks(Args A, Launch launch) {
+    for (int c0 = 0; c0 < A.C; c0 += PT_CHUNK) {
         A.c0 = c0;
-        A.cn = C - c0 > PT_CHUNK ? PT_CHUNK : C - c0;
-        A.corner_T = c0 == 0 ? corner_T : nullptr;   // every chunk walks the same lists: the first one reports them
-        A.corner_n = c0 == 0 ? corner_ncontrib : nullptr;
-        int rc;
+        A.cn = A.C - c0 > PT_CHUNK ? PT_CHUNK : A.C - c0;
         switch ((A.cn + 63) / 64) {
-            case 1: rc = launch_points<1>(A, Q, live, stream, batch); break;
-            case 2: rc = launch_points<2>(A, Q, live, stream, batch); break;
-            case 3: rc = launch_points<3>(A, Q, live, stream, batch); break;
-            default: rc = launch_points<4>(A, Q, live, stream, batch); break;
+            case 1: launch(A, std::integral_constant<int, 1>()); break;
+            case 2: launch(A, std::integral_constant<int, 2>()); break;
+            case 3: launch(A, std::integral_constant<int, 3>()); break;
+            default: launch(A, std::integral_constant<int, 4>()); break;
         }
-        if (rc != SPLAT_OK) return rc;
+        SPLAT_POST_LAUNCH();
     }
     return SPLAT_OK;
+}
+
+// the launches of the validated forward
+int points_forward(const PointsArgs &A0, int Q, bool live, hipStream_t s, const PointsBatch *batch = nullptr) {
+    const PointsBatch B = batch ? *batch : points_batch(0, 0, 0, nullptr, 0, 0, 0, 0);
+    return points_chunks(A0, [&](PointsArgs A, auto na) {
+        constexpr int NA = decltype(na)::value;
+        if (A.c0 != 0) {   // every chunk walks the same lists: the first one reports them
+            A.corner_T = nullptr;
+            A.corner_n = nullptr;
+        }
+        if (batch) SPLAT_LAUNCH("blend_points", (points_fwd_kernel<NA, true, true>), dim3((unsigned)Q), dim3(256), 0, s, A, B);
+        else if (live) SPLAT_LAUNCH("blend_points", (points_fwd_kernel<NA, true, false>), dim3((unsigned)Q), dim3(256), 0, s, A, B);
+        else SPLAT_LAUNCH("blend_points", (points_fwd_kernel<NA, false, false>), dim3((unsigned)Q), dim3(256), 0, s, A, B);
+    });
+}
+
+int points_forward_entry(const char *fn, bool live, int P, int C, const float *uv, const float *conic, const float *opacity,
+                         const float *feature, const int32_t *idx_sorted, const int32_t *tile_range, float bg, int W, int H, int Q,
+                         const float *points, float *out, float *corner_T, int32_t *corner_ncontrib, splat_stream_t stream) {
+    PT_CHECK(fn, P >= 0 && C >= 1 && W > 0 && H > 0 && Q >= 0, "bad sizes (P, Q >= 0, C, W, H >= 1)");
+    PT_CHECK(fn, W <= (1 << 24) && H <= (1 << 24), "sizes too large (W, H <= 2^24: pixel indices are compared in float32)");
+    if (Q == 0) return SPLAT_OK;
+    PT_CHECK(fn, points && out, "null pointer (points / out)");
+    // idx_sorted may be NULL when no Gaussian touches any tile (every tile range is empty, nothing dereferences it)
+    PT_CHECK(fn, P == 0 || (uv && conic && opacity && feature && tile_range), "null pointer");
+    PointsArgs A = points_args<PointsArgs>(P, C, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, points);
+    A.out = out; A.corner_T = corner_T; A.corner_n = corner_ncontrib;
+    return points_forward(A, Q, live, (hipStream_t)stream);
 }
 
 // ---- backward of the sparse compositing: the gradient of grid_sample(alpha_blending(...)) w.r.t. uv, conic, opacity, feature.
@@ -287,21 +393,6 @@ int points_forward_chunks(int P, int C, const float *uv, const float *conic, con
 //     atomics; the entry's dL_dalpha stays in the entry's lane.
 //   * lane = entry again: the uv / conic / opacity atomics of the block issue from up to 64 lanes at once.
 // Many queries hit one Gaussian: float atomics, outputs ADDED (the host entry refuses deterministic mode).
-struct PointsBwdArgs {
-    int P, C, c0, cn;
-    const float2 *uv;
-    const float *conic, *opacity, *feature;
-    const int *idx_sorted;
-    const int2 *tile_range;
-    float bg;
-    int W, H, gx;
-    const float2 *points;
-    const float *corner_T;   // [Q, 4]
-    const int *corner_n;     // [Q, 4]
-    const float *dL_dout;    // [Q, C]
-    float *dL_duv, *dL_dconic, *dL_dopacity, *dL_dfeature;   // each may be NULL
-};
-
 // BATCH: the queries of F frames (PointsBatch).  The geometry gradients of an applied entry at list position e of frame f are
 // added to the pair record at slot slot_sorted[f, range.x + e] of that frame -- the record the tile backward of the same forward
 // wrote for this (Gaussian, tile) pair, which the Gaussian-side walk sums per Gaussian afterwards.
@@ -324,26 +415,17 @@ __global__ void __launch_bounds__(256) points_bwd_kernel(const PointsBwdArgs A0,
         }
     }
     const float2 ptv = A.points[q];
-    const float ptx = lane_f(ptv.x, 0), pty = lane_f(ptv.y, 0);   // (uniform: the exits below are scalar branches)
-    // the forward's corner, in / out test and bilinear weight
-    const float x0f = floorf(ptx), y0f = floorf(pty);
-    const float cxf = x0f + (float)(w & 1), cyf = y0f + (float)(w >> 1);
-    const bool in = cxf >= 0.f && cxf <= (float)(A.W - 1) && cyf >= 0.f && cyf <= (float)(A.H - 1);
-    if (!in) return;
-    const float x1f = x0f + 1.f, y1f = y0f + 1.f;
-    const float cw = ((w & 1) ? ptx - x0f : x1f - ptx) * ((w >> 1) ? pty - y0f : y1f - pty);
+    // (uniform: the exits below are scalar branches)
+    const PointsCorner K = points_corner(make_float2(lane_f(ptv.x, 0), lane_f(ptv.y, 0)), w, A.W, A.H);
+    if (!K.in) return;
+    const float cw = K.cw;
     if (cw == 0.f) return;
-    const int px = (int)cxf, py = (int)cyf;
-    const int tx = px / TILE, ty = py / TILE;
-    const int2 range = A.tile_range[ty * A.gx + tx];
+    const int2 range = A.tile_range[K.ty * A.gx + K.tx];
     const int n = imax_(range.y - range.x, 0);
     const int last = imin_(__builtin_amdgcn_readfirstlane(A.corner_n[q * 4 + w]), n);   // (never past the list)
     if (last <= 0) return;   // nothing applied: no Gaussian saw this corner
     const float Tf = lane_f(A.corner_T[q * 4 + w], 0);
-    const float pxf = (float)px, pyf = (float)py;
-    const float x = (float)(px - tx * TILE) - 7.5f, y = (float)(py - ty * TILE) - 7.5f;
-    const float xx = x * x, xy = x * y, yy = y * y;
-    const float tcx = (float)(tx * TILE) + 7.5f, tcy = (float)(ty * TILE) + 7.5f;
+    const float pxf = (float)K.px, pyf = (float)K.py;
 
     float g[NA], acc[NA];
     float gsum = 0.f;
@@ -361,27 +443,10 @@ __global__ void __launch_bounds__(256) points_bwd_kernel(const PointsBwdArgs A0,
     for (int base = ((last - 1) / WAVE) * WAVE; base >= 0; base -= WAVE) {
         // ---- lane = entry: its alpha on this pixel (the forward's bits)
         const int e = base + lane;
-        int id = 0;
-        float alpha = 0.f, araw = 0.f, ux = 0.f, uy = 0.f, cA = 0.f, cB = 0.f, cC = 0.f, o = 1.f;
-        bool aok = false;
-        if (e < last) {
-            id = A.idx_sorted[range.x + e];
-            if ((unsigned)id < (unsigned)A.P) {   // (an id outside the set is skipped, never dereferenced)
-                const float2 c = A.uv[id];
-                ux = c.x; uy = c.y;
-                cA = A.conic[3 * (size_t)id]; cB = A.conic[3 * (size_t)id + 1]; cC = A.conic[3 * (size_t)id + 2];
-                o = A.opacity[id];
-                const PowerCoef k = power_coeffs(ux, uy, cA, cB, cC, o, tcx, tcy);
-                const float pw = power_poly(make_float4(k.q0, k.qx, k.qy, k.qxx), make_float4(k.qxy, k.qyy, 0.f, 0.f), x, y, xx, xy, yy);
-                bool pw_ok;
-                araw = exp2_guard(pw, pw_ok);
-                const float a = fminf(0.99f, araw);
-                aok = pw_ok && !(a < (1.0f / 255.0f));
-                alpha = aok ? a : 0.f;
-            } else {
-                id = 0;
-            }
-        }
+        PointsEntry E;
+        const bool aok = points_entry(A, K, range.x, e, last, E);
+        const int id = E.id;
+        const float alpha = E.alpha;
         // ---- lane = channel: the applied entries back to front, four rows in flight
         unsigned long long ap = __ballot(aok);
         float dLa_v = 0.f;   // lane j: dL_dalpha of entry base + j, if it applied
@@ -427,46 +492,56 @@ __global__ void __launch_bounds__(256) points_bwd_kernel(const PointsBwdArgs A0,
         }
         // ---- lane = entry: the geometry gradients of the block's applied entries (replay_one's expressions)
         if (aok) {
-            const float dx = ux - pxf, dy = uy - pyf;
-            const float G = araw * __builtin_amdgcn_rcpf(o);
-            const float dLG = o * dLa_v;
+            const PointsGeoTerms t = points_geo_terms(E, pxf, pyf, dLa_v);
             if (BATCH) {
                 if (recs) {
                     const int slot = slots[range.x + e];
                     if (slot >= 0 && (long long)slot < B.cap) {   // (a slot outside the frame's records is skipped, never written)
                         float *r = recs + (size_t)slot * (size_t)B.rec_stride;
-                        atomic_add_f32(r + REC_UX, dLG * (-G * dx * cA - G * dy * cB));
-                        atomic_add_f32(r + REC_UY, dLG * (-G * dy * cC - G * dx * cB));
-                        atomic_add_f32(r + REC_CA, -0.5f * G * dx * dx * dLG);
-                        atomic_add_f32(r + REC_CB, -G * dx * dy * dLG);
-                        atomic_add_f32(r + REC_CC, -0.5f * G * dy * dy * dLG);
-                        if (!B.detach_opacity) atomic_add_f32(r + REC_O, G * dLa_v);
+#pragma unroll
+                        for (int i = REC_UX; i < REC_O; ++i) atomic_add_f32(r + i, t.a[i] * t.b[i]);
+                        if (!B.detach_opacity) atomic_add_f32(r + REC_O, t.a[REC_O] * t.b[REC_O]);
                     }
                 }
             } else {
                 if (A.dL_duv) {
-                    atomic_add_f32(A.dL_duv + 2 * (size_t)id, dLG * (-G * dx * cA - G * dy * cB));
-                    atomic_add_f32(A.dL_duv + 2 * (size_t)id + 1, dLG * (-G * dy * cC - G * dx * cB));
+                    atomic_add_f32(A.dL_duv + 2 * (size_t)id, t.a[REC_UX] * t.b[REC_UX]);
+                    atomic_add_f32(A.dL_duv + 2 * (size_t)id + 1, t.a[REC_UY] * t.b[REC_UY]);
                 }
                 if (A.dL_dconic) {
-                    atomic_add_f32(A.dL_dconic + 3 * (size_t)id, -0.5f * G * dx * dx * dLG);
-                    atomic_add_f32(A.dL_dconic + 3 * (size_t)id + 1, -G * dx * dy * dLG);
-                    atomic_add_f32(A.dL_dconic + 3 * (size_t)id + 2, -0.5f * G * dy * dy * dLG);
+                    atomic_add_f32(A.dL_dconic + 3 * (size_t)id, t.a[REC_CA] * t.b[REC_CA]);
+                    atomic_add_f32(A.dL_dconic + 3 * (size_t)id + 1, t.a[REC_CB] * t.b[REC_CB]);
+                    atomic_add_f32(A.dL_dconic + 3 * (size_t)id + 2, t.a[REC_CC] * t.b[REC_CC]);
                 }
-                if (A.dL_dopacity) atomic_add_f32(A.dL_dopacity + id, G * dLa_v);
+                if (A.dL_dopacity) atomic_add_f32(A.dL_dopacity + id, t.a[REC_O] * t.b[REC_O]);
             }
         }
     }
 }
 
-template <int NA>
-int launch_points_bwd(const PointsBwdArgs &A, int Q, hipStream_t s, const PointsBatch *batch = nullptr) {
-    PointsBatch B;
-    memset(&B, 0, sizeof(B));
-    if (batch) SPLAT_LAUNCH("blend_points_bwd", (points_bwd_kernel<NA, true>), dim3((unsigned)Q), dim3(256), 0, s, A, *batch);
-    else SPLAT_LAUNCH("blend_points_bwd", (points_bwd_kernel<NA, false>), dim3((unsigned)Q), dim3(256), 0, s, A, B);
-    SPLAT_POST_LAUNCH();
-    return SPLAT_OK;
+PointsBwdArgs points_bwd_args(int P, int C, const float *uv, const float *conic, const float *opacity, const float *feature,
+                              const int32_t *idx_sorted, const int32_t *tile_range, float bg, int W, int H, const float *points,
+                              const float *corner_T, const int32_t *corner_ncontrib, const float *dL_dout) {
+    PointsBwdArgs A = points_args<PointsBwdArgs>(P, C, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, points);
+    A.corner_T = corner_T; A.corner_n = corner_ncontrib; A.dL_dout = dL_dout;
+    return A;
+}
+
+// the launches of a validated atomic backward.  Every chunk adds its share of the geometry gradients: dL_dalpha is linear in the
+// channels.
+int points_backward(const PointsBwdArgs &A0, int Q, hipStream_t s, const PointsBatch *batch = nullptr) {
+    const PointsBatch B = batch ? *batch : points_batch(0, 0, 0, nullptr, 0, 0, 0, 0);
+    return points_chunks(A0, [&](const PointsBwdArgs &A, auto na) {
+        constexpr int NA = decltype(na)::value;
+        if (batch) SPLAT_LAUNCH("blend_points_bwd", (points_bwd_kernel<NA, true>), dim3((unsigned)Q), dim3(256), 0, s, A, B);
+        else SPLAT_LAUNCH("blend_points_bwd", (points_bwd_kernel<NA, false>), dim3((unsigned)Q), dim3(256), 0, s, A, B);
+    });
+}
+
+int points_refuse_deterministic(const char *fn, const char *instead) {
+    splat_set_error("%s: deterministic mode: the backward of the sparse compositing adds with float atomics (many queries hit "
+                    "one Gaussian); %s", fn, instead);
+    return SPLAT_E_ARG;
 }
 
 // ---- the ORDERED backward: the same gradient without a float atomic, every sum in a fixed order.
@@ -474,7 +549,7 @@ int launch_points_bwd(const PointsBwdArgs &A, int Q, hipStream_t s, const Points
 // same list, and every (Gaussian, tile) pair of that list has exactly one slot (slot_sorted of the pair map): the wave that owns
 // a tile is the only writer of its slots and adds with plain loads and stores.
 //   1. points_ord_corners_kernel<.., false>: thread = query; its LIVE corners (in the image, bilinear weight != 0,
-//      corner_ncontrib > 0: the tests of points_bwd_kernel) are counted per (frame, tile) with an INTEGER atomic (a count does
+//      corner_ncontrib > 0: points_bwd_kernel's exits, through the same points_corner) are counted per (frame, tile) with an INTEGER atomic (a count does
 //      not depend on the arrival order);
 //   2. points_ord_scan_kernel: exclusive scan of the counts (one workgroup);
 //   3. points_ord_corners_kernel<.., true>: the corners' keys 4 q + k go into their tile's segment through an integer cursor,
@@ -502,15 +577,10 @@ struct PointsOrd {
 
 // corner k of a query at pt: the tile of a live corner, else -1
 __device__ __forceinline__ int points_live_corner_tile(const PointsBwdArgs &A, size_t q, float2 pt, int k) {
-    const float x0f = floorf(pt.x), y0f = floorf(pt.y);
-    const float cxf = x0f + (float)(k & 1), cyf = y0f + (float)(k >> 1);
-    const bool in = cxf >= 0.f && cxf <= (float)(A.W - 1) && cyf >= 0.f && cyf <= (float)(A.H - 1);
-    if (!in) return -1;
-    const float x1f = x0f + 1.f, y1f = y0f + 1.f;
-    const float cw = ((k & 1) ? pt.x - x0f : x1f - pt.x) * ((k >> 1) ? pt.y - y0f : y1f - pt.y);
-    if (cw == 0.f) return -1;
+    const PointsCorner K = points_corner(pt, k, A.W, A.H);
+    if (!K.in || K.cw == 0.f) return -1;
     if (A.corner_n[q * 4 + k] <= 0) return -1;
-    return ((int)cyf / TILE) * A.gx + (int)cxf / TILE;
+    return K.ty * A.gx + K.tx;
 }
 
 template <bool BATCH, bool FILL>
@@ -594,8 +664,6 @@ __global__ void __launch_bounds__(256) points_bwd_ordered_kernel(const PointsBwd
     long long nn = (long long)range.y - (long long)range.x;
     nn = nn > B.cap - (long long)range.x ? B.cap - (long long)range.x : nn;
     const int n = range.x < 0 || nn < 0 ? 0 : (int)nn;
-    const int tx = tile % A.gx, ty = tile / A.gx;
-    const float tcx = (float)(tx * TILE) + 7.5f, tcy = (float)(ty * TILE) + 7.5f;
     const float *fbase = A.feature + A.c0 + lane;
 
     for (int ci = s0; ci < s1; ++ci) {   // the tile's live corners in ascending (q, k)
@@ -603,19 +671,13 @@ __global__ void __launch_bounds__(256) points_bwd_ordered_kernel(const PointsBwd
         const size_t q = (size_t)(key >> 2);
         const int w = key & 3;
         const float2 ptv = A.points[q];
-        const float ptx = lane_f(ptv.x, 0), pty = lane_f(ptv.y, 0);
-        // the forward's corner and bilinear weight (the corner is live: inside the image, cw != 0)
-        const float x0f = floorf(ptx), y0f = floorf(pty);
-        const float cxf = x0f + (float)(w & 1), cyf = y0f + (float)(w >> 1);
-        const float x1f = x0f + 1.f, y1f = y0f + 1.f;
-        const float cw = ((w & 1) ? ptx - x0f : x1f - ptx) * ((w >> 1) ? pty - y0f : y1f - pty);
-        const int px = (int)cxf, py = (int)cyf;
+        // (the corner is live: inside the image, cw != 0, and its pixel lies in this tile)
+        const PointsCorner K = points_corner(make_float2(lane_f(ptv.x, 0), lane_f(ptv.y, 0)), w, A.W, A.H);
+        const float cw = K.cw;
         const int last = imin_(__builtin_amdgcn_readfirstlane(A.corner_n[q * 4 + w]), n);   // (never past the list)
         if (last <= 0) continue;
         const float Tf = lane_f(A.corner_T[q * 4 + w], 0);
-        const float pxf = (float)px, pyf = (float)py;
-        const float x = (float)(px - tx * TILE) - 7.5f, y = (float)(py - ty * TILE) - 7.5f;
-        const float xx = x * x, xy = x * y, yy = y * y;
+        const float pxf = (float)K.px, pyf = (float)K.py;
 
         float g[NA], acc[NA];
         float gsum = 0.f;
@@ -631,29 +693,11 @@ __global__ void __launch_bounds__(256) points_bwd_ordered_kernel(const PointsBwd
         for (int base = ((last - 1) / WAVE) * WAVE; base >= 0; base -= WAVE) {
             // ---- lane = entry: its alpha on this pixel (the forward's bits) and its slot
             const int e = base + lane;
-            int id = 0, slot = -1;
-            float alpha = 0.f, araw = 0.f, ux = 0.f, uy = 0.f, cA = 0.f, cB = 0.f, cC = 0.f, o = 1.f;
-            bool aok = false;
-            if (e < last) {
-                id = A.idx_sorted[range.x + e];
-                if ((unsigned)id < (unsigned)A.P) {   // (an id outside the set is skipped, never dereferenced)
-                    const float2 c = A.uv[id];
-                    ux = c.x; uy = c.y;
-                    cA = A.conic[3 * (size_t)id]; cB = A.conic[3 * (size_t)id + 1]; cC = A.conic[3 * (size_t)id + 2];
-                    o = A.opacity[id];
-                    const PowerCoef k = power_coeffs(ux, uy, cA, cB, cC, o, tcx, tcy);
-                    const float pw = power_poly(make_float4(k.q0, k.qx, k.qy, k.qxx), make_float4(k.qxy, k.qyy, 0.f, 0.f), x, y, xx, xy, yy);
-                    bool pw_ok;
-                    araw = exp2_guard(pw, pw_ok);
-                    const float a = fminf(0.99f, araw);
-                    aok = pw_ok && !(a < (1.0f / 255.0f));
-                    alpha = aok ? a : 0.f;
-                    const int s = slots[range.x + e];
-                    slot = (s >= 0 && (long long)s < B.cap) ? s : -1;   // (a slot outside the frame's records is skipped, never written)
-                } else {
-                    id = 0;
-                }
-            }
+            PointsEntry E;
+            const bool aok = points_entry(A, K, range.x, e, last, E, slots);
+            const int id = E.id;
+            const float alpha = E.alpha;
+            const int slot = (long long)E.slot < B.cap ? E.slot : -1;   // (a slot outside the frame's records is skipped, never written)
             // ---- lane = channel: the applied entries back to front, four rows in flight
             unsigned long long ap = __ballot(aok);
             float dLa_v = 0.f;   // lane j: dL_dalpha of entry base + j, if it applied
@@ -706,16 +750,11 @@ __global__ void __launch_bounds__(256) points_bwd_ordered_kernel(const PointsBwd
             // ---- lane = entry: the geometry terms of the block's applied entries (replay_one's expressions); list position e is
             //      this lane's in every corner of the tile, and its slot is nobody else's
             if (aok && geo && slot >= 0) {
-                const float dx = ux - pxf, dy = uy - pyf;
-                const float G = araw * __builtin_amdgcn_rcpf(o);
-                const float dLG = o * dLa_v;
+                const PointsGeoTerms t = points_geo_terms(E, pxf, pyf, dLa_v);
                 float *r = geo + (size_t)slot * (size_t)O.geo_stride;
-                r[REC_UX] = r[REC_UX] + dLG * (-G * dx * cA - G * dy * cB);
-                r[REC_UY] = r[REC_UY] + dLG * (-G * dy * cC - G * dx * cB);
-                r[REC_CA] = r[REC_CA] + -0.5f * G * dx * dx * dLG;
-                r[REC_CB] = r[REC_CB] + -G * dx * dy * dLG;
-                r[REC_CC] = r[REC_CC] + -0.5f * G * dy * dy * dLG;
-                if (!B.detach_opacity) r[REC_O] = r[REC_O] + G * dLa_v;
+#pragma unroll
+                for (int i = REC_UX; i < REC_O; ++i) r[i] = r[i] + t.a[i] * t.b[i];
+                if (!B.detach_opacity) r[REC_O] = r[REC_O] + t.a[REC_O] * t.b[REC_O];
             }
         }
     }
@@ -778,7 +817,7 @@ bool points_ord_layout(long long NT, long long Q, double rec_floats, OrdLayout &
 }
 
 // the launches of a validated ordered backward.  A / B as the atomic entries fill them (single frame: F = 1, no offsets).
-int points_ordered_run(PointsBwdArgs A, const PointsBatch &B, PointsOrd O, bool batch, const OrdLayout &L, char *scratch,
+int points_ordered_run(const PointsBwdArgs &A, const PointsBatch &B, PointsOrd O, bool batch, const OrdLayout &L, char *scratch,
                        size_t rec_bytes_to_zero, hipStream_t s) {
     const int Q = (int)B.Q;
     O.seg = (int *)(scratch + L.seg); O.cursor = (int *)(scratch + L.cursor);
@@ -800,18 +839,10 @@ int points_ordered_run(PointsBwdArgs A, const PointsBatch &B, PointsOrd O, bool 
     SPLAT_LAUNCH("blend_points_ord_lists", points_ord_rank_kernel, cgrid, dim3(256), 0, s, O);
     SPLAT_POST_LAUNCH();
     const dim3 tgrid((unsigned)(((size_t)O.NT + 3) / 4));
-    for (int c0 = 0; c0 < A.C; c0 += PT_CHUNK) {   // every chunk adds its share of the geometry terms: dL_dalpha is linear in the channels
-        A.c0 = c0;
-        A.cn = A.C - c0 > PT_CHUNK ? PT_CHUNK : A.C - c0;
-        switch ((A.cn + 63) / 64) {
-            case 1: SPLAT_LAUNCH("blend_points_bwd_ord", points_bwd_ordered_kernel<1>, tgrid, dim3(256), 0, s, A, B, O); break;
-            case 2: SPLAT_LAUNCH("blend_points_bwd_ord", points_bwd_ordered_kernel<2>, tgrid, dim3(256), 0, s, A, B, O); break;
-            case 3: SPLAT_LAUNCH("blend_points_bwd_ord", points_bwd_ordered_kernel<3>, tgrid, dim3(256), 0, s, A, B, O); break;
-            default: SPLAT_LAUNCH("blend_points_bwd_ord", points_bwd_ordered_kernel<4>, tgrid, dim3(256), 0, s, A, B, O); break;
-        }
-        SPLAT_POST_LAUNCH();
-    }
-    return SPLAT_OK;
+    // every chunk adds its share of the geometry terms: dL_dalpha is linear in the channels
+    return points_chunks(A, [&](const PointsBwdArgs &a, auto na) {
+        SPLAT_LAUNCH("blend_points_bwd_ord", points_bwd_ordered_kernel<decltype(na)::value>, tgrid, dim3(256), 0, s, a, B, O);
+    });
 }
 
 // rows[n, t] = (u_t - u_ref, v_t - v_ref, depth_t) of Gaussian n at the t-th time of the table: get_position(t) (the segment
@@ -858,27 +889,16 @@ extern "C" int splat_alpha_blending_points_forward(int P, int C, const float *uv
                                                    const float *feature, const int32_t *idx_sorted, const int32_t *tile_range,
                                                    float bg, int W, int H, int Q, const float *points, float *out,
                                                    float *corner_T, int32_t *corner_ncontrib, splat_stream_t stream) {
-    SPLAT_CHECK_ARG(P >= 0 && C >= 1 && W > 0 && H > 0 && Q >= 0, "bad sizes (P, Q >= 0, C, W, H >= 1)");
-    SPLAT_CHECK_ARG(W <= (1 << 24) && H <= (1 << 24), "sizes too large (W, H <= 2^24: pixel indices are compared in float32)");
-    if (Q == 0) return SPLAT_OK;
-    SPLAT_CHECK_ARG(points && out, "null pointer (points / out)");
-    // idx_sorted may be NULL when no Gaussian touches any tile (every tile range is empty, nothing dereferences it)
-    SPLAT_CHECK_ARG(P == 0 || (uv && conic && opacity && feature && tile_range), "null pointer");
-    return points_forward_chunks(P, C, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, Q, points, out, corner_T,
-                                 corner_ncontrib, false, (hipStream_t)stream);
+    return points_forward_entry(__func__, false, P, C, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, Q, points, out,
+                                corner_T, corner_ncontrib, stream);
 }
 
 extern "C" int splat_alpha_blending_points_forward_live(int P, int C, const float *uv, const float *conic, const float *opacity,
                                                         const float *feature, const int32_t *idx_sorted, const int32_t *tile_range,
                                                         float bg, int W, int H, int Q, const float *points, float *out,
                                                         float *corner_T, int32_t *corner_ncontrib, splat_stream_t stream) {
-    SPLAT_CHECK_ARG(P >= 0 && C >= 1 && W > 0 && H > 0 && Q >= 0, "bad sizes (P, Q >= 0, C, W, H >= 1)");
-    SPLAT_CHECK_ARG(W <= (1 << 24) && H <= (1 << 24), "sizes too large (W, H <= 2^24: pixel indices are compared in float32)");
-    if (Q == 0) return SPLAT_OK;
-    SPLAT_CHECK_ARG(points && out, "null pointer (points / out)");
-    SPLAT_CHECK_ARG(P == 0 || (uv && conic && opacity && feature && tile_range), "null pointer");
-    return points_forward_chunks(P, C, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, Q, points, out, corner_T,
-                                 corner_ncontrib, true, (hipStream_t)stream);
+    return points_forward_entry(__func__, true, P, C, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, Q, points, out,
+                                corner_T, corner_ncontrib, stream);
 }
 
 extern "C" int splat_alpha_blending_points_backward(int P, int C, const float *uv, const float *conic, const float *opacity,
@@ -890,52 +910,41 @@ extern "C" int splat_alpha_blending_points_backward(int P, int C, const float *u
     SPLAT_CHECK_ARG(W <= (1 << 24) && H <= (1 << 24), "sizes too large (W, H <= 2^24: pixel indices are compared in float32)");
     if (Q == 0) return SPLAT_OK;
     SPLAT_CHECK_ARG(points && corner_T && corner_ncontrib && dL_dout, "null pointer (points / corner_T / corner_ncontrib / dL_dout)");
-    // idx_sorted may be NULL when no Gaussian touches any tile (every tile range is empty, nothing dereferences it)
     SPLAT_CHECK_ARG(P == 0 || (uv && conic && opacity && feature && tile_range), "null pointer");
     if (P == 0 || !(dL_duv || dL_dconic || dL_dopacity || dL_dfeature)) return SPLAT_OK;   // nothing to add to
-    if (splat_deterministic()) {   // refused before any launch
-        splat_set_error("%s: deterministic mode: the backward of the sparse compositing adds with float atomics (many queries hit "
-                        "one Gaussian); use the dense alpha_blending route", __func__);
-        return SPLAT_E_ARG;
-    }
-    PointsBwdArgs A;
-    memset(&A, 0, sizeof(A));
-    A.P = P; A.C = C;
-    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
-    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
-    A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
-    A.points = (const float2 *)points; A.corner_T = corner_T; A.corner_n = corner_ncontrib; A.dL_dout = dL_dout;
-    A.dL_dfeature = dL_dfeature;
-    for (int c0 = 0; c0 < C; c0 += PT_CHUNK) {
-        A.c0 = c0;
-        A.cn = C - c0 > PT_CHUNK ? PT_CHUNK : C - c0;
-        // every chunk adds its share of the geometry gradients: dL_dalpha is linear in the channels
-        A.dL_duv = dL_duv; A.dL_dconic = dL_dconic; A.dL_dopacity = dL_dopacity;
-        int rc;
-        switch ((A.cn + 63) / 64) {
-            case 1: rc = launch_points_bwd<1>(A, Q, (hipStream_t)stream); break;
-            case 2: rc = launch_points_bwd<2>(A, Q, (hipStream_t)stream); break;
-            case 3: rc = launch_points_bwd<3>(A, Q, (hipStream_t)stream); break;
-            default: rc = launch_points_bwd<4>(A, Q, (hipStream_t)stream); break;
-        }
-        if (rc != SPLAT_OK) return rc;
-    }
-    return SPLAT_OK;
+    if (splat_deterministic()) return points_refuse_deterministic(__func__, "use the dense alpha_blending route");   // before any launch
+    PointsBwdArgs A = points_bwd_args(P, C, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, points, corner_T,
+                                      corner_ncontrib, dL_dout);
+    A.dL_duv = dL_duv; A.dL_dconic = dL_dconic; A.dL_dopacity = dL_dopacity; A.dL_dfeature = dL_dfeature;
+    return points_backward(A, Q, (hipStream_t)stream);
 }
 
 // ---- the frame-batched entries: the queries of F frames of a FrameBatch in one launch per 256-channel chunk
 namespace {
 int points_batch_check(const char *fn, int F, int P, int C, int W, int H, int64_t Q, int64_t capacity, int64_t opacity_fs,
                        int64_t feature_fs) {
-    if (!(F >= 1 && P >= 0 && C >= 1 && W > 0 && H > 0 && Q >= 0 && capacity >= 0 && opacity_fs >= 0 && feature_fs >= 0)) {
-        splat_set_error("%s: bad sizes (F, C, W, H >= 1; P, Q, capacity, frame strides >= 0)", fn);
-        return SPLAT_E_ARG;
-    }
-    if (!(W <= (1 << 24) && H <= (1 << 24) && Q <= 0x7fffffffLL && F <= (1 << 16))) {
-        splat_set_error("%s: sizes too large (W, H <= 2^24: pixel indices are compared in float32; Q < 2^31, F <= 2^16)", fn);
-        return SPLAT_E_ARG;
-    }
+    PT_CHECK(fn, F >= 1 && P >= 0 && C >= 1 && W > 0 && H > 0 && Q >= 0 && capacity >= 0 && opacity_fs >= 0 && feature_fs >= 0,
+             "bad sizes (F, C, W, H >= 1; P, Q, capacity, frame strides >= 0)");
+    PT_CHECK(fn, W <= (1 << 24) && H <= (1 << 24) && Q <= 0x7fffffffLL && F <= (1 << 16),
+             "sizes too large (W, H <= 2^24: pixel indices are compared in float32; Q < 2^31, F <= 2^16)");
     return SPLAT_OK;
+}
+
+// the size checks that the two batch backward entries add
+int points_batch_bwd_check(const char *fn, int64_t dfeature_fs, const float *pair_records, int record_stride, int64_t capacity) {
+    PT_CHECK(fn, dfeature_fs >= 0, "bad sizes (dL_dfeature frame stride >= 0)");
+    PT_CHECK(fn, !pair_records || (record_stride >= REC_GEOM && record_stride % 4 == 0 && capacity >= 1),
+             "bad sizes (pair records: a stride of whole 16-byte chunks >= 8 floats, capacity >= 1)");
+    return SPLAT_OK;
+}
+
+PointsBatch points_batch_bwd(int F, int W, int H, const int64_t *offsets, int64_t Q, int64_t capacity, int64_t opacity_fs,
+                             int64_t feature_fs, int64_t dfeature_fs, const int32_t *slot_sorted, float *pair_records,
+                             int record_stride, int detach_opacity) {
+    PointsBatch B = points_batch(F, W, H, offsets, Q, capacity, opacity_fs, feature_fs);
+    B.dfeature_fs = dfeature_fs;
+    B.slot_sorted = slot_sorted; B.rec = pair_records; B.rec_stride = record_stride; B.detach_opacity = detach_opacity ? 1 : 0;
+    return B;
 }
 }  // namespace
 
@@ -949,15 +958,11 @@ extern "C" int splat_alpha_blending_points_forward_batch(int F, int P, int C, co
     if (rc != SPLAT_OK) return rc;
     if (Q == 0) return SPLAT_OK;
     SPLAT_CHECK_ARG(points && out && offsets, "null pointer (points / out / offsets)");
-    // idx_sorted may be NULL when no Gaussian touches any tile (every tile range is empty, nothing dereferences it)
     SPLAT_CHECK_ARG(P == 0 || (uv && conic && opacity && feature && tile_range), "null pointer");
-    PointsBatch B;
-    memset(&B, 0, sizeof(B));
-    B.F = F; B.T = ((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
-    B.offsets = (const long long *)offsets; B.Q = Q; B.cap = capacity;
-    B.opacity_fs = opacity_frame_stride; B.feature_fs = feature_frame_stride;
-    return points_forward_chunks(P, C, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, (int)Q, points, out, corner_T,
-                                 corner_ncontrib, true, (hipStream_t)stream, &B);
+    const PointsBatch B = points_batch(F, W, H, offsets, Q, capacity, opacity_frame_stride, feature_frame_stride);
+    PointsArgs A = points_args<PointsArgs>(P, C, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, points);
+    A.out = out; A.corner_T = corner_T; A.corner_n = corner_ncontrib;
+    return points_forward(A, (int)Q, true, (hipStream_t)stream, &B);
 }
 
 // RELIES ON: (1) corner_T / corner_ncontrib of splat_alpha_blending_points_forward_batch on the same buffers; (2) the tile
@@ -974,11 +979,10 @@ extern "C" int splat_alpha_blending_points_backward_batch(int F, int P, int C, c
                                                           const float *dL_dout, const int32_t *slot_sorted, float *pair_records,
                                                           int record_stride, int detach_opacity, float *dL_dfeature,
                                                           int64_t dfeature_frame_stride, splat_stream_t stream) {
-    const int rc = points_batch_check(__func__, F, P, C, W, H, Q, capacity, opacity_frame_stride, feature_frame_stride);
+    int rc = points_batch_check(__func__, F, P, C, W, H, Q, capacity, opacity_frame_stride, feature_frame_stride);
     if (rc != SPLAT_OK) return rc;
-    SPLAT_CHECK_ARG(dfeature_frame_stride >= 0, "bad sizes (dL_dfeature frame stride >= 0)");
-    SPLAT_CHECK_ARG(!pair_records || (record_stride >= REC_GEOM && record_stride % 4 == 0 && capacity >= 1),
-                    "bad sizes (pair records: a stride of whole 16-byte chunks >= 8 floats, capacity >= 1)");
+    rc = points_batch_bwd_check(__func__, dfeature_frame_stride, pair_records, record_stride, capacity);
+    if (rc != SPLAT_OK) return rc;
     if (Q == 0) return SPLAT_OK;
     SPLAT_CHECK_ARG(points && offsets && corner_T && corner_ncontrib && dL_dout,
                     "null pointer (points / offsets / corner_T / corner_ncontrib / dL_dout)");
@@ -986,46 +990,19 @@ extern "C" int splat_alpha_blending_points_backward_batch(int F, int P, int C, c
     SPLAT_CHECK_ARG(!pair_records || slot_sorted, "null pointer (slot_sorted goes with pair_records)");
     if (P == 0 || !(pair_records || dL_dfeature)) return SPLAT_OK;   // nothing to add to
     SPLAT_CHECK_ARG(idx_sorted, "null pointer (idx_sorted)");
-    if (splat_deterministic()) {   // refused before any launch
-        splat_set_error("%s: deterministic mode: the backward of the sparse compositing adds with float atomics (many queries hit "
-                        "one Gaussian); render the set densely instead", __func__);
-        return SPLAT_E_ARG;
-    }
-    PointsBatch B;
-    memset(&B, 0, sizeof(B));
-    B.F = F; B.T = ((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
-    B.offsets = (const long long *)offsets; B.Q = Q; B.cap = capacity;
-    B.opacity_fs = opacity_frame_stride; B.feature_fs = feature_frame_stride; B.dfeature_fs = dfeature_frame_stride;
-    B.slot_sorted = slot_sorted; B.rec = pair_records; B.rec_stride = record_stride; B.detach_opacity = detach_opacity ? 1 : 0;
-    PointsBwdArgs A;
-    memset(&A, 0, sizeof(A));
-    A.P = P; A.C = C;
-    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
-    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
-    A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
-    A.points = (const float2 *)points; A.corner_T = corner_T; A.corner_n = corner_ncontrib; A.dL_dout = dL_dout;
+    if (splat_deterministic()) return points_refuse_deterministic(__func__, "render the set densely instead");   // before any launch
+    const PointsBatch B = points_batch_bwd(F, W, H, offsets, Q, capacity, opacity_frame_stride, feature_frame_stride,
+                                           dfeature_frame_stride, slot_sorted, pair_records, record_stride, detach_opacity);
+    PointsBwdArgs A = points_bwd_args(P, C, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, points, corner_T,
+                                      corner_ncontrib, dL_dout);
     A.dL_dfeature = dL_dfeature;
-    for (int c0 = 0; c0 < C; c0 += PT_CHUNK) {
-        A.c0 = c0;
-        A.cn = C - c0 > PT_CHUNK ? PT_CHUNK : C - c0;
-        int r;   // every chunk adds its share of the geometry gradients: dL_dalpha is linear in the channels
-        switch ((A.cn + 63) / 64) {
-            case 1: r = launch_points_bwd<1>(A, (int)Q, (hipStream_t)stream, &B); break;
-            case 2: r = launch_points_bwd<2>(A, (int)Q, (hipStream_t)stream, &B); break;
-            case 3: r = launch_points_bwd<3>(A, (int)Q, (hipStream_t)stream, &B); break;
-            default: r = launch_points_bwd<4>(A, (int)Q, (hipStream_t)stream, &B); break;
-        }
-        if (r != SPLAT_OK) return r;
-    }
-    return SPLAT_OK;
+    return points_backward(A, (int)Q, (hipStream_t)stream, &B);
 }
 
 // ---- the ordered entries: no float atomic, run with the deterministic flag on or off
 namespace {
 constexpr long long ORD_MAX_Q = 1ll << 29;    // a corner's key 4 q + k is an int32
 constexpr long long ORD_MAX_NT = 1ll << 30;   // (frame, tile) owners
-
-long long points_num_tiles(int W, int H) { return (long long)((W + TILE - 1) / TILE) * (long long)((H + TILE - 1) / TILE); }
 
 int points_ord_gauss(int F, int P, int ncol, const float *sc, long long stride, long long fs, long long cap, const int32_t *goff,
                      int geom, float *duv, float *dconic, float *dopac, float *dfeat, int C, long long dfeat_fs, hipStream_t s) {
@@ -1083,23 +1060,17 @@ extern "C" int splat_alpha_blending_points_backward_ordered(int P, int C, const 
     const int S = PAIR_STRIDE(REC_GEOM + C);
     OrdLayout L;
     points_ord_layout(T, Q, (double)capacity * (double)S, L);
-    PointsBatch B;
-    memset(&B, 0, sizeof(B));
-    B.F = 1; B.T = T; B.Q = Q; B.cap = capacity; B.slot_sorted = slot_sorted;
-    PointsBwdArgs A;
-    memset(&A, 0, sizeof(A));
-    A.P = P; A.C = C;
-    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
-    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
-    A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
-    A.points = (const float2 *)points; A.corner_T = corner_T; A.corner_n = corner_ncontrib; A.dL_dout = dL_dout;
+    PointsBatch B = points_batch(1, W, H, nullptr, Q, capacity, 0, 0);
+    B.slot_sorted = slot_sorted;
+    const PointsBwdArgs A = points_bwd_args(P, C, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, points, corner_T,
+                                            corner_ncontrib, dL_dout);
     float *rec = (float *)((char *)scratch + L.rec);
     PointsOrd O;
     memset(&O, 0, sizeof(O));
     O.NT = T;
     if (dL_duv || dL_dconic || dL_dopacity) { O.geo = rec; O.geo_stride = S; }
     if (dL_dfeature) { O.fsc = rec + REC_GEOM; O.fsc_stride = S; }
-    int rc = points_ordered_run(A, B, O, false, L, (char *)scratch, (size_t)capacity * (size_t)S * 4, (hipStream_t)stream);
+    const int rc = points_ordered_run(A, B, O, false, L, (char *)scratch, (size_t)capacity * (size_t)S * 4, (hipStream_t)stream);
     if (rc != SPLAT_OK) return rc;
     return points_ord_gauss(1, P, REC_GEOM + C, rec, S, 0, capacity, goff_incl, 1, dL_duv, dL_dconic, dL_dopacity, dL_dfeature, C, 0,
                             (hipStream_t)stream);
@@ -1113,13 +1084,12 @@ extern "C" int splat_alpha_blending_points_backward_batch_ordered(
     int64_t Q, const int64_t *offsets, const float *points, const float *corner_T, const int32_t *corner_ncontrib,
     const float *dL_dout, const int32_t *slot_sorted, float *pair_records, int record_stride, int detach_opacity, float *dL_dfeature,
     int64_t dfeature_frame_stride, const int32_t *goff_incl, void *scratch, size_t scratch_bytes, splat_stream_t stream) {
-    const int rc = points_batch_check(__func__, F, P, C, W, H, Q, capacity, opacity_frame_stride, feature_frame_stride);
+    int rc = points_batch_check(__func__, F, P, C, W, H, Q, capacity, opacity_frame_stride, feature_frame_stride);
     if (rc != SPLAT_OK) return rc;
     SPLAT_CHECK_ARG(Q <= ORD_MAX_Q && (long long)F * points_num_tiles(W, H) <= ORD_MAX_NT,
                     "sizes too large (Q <= 2^29, F * tiles <= 2^30)");
-    SPLAT_CHECK_ARG(dfeature_frame_stride >= 0, "bad sizes (dL_dfeature frame stride >= 0)");
-    SPLAT_CHECK_ARG(!pair_records || (record_stride >= REC_GEOM && record_stride % 4 == 0 && capacity >= 1),
-                    "bad sizes (pair records: a stride of whole 16-byte chunks >= 8 floats, capacity >= 1)");
+    rc = points_batch_bwd_check(__func__, dfeature_frame_stride, pair_records, record_stride, capacity);
+    if (rc != SPLAT_OK) return rc;
     if (Q == 0) return SPLAT_OK;
     SPLAT_CHECK_ARG(points && offsets && corner_T && corner_ncontrib && dL_dout,
                     "null pointer (points / offsets / corner_T / corner_ncontrib / dL_dout)");
@@ -1137,19 +1107,10 @@ extern "C" int splat_alpha_blending_points_backward_batch_ordered(
     const int S = PAIR_STRIDE(C);
     OrdLayout L;
     points_ord_layout((long long)F * T, Q, (double)F * (double)capacity * (double)S, L);
-    PointsBatch B;
-    memset(&B, 0, sizeof(B));
-    B.F = F; B.T = T;
-    B.offsets = (const long long *)offsets; B.Q = Q; B.cap = capacity;
-    B.opacity_fs = opacity_frame_stride; B.feature_fs = feature_frame_stride; B.dfeature_fs = dfeature_frame_stride;
-    B.slot_sorted = slot_sorted; B.rec = pair_records; B.rec_stride = record_stride; B.detach_opacity = detach_opacity ? 1 : 0;
-    PointsBwdArgs A;
-    memset(&A, 0, sizeof(A));
-    A.P = P; A.C = C;
-    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
-    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
-    A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
-    A.points = (const float2 *)points; A.corner_T = corner_T; A.corner_n = corner_ncontrib; A.dL_dout = dL_dout;
+    const PointsBatch B = points_batch_bwd(F, W, H, offsets, Q, capacity, opacity_frame_stride, feature_frame_stride,
+                                           dfeature_frame_stride, slot_sorted, pair_records, record_stride, detach_opacity);
+    const PointsBwdArgs A = points_bwd_args(P, C, uv, conic, opacity, feature, idx_sorted, tile_range, bg, W, H, points, corner_T,
+                                            corner_ncontrib, dL_dout);
     float *rec = (float *)((char *)scratch + L.rec);
     PointsOrd O;
     memset(&O, 0, sizeof(O));
@@ -1157,8 +1118,8 @@ extern "C" int splat_alpha_blending_points_backward_batch_ordered(
     if (pair_records) { O.geo = pair_records; O.geo_stride = record_stride; O.geo_fs = (long long)capacity * record_stride; }
     if (dL_dfeature) { O.fsc = rec; O.fsc_stride = S; O.fsc_fs = (long long)capacity * S; }
     const size_t zero = dL_dfeature ? (size_t)F * (size_t)capacity * (size_t)S * 4 : 0;
-    int r = points_ordered_run(A, B, O, true, L, (char *)scratch, zero, (hipStream_t)stream);
-    if (r != SPLAT_OK) return r;
+    rc = points_ordered_run(A, B, O, true, L, (char *)scratch, zero, (hipStream_t)stream);
+    if (rc != SPLAT_OK) return rc;
     if (!dL_dfeature) return SPLAT_OK;
     return points_ord_gauss(F, P, C, rec, S, (long long)capacity * S, capacity, goff_incl, 0, nullptr, nullptr, nullptr, dL_dfeature, C,
                             dfeature_frame_stride, (hipStream_t)stream);
