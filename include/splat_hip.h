@@ -1003,6 +1003,36 @@ size_t splat_knn_brute_scratch_bytes(int B, int N, int S);
 int splat_knn_brute_batch(int B, int N, int S, int K, const float *points, int64_t points_batch_stride,
                           const int64_t *query_idx, float *dists, int32_t *idx, void *scratch, splat_stream_t stream);
 
+/* ---- seeding the dynamic Gaussians from 2-D tracks and depth (seed.hip): what the reference runs on the CPU before its
+ *      first step -- src/video3Dflow/utils.py:69-174,198-210, src/video3Dflow/video_3d_flow.py:48-94,126-137,164-248,
+ *      src/dynamic_gaussian_with_base_point_cloud.py:55-78.  No float atomics: all three run under
+ *      splat_set_deterministic(1) and give the same bits on every run. ---- */
+/* k x k median of P planes [H, W] with reflect padding of k / 2 (median_filter_2d(x, k, 1), same=True): out = the element
+ * of rank (k*k-1)/2 of every window, one of the input values bit for bit (NaN is not an input; -0 orders below +0).
+ * k odd, 3 .. 11; H > k / 2 and W > k / 2, else SPLAT_E_ARG.  P = 0: SPLAT_OK without a launch. */
+int splat_median_filter_2d(int P, int H, int W, int k, const float *x, float *out, splat_stream_t stream);
+/* get_tracks_3d_for_query_frame before its `valid` selection: tracks_2d [N,T,4] (x, y, occlusion logit, expected-distance
+ * logit), depths / masks [T,H,W], query_img [H,W,3].  Per (track, frame): tracks_3d [N,T,3] = ((x - W/2)/(W/2),
+ * (y - H/2)/(H/2), bilinear depth with border padding); in_mask [N,T] = (bilinear mask with zero padding == 1); visibles /
+ * invisibles [N,T] (0 / 1) and confidences [N,T] after the in-mask product; per track: counts [N,2] = (visible frames,
+ * frames of confidence > 0.5) and colors [N,3] sampled at the track's position in frame query_index.  The bilinear value is
+ * ((nw v00 + ne v01) + sw v10) + se v11 in float32 with every operation rounded once (torch's grid_sample with
+ * align_corners=True on the CPU).  grid_coords != 0: x, y are grid coordinates in [-1, 1] already (extend_track3d) and are
+ * copied to the point unchanged.  N = 0 or T * H * W = 0: SPLAT_OK without a launch. */
+int splat_lift_tracks(int N, int T, int H, int W, const float *tracks_2d, const float *depths, const float *masks,
+                      int query_index, const float *query_img, int grid_coords, float *tracks_3d, float *colors,
+                      uint8_t *visibles, uint8_t *invisibles, float *confidences, uint8_t *in_mask, int32_t *counts,
+                      splat_stream_t stream);
+/* Not-a-knot cubic spline per Gaussian and coordinate through the knot frames of its track (scipy.interpolate.CubicSpline
+ * of the reference's setup): tracks_3d [N,T,3]; knots_host [n_knots] float32 in increasing order and knot_frames_host
+ * [n_knots] (HOST arrays, frame index of every knot, < T); position [N,3] = the frame-0 point; pos_cubic_node [N,4,I,3]
+ * (I = n_knots - 1, highest power first) = the coefficients of y = track - frame-0 point.  2 knots: a line; 3 knots: the
+ * parabola through them.  Float64 solve, stored as float32.  Fewer than 2 or more than SPLAT_SPLINE_MAX_KNOTS knots,
+ * non-increasing knots, a knot frame outside the clip: SPLAT_E_ARG.  N = 0: SPLAT_OK without a launch. */
+#define SPLAT_SPLINE_MAX_KNOTS 64
+int splat_fit_cubic_nodes(int N, int T, int n_knots, const float *knots_host, const int32_t *knot_frames_host,
+                          const float *tracks_3d, float *position, float *pos_cubic_node, splat_stream_t stream);
+
 /* ---- measurement hooks (bench.py: live per-kernel timing with HIP events on the launch stream) ---- */
 void splat_profile_enable(int on);
 void splat_profile_reset(void);

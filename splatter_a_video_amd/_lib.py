@@ -63,6 +63,7 @@ SYMBOLS = [
     "splat_alpha_blending_points_forward_batch", "splat_alpha_blending_points_backward_batch", "splat_track_loss_grad_points",
     "splat_alpha_blending_points_backward_ordered", "splat_alpha_blending_points_backward_ordered_scratch_bytes",
     "splat_alpha_blending_points_backward_batch_ordered", "splat_alpha_blending_points_backward_batch_ordered_scratch_bytes",
+    "splat_median_filter_2d", "splat_lift_tracks", "splat_fit_cubic_nodes",
 ]
 
 
@@ -139,6 +140,9 @@ def lib() -> ctypes.CDLL:
         L.splat_alpha_blending_points_backward_batch_ordered_scratch_bytes.argtypes = [i, i, i, i, i64, i64]
         L.splat_alpha_blending_points_backward_batch_ordered.argtypes = (
             L.splat_alpha_blending_points_backward_batch.argtypes[:-1] + [p, p, ctypes.c_size_t, p])
+        L.splat_median_filter_2d.argtypes = [i, i, i, i, p, p, p]
+        L.splat_lift_tracks.argtypes = [i, i, i, i, p, p, p, i, p, i, p, p, p, p, p, p, p, p]
+        L.splat_fit_cubic_nodes.argtypes = [i, i, i, p, p, p, p, p, p]
         if L.splat_abi_version() != ABI_VERSION:
             raise SplatError("libsplat_hip.so ABI version mismatch; rebuild it")
         _lib = L
