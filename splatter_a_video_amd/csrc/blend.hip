@@ -581,9 +581,10 @@ blend_fwd_kernel(const BlendArgs B) {
     static_assert(BIAS ? CSB == 32 : true, "with a bias the list entries address the records (32-byte unit)");
     // Those rows (BC) take a survivor's operands from a lane of the DPP row instead of from LDS: the 16 lanes of a row are one 4x4
     // quarter (as in MF), a quarter's list is FETCHED 16 entries at a time -- lane l of the row holds entry j0 + l's 48-byte
-    // block -- and evaluation u of the chunk reads coefficient and channel operands from lane u of the row inside the consuming
-    // instruction (v_fmac_f32_dpp .. row_newbcast:u).  The reads that returned one block to all 16 lanes of a quarter (30 LDS-array
-    // cycles per two evaluations) become 14 cycles per 16 evaluations; the arithmetic per (pixel, survivor) and its order stay.
+    // block -- and evaluation u of the chunk reads the channel operands from lane u of the row inside the consuming instruction
+    // (v_fmac_f32_dpp .. row_newbcast:u), the coefficients as the A operand of a 4x4x1 MFMA.  The reads that
+    // returned one block to all 16 lanes of a quarter (30 LDS-array cycles per two evaluations) become 14 cycles per 16
+    // evaluations; the arithmetic per (pixel, survivor) and its order stay.
     constexpr bool BC = !MF && CS == 3;
     constexpr bool QM = MF || BC;                 // quarter-major lanes
     constexpr int FW = BC ? 16 : U;               // list entries fetched at a time: the lists are padded to a multiple of it
@@ -720,20 +721,8 @@ blend_fwd_kernel(const BlendArgs B) {
                     // evaluation u: the survivor in lane u of the row.  Same operations in the same order as the lane = pixel loop
                     // below -- fma(qx, x, q0) and fma(x, qx, q0) are the same bits.  EXEC is all ones here (uniform flow, branch-free
                     // compositing), so every lane a row_newbcast names is a live one.
-                    auto eval = [&](auto uc) {
+                    auto eval = [&](auto uc, const float pw) {
                         constexpr int u = decltype(uc)::value;
-                        float pw;
-                        // (s_nop 1: the two wait states between a VALU write of a register and a DPP read of it, should the
-                        // compiler have copied a coefficient just in front)
-                        asm("s_nop 1\n\t"
-                            "v_mov_b32_dpp %0, %1 row_newbcast:%c12 row_mask:0xf bank_mask:0xf\n\t"
-                            "v_fmac_f32_dpp %0, %2, %7 row_newbcast:%c12 row_mask:0xf bank_mask:0xf\n\t"
-                            "v_fmac_f32_dpp %0, %3, %8 row_newbcast:%c12 row_mask:0xf bank_mask:0xf\n\t"
-                            "v_fmac_f32_dpp %0, %4, %9 row_newbcast:%c12 row_mask:0xf bank_mask:0xf\n\t"
-                            "v_fmac_f32_dpp %0, %5, %10 row_newbcast:%c12 row_mask:0xf bank_mask:0xf\n\t"
-                            "v_fmac_f32_dpp %0, %6, %11 row_newbcast:%c12 row_mask:0xf bank_mask:0xf"
-                            : "=&v"(pw)
-                            : "v"(c0.x), "v"(c0.y), "v"(c0.z), "v"(c0.w), "v"(c1.x), "v"(c1.y), "v"(x), "v"(y), "v"(xx), "v"(xy), "v"(yy), "n"(u));
                         bool pw_ok;
                         const float a = fminf(0.99f, exp2_guard(pw, pw_ok));
                         const bool aok = pw_ok && !(a < (1.0f / 255.0f));
@@ -759,12 +748,31 @@ blend_fwd_kernel(const BlendArgs B) {
                             }
                         }
                     };
-#define FWD_EVAL2(u) eval(std::integral_constant<int, u>{}); eval(std::integral_constant<int, u + 1>{});
-#define FWD_NEXT2(u) if (rem <= u) break; FWD_EVAL2(u)
+                    // The exponents of group t = evaluations 4 t .. 4 t + 3 on the matrix pipe: v_mfma_f32_4x4x1_16b_f32 with cbsz:2 abid:t
+                    // makes the four 4-lane blocks of a DPP row all take A from block t of the row, so D[i] of a lane is (coefficient
+                    // fetched by lane 4 t + i of the row) x (the lane's own B) + C: six of them chained from C = 0 over the monomials
+                    // 1 x y xx xy yy are power_poly()'s fma chain of the lane's pixel for the four survivors, in the lane = pixel layout
+                    // (tools/probes/mfma_4x4x1_probe.hip, profiles/fwd_poly_mfma_probe.json: layout, and the chain bit for bit but for
+                    // fma(1, -0, +0) = +0 where the VALU chain starts from q0 = -0 -- a zero exponent of the other sign, exp2 = 1 alike).
+                    // The A operand comes from other lanes of the row as a row_newbcast operand does: EXEC is all ones (above).
+                    auto poly = [&](auto tc) {
+                        constexpr int t = decltype(tc)::value;
+                        f32x4 P = __builtin_amdgcn_mfma_f32_4x4x1f32(c0.x, 1.0f, f32x4{0.f, 0.f, 0.f, 0.f}, 2, t, 0);
+                        P = __builtin_amdgcn_mfma_f32_4x4x1f32(c0.y, x, P, 2, t, 0);
+                        P = __builtin_amdgcn_mfma_f32_4x4x1f32(c0.z, y, P, 2, t, 0);
+                        P = __builtin_amdgcn_mfma_f32_4x4x1f32(c0.w, xx, P, 2, t, 0);
+                        P = __builtin_amdgcn_mfma_f32_4x4x1f32(c1.x, xy, P, 2, t, 0);
+                        return __builtin_amdgcn_mfma_f32_4x4x1f32(c1.y, yy, P, 2, t, 0);
+                    };
+#define FWD_EVAL2(u) eval(std::integral_constant<int, u>{}, P[(u) & 3]); eval(std::integral_constant<int, u + 1>{}, P[((u) + 1) & 3]);
+                    // one group in flight: its chain, then its four evaluations (the next group's chain ahead of them, two groups'
+                    // chains interleaved or all four ahead of the chunk were no faster and cost registers:
+                    // profiles/fwd_poly_mfma_variants.json).  A group's MFMAs are issued only if the wave evaluates an entry of it.
+#define FWD_GROUP(t) { if (rem <= 4 * t) break; const f32x4 P = poly(std::integral_constant<int, t>{}); FWD_EVAL2(4 * t) if (rem <= 4 * t + 2) break; FWD_EVAL2(4 * t + 2) }
                     do {
-                        FWD_EVAL2(0) FWD_NEXT2(2) FWD_NEXT2(4) FWD_NEXT2(6) FWD_NEXT2(8) FWD_NEXT2(10) FWD_NEXT2(12) FWD_NEXT2(14)
+                        FWD_GROUP(0) FWD_GROUP(1) FWD_GROUP(2) FWD_GROUP(3)
                     } while (false);
-#undef FWD_NEXT2
+#undef FWD_GROUP
 #undef FWD_EVAL2
                     // evaluation u of the chunk -> bit 15 - u, however early the wave left it (a chunk cut short is the list's last)
                     acc <<= 16 - imin_(rem, 16);
