@@ -550,6 +550,38 @@ int splat_alpha_blending_backward_batch_set(int F, int P, int C, int c0, int cn,
                                             const float *final_T, const int32_t *ncontrib, const float *dL_dout,
                                             int want_abs, const int32_t *slot_sorted, float *pair_records,
                                             float *pack_scratch, float *dbg_T_front, splat_stream_t stream);
+/* WIDE detached feature sets beside the composited row (render_attributes wider than a row holds: dptr_ortho_enhanced.py:361-376
+ * blends them with opacity.detach() in chunks of 32 channels, alpha_blending.cu:287-394, 440-577).  The set [P, C] (any C >= 1)
+ * is composited over the batch's sorted lists chunk by chunk, outside the row:
+ * splat_alpha_blending_forward_batch_set: the forward of channels [c0, c0 + cn) (cn <= 32) of `feature` [P, C] into channels
+ *   [c0, c0 + cn) of `out` [F, C, H, W]; final_T / ncontrib [F, H, W] and pack_scratch (F * P * splat_blend_pack_floats(cn)
+ *   floats) belong to the chunk (NOT the row's: the row's backward reads its own); cull_flags NULL or [F, capacity], the chunk's
+ *   own as well (forwards of different widths write different words).
+ * splat_alpha_blending_backward_batch_set_packed: the chunk's tile backward from what that forward left (pack, cull_flags or NULL:
+ *   splat_alpha_blending_backward_batch on the window of dL_dout [F, C, H, W]; no packing launch, the quarter-list kernels with the
+ *   cull words) writes the chunk's TAIL records (stride splat_blend_pair_stride(cn, 0, 0), layout [ux uy ca cb cc o |
+ *   dL_dfeature[0 .. cn) | pad]; splat_alpha_blending_backward_batch_set above writes the same records from the inputs), and
+ * splat_frames_wide_fold, ONE streaming launch, (a) adds ux uy ca cb cc of every tail record at slot s < goff_incl[f, P - 1] of
+ *   frame f into the row's record at the same slot (row_records: stride row_stride floats, a multiple of 4 and >= 8, any layout
+ *   that begins ux uy ca cb cc o; `o` is left out: the opacity is detached) and (b) ADDS, per Gaussian, the sum of the feature
+ *   part of its tail records -- slots [goff_incl[f, i-1], goff_incl[f, i]) in ascending order, frames in ascending order -- into
+ *   d_feature[i * d_feature_stride + c0 + k], k < cn (d_feature NULL: (a) only).  No float atomics: a slot has one owner, every sum
+ *   has a fixed order.  Slots at or beyond min(goff_incl[f, P - 1], capacity) are neither read nor written.  The Gaussian-side
+ *   walk (splat_frames_gauss_backward_*_sets / _sources) then runs once on row_records, unchanged. */
+int splat_alpha_blending_forward_batch_set(int F, int P, int C, int c0, int cn, const float *uv, const float *conic,
+                                           const float *opacity, int64_t opacity_frame_stride, const float *feature,
+                                           int64_t feature_frame_stride, const int32_t *idx_sorted,
+                                           const int32_t *tile_range, int64_t capacity, float bg, int W, int H, float *out,
+                                           float *final_T, int32_t *ncontrib, float *pack_scratch, uint32_t *cull_flags,
+                                           splat_stream_t stream);
+int splat_alpha_blending_backward_batch_set_packed(int F, int P, int C, int c0, int cn, const int32_t *idx_sorted,
+                                                   const int32_t *tile_range, int64_t capacity, float bg, int W, int H,
+                                                   const float *final_T, const int32_t *ncontrib, const float *dL_dout,
+                                                   const int32_t *slot_sorted, float *pair_records, const float *pack,
+                                                   const uint32_t *cull_flags, float *dbg_T_front, splat_stream_t stream);
+int splat_frames_wide_fold(int F, int P, int cn, int64_t capacity, const int32_t *goff_incl, const float *tail_records,
+                           float *row_records, int row_stride, float *d_feature, int64_t d_feature_stride, int c0,
+                           splat_stream_t stream);
 int splat_frames_gauss_backward_static_set(int F, int P, int cn, int W, int H, int64_t capacity, int want_abs,
                                            const float *pair_records, const int32_t *goff_incl, const int32_t *radius,
                                            const float *xyz, const float *scales, const float *uquats, const float *extr,

@@ -4396,6 +4396,74 @@ extern "C" int splat_alpha_blending_backward_batch_set(int F, int P, int C, int 
     return bwd_chunk(A, T, false, true, (hipStream_t)stream);
 }
 
+// The forward twin of splat_alpha_blending_backward_batch_set: channels [c0, c0 + cn) of a feature set [P, C] of ANY width into
+// channels [c0, c0 + cn) of out [F, C, H, W] -- one chunk of the reference's 32-channel chunking (src/alpha_blending.cu:287-394)
+// over a frame batch's sorted lists.  The chunk packs its own records and leaves its own final_T / ncontrib (the caller keeps
+// them for the chunk's backward); the kernels are the frame batch's blend_fwd instantiations.
+extern "C" int splat_alpha_blending_forward_batch_set(int F, int P, int C, int c0, int cn, const float *uv, const float *conic,
+                                                      const float *opacity, int64_t opacity_frame_stride, const float *feature,
+                                                      int64_t feature_frame_stride, const int32_t *idx_sorted,
+                                                      const int32_t *tile_range, int64_t capacity, float bg, int W, int H,
+                                                      float *out, float *final_T, int32_t *ncontrib, float *pack_scratch,
+                                                      uint32_t *cull_flags, splat_stream_t stream) {
+    SPLAT_CHECK_ARG(F >= 1 && P >= 1 && C >= 1 && W > 0 && H > 0 && capacity >= 1 && opacity_frame_stride >= 0 &&
+                        feature_frame_stride >= 0,
+                    "bad sizes");
+    SPLAT_CHECK_ARG(c0 >= 0 && cn >= 1 && cn <= 32 && (long long)c0 + cn <= C, "the chunk must be 1..32 channels inside the set");
+    SPLAT_CHECK_ARG(uv && conic && opacity && feature && idx_sorted && tile_range && out && final_T && ncontrib && pack_scratch,
+                    "null pointer");
+    BlendArgs A;
+    memset(&A, 0, sizeof(A));
+    A.P = P; A.C = C;
+    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
+    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
+    A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
+    A.out = out; A.final_T = final_T; A.ncontrib = ncontrib;
+    A.pack = pack_scratch;
+    A.cull_flags = cull_flags;
+    const int T = A.gx * ((H + TILE - 1) / TILE);
+    SPLAT_CHECK_ARG((long long)F * T < (1ll << 31), "too many tiles");
+    A.F = F; A.T = T; A.cap = capacity;
+    A.pack_fs = (long long)P * (long long)splat_blend_pack_floats(cn);
+    A.opacity_fs = opacity_frame_stride; A.feature_fs = feature_frame_stride;
+    A.c0 = c0; A.cn = cn;
+    return fwd_chunk(A, T, false, false, (hipStream_t)stream);
+}
+
+// ... and the chunk's tile backward from what that forward left: its packed records (`pack`, untouched since) and, optionally,
+// its cull words -- splat_alpha_blending_backward_batch on the channel window [c0, c0 + cn) of dL_dout [F, C, H, W].  With the
+// cull words the quarter-list kernels run (narrow chunks: the forward's applied bits; chunks of 16 channels and more: the wide
+// quarter kernel), as for a row of that width; no packing launch.  Tail records: stride splat_blend_pair_stride(cn, 0, 0).
+extern "C" int splat_alpha_blending_backward_batch_set_packed(int F, int P, int C, int c0, int cn, const int32_t *idx_sorted,
+                                                              const int32_t *tile_range, int64_t capacity, float bg, int W, int H,
+                                                              const float *final_T, const int32_t *ncontrib,
+                                                              const float *dL_dout, const int32_t *slot_sorted,
+                                                              float *pair_records, const float *pack,
+                                                              const uint32_t *cull_flags, float *dbg_T_front,
+                                                              splat_stream_t stream) {
+    SPLAT_CHECK_ARG(F >= 1 && P >= 1 && C >= 1 && W > 0 && H > 0 && capacity >= 1, "bad sizes");
+    SPLAT_CHECK_ARG(c0 >= 0 && cn >= 1 && cn <= 32 && (long long)c0 + cn <= C, "the chunk must be 1..32 channels inside the set");
+    SPLAT_CHECK_ARG(idx_sorted && tile_range && final_T && ncontrib && dL_dout && slot_sorted && pair_records && pack,
+                    "null pointer");
+    BlendArgs A;
+    memset(&A, 0, sizeof(A));
+    A.P = P; A.C = C;
+    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
+    A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
+    A.final_T = const_cast<float *>(final_T); A.ncontrib = const_cast<int *>(ncontrib);
+    A.dL_dout = dL_dout;
+    A.slot_sorted = slot_sorted; A.pair_buf = pair_records;
+    A.pack = const_cast<float *>(pack); A.pack_valid = 1;
+    A.dbg_T_front = dbg_T_front;
+    A.cull_flags = const_cast<uint32_t *>(cull_flags);
+    const int T = A.gx * ((H + TILE - 1) / TILE);
+    SPLAT_CHECK_ARG((long long)F * T < (1ll << 31), "too many tiles");
+    A.F = F; A.T = T; A.cap = capacity; A.tile_only = 1;
+    A.pack_fs = (long long)P * (long long)splat_blend_pack_floats(cn);
+    A.c0 = c0; A.cn = cn;
+    return bwd_chunk(A, T, false, true, (hipStream_t)stream);
+}
+
 // Backward tile pass of up to three feature sets of one geometry in ONE launch (blend_bwd_sets_kernel): set 0 = the tap set
 // (<= 4 channels: full gradients + the densification taps), set 1 = a second set blended with the live opacity (<= 4
 // channels), set 2 = the set blended with opacity.detach() (<= 20 channels); set_cn[g] = 0: no such set.  The sets must tile

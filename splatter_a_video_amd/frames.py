@@ -414,7 +414,8 @@ class FrameBatch:
     def render_dynamic_sets(self, clock, times, extr: Tensor, sets, *, position: Tensor, pos_cubic_node: Tensor,
                             rotation: Tensor, rot_poly_feat: Tensor, rot_fourier_feat: Tensor, opacity: Tensor, scaling: Tensor,
                             cubic_layout: int = 1, K: int = 0, nearest: float = 0.01, extent: float = 1.3,
-                            grad_sink: Optional[Dict[str, Tensor]] = None, points: Optional[dict] = None):
+                            grad_sink: Optional[Dict[str, Tensor]] = None, points: Optional[dict] = None,
+                            wide: Optional[dict] = None):
         """The reference's real training frame, for all frames of the batch: its dynamic Gaussians (``render_dynamic``)
         through the three blends of ``render_iter`` (``render_sets``: same ``sets`` list, same return value).  The sets must
         fit the one-pass backward (one set per routing group, <= 4 / 4 / 20 channels).
@@ -436,7 +437,18 @@ class FrameBatch:
         records between the tile backward and the Gaussian-side backward (float atomics: it raises in deterministic mode;
         ``ordered=True`` in the dict takes splat_alpha_blending_points_backward_batch_ordered instead: no float atomic, a fixed
         order of every sum, bit-reproducible and allowed in deterministic mode); the feature's gradient is ADDED to ``grad_sink["points"]`` (the feature's shape) when given, else returned through autograd.
-        Not differentiable w.r.t. the points.  A ``None`` gradient of the sparse output launches nothing."""
+        Not differentiable w.r.t. the points.  A ``None`` gradient of the sparse output launches nothing.
+
+        ``wide``: one more DENSE feature set composited over the same sorted lists, outside the row (its channels do not count
+        towards ``C``) -- render attributes wider than a one-pass plan holds, e.g. a 64-dimensional feature field
+        (dptr_ortho_enhanced.py:361-376: the reference blends them with opacity.detach() in chunks of 32 channels): a dict
+        ``feature`` ([P, c] float32 shared by the frames, any c >= 1), ``bg`` (default 0.0) and ``detach_opacity``, which must be
+        True.  The call then returns one more tensor [F, c, H, W] behind the row's images and in front of the sparse output and
+        ``gs_idx``, an output of the same autograd node.  Differentiable w.r.t. ``feature`` and, through uv / conic, the geometry
+        parameters; not w.r.t. the opacity, and it feeds no taps.  Per 32-channel chunk its backward runs the tile kernels of the
+        window and folds the chunk's records into the row's pair records before the Gaussian-side backward (no float atomics); the
+        feature's gradient is ADDED to ``grad_sink["wide"]`` ([P, c]) when given, else returned through autograd.  A ``None``
+        gradient of the wide output launches nothing."""
         tab = self.frame_table(clock, times)
         meta, parts, feats = _parse_sets(sets, self.F, self.P)
         widths = [1 if m[0] == "depth" else m[0] for m in meta]
@@ -447,10 +459,11 @@ class FrameBatch:
             raise ValueError("render_dynamic_sets needs sets that fit the one-pass backward: one set per routing group "
                              "(taps / live opacity / detached opacity) of at most 4 / 4 / 20 channels")
         fsink = {k: v for k, v in (grad_sink or {}).items() if k.startswith("feature:")}
-        psink = {k: v for k, v in (grad_sink or {}).items() if not k.startswith("feature:") and k != "points"}
+        psink = {k: v for k, v in (grad_sink or {}).items() if not k.startswith("feature:") and k not in ("points", "wide")}
         pts = _parse_points(points, (grad_sink or {}).get("points"), self.F, self.P)
         if pts is None and "points" in (grad_sink or {}):
             raise ValueError('grad_sink["points"] belongs to the sparse set: pass points=...')
+        wd = _parse_wide(wide, (grad_sink or {}).get("wide"), self.P)
         sink = check_sink(psink, {"position": position, "pos_cubic_node": pos_cubic_node, "rotation": rotation,
                                   "opacity": opacity, "scaling": scaling})
         for k, buf in fsink.items():
@@ -460,20 +473,24 @@ class FrameBatch:
                 raise ValueError(f"grad_sink[{k!r}] must be a float32 GPU buffer of the feature tensor's shape with dense rows")
         return _RenderDynamicSets.apply(position, pos_cubic_node, rotation, opacity, scaling, rot_poly_feat, rot_fourier_feat, extr,
                                         tab, self, int(clock.interval_num), int(cubic_layout), meta, int(K), float(nearest),
-                                        float(extent), sink, parts, fsink or None, pts,
-                                        *(list(feats) + ([pts["feature"]] if pts is not None else [])))
+                                        float(extent), sink, parts, fsink or None, pts, wd,
+                                        *(list(feats) + ([pts["feature"]] if pts is not None else [])
+                                          + ([wide["feature"]] if wd is not None else [])))
 
     # ------------------------------------------------------------------ several feature sets of one geometry (row a1)
     def render_sets(self, xyz: Tensor, scales: Tensor, uquats: Tensor, opacity: Tensor, sets, offsets: Optional[Tensor],
                     extr: Tensor, K: int = 0, nearest: float = 0.01, extent: float = 1.3,
-                    grad_sink: Optional[Dict[str, Tensor]] = None, intr: Optional[Tensor] = None):
+                    grad_sink: Optional[Dict[str, Tensor]] = None, intr: Optional[Tensor] = None, wide: Optional[dict] = None):
         """The reference renderer's blends of ONE geometry over all frames of the batch (render_iter,
         src/pointrix/renderer/dptr_ortho_enhanced.py:331-375: rgb through alpha_blending_enhanced with the taps; depth with
         bg = 1; the extra attributes with opacity.detach()).  ``sets``: a list of dicts ``feature`` ([P,c] tensor shared by
         the frames, or the string "depth" for the per-frame depth of the projection), ``bg``, ``detach_opacity``, ``taps``.
         The widths must add up to the batch's ``C``.  One forward pass composites the concatenated row; per set one
         backward pass of the tile kernels and one Gaussian-side reduction.  Returns ``(images per set ..., gs_idx)`` with
-        images [F,c,H,W] and gs_idx [F,H,W,K] (None for K = 0).  Cameras (``extr`` per frame, ``intr``) as in ``render``."""
+        images [F,c,H,W] and gs_idx [F,H,W,K] (None for K = 0).  Cameras (``extr`` per frame, ``intr``) as in ``render``.
+        ``wide``: one more detached feature set of any width outside the row, as in ``render_dynamic_sets`` (its image [F,c,H,W]
+        comes behind the sets' images, in front of ``gs_idx``; ``grad_sink["wide"]``); the sets must then fit the one-pass
+        backward."""
         def one(f):
             # a list of shared tensors = their concatenation along the channels, as the reference's renderer concatenates its
             # attributes (RenderFeatures.combine); per-frame tensors belong to the dynamic renderer (render_dynamic_sets)
@@ -491,9 +508,16 @@ class FrameBatch:
             raise ValueError(f"the sets hold {width} channels, the batch was built for C = {self.C}")
         if sum(1 for m in meta if m[3]) > 1:
             raise ValueError("at most one set feeds the densification taps")
+        wd = _parse_wide(wide, (grad_sink or {}).get("wide"), self.P)
+        if wd is not None:
+            grad_sink = {k: v for k, v in (grad_sink or {}).items() if k != "wide"} or None
+            if not OPTIONS["sets_one_pass"] or _one_pass_plan(meta, [1 if m[0] == "depth" else m[0] for m in meta], self.C) is None:
+                raise ValueError("render_sets(wide=...) needs sets that fit the one-pass backward: one set per routing group "
+                                 "(taps / live opacity / detached opacity) of at most 4 / 4 / 20 channels")
+            feats = feats + [wide["feature"]]
         sink = check_sink(grad_sink, {"xyz": xyz, "scales": scales, "uquats": uquats, "opacity": opacity})
         res = _RenderSets.apply(xyz, scales, uquats, opacity, offsets, extr, self, meta, int(K), float(nearest), float(extent),
-                                sink, intr, *feats)
+                                sink, intr, wd, *feats)
         return res
 
 
@@ -564,13 +588,15 @@ class _RenderDynamic(torch.autograd.Function):
 
 
 class _RenderDynamicSets(torch.autograd.Function):
-    N_FIXED = 20      # arguments in front of the feature tensors
+    N_FIXED = 21      # arguments in front of the feature tensors
 
     @staticmethod
     def forward(ctx, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr, tab, fb, I, layout, meta, K,
-                nearest, extent, sink, parts, fsink, pts, *feats):
+                nearest, extent, sink, parts, fsink, pts, wd, *feats):
         P, F = fb.P, fb.F
-        pfeat = None
+        pfeat = wfeat = None
+        if wd is not None:        # the wide set's feature rides last
+            feats, wfeat = feats[:-1], L.need(feats[-1], "wide feature")
         if pts is not None:       # the sparse set's feature rides behind the sets' tensors
             feats, pfeat = feats[:-1], feats[-1]
         position = _points(position, "position", 3)
@@ -613,6 +639,11 @@ class _RenderDynamicSets(torch.autograd.Function):
             sparse = (_points_forward(fb, pts, pfeat, opa_t),)
             ctx.pts = pts
             feats = tuple(feats) + (pfeat,)
+        ctx.wd = wd
+        wide_out = ()
+        if wd is not None:
+            wide_out = (_wide_forward(fb, wd, wfeat, opa_t, 0),)
+            feats = tuple(feats) + (wfeat,)
         ctx.save_for_backward(position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr_c, tab, *feats)
         ctx.set_materialize_grads(False)
         imgs, c0 = [], 0
@@ -622,7 +653,7 @@ class _RenderDynamicSets(torch.autograd.Function):
             c0 += w
         if gs_idx is not None:
             ctx.mark_non_differentiable(gs_idx)
-        return tuple(imgs) + sparse + (gs_idx,)
+        return tuple(imgs) + wide_out + sparse + (gs_idx,)
 
     @staticmethod
     def backward(ctx, *grads):
@@ -637,10 +668,25 @@ class _RenderDynamicSets(torch.autograd.Function):
         dev = fb.dev
         widths = ctx.blend["widths"]
         pts, pfeat, g_pts, d_pts = ctx.pts, None, None, ()
+        wd, wfeat, g_wide = ctx.wd, None, None
+        if wd is not None:
+            feats, wfeat = feats[:-1], feats[-1]
+            g_wide = grads[len(meta)]
         if pts is not None:
             feats, pfeat = feats[:-1], feats[-1]
-            g_pts = grads[len(meta)]
+            g_pts = grads[len(meta) + (1 if wd is not None else 0)]
             d_pts = (None,)
+
+        def wide_backward(rec):
+            # the wide set's chunks: their geometry terms into the pair records, their feature sums into the feature's gradient
+            if g_wide is None:
+                return (None,) if wd is not None else ()
+            want = ctx.needs_input_grad[NF + len(feats) + (1 if pts is not None else 0)] or wd["sink"] is not None
+            buf, ret = wd["sink"], None
+            if want and buf is None:
+                buf = ret = torch.zeros(wfeat.shape, dtype=torch.float32, device=dev)
+            _wide_backward(fb, wd, wfeat, ctx.opa_t, 0, g_wide, rec, buf if want else None)
+            return (ret,)
 
         def sparse_backward(rec):
             # the sparse set's gradient: into the pair records the tile backward has just written, before the Gaussian-side walk
@@ -662,6 +708,7 @@ class _RenderDynamicSets(torch.autograd.Function):
             # the row by SOURCES: a shared tensor's gradient is the sum over the frames, a per-frame tensor gets every frame's own
             rec = _blend_sets_backward_one_pass(fb, meta, ctx.blend, grads[:len(meta)], ctx.opa_t, 0, want_abs)
             d_pts = sparse_backward(rec)
+            d_wide = wide_backward(rec)
             table = (L.FeatureSource * L.MAX_SOURCES)()
             dfe, n, fi, c0 = [], 0, 0, 0
             for si, ((w, _, _, _), pp) in enumerate(zip(meta, ctx.parts)):
@@ -692,7 +739,7 @@ class _RenderDynamicSets(torch.autograd.Function):
                 table, L.ci(depth_ch), L.ptr(fb.tap if has_tap else None),
                 L.ptr(fb.abs_tap if (has_tap and want_abs) else None), L.ptr(fb.radii_max if has_tap else None), st))
             ret = tuple(None if k in sink else bufs[k] for k in like)
-            return ret + (None,) * (NF - 5) + tuple(dfe) + d_pts
+            return ret + (None,) * (NF - 5) + tuple(dfe) + d_pts + d_wide
         group_of = _set_groups(meta)
         fi, dfe, dfs, strides = 0, [], [None, None, None], [0, 0, 0]
         for si, (w, _, _, _) in enumerate(meta):
@@ -705,6 +752,7 @@ class _RenderDynamicSets(torch.autograd.Function):
             fi += 1
         rec = _blend_sets_backward_one_pass(fb, meta, ctx.blend, grads[:len(meta)], ctx.opa_t, 0, want_abs)
         d_pts = sparse_backward(rec)
+        d_wide = wide_backward(rec)
         i3 = ctypes.c_int32 * 3
         p3 = (ctypes.c_void_p * 3)(*[0 if d is None else d.data_ptr() for d in dfs])
         L.check(lib.splat_frames_gauss_backward_dynamic_sets(
@@ -715,7 +763,7 @@ class _RenderDynamicSets(torch.autograd.Function):
             L.ci(depth_ch), L.ptr(fb.tap if has_tap else None), L.ptr(fb.abs_tap if (has_tap and want_abs) else None),
             L.ptr(fb.radii_max if has_tap else None), st))
         ret = tuple(None if k in sink else bufs[k] for k in like)
-        return ret + (None,) * (NF - 5) + tuple(dfe) + d_pts
+        return ret + (None,) * (NF - 5) + tuple(dfe) + d_pts + d_wide
 
 
 def _parse_points(points, sink, F, P):
@@ -789,6 +837,81 @@ def _points_backward(fb, pts, pfeat, opacity, g, rec, d_feature):
         L.ptr(pts["points"]), L.ptr(pts["corner_T"]), L.ptr(pts["corner_n"]), L.ptr(g), L.ptr(fb.slot_sorted), L.ptr(rec),
         L.ci(int(L.lib().splat_blend_sets_pair_stride(fb.C))), L.ci(1 if pts["detach_opacity"] else 0), L.ptr(d_feature),
         ctypes.c_int64(dfs), L.stream()))
+
+
+def _parse_wide(wide, sink, P):
+    """the wide detached set of ``render_sets`` / ``render_dynamic_sets``: None, or its checked description (feature [P, c], bg,
+    the feature's gradient sink or None); nothing here reads device memory"""
+    if wide is None:
+        if sink is not None:
+            raise ValueError('grad_sink["wide"] belongs to the wide set: pass wide=...')
+        return None
+    if not isinstance(wide, dict):
+        raise ValueError("wide: a dict feature / bg / detach_opacity")
+    unknown = set(wide) - {"feature", "bg", "detach_opacity"}
+    if unknown:
+        raise ValueError(f"wide: unknown keys {sorted(unknown)}")
+    if wide.get("detach_opacity") is not True:
+        raise ValueError("wide: detach_opacity must be True (the reference blends its render attributes with opacity.detach(); "
+                         "a set blended with the live opacity belongs in the row)")
+    f = wide.get("feature")
+    if not isinstance(f, Tensor) or f.dim() != 2 or f.shape[0] != P or f.shape[1] < 1 or f.dtype != torch.float32:
+        raise ValueError(f"wide['feature'] must be a float32 tensor [P={P}, c] with c >= 1, shared by the frames")
+    if not f.is_cuda:
+        raise ValueError("wide['feature'] must be a CUDA (ROCm) tensor (there is no CPU path)")
+    if sink is not None and (not isinstance(sink, Tensor) or tuple(sink.shape) != tuple(f.shape) or sink.dtype != torch.float32
+                             or not sink.is_cuda or not sink.is_contiguous()):
+        raise ValueError('grad_sink["wide"] must be a contiguous float32 GPU buffer of the wide feature\'s shape')
+    return dict(bg=float(wide.get("bg", 0.0)), sink=sink)
+
+
+def _wide_forward(fb, wd, wfeat, opacity, op_fs):
+    """the wide set over the batch's sorted lists, 32 channels at a time (splat_alpha_blending_forward_batch_set): [F, c, H, W].
+    Every chunk leaves its own final_T / ncontrib (in ``wd``), packed records and cull words (pooled on the batch) for its
+    backward: the row's fb.pack / final_T / ncontrib / cull_flags are not touched (the row's backward reads them), and a chunk's
+    cull words are those of ITS forward kernel (a narrow chunk's hold the applied pairs, a wide one's the geometric cull's)."""
+    lib, st = L.lib(), L.stream()
+    F, P, W, H, cap = fb.F, fb.P, fb.W, fb.H, fb.capacity
+    c = int(wfeat.shape[1])
+    chunks = [(c0, min(32, c - c0)) for c0 in range(0, c, 32)]
+    out = torch.empty(F, c, H, W, dtype=torch.float32, device=fb.dev)
+    wd["chunks"] = chunks
+    wd["final_T"] = torch.empty(len(chunks), F, H, W, dtype=torch.float32, device=fb.dev)
+    wd["ncontrib"] = torch.empty(len(chunks), F, H, W, dtype=torch.int32, device=fb.dev)
+    for k, (c0, cn) in enumerate(chunks):
+        pack = fb._set_buffer(("wide", "pack", k), F * P * int(lib.splat_blend_pack_floats(cn)))
+        cull = fb._set_buffer(("wide", "cull", k), F * cap)          # (raw 32-bit words)
+        L.check(lib.splat_alpha_blending_forward_batch_set(
+            L.ci(F), L.ci(P), L.ci(c), L.ci(c0), L.ci(cn), L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), ctypes.c_int64(op_fs),
+            L.ptr(wfeat), ctypes.c_int64(0), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), ctypes.c_int64(cap), L.cf(wd["bg"]),
+            L.ci(W), L.ci(H), L.ptr(out), L.ptr(wd["final_T"][k]), L.ptr(wd["ncontrib"][k]), L.ptr(pack), L.ptr(cull), st))
+    return out
+
+
+def _wide_backward(fb, wd, wfeat, opacity, op_fs, g, rec, d_feature):
+    """per chunk of the wide set: the tile backward of its channel window from the records and cull words its forward left
+    (splat_alpha_blending_backward_batch_set_packed) into ONE tail-record buffer (reused by the chunks), then
+    splat_frames_wide_fold -- the tail records' ux uy ca cb cc into the SETS pair records ``rec`` the row's tile backward has written
+    (not o: the opacity is detached), their feature part summed per Gaussian into ``d_feature`` [P, c] (None: not wanted)"""
+    lib, st = L.lib(), L.stream()
+    F, P, W, H, cap = fb.F, fb.P, fb.W, fb.H, fb.capacity
+    c = int(wfeat.shape[1])
+    g = L.need(g, "gradient of the wide output")
+    if tuple(g.shape) != (F, c, H, W):
+        raise ValueError(f"the gradient of the wide output must be [{F}, {c}, {H}, {W}]")
+    from .gs.raster_ops import _debug_T_front
+    tail = fb._set_buffer(("wide", "rec"), F * cap * int(lib.splat_blend_pair_stride(min(c, 32), 0, 0)))
+    row_stride = int(lib.splat_blend_sets_pair_stride(fb.C))
+    for k, (c0, cn) in enumerate(wd["chunks"]):
+        pack = fb._set_buffer(("wide", "pack", k), F * P * int(lib.splat_blend_pack_floats(cn)))
+        cull = fb._set_buffer(("wide", "cull", k), F * cap)
+        L.check(lib.splat_alpha_blending_backward_batch_set_packed(
+            L.ci(F), L.ci(P), L.ci(c), L.ci(c0), L.ci(cn), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), ctypes.c_int64(cap),
+            L.cf(wd["bg"]), L.ci(W), L.ci(H), L.ptr(wd["final_T"][k]), L.ptr(wd["ncontrib"][k]), L.ptr(g), L.ptr(fb.slot_sorted),
+            L.ptr(tail), L.ptr(pack), L.ptr(cull), L.ptr(_debug_T_front(F * H, W, fb.dev)), st))
+        L.check(lib.splat_frames_wide_fold(
+            L.ci(F), L.ci(P), L.ci(cn), ctypes.c_int64(cap), L.ptr(fb.goff), L.ptr(tail), L.ptr(rec), L.ci(row_stride),
+            L.ptr(d_feature), ctypes.c_int64(c), L.ci(c0), st))
 
 
 def _parse_sets(sets, F, P):
@@ -1044,7 +1167,10 @@ def _one_pass_plan(meta, widths, C):
 
 class _RenderSets(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, xyz, scales, uquats, opacity, offsets, extr, fb, meta, K, nearest, extent, sink, intr, *feats):
+    def forward(ctx, xyz, scales, uquats, opacity, offsets, extr, fb, meta, K, nearest, extent, sink, intr, wd, *feats):
+        wfeat = None
+        if wd is not None:        # the wide set's feature rides last
+            feats, wfeat = feats[:-1], L.need(feats[-1], "wide feature")
         xyz = _points(xyz, "xyz", 3)
         scales = _points(scales, "scales", 3)
         uquats = _points(uquats, "uquats", 4)
@@ -1067,9 +1193,16 @@ class _RenderSets(torch.autograd.Function):
         op_fs = 0
         C = fb.C
         out, gs_idx, ctx.blend = _blend_sets_forward(fb, meta, feats, opacity, op_fs, K)
+        if wd is not None and ctx.blend["plan"] is None:
+            raise ValueError("render_sets(wide=...) needs sets that fit the one-pass backward")
         ctx.fb, ctx.meta, ctx.sink, ctx.K = fb, meta, sink, K
         ctx.cam, ctx.off = cam, off
         ctx.cam_versions = _versions(cam.extr, cam.intr, off)
+        ctx.wd = wd
+        wide_out = ()
+        if wd is not None:
+            wide_out = (_wide_forward(fb, wd, wfeat, opacity, op_fs),)
+            feats = tuple(feats) + (wfeat,)
         ctx.save_for_backward(xyz, scales, uquats, opacity, *feats)
         ctx.set_materialize_grads(False)
         imgs, c0 = [], 0
@@ -1079,8 +1212,8 @@ class _RenderSets(torch.autograd.Function):
             c0 += w
         if gs_idx is not None:
             ctx.mark_non_differentiable(gs_idx)
-            return tuple(imgs) + (gs_idx,)
-        return tuple(imgs) + (None,)
+            return tuple(imgs) + wide_out + (gs_idx,)
+        return tuple(imgs) + wide_out + (None,)
 
     @staticmethod
     def backward(ctx, *grads):
@@ -1088,6 +1221,10 @@ class _RenderSets(torch.autograd.Function):
         fb._check_generation(ctx.gen)
         xyz, scales, uquats, opacity = ctx.saved_tensors[:4]
         feats = ctx.saved_tensors[4:]
+        wd, wfeat, g_wide, d_wide = ctx.wd, None, None, ()
+        if wd is not None:
+            feats, wfeat = feats[:-1], feats[-1]
+            g_wide, d_wide = grads[len(ctx.meta)], (None,)
         _check_versions(ctx.cam_versions, "a camera / offset tensor")
         camc = ctx.cam.struct(ctx.off)
         meta, sink = ctx.meta, (ctx.sink or {})
@@ -1111,12 +1248,20 @@ class _RenderSets(torch.autograd.Function):
             for si, (w, _, _, _) in enumerate(meta):
                 if w == "depth":
                     continue
-                need = grads[si] is not None and ctx.needs_input_grad[13 + fi]
+                need = grads[si] is not None and ctx.needs_input_grad[14 + fi]
                 dfeat = torch.zeros_like(feats[fi]) if need else None
                 dfe.append(dfeat)
                 dfs[group_of[si]], strides[group_of[si]] = dfeat, int(feats[fi].shape[1])
                 fi += 1
             rec = _blend_sets_backward_one_pass(fb, meta, ctx.blend, grads[:len(meta)], opacity, op_fs, want_abs)
+            if g_wide is not None:
+                # the wide set's chunks: their geometry terms into the pair records, their feature sums into the feature's gradient
+                want = ctx.needs_input_grad[14 + len(feats)] or wd["sink"] is not None
+                buf, wret = wd["sink"], None
+                if want and buf is None:
+                    buf = wret = torch.zeros(wfeat.shape, dtype=torch.float32, device=dev)
+                _wide_backward(fb, wd, wfeat, opacity, op_fs, g_wide, rec, buf if want else None)
+                d_wide = (wret,)
             i3 = ctypes.c_int32 * 3
             p3 = (ctypes.c_void_p * 3)(*[0 if d is None else d.data_ptr() for d in dfs])
             has_tap = tap_set is not None
@@ -1127,7 +1272,7 @@ class _RenderSets(torch.autograd.Function):
                 L.ptr(fb.tap if has_tap else None), L.ptr(fb.abs_tap if (has_tap and want_abs) else None),
                 L.ptr(fb.radii_max if has_tap else None), st))
             ret = tuple(None if k in sink else bufs[k] for k in ("xyz", "scales", "uquats", "opacity"))
-            return ret + (None,) * 9 + tuple(dfe)
+            return ret + (None,) * 10 + tuple(dfe) + d_wide
         row = ctx.blend["row"]
         dL = torch.cat([(g if g is not None else torch.zeros(F, w, H, W, dtype=torch.float32, device=dev))
                         for g, w in zip(grads[:len(meta)], widths)], dim=1).contiguous()
@@ -1137,7 +1282,7 @@ class _RenderSets(torch.autograd.Function):
             is_depth = w == "depth"
             dfeat = None
             if not is_depth:
-                dfeat = torch.zeros_like(feats[fi]) if g is not None and ctx.needs_input_grad[13 + fi] else None
+                dfeat = torch.zeros_like(feats[fi]) if g is not None and ctx.needs_input_grad[14 + fi] else None
                 dfe.append(dfeat)
                 fi += 1
             if g is not None:
@@ -1158,7 +1303,7 @@ class _RenderSets(torch.autograd.Function):
                     L.ptr(fb.abs_tap if (taps and want_abs) else None), L.ptr(fb.radii_max if taps else None), st))
             c0 += cn
         ret = tuple(None if k in sink else bufs[k] for k in ("xyz", "scales", "uquats", "opacity"))
-        return ret + (None,) * 9 + tuple(dfe)
+        return ret + (None,) * 10 + tuple(dfe) + d_wide
 
 
 class _RenderFrames(torch.autograd.Function):

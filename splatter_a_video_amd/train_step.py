@@ -56,6 +56,7 @@ from .parallel import (FlatGradBucket, OwnerShards, PositionExchangePlan, Zero1S
                        owner_reduce, reduce_densify_batch)
 from .tracks import TrackTargets, _upload, frame_weights
 
+WIDE_ATTRS_FROM = 17      # attrs [N, A] with A above this leave the composited row (its detached group holds 3 + 17 channels)
 TRAINABLE = ("pos_cubic_node", "rotation", "opacity", "scaling", "shs", "attrs")
 FROZEN = ("position", "rot_poly_feat", "rot_fourier_feat")          # :90 position is not optimised; :195-197 detached tables
 # learning rates of the reference's configuration (src/configs/frag_gs_v10.yaml:40-66).  The SH block is ONE [N,16,3] tensor here;
@@ -134,7 +135,10 @@ class TrainingStep:
     ``params``: per-Gaussian tensors on the GPU -- position [N,3], pos_cubic_node [N, 4*I*3] (the reference's layout; stored
     segment-major), rotation [N,4], rot_poly_feat [N,4,4], rot_fourier_feat [N,8,4], opacity [N,1] (logit), scaling [N,3]
     (log), shs [N,16,3], attrs [N,A] (the render attributes behind track_gs; 3 + 1 + 3 + A = the composited row, A = 16 for
-    the renderer's own 23-channel plan).  ``sparse_track=True`` (needs LossWeights.track > 0 and attr == 0; default False: the
+    the renderer's own 23-channel plan; A > 17 no longer fits the plan's detached group behind track_gs: the row is then rgb |
+    depth | track_gs (C = 7), all A attribute channels are composited beside it as the frame batch's wide set, and the step takes the
+    gradient-image path -- gt["attr"] stays [F, 3 + A, H, W], last["l1_attr"] keeps its definition).
+    ``sparse_track=True`` (needs LossWeights.track > 0 and attr == 0; default False: the
     step as it was, bit for bit): the attribute set leaves the frame batch (C = 4: rgb + depth) and the track term runs on
     track_gs composited at the query pixels of gt["tracks"] only; gt["attr"] is not read, the attributes keep a zero gradient,
     last["l1_attr"] is a zero scalar, and step() raises in deterministic mode (float atomics) -- unless ``ordered_track=True``
@@ -242,7 +246,10 @@ class TrainingStep:
                     dst[a:b].copy_(src.reshape(-1))
             self.opt.load_moments(full[0], full[1])
         A = self.p["attrs"].shape[1]
-        self.C = 4 if self.sparse_track else 3 + 1 + 3 + A
+        # more attributes than the one-pass plan's detached group holds (3 track channels + 17): the row keeps rgb | depth |
+        # track_gs and ALL attribute channels form the wide set beside it (FrameBatch.render_dynamic_sets(wide=...))
+        self.wide = not self.sparse_track and A > WIDE_ATTRS_FROM
+        self.C = 4 if self.sparse_track else (7 if self.wide else 3 + 1 + 3 + A)
         self.fb = FrameBatch(self.F, N, self.W, self.H, self.C, self.dev, want_abs=False)
         self.dstate = D.DensifyState(N, self.dev)
         self.dirs = torch.zeros(N, 3, device=self.dev)
@@ -337,6 +344,22 @@ class TrainingStep:
             L.check(lib.splat_l1_loss_grad(1, ctypes.c_int64(inner), L.ptr(pred[f, 3:]), ctypes.c_int64(inner), L.ptr(target[f, 3:]),
                                            L.cf(self.w.attr / (F * inner)), L.ptr(grad[f, 3:]), L.ptr(loss_slot), L.stream()))
 
+    def _l1_channels(self, pred: Tensor, target: Tensor, t0: int, grad: Tensor, scale: float, loss_slot: Tensor) -> None:
+        """L1 of the image ``pred`` [F, c, H, W] against channels [t0, t0 + c) of ``target``: grad = scale * sign(pred - target),
+        the sum of |.| added to ``loss_slot``; one splat_l1_loss_grad per frame (a frame's channel block is contiguous in the
+        image, the ground truth and the gradient image)"""
+        import ctypes
+        F, c, H, W = grad.shape
+        inner = c * H * W
+        pred = L.need(pred, "rendered image")
+        target = L.need(target, "ground truth")
+        if tuple(pred.shape) != (F, c, H, W) or target.shape[0] != F or target.shape[1] < t0 + c or tuple(target.shape[2:]) != (H, W):
+            raise ValueError(f"ground truth must be [{F}, >= {t0 + c}, {H}, {W}]")
+        lib = L.lib()
+        for f in range(F):
+            L.check(lib.splat_l1_loss_grad(1, ctypes.c_int64(inner), L.ptr(pred[f]), ctypes.c_int64(inner), L.ptr(target[f, t0:t0 + c]),
+                                           L.cf(scale), L.ptr(grad[f]), L.ptr(loss_slot), L.stream()))
+
     # ------------------------------------------------------------------ the step
     def step(self, times1: Sequence[float], times2: Sequence[float], gt: Dict[str, Tensor]) -> Dict[str, Tensor]:
         """one gradient step on the pairs (times1[f], times2[f]); ``gt``: rgb [F,3,H,W], depth [F,1,H,W], attr [F,3+A,H,W] of
@@ -390,7 +413,7 @@ class TrainingStep:
         tab1 = self.fb.frame_table(self.clock, times)
         sets = [dict(feature=rgb, bg=self.bg, taps=True), dict(feature="depth", bg=1.0)]
         sink = {k: g[k] for k in ("pos_cubic_node", "rotation", "opacity", "scaling")}
-        sparse = None
+        sparse = wide = None
         if self.sparse_track:
             # track_gs at the integer query pixels only: one corner of weight 1 per query, the gradient next to ARAP's
             tt = gt["tracks"]
@@ -398,6 +421,11 @@ class TrainingStep:
             sparse = dict(feature=self.pairs[:, 1], points=torch.stack([pix % self.W, pix // self.W], dim=1).to(torch.float32),
                           offsets=tt.offsets, bg=0.0, detach_opacity=True, ordered=self.ordered_track)
             sink["points"] = self.g_pairs[:, 1]
+        elif self.wide:
+            sets.append(dict(feature=[self.pairs[:, 1]], bg=0.0, detach_opacity=True))
+            sink["feature:1"] = self.g_pairs[:, 1]
+            wide = dict(feature=p["attrs"], bg=0.0, detach_opacity=True)
+            sink["wide"] = g["attrs"]
         else:
             sets.append(dict(feature=[self.pairs[:, 1], p["attrs"]], bg=0.0, detach_opacity=True))
             sink["feature:1"] = self.g_pairs[:, 1]          # track_gs' gradient: next to the ARAP gradient of position(ids2)
@@ -406,7 +434,7 @@ class TrainingStep:
                                           pos_cubic_node=p["pos_cubic_node"], rotation=p["rotation"],
                                           rot_poly_feat=fz["rot_poly_feat"], rot_fourier_feat=fz["rot_fourier_feat"],
                                           opacity=p["opacity"], scaling=p["scaling"], cubic_layout=SEGMENT_MAJOR, K=self.K,
-                                          grad_sink=sink, points=sparse)
+                                          grad_sink=sink, points=sparse, **({"wide": wide} if wide is not None else {}))
         ph.mark("render_forward")
         dssim = self.w.dssim > 0
         dpt = self.w.depth_dpt > 0
@@ -421,6 +449,25 @@ class TrainingStep:
                        else self._l1(out[1], gt["depth"], self.w.depth, sums[1:2]))
             ph.mark("loss")
             torch.autograd.backward(list(out[:3]), [g_rgb, g_depth, g_pts])
+        elif self.wide:
+            # rgb | depth | track_gs in the row, the A attributes beside it: gradient images (the fused L1 reads ONE output row)
+            A = self.p["attrs"].shape[1]
+            sums = torch.zeros(6 if dpt else (5 if track else (4 if dssim else 3)), dtype=torch.float32, device=self.dev)
+            g_rgb = (self._rgb_loss_grad(out[0], gt["rgb"], sums) if dssim else self._l1(out[0], gt["rgb"], self.w.rgb, sums[0:1]))
+            g_trk = torch.empty(F, 3, self.H, self.W, dtype=torch.float32, device=self.dev)
+            g_att = torch.empty(F, A, self.H, self.W, dtype=torch.float32, device=self.dev)
+            if track:
+                wts = _upload(frame_weights(times1, times2, self.clock.num_frames), self.dev)
+                self._track_loss_grad(out[2], gt["tracks"], wts, g_trk, sums[4:5])
+                self._l1_channels(out[3], gt["attr"], 3, g_att, self.w.attr / (F * A * self.H * self.W), sums[2:3])
+            else:       # one L1 over the 3 + A channels, as the row route's attribute term
+                scale = self.w.attr / (F * (3 + A) * self.H * self.W)
+                self._l1_channels(out[2], gt["attr"], 0, g_trk, scale, sums[2:3])
+                self._l1_channels(out[3], gt["attr"], 3, g_att, scale, sums[2:3])
+            g_depth = (self._depth_loss_grad(out[1], gt, sums, sums[5:6]) if dpt
+                       else self._l1(out[1], gt["depth"], self.w.depth, sums[1:2]))
+            ph.mark("loss")
+            torch.autograd.backward(list(out[:4]), [g_rgb, g_depth, g_trk, g_att])
         elif self.fused_l1 and not dssim and not track and not dpt and L.get_option("bwd_quarters"):
             # the L1 terms' gradient images are never materialised: the tile kernel derives them from the forward's output row and
             # the ground-truth frames where it hoists the image gradient (splat_alpha_blending_backward_batch_sets_l1)
@@ -479,15 +526,16 @@ class TrainingStep:
         ph.mark("densify_stats")
         self.iteration += 1
         hw = self.W * self.H
+        n_attr = 3 + self.p["attrs"].shape[1] if self.wide else max(self.C - 4, 1)      # channels of the attribute term
         self.last = {"l1_rgb": sums[0] / (F * 3 * hw), "l1_depth": sums[1] / (F * hw),
-                     "l1_attr": sums[2] / (F * max(self.C - 4, 1) * hw), "arap": arap.mean()}
+                     "l1_attr": sums[2] / (F * n_attr * hw), "arap": arap.mean()}
         if dssim:
             self.last["ssim_rgb"] = sums[3] / (F * 3 * hw)
         if track and self.sparse_track:
             self.last["l1_attr"] = sums[2]            # the attribute images are not rendered: a zero device scalar
             self.last["track"] = sums[4]
         elif track:
-            A = self.C - 7
+            A = self.p["attrs"].shape[1] if self.wide else self.C - 7
             self.last["l1_attr"] = sums[2] / (F * A * hw) if A > 0 else sums[2]      # A = 0: no attribute term (0)
             self.last["track"] = sums[4]
         if dpt:
@@ -674,16 +722,19 @@ def render_ground_truth(params: Dict[str, Tensor], clock: FrameClock, W: int, H:
     dev = params["position"].device
     F, N, I = len(times1), params["position"].shape[0], clock.interval_num
     A = params["attrs"].shape[1]
-    fb = FrameBatch(F, N, W, H, 3 + 1 + 3 + A, dev)
+    wide = A > WIDE_ATTRS_FROM      # the attributes beside the row (as TrainingStep composites them)
+    fb = FrameBatch(F, N, W, H, 7 if wide else 3 + 1 + 3 + A, dev)
     dirs = torch.zeros(N, 3, device=dev)
     dirs[:, 2] = 1.0
     rgb = compute_sh(params["shs"], 3, dirs)
     cubic = params["pos_cubic_node"].reshape(N, -1)
     pos2 = positions_batch_forward(frame_table(clock, list(times2), dev), params["position"], cubic, I, GAUSSIAN_MAJOR)
     sets = [dict(feature=rgb, bg=bg, taps=True), dict(feature="depth", bg=1.0),
-            dict(feature=[pos2, params["attrs"]], bg=0.0, detach_opacity=True)]
+            dict(feature=[pos2] if wide else [pos2, params["attrs"]], bg=0.0, detach_opacity=True)]
+    extra = {"wide": dict(feature=params["attrs"].contiguous(), bg=0.0, detach_opacity=True)} if wide else {}
     out = fb.render_dynamic_sets(clock, list(times1), extr, sets, position=params["position"], pos_cubic_node=cubic,
                                  rotation=params["rotation"], rot_poly_feat=params["rot_poly_feat"],
                                  rot_fourier_feat=params["rot_fourier_feat"], opacity=params["opacity"], scaling=params["scaling"],
-                                 cubic_layout=GAUSSIAN_MAJOR, K=K)
-    return {"rgb": out[0].clone(), "depth": out[1].clone(), "attr": out[2].clone()}
+                                 cubic_layout=GAUSSIAN_MAJOR, K=K, **extra)
+    attr = torch.cat([out[2], out[3]], dim=1) if wide else out[2].clone()
+    return {"rgb": out[0].clone(), "depth": out[1].clone(), "attr": attr}
