@@ -1065,6 +1065,33 @@ int splat_lift_tracks(int N, int T, int H, int W, const float *tracks_2d, const 
 int splat_fit_cubic_nodes(int N, int T, int n_knots, const float *knots_host, const int32_t *knot_frames_host,
                           const float *tracks_3d, float *position, float *pos_cubic_node, splat_stream_t stream);
 
+/* ---- appearance editing: fit the colours of frozen geometry to an edited frame (the reference's
+ *      optimize_appearance_from_mask / _from_img, src/trainer_fragGS.py:999-1120; csrc/edit.hip).  Geometry and opacity are
+ *      frozen, so every weight alpha * T is constant, the image is linear in the colours and the only gradient is
+ *      dL/dcolour_g = sum_p w_pg dL/dout_p.
+ *      splat_blend_fit_color, ONE launch, no host synchronisation: composite feature [P, 3] over the tile lists (the forward of
+ *      splat_alpha_blending_forward: skip alpha < 1/255, stop the pixel when T (1 - alpha) < 1e-4, + T bg; the exponent from
+ *      csrc/blend_power.h relative to the tile centre, so every decision is that forward's bit for bit), form the loss
+ *        L = sum_p pixel_weight_p sum_c (out_pc - target_pc)^2 / (3 H W)          (F.mse_loss of the [H, W, 3] image; weight 1: NULL)
+ *      and write, per tile, its share of L to tile_loss[tile] (plain store) and, per list entry, the tile's share of dL/dcolour
+ *      {g0, g1, g2, 0} to pair_grad[slot_sorted[entry]] (one 16-byte store; pair_grad [capacity, 4], 16-byte aligned).  Every
+ *      entry of a launched tile's list is written (zeros behind the tile's last contributor), so
+ *      splat_pair_records_segment_sum(P, 4, pair_grad, goff_incl, dcolor [P, 4]) gives dL/dcolour with the pair map of the sort
+ *      that made idx_sorted.  target [H, W, 3]; pixel_weight [H, W] or NULL; out [3, H, W] and ncontrib [H, W] optional (NULL:
+ *      not stored; ncontrib = the forward's).  One workgroup per launched tile: active_tiles int32 [n_active] names them
+ *      (each < T, no tile twice), NULL launches every tile and then n_active must be T = ceil(W/16) ceil(H/16); n_active = 0:
+ *      SPLAT_OK without a launch.  A tile that is not launched keeps its tile_loss and its pair_grad slots: when only some
+ *      colours change between calls, only the tiles whose list holds one of them need to run again.
+ *      C != 3, sizes < 1, n_active < 0 or > T, a NULL required pointer, a misaligned pair_grad: SPLAT_E_ARG before any HIP call.
+ *      splat_tile_loss_sum: history[slot] = the sum of tile_loss[0 .. T) in a fixed order (one workgroup).
+ *      No float atomics: both run under splat_set_deterministic(1) and give the same bits on every run. ---- */
+int splat_blend_fit_color(int P, int C, const float *uv, const float *conic, const float *opacity, const float *feature,
+                          const int32_t *idx_sorted, const int32_t *tile_range, const int32_t *slot_sorted, int64_t capacity,
+                          float bg, int W, int H, const float *target, const float *pixel_weight, int n_active,
+                          const int32_t *active_tiles, float *tile_loss, float *pair_grad, float *out, int32_t *ncontrib,
+                          splat_stream_t stream);
+int splat_tile_loss_sum(int T, const float *tile_loss, float *history, int64_t slot, splat_stream_t stream);
+
 /* ---- measurement hooks (bench.py: live per-kernel timing with HIP events on the launch stream) ---- */
 void splat_profile_enable(int on);
 void splat_profile_reset(void);

@@ -4,5 +4,6 @@ Drop-in for the reference's ``dptr.gs`` operator package: hand-written HIP kerne
 ``csrc/`` behind the C ABI of ``include/splat_hip.h``, reached through ctypes.  See DESIGN.md.
 """
 from . import gs  # noqa: F401
+from .edit import AppearanceFit, fit_appearance, select_gaussians  # noqa: F401
 
 __version__ = "0.1.0"

@@ -65,6 +65,7 @@ SYMBOLS = [
     "splat_alpha_blending_points_backward_batch_ordered", "splat_alpha_blending_points_backward_batch_ordered_scratch_bytes",
     "splat_median_filter_2d", "splat_lift_tracks", "splat_fit_cubic_nodes",
     "splat_alpha_blending_forward_batch_set", "splat_alpha_blending_backward_batch_set_packed", "splat_frames_wide_fold",
+    "splat_blend_fit_color", "splat_tile_loss_sum",
 ]
 
 
@@ -147,6 +148,8 @@ def lib() -> ctypes.CDLL:
         L.splat_alpha_blending_forward_batch_set.argtypes = [i, i, i, i, i, p, p, p, i64, p, i64, p, p, i64, f, i, i, p, p, p, p, p, p]
         L.splat_alpha_blending_backward_batch_set_packed.argtypes = [i, i, i, i, i, p, p, i64, f, i, i, p, p, p, p, p, p, p, p, p]
         L.splat_frames_wide_fold.argtypes = [i, i, i, i64, p, p, p, i, p, i64, i, p]
+        L.splat_blend_fit_color.argtypes = [i, i, p, p, p, p, p, p, p, i64, f, i, i, p, p, i, p, p, p, p, p, p]
+        L.splat_tile_loss_sum.argtypes = [i, p, p, i64, p]
         if L.splat_abi_version() != ABI_VERSION:
             raise SplatError("libsplat_hip.so ABI version mismatch; rebuild it")
         _lib = L
