@@ -1092,6 +1092,37 @@ int splat_blend_fit_color(int P, int C, const float *uv, const float *conic, con
                           splat_stream_t stream);
 int splat_tile_loss_sum(int T, const float *tile_loss, float *history, int64_t slot, splat_stream_t stream);
 
+/* ---- layer editing: a clip from selected, moved and copied layers of ONE dynamic model (the reference's render_part and
+ *      add_fg, src/trainer_fragGS.py:1310-1405; csrc/preprocess.hip).  A batch holds Q INSTANCES in F frames; a layer owns the
+ *      rows q0 .. q0 + S of uv / depth / conic / radius [F, Q, ..] and opa_t [Q], its instance s being source Gaussian src[s]
+ *      (int32 [S], ascending ids < P; NULL: every Gaussian in place, S must be P) of the model of P Gaussians, evaluated at the
+ *      layer's OWN frame times: tab is the device table of splat_frame_preprocess_forward_batch for those times (a delayed copy
+ *      has another table than the base layer).  Forward only.
+ *      splat_frame_preprocess_layer_batch, one launch per layer: splat_frame_preprocess_forward_batch read through src, with an
+ *      optional similarity between the dynamic evaluation and the projection: centroid [F, 3] (non-NULL: position =
+ *      (p - centroid[f]) * scale + centroid[f], every step rounded to float32), delta [F, 3] (non-NULL: + delta[f] after it),
+ *      scale_splats != 0: the activated scale times `scale` as well (the reference scales positions only).  Rotation is the
+ *      model's normalised rotation at the layer's time; opa_t = sigmoid(opacity[src]).  With centroid == delta == NULL and
+ *      (scale == 1 or scale_splats == 0) no transform arithmetic runs and the rows are, bit for bit, those of
+ *      splat_frame_preprocess_forward_batch on the compacted model.  No LDS, no atomics.
+ *      splat_layer_centroids: centroid[f] = mean over the S ids of position(t_f) -- the spline expression of the preprocess in
+ *      float32, summed in float64 in a fixed order (per-block partials in scratch, then a second launch in block order) and
+ *      rounded to float32 once.  No float atomics: two runs give the same bits.  scratch: 8-byte aligned device memory of at
+ *      least splat_layer_centroids_scratch_bytes(F, S) bytes.
+ *      Both validate on the host before any HIP call (sizes, F <= 65535, S <= P, q0 + S <= Q, src == NULL only with S == P, a
+ *      finite scale, centroid required when scale != 1, NULL pointers, the scratch size): SPLAT_E_ARG.  S == 0 or F == 0:
+ *      SPLAT_OK without a launch. ---- */
+int splat_frame_preprocess_layer_batch(int F, int P, int S, int Q, int q0, int I, const void *tab, const int32_t *src,
+                                       const float *position, const float *cubic, int cubic_layout, const float *rotation,
+                                       const float *rot_poly, const float *rot_fourier, const float *opacity,
+                                       const float *scaling, const float *extr, int W, int H, float nearest, float extent,
+                                       const float *centroid, const float *delta, float scale, int scale_splats, float *uv,
+                                       float *depth, float *conic, int32_t *radius, float *opa_t, splat_stream_t stream);
+size_t splat_layer_centroids_scratch_bytes(int F, int S);
+int splat_layer_centroids(int F, int P, int S, int I, const void *tab, const int32_t *src, const float *position,
+                          const float *cubic, int cubic_layout, float *centroid, void *scratch, size_t scratch_bytes,
+                          splat_stream_t stream);
+
 /* ---- measurement hooks (bench.py: live per-kernel timing with HIP events on the launch stream) ---- */
 void splat_profile_enable(int on);
 void splat_profile_reset(void);

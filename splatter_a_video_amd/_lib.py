@@ -66,6 +66,7 @@ SYMBOLS = [
     "splat_median_filter_2d", "splat_lift_tracks", "splat_fit_cubic_nodes",
     "splat_alpha_blending_forward_batch_set", "splat_alpha_blending_backward_batch_set_packed", "splat_frames_wide_fold",
     "splat_blend_fit_color", "splat_tile_loss_sum",
+    "splat_frame_preprocess_layer_batch", "splat_layer_centroids_scratch_bytes", "splat_layer_centroids",
 ]
 
 
@@ -150,6 +151,11 @@ def lib() -> ctypes.CDLL:
         L.splat_frames_wide_fold.argtypes = [i, i, i, i64, p, p, p, i, p, i64, i, p]
         L.splat_blend_fit_color.argtypes = [i, i, p, p, p, p, p, p, p, i64, f, i, i, p, p, i, p, p, p, p, p, p]
         L.splat_tile_loss_sum.argtypes = [i, p, p, i64, p]
+        L.splat_frame_preprocess_layer_batch.argtypes = [i, i, i, i, i, i, p, p, p, p, i, p, p, p, p, p, p, i, i, f, f, p, p, f, i,
+                                                         p, p, p, p, p, p]
+        L.splat_layer_centroids_scratch_bytes.restype = ctypes.c_size_t
+        L.splat_layer_centroids_scratch_bytes.argtypes = [i, i]
+        L.splat_layer_centroids.argtypes = [i, i, i, i, p, p, p, p, i, p, p, ctypes.c_size_t, p]
         if L.splat_abi_version() != ABI_VERSION:
             raise SplatError("libsplat_hip.so ABI version mismatch; rebuild it")
         _lib = L

@@ -755,6 +755,159 @@ frame_preprocess_fwd_batch_kernel(int F, int P, int I, int layout, const DynTab 
     }
 }
 
+// ------------------------------------------------------------------ layered scenes (reference: render_part / add_fg,
+// src/trainer_fragGS.py:1310-1405): the kernel above reading its Gaussians through an instance list.  Quad s of the layer
+// evaluates source Gaussian src[s] (src == NULL: s itself) at the LAYER's frame times (its own table) and writes row q0 + s of
+// a batch of Q instances.  XF: the layer is transformed -- the position becomes ((p - c) * scale + c) + delta with c the
+// layer's centroid at that frame's time (:1359-1362: every step rounded to float32, nothing contracted), and with
+// scale_splats the activated scale is multiplied by `scale` too.  XF = false holds none of that arithmetic: the same device
+// functions in the same order as frame_preprocess_fwd_batch_kernel, so an untransformed layer gives that kernel's bits on
+// the compacted model.  No LDS, no atomics; the gathered rows are ascending, so the table reads stay mostly coalesced.
+__device__ __forceinline__ float layer_place(float p, float c, float s) {
+#pragma clang fp contract(off)
+    float r = (p - c) * s;
+    r = r + c;
+    return r;
+}
+__device__ __forceinline__ float layer_shift(float p, float d) {
+#pragma clang fp contract(off)
+    return p + d;
+}
+
+template <bool XF>
+__global__ void __launch_bounds__(DYN_BLOCK)
+frame_preprocess_fwd_layer_kernel(int F, int P, int S, int Q, int q0, int I, int layout, const DynTab *__restrict__ tab,
+                                  const int *__restrict__ src, const float *__restrict__ position,
+                                  const float *__restrict__ cubic, const float *__restrict__ rotation,
+                                  const float4 *__restrict__ rot_poly, const float4 *__restrict__ rot_fourier,
+                                  const float *__restrict__ opacity, const float *__restrict__ scaling,
+                                  const float *__restrict__ extr, int W, int H, float nearest, float extent,
+                                  const float *__restrict__ centroid, const float *__restrict__ delta, float scale,
+                                  int scale_splats, float *__restrict__ uv, float *__restrict__ depth,
+                                  float *__restrict__ conic, int *__restrict__ radius, float *__restrict__ opa_t) {
+    const int t = blockIdx.x * DYN_BLOCK + threadIdx.x;
+    const int s = t >> 2, j = t & 3;
+    if (s >= S) return;  // whole quads leave together
+    const int n = src ? src[s] : s;
+    if ((unsigned)n >= (unsigned)P) return;  // (an id outside the model: the quad writes nothing instead of reading past the tables)
+    const DynStatic stc = dyn_static(n, j, position, rotation, rot_poly, rot_fourier, scaling);
+    Cam c;
+    load_cam(nullptr, extr, c);
+    const int per = (F + gridDim.y - 1) / gridDim.y;
+    const int f0 = blockIdx.y * per, f1 = imin_(F, f0 + per);
+    if (blockIdx.y == 0 && j == 3) opa_t[q0 + s] = 1.0f / (1.0f + expf(-opacity[n]));  // the source Gaussian's, frame independent
+    float scl3[3] = {quad_bcast<0>(stc.scl_j), quad_bcast<1>(stc.scl_j), quad_bcast<2>(stc.scl_j)};
+    if (XF && scale_splats) {
+        scl3[0] *= scale; scl3[1] *= scale; scl3[2] *= scale;
+    }
+    for (int f = f0; f < f1; f += 4) {
+        float m_pos[3] = {0.f, 0.f, 0.f}, m_q[4] = {1.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int ff = imin_(f + k, f1 - 1);  // (a repeated last frame: its lane does not store)
+            const CubicAddr ca = cubic_addr(layout, P, I, tab[ff].seg);
+            const DynFrame fr = dyn_frame_rows(n, j, ca, tab[ff].d, tab[ff].basis, stc, cubic);
+            if (j == k) {
+                m_pos[0] = fr.pos[0]; m_pos[1] = fr.pos[1]; m_pos[2] = fr.pos[2];
+                m_q[0] = fr.q[0]; m_q[1] = fr.q[1]; m_q[2] = fr.q[2]; m_q[3] = fr.q[3];
+            }
+        }
+        if (f + j >= f1) continue;
+        if (XF) {
+            if (centroid) {
+                const float *cf = centroid + (size_t)(f + j) * 3;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) m_pos[k] = layer_place(m_pos[k], cf[k], scale);
+            }
+            if (delta) {
+                const float *df = delta + (size_t)(f + j) * 3;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) m_pos[k] = layer_shift(m_pos[k], df[k]);
+            }
+        }
+        float u, v, dep;
+        const bool cull = project_ortho_pt(c, m_pos[0], m_pos[1], m_pos[2], W, H, nearest, extent, u, v, dep);
+        u = cull ? 0.f : u; v = cull ? 0.f : v; dep = cull ? 0.f : dep;
+        float o[3] = {0.f, 0.f, 0.f};
+        int orad = 0, otiles = 0;
+        if (dep != 0.f) {
+            float c3[6], a[3], bb[3], tt[3], Jm[4], cov[3];
+            cov3d_pt(scl3, m_q, c3);
+            ewa_T<true>(c, m_pos, W, H, a, bb, tt, Jm);
+            ewa_cov2d<true>(a, bb, c3, cov);
+            ewa_finish_pt<true>(cov, make_float2(u, v), W, H, o[0], o[1], o[2], orad, otiles);
+        }
+        const size_t fn = (size_t)(f + j) * Q + q0 + s;
+        *reinterpret_cast<float2 *>(uv + fn * 2) = make_float2(u, v);
+        conic[fn * 3] = o[0]; conic[fn * 3 + 1] = o[1]; conic[fn * 3 + 2] = o[2];
+        depth[fn] = dep;
+        radius[fn] = orad;
+    }
+}
+
+// centroid[f] = mean over the layer's S selected Gaussians of position(t_f) (add_fg's fg_pos.mean, :1359-1360), the spline
+// expression of the preprocess in float32, the sum in float64 in a FIXED order: a wave of 64 lanes sums CEN_ITEMS strided
+// elements per lane and folds the lanes with xor shuffles into partial[f][block][3]; a second launch sums a frame's partials
+// (lane l takes blocks l, l + 64, .., then the same fold) and rounds sum / S to float32 once.  No float atomics, no LDS: two
+// runs give the same bits.
+constexpr int CEN_BLOCK = 64, CEN_ITEMS = 16;
+inline unsigned cen_blocks(int S) { return (unsigned)(((size_t)S + CEN_BLOCK * CEN_ITEMS - 1) / (CEN_BLOCK * CEN_ITEMS)); }
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+__global__ void __launch_bounds__(CEN_BLOCK)
+layer_centroid_partial_kernel(int P, int S, int I, int layout, const DynTab *__restrict__ tab, const int *__restrict__ src,
+                              const float *__restrict__ position, const float *__restrict__ cubic,
+                              double *__restrict__ partial) {
+    const int f = blockIdx.y;
+    const CubicAddr ca = cubic_addr(layout, P, I, tab[f].seg);
+    const float d = tab[f].d;
+    double a[3] = {0.0, 0.0, 0.0};
+    const int base = blockIdx.x * (CEN_BLOCK * CEN_ITEMS) + threadIdx.x;
+    for (int k = 0; k < CEN_ITEMS; ++k) {
+        const int s = base + k * CEN_BLOCK;
+        if (s >= S) break;
+        const int n = src ? src[s] : s;
+        if ((unsigned)n >= (unsigned)P) continue;
+        const float *c = cubic + ca.seg_off + (size_t)n * ca.stride_n;
+        const size_t row = ca.stride_k;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float c0 = c[j], c1 = c[row + j], c2 = c[2 * row + j], c3 = c[3 * row + j];
+            float p = c3 + c2 * d;
+            p = p + c1 * (d * d);
+            p = p + c0 * (d * d * d);
+            a[j] += (double)(p + position[(size_t)n * 3 + j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) a[j] = wave_sum_f64(a[j]);
+    if (threadIdx.x == 0) {
+        double *o = partial + ((size_t)f * gridDim.x + blockIdx.x) * 3;
+        o[0] = a[0]; o[1] = a[1]; o[2] = a[2];
+    }
+}
+
+__global__ void __launch_bounds__(CEN_BLOCK)
+layer_centroid_final_kernel(int S, int blocks, const double *__restrict__ partial, float *__restrict__ centroid) {
+    const int f = blockIdx.x;
+    const double *p = partial + (size_t)f * blocks * 3;
+    double a[3] = {0.0, 0.0, 0.0};
+    for (int b = threadIdx.x; b < blocks; b += CEN_BLOCK) {
+        a[0] += p[(size_t)b * 3]; a[1] += p[(size_t)b * 3 + 1]; a[2] += p[(size_t)b * 3 + 2];
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) a[j] = wave_sum_f64(a[j]);
+    if (threadIdx.x == 0) {
+        float *o = centroid + (size_t)f * 3;
+        o[0] = (float)(a[0] / (double)S); o[1] = (float)(a[1] / (double)S); o[2] = (float)(a[2] / (double)S);
+    }
+}
+
 // Backward: one quad per Gaussian walks ALL frames: per frame it sums the Gaussian's pair records (lane `sub` owns the
 // record chunks sub, sub + 4, ..), re-evaluates the frame's position / rotation (dyn_frame), runs projection + EWA +
 // cov3d backward and chains through the activations -- scale = exp, rotation = normalize(raw + detached sums), opacity =
@@ -1515,6 +1668,69 @@ extern "C" int splat_frame_preprocess_forward_batch(int F, int P, int I, const v
     SPLAT_LAUNCH("frame_preprocess_fwd", frame_preprocess_fwd_batch_kernel, dim3(g.x, slices), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
                  F, P, I, cubic_layout, (const DynTab *)tab, position, cubic, rotation, (const float4 *)rot_poly,
                  (const float4 *)rot_fourier, opacity, scaling, extr, W, H, nearest, extent, uv, depth, conic, radius, opa_t);
+    SPLAT_POST_LAUNCH();
+    return SPLAT_OK;
+}
+
+// ---- layered scenes: one layer of a batch of Q instances (rows q0 .. q0 + S), see frame_preprocess_fwd_layer_kernel
+extern "C" int splat_frame_preprocess_layer_batch(int F, int P, int S, int Q, int q0, int I, const void *tab, const int32_t *src,
+                                                  const float *position, const float *cubic, int cubic_layout,
+                                                  const float *rotation, const float *rot_poly, const float *rot_fourier,
+                                                  const float *opacity, const float *scaling, const float *extr, int W, int H,
+                                                  float nearest, float extent, const float *centroid, const float *delta,
+                                                  float scale, int scale_splats, float *uv, float *depth, float *conic,
+                                                  int32_t *radius, float *opa_t, void *stream) {
+    SPLAT_CHECK_ARG(F >= 0 && F <= 65535 && P >= 1 && S >= 0 && Q >= 1 && q0 >= 0 && I >= 1 && W > 0 && H > 0, "bad sizes");
+    SPLAT_CHECK_ARG(S <= P, "a layer selects at most P Gaussians (src: ascending ids)");
+    SPLAT_CHECK_ARG((long long)q0 + S <= (long long)Q, "q0 + S exceeds the batch's Q instances");
+    SPLAT_CHECK_ARG(cubic_layout == SPLAT_CUBIC_GAUSSIAN_MAJOR || cubic_layout == SPLAT_CUBIC_SEGMENT_MAJOR, "unknown cubic_layout");
+    SPLAT_CHECK_ARG(std::isfinite(scale), "scale must be finite");
+    SPLAT_CHECK_ARG(scale == 1.0f || centroid, "scale != 1 needs the layer's centroid");
+    SPLAT_CHECK_ARG(src || S == P, "src == NULL means every Gaussian in place: S must be P");
+    if (S == 0 || F == 0) return SPLAT_OK;
+    SPLAT_CHECK_ARG(tab && position && cubic && rotation && rot_poly && rot_fourier && opacity && scaling && extr, "null input pointer");
+    SPLAT_CHECK_ARG(uv && depth && conic && radius && opa_t, "null output pointer");
+    const dim3 g = dyn_grid(S);
+    int slices = (int)((4096 + g.x - 1) / g.x);   // frames per thread: as in splat_frame_preprocess_forward_batch
+    if (slices < 1) slices = 1;
+    if (slices > F) slices = F;
+    const bool xf = centroid || delta || (scale_splats && scale != 1.0f);
+    if (xf)
+        SPLAT_LAUNCH("frame_preprocess_fwd_layer", frame_preprocess_fwd_layer_kernel<true>, dim3(g.x, slices), dim3(DYN_BLOCK), 0,
+                     (hipStream_t)stream, F, P, S, Q, q0, I, cubic_layout, (const DynTab *)tab, src, position, cubic, rotation,
+                     (const float4 *)rot_poly, (const float4 *)rot_fourier, opacity, scaling, extr, W, H, nearest, extent, centroid,
+                     delta, scale, scale_splats, uv, depth, conic, radius, opa_t);
+    else
+        SPLAT_LAUNCH("frame_preprocess_fwd_layer", frame_preprocess_fwd_layer_kernel<false>, dim3(g.x, slices), dim3(DYN_BLOCK), 0,
+                     (hipStream_t)stream, F, P, S, Q, q0, I, cubic_layout, (const DynTab *)tab, src, position, cubic, rotation,
+                     (const float4 *)rot_poly, (const float4 *)rot_fourier, opacity, scaling, extr, W, H, nearest, extent, centroid,
+                     delta, scale, scale_splats, uv, depth, conic, radius, opa_t);
+    SPLAT_POST_LAUNCH();
+    return SPLAT_OK;
+}
+
+extern "C" size_t splat_layer_centroids_scratch_bytes(int F, int S) {
+    if (F < 1 || S < 1) return 0;
+    return (size_t)F * cen_blocks(S) * 3 * sizeof(double);
+}
+
+extern "C" int splat_layer_centroids(int F, int P, int S, int I, const void *tab, const int32_t *src, const float *position,
+                                     const float *cubic, int cubic_layout, float *centroid, void *scratch, size_t scratch_bytes,
+                                     void *stream) {
+    SPLAT_CHECK_ARG(F >= 0 && F <= 65535 && P >= 1 && S >= 0 && I >= 1, "bad sizes");
+    SPLAT_CHECK_ARG(S <= P, "a layer selects at most P Gaussians (src: ascending ids)");
+    SPLAT_CHECK_ARG(cubic_layout == SPLAT_CUBIC_GAUSSIAN_MAJOR || cubic_layout == SPLAT_CUBIC_SEGMENT_MAJOR, "unknown cubic_layout");
+    SPLAT_CHECK_ARG(src || S == P, "src == NULL means every Gaussian: S must be P");
+    if (S == 0 || F == 0) return SPLAT_OK;
+    SPLAT_CHECK_ARG(tab && position && cubic, "null input pointer");
+    SPLAT_CHECK_ARG(centroid, "null output pointer");
+    SPLAT_CHECK_ARG(scratch && ((uintptr_t)scratch & 7) == 0, "scratch (8-byte aligned) is required");
+    SPLAT_CHECK_ARG(scratch_bytes >= splat_layer_centroids_scratch_bytes(F, S), "scratch too small (splat_layer_centroids_scratch_bytes)");
+    const unsigned nb = cen_blocks(S);
+    SPLAT_LAUNCH("layer_centroid_partial", layer_centroid_partial_kernel, dim3(nb, F), dim3(CEN_BLOCK), 0, (hipStream_t)stream, P, S,
+                 I, cubic_layout, (const DynTab *)tab, src, position, cubic, (double *)scratch);
+    SPLAT_LAUNCH("layer_centroid_final", layer_centroid_final_kernel, dim3(F), dim3(CEN_BLOCK), 0, (hipStream_t)stream, S, (int)nb,
+                 (const double *)scratch, centroid);
     SPLAT_POST_LAUNCH();
     return SPLAT_OK;
 }
