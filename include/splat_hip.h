@@ -63,6 +63,8 @@ int splat_fill_f32(float *dst, size_t n, float value, splat_stream_t stream);
      "sets_std"       (1)  the three-set backward's float4 record stores + the forward's packed records for the renderer's own
                            plan (rgb 0-2 | depth 3 | 19 attributes 4-22); 0: the generic slot -> channel routing for every plan
      "bin_slot_keys"  (0)  1: pair-slot sort keys + owner array also where the packed (id, k) keys fit (tests: small sizes)
+     "bin_short_segments" (0)  1: the binning kernels keep their list of deferred (large) rectangles per 256 Gaussians instead of
+                           per 2048 (tests: chunks of several segments at small sizes; results do not depend on it)
      "deterministic"  (0)  = splat_set_deterministic
    Unknown key: SPLAT_E_ARG.  Set them before the first launch that depends on them (they are read at launch time). */
 int splat_set_option(const char *key, int value);

@@ -212,7 +212,7 @@ def build_id() -> str:
 
 def set_option(key: str, value: int) -> None:
     """process-wide option of the library (include/splat_hip.h: splat_set_option): "bwd_quarters", "sets_std", "bin_slot_keys",
-    "deterministic"; read at launch time"""
+    "bin_short_segments", "deterministic"; read at launch time"""
     check(lib().splat_set_option(key.encode(), ctypes.c_int(int(value))))
 
 

@@ -30,6 +30,7 @@
 #define BIN_BATCH_FRAMES 4
 #define BIN_LDS_TILES 12288     // <= 48 KB of LDS counters; larger tile grids use global atomics
 #define BIN_GLOBAL_BLOCKS 2048   // grid of K1/K3 on the global-atomic path
+#define BIN_SEG 2048            // Gaussians per segment of a chunk (see "area order"): 16-bit local indices of the deferred list
 #define SORT_BLOCK 256
 #define SORT_LDS_KEYS 2048      // 16 KB of LDS per sort workgroup: the exchange buffer of the two widest strides of a 2048-key block
 
@@ -69,6 +70,10 @@ static int pair_key_kbits(int P, int T) {
     const int kb = bits_for(T), ib = bits_for(P);
     return kb + ib <= 32 ? kb : 0;
 }
+
+// Gaussians per segment of the deferred list (see "area order"): BIN_SEG, or one BIN_BLOCK -- how the tests reach chunks of several
+// segments at small sizes
+static int bin_segment() { return splat_option(SPLAT_OPT_BIN_SHORT_SEGMENTS) != 0 ? BIN_BLOCK : BIN_SEG; }
 
 static BinPlan make_plan(int P, int W, int H, int F = 1) {
     BinPlan p;
@@ -141,15 +146,51 @@ __device__ __forceinline__ int reach_big_count(unsigned word, int w, int h) {
     return n;
 }
 
+// ------------------------------------------------------------------ area order (which Gaussians of its chunk share a wave)
+// K1 and K3 give one Gaussian to one lane, and the lane loops over the tiles of the splat's rectangle: a wave runs as many trips
+// as its LARGEST rectangle -- 11 on the bench scene, for 3.8 tiles per lane (tools/binning_lane_model.py).  Five Gaussians in six
+// have at most BIN_INLINE_AREA tiles; the tail (up to 49 tiles) sets the trip count of nearly every wave.  So a lane only walks a
+// rectangle of at most BIN_INLINE_AREA tiles where it meets it; a larger one it appends to a list in LDS (rectangles of at least
+// BIN_BIG_AREA tiles from the front, the others from the back), and after the pass the workgroup walks that list, again one
+// Gaussian per lane: large beside large.  Every Gaussian still has one lane and everything the kernels produce per Gaussian or
+// per tile is an integer that does not depend on the visiting order; only the order of the slots inside a (chunk, tile) segment
+// moves, which tile_sort's unique keys make irrelevant (it never was fixed: the waves of a workgroup race for the slots).
+// The list holds 16-bit local indices of a SEGMENT of at most BIN_SEG Gaussians (chunks are longer above ~1.05 M Gaussians, where
+// BIN_MAX_NB caps the rows): 4 KB + 8 B of LDS beside the tile counters.
+// (A full counting sort of the chunk by area class -- 4.4 trips per wave instead of 6.0 -- was built first and was SLOWER than
+// no order at all: every lane then gathers its Gaussian's inputs through the permutation.  DESIGN 4ae.)
+#define BIN_INLINE_AREA 4
+#define BIN_BIG_AREA 10
+// Called by whole waves (uniform flow).  defer: this lane's Gaussian, local index p, goes on the list.
+__device__ __forceinline__ void defer_append(bool defer, bool big, int p, int lane, int *dcnt, unsigned short *dl) {
+    const unsigned long long mb = __ballot(defer && big), mm = __ballot(defer && !big);
+    if ((mb | mm) == 0ull) return;
+    int bb = 0, bm = 0;
+    if (lane == 0) {   // one add per wave and list end
+        if (mb) bb = atomicAdd(&dcnt[0], __popcll(mb));
+        if (mm) bm = atomicAdd(&dcnt[1], __popcll(mm));
+    }
+    bb = __shfl(bb, 0);
+    bm = __shfl(bm, 0);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (defer) dl[big ? bb + __popcll(mb & below) : BIN_SEG - 1 - (bm + __popcll(mm & below))] = (unsigned short)p;
+}
+// entry k of the list: the large rectangles first
+__device__ __forceinline__ int deferred_at(int k, int nbig, const unsigned short *dl) {
+    return dl[k < nbig ? k : BIN_SEG - 1 - (k - nbig)];
+}
+
 // ------------------------------------------------------------------ K1
 template <bool LDS>
 __global__ void __launch_bounds__(BIN_BLOCK)
 bin_count_kernel(int P, const float2 *__restrict__ uv, const int *__restrict__ radius, int gx, int gy, int T,
                  int chunk, int *__restrict__ matrix, int *__restrict__ gcount, int *__restrict__ chunk_sum,
                  long long S, const float *__restrict__ conic, const float *__restrict__ opacity, long long opacity_fs,
-                 unsigned *__restrict__ reach) {
+                 unsigned *__restrict__ reach, int seg) {
     extern __shared__ __attribute__((aligned(16))) int cnt[];
     __shared__ int wave_pairs[BIN_BLOCK / 64];
+    __shared__ unsigned short dl[BIN_SEG];   // the deferred list (see "area order")
+    __shared__ int dcnt[2];
     const int wg = blockIdx.x;
     {   // frame batch: blockIdx.y = frame; per-Gaussian arrays are [F,P,..], scratch blocks S ints apart
         const size_t f = blockIdx.y;
@@ -160,26 +201,34 @@ bin_count_kernel(int P, const float2 *__restrict__ uv, const int *__restrict__ r
     int pairs = 0;  // this thread's share of the chunk's pair count
     if (LDS) {
         for (int t = threadIdx.x; t < T; t += BIN_BLOCK) cnt[t] = 0;
-        __syncthreads();
     }
-    const int beg = wg * chunk, end = imin_(P, beg + chunk);
-    for (int i = beg + threadIdx.x; i < end; i += BIN_BLOCK) {
-        const int r = radius[i];
-        if (r <= 0) {
-            if (gcount) gcount[i] = 0;
-            if (reach) reach[i] = 0u;
-            continue;
+    const int lane = threadIdx.x & 63;
+    // One Gaussian's inputs, loaded together (no chain radius -> uv -> conic of dependent loads).  Loading them a trip ahead, as the
+    // scatter kernel does, bought nothing here (123.2 against 123.9 us): no barrier separates this kernel's trips.
+    struct In {
+        int r;
+        float2 q;
+        float cA, cB, cC, o;
+    };
+    auto load = [&](int i, bool valid) -> In {
+        In v;
+        v.r = 0; v.q = make_float2(0.f, 0.f); v.cA = v.cB = v.cC = v.o = 0.f;
+        if (valid) {
+            v.r = radius[i];
+            v.q = uv[i];
+            if (reach) { v.cA = conic[3 * (size_t)i]; v.cB = conic[3 * (size_t)i + 1]; v.cC = conic[3 * (size_t)i + 2]; v.o = opacity[i]; }
         }
-        const float2 q = uv[i];
-        int x0, y0, x1, y1;
-        tile_rect(q.x, q.y, r, gx, gy, x0, y0, x1, y1);
-        const int area = (x1 - x0) * (y1 - y0);
+        return v;
+    };
+    // the tiles of Gaussian i (area > 0); small_only: the caller knows area <= BIN_INLINE_AREA
+    auto tiles = [&](int i, const In &g, int x0, int y0, int x1, int y1, int area, const bool small_only) {
+        const float2 q = g.q;
         if (reach) {   // only the tiles the splat can reach with alpha >= 1/255 (see "reach masks")
-            const float cA = conic[3 * (size_t)i], cB = conic[3 * (size_t)i + 1], cC = conic[3 * (size_t)i + 2], o = opacity[i];
+            const float cA = g.cA, cB = g.cB, cC = g.cC, o = g.o;
+            const CullP cp = cull_params(cA, cB, cC, o);
             unsigned word;
             int kept = 0;
-            if (area < 32) {
-                const CullP cp = cull_params(cA, cB, cC, o);
+            if (small_only || area < 32) {
                 unsigned m = 0u, bit = 1u;
                 for (int ty = y0; ty < y1; ++ty)
                     for (int tx = x0; tx < x1; ++tx, bit <<= 1) {
@@ -193,7 +242,6 @@ bin_count_kernel(int P, const float2 *__restrict__ uv, const int *__restrict__ r
                 kept = __popc(m);
                 word = m;
             } else {   // a large rectangle: cells of c x c tiles, each tested as one rectangle of pixel centres
-                const CullP cp = cull_params(cA, cB, cC, o);
                 const int w = x1 - x0, h = y1 - y0, sh = reach_cell_shift(w, h), c = 1 << sh;
                 const int ncx = ((w - 1) >> sh) + 1, ncy = ((h - 1) >> sh) + 1;
                 unsigned m = 0u, bit = 1u;
@@ -216,7 +264,7 @@ bin_count_kernel(int P, const float2 *__restrict__ uv, const int *__restrict__ r
             reach[i] = word;
             if (gcount) gcount[i] = kept;
             pairs += kept;
-            continue;
+            return;
         }
         if (gcount) gcount[i] = area;
         pairs += area;
@@ -225,6 +273,40 @@ bin_count_kernel(int P, const float2 *__restrict__ uv, const int *__restrict__ r
                 if (LDS) atomicAdd(&cnt[ty * gx + tx], 1);
                 else atomicAdd(&matrix[ty * gx + tx], 1);
             }
+    };
+    const int beg = wg * chunk, end = imin_(P, beg + chunk);
+    for (int sbeg = beg; sbeg < end; sbeg += seg) {   // segments of the deferred list (one, unless BIN_MAX_NB capped the rows)
+        const int n = imin_(seg, end - sbeg);
+        __syncthreads();   // the last segment's list has been walked (first segment: the tile counters are zero)
+        if (threadIdx.x < 2) dcnt[threadIdx.x] = 0;
+        __syncthreads();
+        for (int base = 0; base < n; base += BIN_BLOCK) {   // uniform trip count: defer_append is called by whole waves
+            const int p = base + threadIdx.x, i = sbeg + p;
+            const In g = load(i, p < n);
+            int area = 0, x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+            if (p < n) {
+                if (g.r > 0) {
+                    tile_rect(g.q.x, g.q.y, g.r, gx, gy, x0, y0, x1, y1);
+                    area = (x1 - x0) * (y1 - y0);
+                }
+                if (area == 0) {   // no tiles: radius <= 0, or the rectangle clipped away
+                    if (gcount) gcount[i] = 0;
+                    if (reach) reach[i] = 0u;
+                }
+            }
+            const bool defer = area > BIN_INLINE_AREA;
+            defer_append(defer, area >= BIN_BIG_AREA, p, lane, dcnt, dl);
+            if (area > 0 && !defer) tiles(i, g, x0, y0, x1, y1, area, true);
+        }
+        __syncthreads();
+        const int nbig = dcnt[0], nlist = nbig + dcnt[1];
+        for (int k = threadIdx.x; k < nlist; k += BIN_BLOCK) {
+            const int i = sbeg + deferred_at(k, nbig, dl);
+            const In g = load(i, true);
+            int x0, y0, x1, y1;
+            tile_rect(g.q.x, g.q.y, g.r, gx, gy, x0, y0, x1, y1);
+            tiles(i, g, x0, y0, x1, y1, (x1 - x0) * (y1 - y0), false);
+        }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) pairs += __shfl_xor(pairs, o);
@@ -355,13 +437,16 @@ bin_scatter_kernel(int P, const float2 *__restrict__ uv, const float *__restrict
                    const int *__restrict__ radius, int gx, int gy, int T, int chunk, int *__restrict__ matrix,
                    const int *__restrict__ tile_range, long long capacity, unsigned long long *__restrict__ keys,
                    int *__restrict__ overflow, int *__restrict__ goff_incl, int *__restrict__ owner,
-                   const int *__restrict__ chunk_off, long long S, int kbits, const unsigned *__restrict__ reach) {
+                   const int *__restrict__ chunk_off, long long S, int kbits, const unsigned *__restrict__ reach, int seg) {
     // Pair-map mode (goff_incl != null): the kernel also produces goff_incl, the inclusive prefix of tiles per
     // Gaussian (chunk offset from K2b + a workgroup scan of the rectangle areas), and the low key word is the pair
     // slot j = goff_excl[i] + k (k-th tile of the splat's rectangle) instead of the Gaussian id: slots grow with
     // the id, so ties still order by ascending id, and the sorted keys directly give the pair map.
     extern __shared__ __attribute__((aligned(16))) int cnt[];
     __shared__ int wave_pairs[BIN_BLOCK / 64];
+    __shared__ unsigned short dl[BIN_SEG];   // the deferred list (see "area order")
+    __shared__ int dcnt[2];
+    __shared__ int jbuf[BIN_SEG];   // slot base of the Gaussians on the list
     const int wg = blockIdx.x;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     {   // frame batch: every frame owns `capacity` key / owner slots
@@ -377,39 +462,11 @@ bin_scatter_kernel(int P, const float2 *__restrict__ uv, const float *__restrict
         for (int t = threadIdx.x; t < T; t += BIN_BLOCK) cnt[t] = tile_range[2 * t] + row[t];
         __syncthreads();
     }
-    const int beg = wg * chunk, end = imin_(P, beg + chunk);
-    for (int base = beg; base < end; base += BIN_BLOCK) {  // uniform trip count: the scan below needs every thread
-        const int i = base + threadIdx.x;
-        const int r = i < end ? radius[i] : 0;
-        int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
-        if (r > 0) {
-            const float2 q = uv[i];
-            tile_rect(q.x, q.y, r, gx, gy, x0, y0, x1, y1);
-        }
-        // reach word of the count kernel: keep flags of the rectangle's tiles, or (REACH_BIG) the kept count of a large one
-        const unsigned rw = (reach && r > 0) ? reach[i] : 0u;
-        const bool big = (rw & REACH_BIG) != 0u;
-        int j = 0;
-        if (goff_incl) {
-            const int area = !reach ? (x1 - x0) * (y1 - y0) : big ? reach_big_count(rw, x1 - x0, y1 - y0) : __popc(rw);
-            const int inc = wave_incl_scan_i(area, lane);
-            if (lane == 63) wave_pairs[w] = inc;
-            __syncthreads();
-            int woff = 0, tot = 0;
-#pragma unroll
-            for (int k = 0; k < BIN_BLOCK / 64; ++k) {
-                const int v = wave_pairs[k];
-                woff += k < w ? v : 0;
-                tot += v;
-            }
-            __syncthreads();
-            // clamped to the capacity: after an overflowing (flagged) sort every consumer still stays inside its buffers
-            if (i < end) goff_incl[i] = (int)(((long long)(running + woff + inc) < capacity) ? (long long)(running + woff + inc) : capacity);
-            j = running + woff + inc - area;
-            running += tot;
-        }
-        if (r <= 0) continue;
-        const unsigned long long dkey = (unsigned long long)__float_as_uint(depth[i]) << 32;
+    // the pairs of Gaussian i (some tile kept); j: its slot base (pair-map mode); small_only: the caller knows the rectangle has at most
+    // BIN_INLINE_AREA tiles (no cell form of the reach word)
+    auto emit = [&](int i, int x0, int y0, int x1, int y1, unsigned rw, unsigned dbits, int j, const bool small_only) {
+        const bool big = !small_only && (rw & REACH_BIG) != 0u;
+        const unsigned long long dkey = (unsigned long long)dbits << 32;
         unsigned bit = 1u;
         const int csh = big ? reach_cell_shift(x1 - x0, y1 - y0) : 0, cnx = big ? ((x1 - x0 - 1) >> csh) + 1 : 0;
         auto kept = [&](int tx, int ty) -> bool {   // (k of the packed keys and the slots count the KEPT tiles, in row-major order)
@@ -432,7 +489,7 @@ bin_scatter_kernel(int P, const float2 *__restrict__ uv, const float *__restrict
                     else *overflow = 1;
                     ++lo;
                 }
-            continue;
+            return;
         }
         for (int ty = y0; ty < y1; ++ty)
             for (int tx = x0; tx < x1; ++tx) {
@@ -449,6 +506,80 @@ bin_scatter_kernel(int P, const float2 *__restrict__ uv, const float *__restrict
                 }
                 ++j;
             }
+    };
+    // One Gaussian's inputs (rw: the reach word; d: the depth's bits).  The pass in index order loads those of its NEXT trip before it
+    // works on this trip's, every load unconditional: the two barriers of a trip's scan kept the chain radius -> uv -> reach word ->
+    // depth of dependent loads from overlapping anything (155 -> 135 us per 25-frame launch on the bench scene).
+    struct In {
+        int r;
+        float2 q;
+        unsigned rw, d;
+    };
+    auto load = [&](int i, bool valid) -> In {
+        In v;
+        v.r = 0; v.q = make_float2(0.f, 0.f); v.rw = 0u; v.d = 0u;
+        if (valid) {
+            v.r = radius[i];
+            v.q = uv[i];
+            if (reach) v.rw = reach[i];
+            v.d = __float_as_uint(depth[i]);
+        }
+        return v;
+    };
+    const int beg = wg * chunk, end = imin_(P, beg + chunk);
+    for (int sbeg = beg; sbeg < end; sbeg += seg) {   // segments of the deferred list (one, unless BIN_MAX_NB capped the rows)
+        const int n = imin_(seg, end - sbeg);
+        __syncthreads();   // the last segment's list has been walked
+        if (threadIdx.x < 2) dcnt[threadIdx.x] = 0;
+        __syncthreads();
+        // ---- in INDEX order (prefix sums over the Gaussian index; uniform trip count: the scan needs every thread): kept tiles per
+        // Gaussian -> goff_incl and the slot base j; the pairs of the small rectangles; the others go on the list with their j
+        In nxt = load(sbeg + threadIdx.x, (int)threadIdx.x < n);
+        for (int base = 0; base < n; base += BIN_BLOCK) {
+            const int p = base + threadIdx.x, i = sbeg + p;
+            const In g = nxt;
+            nxt = load(i + BIN_BLOCK, p + BIN_BLOCK < n);
+            const int r = g.r;
+            int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+            if (r > 0) tile_rect(g.q.x, g.q.y, r, gx, gy, x0, y0, x1, y1);
+            // reach word of the count kernel: keep flags of the rectangle's tiles, or (REACH_BIG) the kept count of a large one
+            const unsigned rw = r > 0 ? g.rw : 0u;
+            int j = 0;
+            if (goff_incl) {
+                const bool big = (rw & REACH_BIG) != 0u;
+                const int area = !reach ? (x1 - x0) * (y1 - y0) : big ? reach_big_count(rw, x1 - x0, y1 - y0) : __popc(rw);
+                const int inc = wave_incl_scan_i(area, lane);
+                if (lane == 63) wave_pairs[w] = inc;
+                __syncthreads();
+                int woff = 0, tot = 0;
+#pragma unroll
+                for (int k = 0; k < BIN_BLOCK / 64; ++k) {
+                    const int v = wave_pairs[k];
+                    woff += k < w ? v : 0;
+                    tot += v;
+                }
+                __syncthreads();
+                // clamped to the capacity: after an overflowing (flagged) sort every consumer still stays inside its buffers
+                if (p < n) goff_incl[i] = (int)(((long long)(running + woff + inc) < capacity) ? (long long)(running + woff + inc) : capacity);
+                j = running + woff + inc - area;
+                running += tot;
+            }
+            // the tile loop walks the whole rectangle (a reach word without a kept tile: nothing to walk)
+            const int walk = (reach && rw == 0u) ? 0 : (x1 - x0) * (y1 - y0);
+            const bool defer = walk > BIN_INLINE_AREA;
+            defer_append(defer, walk >= BIN_BIG_AREA, p, lane, dcnt, dl);
+            if (defer) jbuf[p] = j;
+            if (walk > 0 && !defer) emit(i, x0, y0, x1, y1, rw, g.d, j, true);
+        }
+        __syncthreads();
+        const int nbig = dcnt[0], nlist = nbig + dcnt[1];
+        for (int k = threadIdx.x; k < nlist; k += BIN_BLOCK) {
+            const int p = deferred_at(k, nbig, dl), i = sbeg + p;
+            const In g = load(i, true);
+            int x0, y0, x1, y1;
+            tile_rect(g.q.x, g.q.y, g.r, gx, gy, x0, y0, x1, y1);
+            emit(i, x0, y0, x1, y1, g.rw, g.d, jbuf[p], false);
+        }
     }
 }
 
@@ -817,7 +948,7 @@ static int bin_count_impl(int F, int P, const float *uv, const int32_t *radius, 
     if (p.lds) {
         SPLAT_LAUNCH("bin_count", bin_count_kernel<true>, dim3(p.NB, F), dim3(BIN_BLOCK), (size_t)p.T * sizeof(int), s,
                      P, (const float2 *)uv, radius, p.gx, p.gy, p.T, p.chunk, matrix, gcount, chunk_sum, S, conic, opacity, opacity_fs,
-                     reach);
+                     reach, bin_segment());
     } else {
         // rows: [0] counts, [1] fill counters of K3
         for (int f = 0; f < F; ++f)
@@ -825,7 +956,8 @@ static int bin_count_impl(int F, int P, const float *uv, const int32_t *radius, 
         const int nblk = p.nchunk;
         const int chunk = (P + nblk - 1) / nblk;
         SPLAT_LAUNCH("bin_count", bin_count_kernel<false>, dim3(nblk, F), dim3(BIN_BLOCK), 0, s, P, (const float2 *)uv,
-                     radius, p.gx, p.gy, p.T, chunk > 0 ? chunk : 1, matrix, gcount, chunk_sum, S, conic, opacity, opacity_fs, reach);
+                     radius, p.gx, p.gy, p.T, chunk > 0 ? chunk : 1, matrix, gcount, chunk_sum, S, conic, opacity, opacity_fs, reach,
+                     bin_segment());
     }
     SPLAT_POST_LAUNCH();
     if (p.lds) {
@@ -857,7 +989,7 @@ static int bin_sort_impl(int F, int P, const float *uv, const float *depth, cons
         SPLAT_LAUNCH("bin_scatter", bin_scatter_kernel<true>, dim3(p.NB, F), dim3(BIN_BLOCK), (size_t)p.T * sizeof(int), s,
                      P, (const float2 *)uv, depth, radius, p.gx, p.gy, p.T, p.chunk, matrix, tile_range,
                      (long long)capacity, (unsigned long long *)keys, overflow_out, goff_incl, owner_scratch, chunk_off, S, kbits,
-                     reach);
+                     reach, bin_segment());
     } else {
         // fill counters live in tile_count's neighbour: reuse matrix row "1" = matrix + T (allocated: NB=1 -> need 2 rows)
         for (int f = 0; f < F; ++f)
@@ -866,7 +998,8 @@ static int bin_sort_impl(int F, int P, const float *uv, const float *depth, cons
         const int chunk = (P + nblk - 1) / nblk;
         SPLAT_LAUNCH("bin_scatter", bin_scatter_kernel<false>, dim3(nblk, F), dim3(BIN_BLOCK), 0, s, P, (const float2 *)uv,
                      depth, radius, p.gx, p.gy, p.T, chunk > 0 ? chunk : 1, matrix, tile_range, (long long)capacity,
-                     (unsigned long long *)keys, overflow_out, goff_incl, owner_scratch, chunk_off, S, kbits, reach);
+                     (unsigned long long *)keys, overflow_out, goff_incl, owner_scratch, chunk_off, S, kbits, reach,
+                     bin_segment());
     }
     SPLAT_POST_LAUNCH();
     SPLAT_LAUNCH("tile_sort", tile_sort_kernel, dim3((unsigned)((size_t)p.T * F)), dim3(SORT_BLOCK), 0, s, p.T, tile_range, (long long)capacity,

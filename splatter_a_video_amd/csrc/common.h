@@ -33,7 +33,7 @@ void splat_set_error(const char *fmt, ...);
 
 bool splat_deterministic();   // splat_set_deterministic (runtime.hip)
 // splat_set_option keys (runtime.hip): kernel selection through the ABI, read at launch time
-enum { SPLAT_OPT_BWD_QUARTERS = 0, SPLAT_OPT_SETS_STD, SPLAT_OPT_BIN_SLOT_KEYS, SPLAT_OPT_COUNT };
+enum { SPLAT_OPT_BWD_QUARTERS = 0, SPLAT_OPT_SETS_STD, SPLAT_OPT_BIN_SLOT_KEYS, SPLAT_OPT_BIN_SHORT_SEGMENTS, SPLAT_OPT_COUNT };
 int splat_option(int id);
 
 // ---------------------------------------------------------------- profiled launches

@@ -40,8 +40,8 @@ extern "C" int splat_get_deterministic(void) { return g_deterministic.load(std::
 bool splat_deterministic() { return g_deterministic.load(std::memory_order_relaxed) != 0; }
 
 // Options: kernel selection through the ABI (splat_set_option) instead of getenv() inside the library.
-static const char *const g_opt_key[SPLAT_OPT_COUNT] = {"bwd_quarters", "sets_std", "bin_slot_keys"};
-static std::atomic<int> g_opt[SPLAT_OPT_COUNT] = {{1}, {1}, {0}};
+static const char *const g_opt_key[SPLAT_OPT_COUNT] = {"bwd_quarters", "sets_std", "bin_slot_keys", "bin_short_segments"};
+static std::atomic<int> g_opt[SPLAT_OPT_COUNT] = {{1}, {1}, {0}, {0}};
 int splat_option(int id) { return g_opt[id].load(std::memory_order_relaxed); }
 extern "C" int splat_set_option(const char *key, int value) {
     SPLAT_CHECK_ARG(key != nullptr, "null key");
