@@ -1125,6 +1125,38 @@ int splat_layer_centroids(int F, int P, int S, int I, const void *tab, const int
                           const float *cubic, int cubic_layout, float *centroid, void *scratch, size_t scratch_bytes,
                           splat_stream_t stream);
 
+/* ---- feature lifting: per-Gaussian features from per-frame 2-D maps (csrc/lift.hip).  With geometry and opacity frozen the
+ *      composited image is linear in the feature, out[p, c] = sum_g w[p, g] f[g, c], w = alpha * T under the forward's rules; the
+ *      two calls apply the transposed operator to maps y [F, D, H, W] with pixel weights pw [F, H, W] (NULL: ones):
+ *        num[g, c] = sum_f sum_p pw w y[p, c]      den[g] = sum_f sum_p pw w
+ *      num / den is the visibility-weighted average of what Gaussian g shows; with y = A f - target, num is the gradient of the
+ *      least-squares fit.
+ *      splat_blend_lift_batch, ONE launch over (frame, tile), the lists laid out as splat_alpha_blending_forward_batch_set takes
+ *      them (uv [F, P, 2], conic [F, P, 3], opacity + f * opacity_frame_stride, idx_sorted / slot_sorted [F, capacity],
+ *      tile_range [F, T, 2]).  The walk is the forward's, decision for decision: the exponent from csrc/blend_power.h relative to
+ *      the tile centre, skip alpha < 1/255, stop the pixel when T (1 - alpha) < 1e-4, alpha capped at 0.99, T the sequential
+ *      product in list order.  No replay, no dL/dalpha, no geometry terms.  Per list entry one record
+ *        [sum_p pw w y[c0 .. c0 + cn) | sum_p pw w (want_den != 0) | pad]
+ *      of splat_lift_pair_stride(cn, want_den) floats (a multiple of 4; 0 for cn outside 1..32) goes to
+ *      pair_sums[(f * capacity + slot_sorted[entry]) * stride] (pair_sums 16-byte aligned).  Every entry of every list is written:
+ *      entries behind the last batch of 64 the tile walked get zeros.  A pixel of weight 0 contributes exactly 0 whatever its map
+ *      value, NaN included (selected, not multiplied); pixels outside the image contribute nothing.  The pixel reduction runs on
+ *      v_mfma_f32_16x16x4_f32 (lanes = list entries, the wave's window of pw y staged once as operands, the weight sum as one more
+ *      column); the four waves' partial sums are added through LDS in the order 0 .. 3.
+ *      splat_lift_fold, ONE streaming launch: per Gaussian i it ADDS onto num[i * num_stride + c0 + k] (k < cn) and, with
+ *      want_den, onto den[i] the frames' sums in ascending frame order, a frame's sum being that of the records at slots
+ *      [goff_incl[f, i-1], goff_incl[f, i]) in ascending order.  Slots at or beyond min(goff_incl[f, P - 1], capacity) are not read.
+ *      No float atomics, plain stores only: both run under splat_set_deterministic(1) and give the same bits on every run.
+ *      Sizes < 1, cn outside 1..32, c0 + cn > D (num_stride), a NULL required pointer (den may be NULL without want_den), a
+ *      misaligned pair_sums: SPLAT_E_ARG before any HIP call. ---- */
+size_t splat_lift_pair_stride(int cn, int want_den);
+int splat_blend_lift_batch(int F, int P, int D, int c0, int cn, const float *uv, const float *conic, const float *opacity,
+                           int64_t opacity_frame_stride, const int32_t *idx_sorted, const int32_t *tile_range,
+                           const int32_t *slot_sorted, int64_t capacity, int W, int H, const float *maps,
+                           const float *pixel_weight, int want_den, float *pair_sums, splat_stream_t stream);
+int splat_lift_fold(int F, int P, int cn, int want_den, int64_t capacity, const int32_t *goff_incl, const float *pair_sums,
+                    float *num, int64_t num_stride, int c0, float *den, splat_stream_t stream);
+
 /* ---- measurement hooks (bench.py: live per-kernel timing with HIP events on the launch stream) ---- */
 void splat_profile_enable(int on);
 void splat_profile_reset(void);

@@ -67,6 +67,7 @@ SYMBOLS = [
     "splat_alpha_blending_forward_batch_set", "splat_alpha_blending_backward_batch_set_packed", "splat_frames_wide_fold",
     "splat_blend_fit_color", "splat_tile_loss_sum",
     "splat_frame_preprocess_layer_batch", "splat_layer_centroids_scratch_bytes", "splat_layer_centroids",
+    "splat_lift_pair_stride", "splat_blend_lift_batch", "splat_lift_fold",
 ]
 
 
@@ -156,6 +157,10 @@ def lib() -> ctypes.CDLL:
         L.splat_layer_centroids_scratch_bytes.restype = ctypes.c_size_t
         L.splat_layer_centroids_scratch_bytes.argtypes = [i, i]
         L.splat_layer_centroids.argtypes = [i, i, i, i, p, p, p, p, i, p, p, ctypes.c_size_t, p]
+        L.splat_lift_pair_stride.restype = ctypes.c_size_t
+        L.splat_lift_pair_stride.argtypes = [i, i]
+        L.splat_blend_lift_batch.argtypes = [i, i, i, i, i, p, p, p, i64, p, p, p, i64, i, i, p, p, i, p, p]
+        L.splat_lift_fold.argtypes = [i, i, i, i, i64, p, p, p, i64, i, p, p]
         if L.splat_abi_version() != ABI_VERSION:
             raise SplatError("libsplat_hip.so ABI version mismatch; rebuild it")
         _lib = L

@@ -6,10 +6,11 @@
 // and no gradient image go through memory; no dL/dalpha, no replay by division, no geometry terms; no float atomics.
 #include "blend_power.h"
 #include "common.h"
+#include "tile_stage.h"
 
 namespace {
 
-constexpr int FIT_SB = 64;   // list entries staged per batch: lane l of wave 0 fetches entry l
+constexpr int FIT_SB = STAGE_SB;   // list entries staged per batch (tile_stage.h): lane l of wave 0 fetches entry l
 
 struct FitArgs {
     int P;
@@ -40,67 +41,6 @@ struct FitLDS {
     float red[4];
     int last[4];
 };
-
-// What lane l of wave 0 holds of entry l of a batch between its fetch and the moment it is parked in LDS: the walks fetch one
-// batch ahead (and the ids two ahead), so that no global load's latency is waited for between two batches.
-struct FitFetch {
-    float2 u;
-    float cA, cB, cC, o;
-    float4 col;     // pass 1: the colour
-    int slot;       // pass 2: the pair slot
-    bool valid;
-};
-
-// id of entry q of the tile's list, -1 behind its end (n) and for lanes that fetch nothing
-__device__ __forceinline__ int fit_load_id(const FitArgs &A, int tid, int beg, int q, int n) {
-    return (tid < FIT_SB && q < n) ? A.idx_sorted[beg + q] : -1;
-}
-
-template <bool COLOURS>
-__device__ __forceinline__ FitFetch fit_load(const FitArgs &A, int id, int beg, int q) {
-    FitFetch f;
-    f.valid = (unsigned)id < (unsigned)A.P;   // (an id outside [0, P) becomes an entry that never contributes)
-    f.u = make_float2(0.f, 0.f);
-    f.cA = f.cB = f.cC = f.o = 0.f;
-    f.col = make_float4(0.f, 0.f, 0.f, 0.f);
-    f.slot = -1;
-    if (f.valid) {
-        f.u = A.uv[id];
-        f.cA = A.conic[3 * (size_t)id];
-        f.cB = A.conic[3 * (size_t)id + 1];
-        f.cC = A.conic[3 * (size_t)id + 2];
-        f.o = A.opacity[id];
-        if (COLOURS) f.col = make_float4(A.feature[3 * (size_t)id], A.feature[3 * (size_t)id + 1], A.feature[3 * (size_t)id + 2], 0.f);
-        else f.slot = A.slot_sorted[beg + q];
-    }
-    return f;
-}
-
-// lanes 0 .. FIT_SB - 1 of the workgroup park their entry with the mask of the 8x8 blocks it can reach (the forward's own
-// conservative test: never false for a splat that contributes, so a wave that leaves an entry out makes the decisions it would
-// have made -- alpha < 1/255 on all its pixels); an entry that is not valid reaches none
-template <bool COLOURS>
-__device__ __forceinline__ void fit_park(FitLDS &L, int tid, const FitFetch &f, float tcx, float tcy) {
-    if (tid >= FIT_SB) return;
-    float4 k0 = make_float4(-__builtin_inff(), 0.f, 0.f, 0.f), k1 = make_float4(0.f, 0.f, 0.f, 0.f);
-    int mask = 0;
-    if (f.valid) {
-        const PowerCoef k = power_coeffs(f.u.x, f.u.y, f.cA, f.cB, f.cC, f.o, tcx, tcy);
-        k0 = make_float4(k.q0, k.qx, k.qy, k.qxx);
-        k1 = make_float4(k.qxy, k.qyy, 0.f, 0.f);
-        const CullP cp = cull_params(f.cA, f.cB, f.cC, f.o);
-#pragma unroll
-        for (int ww = 0; ww < 4; ++ww) {
-            const float x0 = tcx - 7.5f + (float)(8 * (ww & 1)), y0 = tcy - 7.5f + (float)(8 * (ww >> 1));
-            if (cull_test(f.u.x, f.u.y, f.cA, f.cB, f.cC, cp, x0, x0 + 7.f, y0, y0 + 7.f)) mask |= 1 << ww;
-        }
-    }
-    L.c0[tid] = k0;
-    L.c1[tid] = k1;
-    L.mask[tid] = mask;
-    if (COLOURS) L.col[tid] = f.col;
-    else L.slot[tid] = f.slot;
-}
 
 // One evaluation of the forward (blend.hip, blend_fwd_kernel): the weight alpha * T of the splat on this pixel, 0 where it is
 // skipped (alpha < 1/255) or the pixel stops; T < 0: the pixel is finished, |T| its final transmittance.
@@ -141,6 +81,7 @@ blend_fit_color_kernel(const FitArgs A) {
     const int2 range = A.tile_range[tile];
     const int beg = imax_(range.x, 0);
     const int n = imax_((int)(A.capacity < (long long)range.y ? A.capacity : (long long)range.y) - beg, 0);
+    const int *idx = A.idx_sorted + beg, *slots = A.slot_sorted + beg;   // the tile's list
 
     if (tid == 0) {   // the inert entry
         L.c0[FIT_SB] = make_float4(-__builtin_inff(), 0.f, 0.f, 0.f);
@@ -152,14 +93,14 @@ blend_fit_color_kernel(const FitArgs A) {
     float T = inside ? 1.f : -1.f, F0 = 0.f, F1 = 0.f, F2 = 0.f;
     int last = 0;
     {
-        int id = fit_load_id(A, tid, beg, tid, n);
-        FitFetch pay = fit_load<true>(A, id, beg, tid);
-        id = fit_load_id(A, tid, beg, FIT_SB + tid, n);
+        int id = stage_load_id(idx, tid, tid, n);
+        StageFetch pay = stage_load<true>(A.P, A.uv, A.conic, A.opacity, A.feature, slots, id, tid);
+        id = stage_load_id(idx, tid, FIT_SB + tid, n);
         for (int base = 0; base < n; base += FIT_SB) {
-            fit_park<true>(L, tid, pay, tcx, tcy);
+            stage_park<true>(L, tid, pay, tcx, tcy);
             __syncthreads();
-            pay = fit_load<true>(A, id, beg, base + FIT_SB + tid);        // the next batch, in flight during this one's walk
-            id = fit_load_id(A, tid, beg, base + 2 * FIT_SB + tid, n);
+            pay = stage_load<true>(A.P, A.uv, A.conic, A.opacity, A.feature, slots, id, base + FIT_SB + tid);   // the next batch, in flight during this one's walk
+            id = stage_load_id(idx, tid, base + 2 * FIT_SB + tid, n);
             if (__ballot(T >= 0.f) != 0ull) {
                 unsigned long long m = __ballot((L.mask[lane] >> w) & 1);
                 while (m) {
@@ -211,16 +152,16 @@ blend_fit_color_kernel(const FitArgs A) {
     // a row, the 16 row sums of the tile through LDS, added in a fixed order by the lane that stores the entry's record
     T = inside ? 1.f : -1.f;
     {
-        int id = fit_load_id(A, tid, beg, tid, nproc);
-        FitFetch pay = fit_load<false>(A, id, beg, tid);
-        id = fit_load_id(A, tid, beg, FIT_SB + tid, nproc);
+        int id = stage_load_id(idx, tid, tid, nproc);
+        StageFetch pay = stage_load<false>(A.P, A.uv, A.conic, A.opacity, A.feature, slots, id, tid);
+        id = stage_load_id(idx, tid, FIT_SB + tid, nproc);
         const int prow = 4 * w + (lane >> 4);
         for (int base = 0; base < nproc; base += FIT_SB) {
             const int nb = imin_(FIT_SB, nproc - base);
-            fit_park<false>(L, tid, pay, tcx, tcy);
+            stage_park<false>(L, tid, pay, tcx, tcy);
             __syncthreads();
-            pay = fit_load<false>(A, id, beg, base + FIT_SB + tid);
-            id = fit_load_id(A, tid, beg, base + 2 * FIT_SB + tid, nproc);
+            pay = stage_load<false>(A.P, A.uv, A.conic, A.opacity, A.feature, slots, id, base + FIT_SB + tid);
+            id = stage_load_id(idx, tid, base + 2 * FIT_SB + tid, nproc);
             unsigned long long m = __ballot((L.mask[lane] >> w) & 1);
             while (m) {
                 float wg[4], g[4][3];
