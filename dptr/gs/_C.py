@@ -9,7 +9,6 @@ No autograd here (the reference's ``_C`` has none either) and no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Optional, Tuple
 
 import torch
@@ -35,8 +34,8 @@ def project_point_forward(xyz, intr, extr, W, H, nearest, extent) -> Tuple[Tenso
     P, dev = xyz.shape[0], xyz.device
     uv = torch.empty(P, 2, dtype=torch.float32, device=dev)
     depth = torch.empty(P, 1, dtype=torch.float32, device=dev)
-    L.check(L.lib().splat_project_point_forward(L.ci(P), L.ptr(xyz), L.ptr(_intr4(intr)), L.ptr(_extr12(extr)), L.ci(W), L.ci(H),
-                                                L.cf(nearest), L.cf(extent), L.ci(0), L.ptr(uv), L.ptr(depth), L.stream()))
+    L.check(L.lib().splat_project_point_forward(P, L.ptr(xyz), L.ptr(_intr4(intr)), L.ptr(_extr12(extr)), W, H,
+                                                nearest, extent, 0, L.ptr(uv), L.ptr(depth), L.stream()))
     return uv, depth
 
 
@@ -47,7 +46,7 @@ def project_point_backward(xyz, intr, extr, W, H, uv, depth, dL_duv, dL_ddepth) 
     dintr = torch.zeros(4, dtype=torch.float32, device=dev)
     dextr12 = torch.zeros(12, dtype=torch.float32, device=dev)
     L.check(L.lib().splat_project_point_backward(
-        L.ci(P), L.ptr(xyz), L.ptr(_intr4(intr)), L.ptr(_extr12(extr)), L.ci(W), L.ci(H), L.ci(0), L.ptr(L.need(depth, "depth")),
+        P, L.ptr(xyz), L.ptr(_intr4(intr)), L.ptr(_extr12(extr)), W, H, 0, L.ptr(L.need(depth, "depth")),
         L.ptr(L.need(dL_duv, "dL_duv")), L.ptr(L.need(dL_ddepth, "dL_ddepth")), L.ptr(dxyz), L.ptr(dintr), L.ptr(dextr12), L.stream()))
     dextr = torch.zeros(extr.shape, dtype=torch.float32, device=dev)
     dextr.view(-1)[:12] = dextr12
@@ -60,7 +59,7 @@ def compute_cov3d_forward(scales, uquats, visible) -> Tensor:
     uquats = _points(uquats, "uquats", 4)
     P = scales.shape[0]
     cov3d = torch.empty(P, 6, dtype=torch.float32, device=scales.device)
-    L.check(L.lib().splat_compute_cov3d_forward(L.ci(P), L.ptr(scales), L.ptr(uquats), L.ptr(_vis(visible, P, scales.device)),
+    L.check(L.lib().splat_compute_cov3d_forward(P, L.ptr(scales), L.ptr(uquats), L.ptr(_vis(visible, P, scales.device)),
                                                 L.ptr(cov3d), L.stream()))
     return cov3d
 
@@ -70,7 +69,7 @@ def compute_cov3d_backward(scales, uquats, visible, dL_dcov3Ds) -> Tuple[Tensor,
     uquats = _points(uquats, "uquats", 4)
     P = scales.shape[0]
     ds, dq = torch.empty_like(scales), torch.empty_like(uquats)
-    L.check(L.lib().splat_compute_cov3d_backward(L.ci(P), L.ptr(scales), L.ptr(uquats), L.ptr(_vis(visible, P, scales.device)),
+    L.check(L.lib().splat_compute_cov3d_backward(P, L.ptr(scales), L.ptr(uquats), L.ptr(_vis(visible, P, scales.device)),
                                                  L.ptr(L.need(dL_dcov3Ds, "dL_dcov3Ds")), L.ptr(ds), L.ptr(dq), L.stream()))
     return ds, dq
 
@@ -83,8 +82,8 @@ def ewa_project_forward(xyz, cov3d, intr, extr, uv, W, H, visible) -> Tuple[Tens
     radius = torch.empty(P, dtype=torch.int32, device=dev)
     tiles = torch.empty(P, dtype=torch.int32, device=dev)
     L.check(L.lib().splat_ewa_project_forward(
-        L.ci(P), L.ptr(xyz), L.ptr(_points(cov3d, "cov3d", 6)), L.ptr(_intr4(intr)), L.ptr(_extr12(extr)), L.ptr(_points(uv, "uv", 2)),
-        L.ci(W), L.ci(H), L.ptr(_vis(visible, P, dev)), L.ci(0), L.ptr(conic), L.ptr(radius), L.ptr(tiles), L.stream()))
+        P, L.ptr(xyz), L.ptr(_points(cov3d, "cov3d", 6)), L.ptr(_intr4(intr)), L.ptr(_extr12(extr)), L.ptr(_points(uv, "uv", 2)),
+        W, H, L.ptr(_vis(visible, P, dev)), 0, L.ptr(conic), L.ptr(radius), L.ptr(tiles), L.stream()))
     return conic, radius, tiles
 
 
@@ -96,7 +95,7 @@ def ewa_project_backward(xyz, cov3d, intr, extr, radius, dL_dconic) -> Tuple[Ten
     dintr = torch.zeros(4, dtype=torch.float32, device=dev)
     dextr12 = torch.zeros(12, dtype=torch.float32, device=dev)
     L.check(L.lib().splat_ewa_project_backward(
-        L.ci(P), L.ptr(xyz), L.ptr(cov3d), L.ptr(_intr4(intr)), L.ptr(_extr12(extr)), L.ci(0), L.ci(0), L.ci(0),
+        P, L.ptr(xyz), L.ptr(cov3d), L.ptr(_intr4(intr)), L.ptr(_extr12(extr)), 0, 0, 0,
         L.ptr(L.need(radius, "radius", torch.int32)), L.ptr(L.need(dL_dconic, "dL_dconic")), L.ptr(dxyz), L.ptr(dcov), L.ptr(dintr),
         L.ptr(dextr12), L.stream()))
     dextr = torch.zeros(extr.shape, dtype=torch.float32, device=dev)
@@ -114,8 +113,8 @@ def compute_gaussian_key(uv, depth, W, H, radius, tiles) -> Tuple[Tensor, Tensor
     M = int(cum[-1].item()) if P > 0 else 0
     key = torch.zeros(M, dtype=torch.int64, device=dev)
     gidx = torch.zeros(M, dtype=torch.int32, device=dev)
-    L.check(L.lib().splat_compute_gaussian_key(L.ci(P), L.ptr(uv), L.ptr(L.need(depth, "depth")),
-                                               L.ptr(L.need(radius.reshape(-1), "radius", torch.int32)), L.ptr(cum), L.ci(W), L.ci(H),
+    L.check(L.lib().splat_compute_gaussian_key(P, L.ptr(uv), L.ptr(L.need(depth, "depth")),
+                                               L.ptr(L.need(radius.reshape(-1), "radius", torch.int32)), L.ptr(cum), W, H,
                                                L.ptr(key), L.ptr(gidx), L.stream()))
     return key, gidx
 
@@ -123,7 +122,7 @@ def compute_gaussian_key(uv, depth, W, H, radius, tiles) -> Tuple[Tensor, Tensor
 def compute_tile_gaussian_range(W, H, tiles, key_sorted) -> Tensor:
     tr = torch.zeros(_tiles(W, H), 2, dtype=torch.int32, device=key_sorted.device)
     ks = L.need(key_sorted, "key_sorted", torch.int64)
-    L.check(L.lib().splat_compute_tile_gaussian_range(ctypes.c_int64(ks.numel()), L.ptr(ks), L.ptr(tr), L.stream()))
+    L.check(L.lib().splat_compute_tile_gaussian_range(ks.numel(), L.ptr(ks), L.ptr(tr), L.stream()))
     return tr
 
 
@@ -133,8 +132,8 @@ def _sh_fwd(shs, degree, view_dirs, visible, free):
     P, dev = shs.shape[0], shs.device
     colors = torch.empty(P, 3, dtype=torch.float32, device=dev)
     clamped = None if free else torch.empty(P, 3, dtype=torch.uint8, device=dev)
-    L.check(L.lib().splat_compute_sh_forward(L.ci(P), L.ptr(shs), L.ci(degree), L.ptr(_points(view_dirs, "view_dirs", 3)),
-                                             L.ptr(_vis(visible, P, dev)), L.ci(1 if free else 0), L.ptr(colors), L.ptr(clamped),
+    L.check(L.lib().splat_compute_sh_forward(P, L.ptr(shs), degree, L.ptr(_points(view_dirs, "view_dirs", 3)),
+                                             L.ptr(_vis(visible, P, dev)), 1 if free else 0, L.ptr(colors), L.ptr(clamped),
                                              L.stream()))
     return colors, clamped
 
@@ -145,9 +144,9 @@ def _sh_bwd(shs, degree, view_dirs, visible, clamped, dL_dcolor, free):
     dirs = _points(view_dirs, "view_dirs", 3)
     dshs = torch.zeros_like(shs)
     ddirs = torch.empty_like(dirs)
-    L.check(L.lib().splat_compute_sh_backward(L.ci(P), L.ptr(shs), L.ci(degree), L.ptr(dirs), L.ptr(_vis(visible, P, dev)),
-                                              L.ptr(clamped), L.ci(1 if free else 0), L.ptr(L.need(dL_dcolor, "dL_dcolor")),
-                                              L.ci(0), L.ptr(dshs), L.ptr(ddirs), L.stream()))
+    L.check(L.lib().splat_compute_sh_backward(P, L.ptr(shs), degree, L.ptr(dirs), L.ptr(_vis(visible, P, dev)),
+                                              L.ptr(clamped), 1 if free else 0, L.ptr(L.need(dL_dcolor, "dL_dcolor")),
+                                              0, L.ptr(dshs), L.ptr(ddirs), L.stream()))
     return dshs, ddirs
 
 
@@ -180,9 +179,9 @@ def _blend_fwd(uv, conic, opacity, feature, bias, idx_sorted, tile_range, bg, W,
     gs_idx = torch.empty(H, W, K, dtype=torch.int32, device=dev) if K > 0 else None
     pack = torch.empty(max(P, 1) * L.lib().splat_blend_pack_floats(C), dtype=torch.float32, device=dev)
     L.check(L.lib().splat_alpha_blending_forward(
-        L.ci(P), L.ci(C), L.ptr(uv), L.ptr(L.need(conic, "conic")), L.ptr(L.need(opacity, "opacity")), L.ptr(feature),
+        P, C, L.ptr(uv), L.ptr(L.need(conic, "conic")), L.ptr(L.need(opacity, "opacity")), L.ptr(feature),
         L.ptr(None if bias is None else L.need(bias, "opacity_bias")), L.ptr(L.need(idx_sorted, "idx_sorted", torch.int32)),
-        L.ptr(L.need(tile_range, "tile_range", torch.int32)), L.cf(bg), L.ptr(None), L.ci(W), L.ci(H), L.ci(K), L.ci(1 if trunc else 0),
+        L.ptr(L.need(tile_range, "tile_range", torch.int32)), bg, L.ptr(None), W, H, K, 1 if trunc else 0,
         L.ptr(out), L.ptr(final_T), L.ptr(ncontrib), L.ptr(gs_idx), L.ptr(pack), L.stream()))
     return out, final_T, ncontrib, gs_idx
 
@@ -199,12 +198,12 @@ def _blend_bwd(uv, conic, opacity, feature, bias, idx_sorted, tile_range, bg, W,
     if idx_sorted.numel() > 0:
         pack = torch.empty(max(P, 1) * L.lib().splat_blend_pack_floats(C), dtype=torch.float32, device=dev)
         L.check(L.lib().splat_alpha_blending_backward(
-            L.ci(P), L.ci(C), L.ptr(uv), L.ptr(L.need(conic, "conic")), L.ptr(L.need(opacity, "opacity")), L.ptr(feature),
+            P, C, L.ptr(uv), L.ptr(L.need(conic, "conic")), L.ptr(L.need(opacity, "opacity")), L.ptr(feature),
             L.ptr(None if bias is None else L.need(bias, "opacity_bias")), L.ptr(L.need(idx_sorted, "idx_sorted", torch.int32)),
-            L.ptr(L.need(tile_range, "tile_range", torch.int32)), L.cf(bg), L.ci(W), L.ci(H), L.ptr(L.need(final_T, "final_T")),
+            L.ptr(L.need(tile_range, "tile_range", torch.int32)), bg, W, H, L.ptr(L.need(final_T, "final_T")),
             L.ptr(L.need(ncontrib, "ncontrib", torch.int32)), L.ptr(L.need(dL_drendered, "dL_drendered")), L.ptr(duv), L.ptr(dabs),
             L.ptr(dconic), L.ptr(dop), L.ptr(dfeat), L.ptr(dbias), L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(None),
-            L.ptr(pack), L.ci(0), L.ptr(None), L.stream()))
+            L.ptr(pack), 0, L.ptr(None), L.stream()))
     return duv, dconic, dop, dfeat, dbias, dabs
 
 

@@ -12,63 +12,19 @@ from typing import Optional
 
 import torch
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SPLAT_LIB_PATH: another build of the same ABI to load instead; default = in-tree library
 LIB_PATH = os.environ.get("SPLAT_LIB_PATH") or os.path.join(_HERE, "libsplat_hip.so")
 _lib: Optional[ctypes.CDLL] = None
 
-ABI_VERSION = 22
-
-# every symbol include/splat_hip.h declares (tests check the .so exports all of them)
-SYMBOLS = [
-    "splat_last_error", "splat_abi_version", "splat_build_id", "splat_set_deterministic", "splat_get_deterministic",
-    "splat_fill_f32", "splat_set_option", "splat_get_option",
-    "splat_project_point_forward", "splat_project_point_backward",
-    "splat_compute_cov3d_forward", "splat_compute_cov3d_backward",
-    "splat_ewa_project_forward", "splat_ewa_project_backward",
-    "splat_compute_sh_forward", "splat_compute_sh_backward",
-    "splat_bin_scratch_bytes", "splat_bin_count", "splat_bin_sort",
-    "splat_compute_gaussian_key", "splat_compute_tile_gaussian_range",
-    "splat_alpha_blending_forward", "splat_alpha_blending_backward", "splat_alpha_blending_forward_flags",
-    "splat_alpha_blending_backward_flags", "splat_blend_pair_floats", "splat_blend_pack_floats",
-    "splat_dynamic_eval_forward", "splat_dynamic_eval_backward",
-    "splat_position_poly_fourier_forward", "splat_position_poly_fourier_backward",
-    "splat_preprocess_ortho_forward", "splat_preprocess_ortho_backward",
-    "splat_frame_preprocess_forward", "splat_frame_preprocess_backward",
-    "splat_densify_accumulate", "splat_densify_update", "splat_densify_masks",
-    "splat_compact_scratch_bytes", "splat_compact_scan", "splat_compact_rows",
-    "splat_gather_rows_repeat", "splat_densify_split_sample", "splat_morton_keys",
-    "splat_knn_grid_cells", "splat_knn_plan_bytes", "splat_knn_build", "splat_knn_scatter", "splat_knn_search",
-    "splat_adam_step", "splat_adam_step_pattern", "splat_arap_energy",
-    "splat_preprocess_ortho_forward_batch", "splat_bin_count_batch", "splat_bin_sort_batch",
-    "splat_alpha_blending_forward_batch", "splat_blend_pair_stride", "splat_alpha_blending_backward_batch",
-    "splat_frame_preprocess_forward_batch", "splat_frames_gauss_backward_dynamic",
-    "splat_frames_count", "splat_frames_forward", "splat_frames_backward",
-    "splat_frames_gauss_backward_static", "splat_alpha_blending_backward_batch_set", "splat_frames_gauss_backward_static_set",
-    "splat_blend_sets_pair_stride", "splat_blend_sets_pack_floats", "splat_alpha_blending_backward_batch_sets",
-    "splat_alpha_blending_forward_batch_sets", "splat_pair_records_segment_sum", "splat_alpha_blending_backward_batch_sets_packed",
-    "splat_frames_gauss_backward_static_sets", "splat_frames_gauss_backward_dynamic_sets",
-    "splat_preprocess_forward_batch_cam", "splat_frames_gauss_backward_static_cam", "splat_frames_gauss_backward_static_sets_cam",
-    "splat_preprocess_persp_forward", "splat_preprocess_persp_backward",
-    "splat_alpha_blending_forward_batch_sources", "splat_frames_gauss_backward_dynamic_sources",
-    "splat_frames_gauss_backward_static_sources_cam", "splat_blend_sets_uses_forward_pack",
-    "splat_dynamic_positions_batch_forward", "splat_dynamic_positions_batch_backward",
-    "splat_arap_energy_batch", "splat_knn_brute_scratch_bytes", "splat_knn_brute_batch", "splat_l1_loss_grad",
-    "splat_alpha_blending_backward_batch_sets_l1", "splat_bin_count_batch_reach", "splat_bin_sort_batch_reach",
-    "splat_profile_enable", "splat_profile_reset", "splat_profile_read",
-    "splat_ssim_scratch_bytes", "splat_ssim_forward", "splat_ssim_backward", "splat_dssim_l1_loss_grad",
-    "splat_track_loss_scratch_bytes", "splat_track_loss_grad",
-    "splat_depth_dpt_scratch_bytes", "splat_depth_stats", "splat_depth_dpt_loss_grad",
-    "splat_alpha_blending_points_forward", "splat_alpha_blending_points_forward_live", "splat_alpha_blending_points_backward", "splat_track_flow_rows",
-    "splat_alpha_blending_points_forward_batch", "splat_alpha_blending_points_backward_batch", "splat_track_loss_grad_points",
-    "splat_alpha_blending_points_backward_ordered", "splat_alpha_blending_points_backward_ordered_scratch_bytes",
-    "splat_alpha_blending_points_backward_batch_ordered", "splat_alpha_blending_points_backward_batch_ordered_scratch_bytes",
-    "splat_median_filter_2d", "splat_lift_tracks", "splat_fit_cubic_nodes",
-    "splat_alpha_blending_forward_batch_set", "splat_alpha_blending_backward_batch_set_packed", "splat_frames_wide_fold",
-    "splat_blend_fit_color", "splat_tile_loss_sum",
-    "splat_frame_preprocess_layer_batch", "splat_layer_centroids_scratch_bytes", "splat_layer_centroids",
-    "splat_lift_pair_stride", "splat_blend_lift_batch", "splat_lift_fold",
-]
+# the header is the only place a prototype, a struct or a constant of the ABI is written (_abi.py reads it)
+HEADER = _abi.load(os.path.join(_HERE, os.pardir, "include", "splat_hip.h"))
+ABI_VERSION = HEADER.defines["SPLAT_ABI_VERSION"]
+MAX_SOURCES = HEADER.defines["SPLAT_MAX_SOURCES"]
+SYMBOLS = list(HEADER.functions)
+FeatureSource = HEADER.structs["splat_feature_source_t"]
 
 
 class SplatError(RuntimeError):
@@ -87,82 +43,11 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C splatter_a_video_amd/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
         L = ctypes.CDLL(LIB_PATH)
-        L.splat_last_error.restype = ctypes.c_char_p
-        L.splat_abi_version.restype = ctypes.c_int
-        L.splat_build_id.restype = ctypes.c_char_p
-        L.splat_set_deterministic.argtypes = [ctypes.c_int]
-        L.splat_set_deterministic.restype = None
-        L.splat_get_deterministic.restype = ctypes.c_int
-        L.splat_fill_f32.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_float, ctypes.c_void_p]
-        L.splat_bin_scratch_bytes.restype = ctypes.c_size_t
-        L.splat_bin_scratch_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.splat_knn_plan_bytes.restype = ctypes.c_size_t
-        L.splat_compact_scratch_bytes.restype = ctypes.c_size_t
-        L.splat_compact_scratch_bytes.argtypes = [ctypes.c_int]
-        L.splat_blend_pack_floats.restype = ctypes.c_size_t
-        L.splat_blend_pack_floats.argtypes = [ctypes.c_int]
-        L.splat_blend_pair_floats.restype = ctypes.c_size_t
-        L.splat_blend_pair_floats.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.splat_blend_pair_stride.restype = ctypes.c_size_t
-        L.splat_blend_pair_stride.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.splat_blend_sets_pair_stride.restype = ctypes.c_size_t
-        L.splat_blend_sets_pair_stride.argtypes = [ctypes.c_int]
-        L.splat_blend_sets_pack_floats.restype = ctypes.c_size_t
-        L.splat_blend_sets_pack_floats.argtypes = []
-        L.splat_profile_read.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
-        L.splat_set_option.argtypes = [ctypes.c_char_p, ctypes.c_int]
-        L.splat_get_option.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
-        L.splat_knn_brute_scratch_bytes.restype = ctypes.c_size_t
-        L.splat_knn_brute_scratch_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        i, f, p, s4 = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)
-        L.splat_ssim_scratch_bytes.restype = ctypes.c_size_t
-        L.splat_ssim_scratch_bytes.argtypes = [i, i, i, i, i]
-        L.splat_ssim_forward.argtypes = [i, i, i, i, i, p, s4, p, s4, p, p, p, p]
-        L.splat_ssim_backward.argtypes = [i, i, i, i, i, p, s4, p, s4, p, i, p, s4, i, p]
-        L.splat_dssim_l1_loss_grad.argtypes = [i, i, i, i, i, p, s4, p, s4, f, f, p, s4, p, p, p, p]
-        L.splat_track_loss_scratch_bytes.restype = ctypes.c_size_t
-        L.splat_track_loss_scratch_bytes.argtypes = [i, ctypes.c_int64]
-        L.splat_track_loss_grad.argtypes = [i, i, i, i, p, s4, p, p, p, ctypes.c_int64, p, f, f, p, s4, i, p, p, p, p, p]
-        L.splat_depth_dpt_scratch_bytes.restype = ctypes.c_size_t
-        L.splat_depth_dpt_scratch_bytes.argtypes = [i, i, i]
-        L.splat_depth_stats.argtypes = [i, i, i, p, s4, p, p, p]
-        L.splat_depth_dpt_loss_grad.argtypes = [i, i, i, p, s4, p, s4, p, f, p, s4, i, p, p, p, p, p, p]
-        L.splat_alpha_blending_points_forward.argtypes = [i, i, p, p, p, p, p, p, f, i, i, i, p, p, p, p, p]
-        L.splat_alpha_blending_points_forward_live.argtypes = L.splat_alpha_blending_points_forward.argtypes
-        L.splat_alpha_blending_points_backward.argtypes = [i, i, p, p, p, p, p, p, f, i, i, i, p, p, p, p, p, p, p, p, p]
-        L.splat_track_flow_rows.argtypes = [i, i, i, p, p, p, i, p, i, i, f, f, p, p, p]
-        i64 = ctypes.c_int64
-        L.splat_alpha_blending_points_forward_batch.argtypes = [i, i, i, p, p, p, i64, p, i64, p, p, i64, f, i, i, i64, p, p, p, p, p, p]
-        L.splat_alpha_blending_points_backward_batch.argtypes = [i, i, i, p, p, p, i64, p, i64, p, p, i64, f, i, i, i64, p, p, p, p, p,
-                                                                 p, p, i, i, p, i64, p]
-        L.splat_track_loss_grad_points.argtypes = [i, i, i, i, p, p, p, p, i64, p, f, f, p, p, p, p, p, p]
-        L.splat_alpha_blending_points_backward_ordered_scratch_bytes.restype = ctypes.c_size_t
-        L.splat_alpha_blending_points_backward_ordered_scratch_bytes.argtypes = [i, i, i, i, i64]
-        L.splat_alpha_blending_points_backward_ordered.argtypes = [i, i, p, p, p, p, p, p, i64, f, i, i, i, p, p, p, p, p, p, p, p,
-                                                                   p, p, p, ctypes.c_size_t, p]
-        L.splat_alpha_blending_points_backward_batch_ordered_scratch_bytes.restype = ctypes.c_size_t
-        L.splat_alpha_blending_points_backward_batch_ordered_scratch_bytes.argtypes = [i, i, i, i, i64, i64]
-        L.splat_alpha_blending_points_backward_batch_ordered.argtypes = (
-            L.splat_alpha_blending_points_backward_batch.argtypes[:-1] + [p, p, ctypes.c_size_t, p])
-        L.splat_median_filter_2d.argtypes = [i, i, i, i, p, p, p]
-        L.splat_lift_tracks.argtypes = [i, i, i, i, p, p, p, i, p, i, p, p, p, p, p, p, p, p]
-        L.splat_fit_cubic_nodes.argtypes = [i, i, i, p, p, p, p, p, p]
-        L.splat_alpha_blending_forward_batch_set.argtypes = [i, i, i, i, i, p, p, p, i64, p, i64, p, p, i64, f, i, i, p, p, p, p, p, p]
-        L.splat_alpha_blending_backward_batch_set_packed.argtypes = [i, i, i, i, i, p, p, i64, f, i, i, p, p, p, p, p, p, p, p, p]
-        L.splat_frames_wide_fold.argtypes = [i, i, i, i64, p, p, p, i, p, i64, i, p]
-        L.splat_blend_fit_color.argtypes = [i, i, p, p, p, p, p, p, p, i64, f, i, i, p, p, i, p, p, p, p, p, p]
-        L.splat_tile_loss_sum.argtypes = [i, p, p, i64, p]
-        L.splat_frame_preprocess_layer_batch.argtypes = [i, i, i, i, i, i, p, p, p, p, i, p, p, p, p, p, p, i, i, f, f, p, p, f, i,
-                                                         p, p, p, p, p, p]
-        L.splat_layer_centroids_scratch_bytes.restype = ctypes.c_size_t
-        L.splat_layer_centroids_scratch_bytes.argtypes = [i, i]
-        L.splat_layer_centroids.argtypes = [i, i, i, i, p, p, p, p, i, p, p, ctypes.c_size_t, p]
-        L.splat_lift_pair_stride.restype = ctypes.c_size_t
-        L.splat_lift_pair_stride.argtypes = [i, i]
-        L.splat_blend_lift_batch.argtypes = [i, i, i, i, i, p, p, p, i64, p, p, p, i64, i, i, p, p, i, p, p]
-        L.splat_lift_fold.argtypes = [i, i, i, i, i64, p, p, p, i64, i, p, p]
+        for name, (restype, argtypes) in HEADER.functions.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if L.splat_abi_version() != ABI_VERSION:
-            raise SplatError("libsplat_hip.so ABI version mismatch; rebuild it")
+            raise SplatError(f"{LIB_PATH} has ABI version {L.splat_abi_version()}, include/splat_hip.h {ABI_VERSION}; rebuild it")
         _lib = L
     return _lib
 
@@ -184,6 +69,8 @@ def stream() -> ctypes.c_void_p:
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# cf / ci: explicit scalar wrappers from before every function had argtypes.  The package passes plain Python values;
+# the two stay for callers outside it (bench.py, scripts and tests written against the earlier binding)
 def cf(x: float) -> ctypes.c_float:
     return ctypes.c_float(float(x))
 
@@ -218,7 +105,7 @@ def build_id() -> str:
 def set_option(key: str, value: int) -> None:
     """process-wide option of the library (include/splat_hip.h: splat_set_option): "bwd_quarters", "sets_std", "bin_slot_keys",
     "bin_short_segments", "deterministic"; read at launch time"""
-    check(lib().splat_set_option(key.encode(), ctypes.c_int(int(value))))
+    check(lib().splat_set_option(key.encode(), int(value)))
 
 
 def get_option(key: str) -> int:
@@ -243,15 +130,6 @@ class option:
         return False
 
 
-class FeatureSource(ctypes.Structure):
-    """mirror of splat_feature_source_t (include/splat_hip.h)"""
-    _fields_ = [("c0", ctypes.c_int32), ("cn", ctypes.c_int32), ("feature", ctypes.c_void_p), ("d_feature", ctypes.c_void_p),
-                ("frame_stride", ctypes.c_int64)]
-
-
-MAX_SOURCES = 8
-
-
 def set_deterministic(on: bool) -> None:
     """process-wide deterministic mode (include/splat_hip.h: splat_set_deterministic): no backward launches a kernel with
     float atomics; a foreign idx_sorted (atomic backward) raises"""
@@ -263,7 +141,7 @@ def deterministic() -> bool:
 
 
 def profile_enable(on: bool) -> None:
-    lib().splat_profile_enable(ctypes.c_int(1 if on else 0))
+    lib().splat_profile_enable(1 if on else 0)
 
 
 def profile_reset() -> None:

@@ -9,7 +9,6 @@ per (vertex, frame), 3x3 SVD by Jacobi rotations), forward and gradient together
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Optional, Tuple
 
 import numpy as np
@@ -35,7 +34,7 @@ class _Arap(torch.autograd.Function):
         energy = torch.zeros(1, dtype=torch.float32, device=nodes_c.device)
         need_grad = ctx.needs_input_grad[0]
         d_nodes = torch.zeros_like(nodes_c) if need_grad else None
-        L.check(L.lib().splat_arap_energy(L.ci(Nt), L.ci(Nv), L.ci(K), L.ci(S), L.ptr(nodes_c), L.ptr(nbr), L.ptr(weight),
+        L.check(L.lib().splat_arap_energy(Nt, Nv, K, S, L.ptr(nodes_c), L.ptr(nbr), L.ptr(weight),
                                           L.ptr(sample_idx), L.ptr(energy), L.ptr(d_nodes), L.ptr(None), L.stream()))
         ctx.Nt = Nt
         if need_grad:
@@ -79,7 +78,7 @@ def arap_rotations(nodes_sequence: Tensor, nbr: Tensor, weight: Optional[Tensor]
     S = sample_idx.numel()
     rot = torch.empty(max(Nt - 1, 0), S, 3, 3, dtype=torch.float32, device=nodes_c.device)
     energy = torch.zeros(1, dtype=torch.float32, device=nodes_c.device)
-    L.check(L.lib().splat_arap_energy(L.ci(Nt), L.ci(Nv), L.ci(nbr.shape[1]), L.ci(S), L.ptr(nodes_c), L.ptr(nbr), L.ptr(weight),
+    L.check(L.lib().splat_arap_energy(Nt, Nv, nbr.shape[1], S, L.ptr(nodes_c), L.ptr(nbr), L.ptr(weight),
                                       L.ptr(L.need(sample_idx.long(), "sample_idx", torch.int64)), L.ptr(energy), L.ptr(None),
                                       L.ptr(rot), L.stream()))
     return rot
@@ -117,7 +116,7 @@ def pair_arap(pairs: Tensor, sample_idx: Tensor, nbr: Tensor, K_table: int = 10,
     if d_pairs is not None and (tuple(d_pairs.shape) != tuple(pairs.shape) or not d_pairs.is_contiguous()):
         raise ValueError("d_pairs must be a contiguous buffer of pairs' shape")
     energy = torch.zeros(B, dtype=torch.float32, device=pairs.device)
-    L.check(L.lib().splat_arap_energy_batch(L.ci(B), L.ci(2), L.ci(Nv), L.ci(K), L.ci(S), L.ptr(pairs), ctypes.c_int64(2 * Nv * 3),
+    L.check(L.lib().splat_arap_energy_batch(B, 2, Nv, K, S, L.ptr(pairs), 2 * Nv * 3,
                                             L.ptr(nbr), L.ptr(None), L.ptr(sample_idx), L.ptr(energy), L.ptr(d_pairs),
-                                            L.cf(grad_scale / 2.0), L.stream()))
+                                            grad_scale / 2.0, L.stream()))
     return energy / 2.0

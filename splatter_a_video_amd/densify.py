@@ -17,7 +17,6 @@ There is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -64,13 +63,13 @@ class DensifyState:
             if tap.numel() != 2 * self.num_points:
                 raise ValueError("tap_grad must be [N, 2]")
         L.check(L.lib().splat_densify_accumulate(
-            L.ci(self.num_points), L.ptr(radius), L.ptr(tap), L.cf(scale[0]), L.cf(scale[1]),
+            self.num_points, L.ptr(radius), L.ptr(tap), scale[0], scale[1],
             L.ptr(self.viewspace_grad if tap is not None else None), L.ptr(self.visibility), L.ptr(self.radii), L.stream()))
 
     def update(self) -> None:
         """statistics part of update_structure for the batch accumulated since begin_batch()"""
         L.check(L.lib().splat_densify_update(
-            L.ci(self.num_points), L.ptr(self.visibility), L.ptr(self.viewspace_grad), L.ptr(self.radii),
+            self.num_points, L.ptr(self.visibility), L.ptr(self.viewspace_grad), L.ptr(self.radii),
             L.ptr(self.max_radii2D), L.ptr(self.pos_gradient_accum), L.ptr(self.denom), L.stream()))
 
     # ---------------------------------------------------------------- decisions
@@ -85,9 +84,9 @@ class DensifyState:
             raise ValueError("scaling_raw must be [N,3] and opacity_raw [N,1]")
         out = [torch.empty(N, dtype=torch.uint8, device=self.device) for _ in range(3)]
         L.check(L.lib().splat_densify_masks(
-            L.ci(N), L.ptr(self.pos_gradient_accum), L.ptr(self.denom), L.ptr(self.max_radii2D), L.ptr(sc), L.ptr(op),
-            L.cf(densify_grad_threshold), L.cf(percent_dense), L.cf(cameras_extent), L.cf(min_opacity),
-            L.cf(size_threshold), L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.stream()))
+            N, L.ptr(self.pos_gradient_accum), L.ptr(self.denom), L.ptr(self.max_radii2D), L.ptr(sc), L.ptr(op),
+            densify_grad_threshold, percent_dense, cameras_extent, min_opacity,
+            size_threshold, L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.stream()))
         return tuple(o.view(torch.bool) for o in out)
 
     def prune_postprocess(self, valid_points_mask: Tensor) -> None:
@@ -111,7 +110,7 @@ def compact(mask: Tensor, tensors: Dict[str, Tensor]) -> Dict[str, Tensor]:
     index = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
     scratch = torch.empty(max(int(lib.splat_compact_scratch_bytes(N)), 4), dtype=torch.uint8, device=dev)
-    L.check(lib.splat_compact_scan(L.ci(N), L.ptr(mask_u8), L.ptr(index), L.ptr(count), L.ptr(scratch), L.stream()))
+    L.check(lib.splat_compact_scan(N, L.ptr(mask_u8), L.ptr(index), L.ptr(count), L.ptr(scratch), L.stream()))
     n = int(count.item())
     out = {}
     for name, t in tensors.items():
@@ -125,8 +124,8 @@ def compact(mask: Tensor, tensors: Dict[str, Tensor]) -> Dict[str, Tensor]:
         row_words = src.numel() // N if N else 1
         dst = torch.empty((n,) + tuple(src.shape[1:]), dtype=src.dtype, device=dev)
         if N and n:
-            L.check(lib.splat_compact_rows(L.ci(N), L.ptr(mask_u8), L.ptr(index), L.ci(row_words),
-                                           ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()), L.stream()))
+            L.check(lib.splat_compact_rows(N, L.ptr(mask_u8), L.ptr(index), row_words,
+                                           src.data_ptr(), dst.data_ptr(), L.stream()))
         out[name] = dst
     return out
 
@@ -142,7 +141,7 @@ def _scan(mask: Tensor):
     index = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
     scratch = torch.empty(max(int(lib.splat_compact_scratch_bytes(N)), 4), dtype=torch.uint8, device=dev)
-    L.check(lib.splat_compact_scan(L.ci(N), L.ptr(mask_u8), L.ptr(index), L.ptr(count), L.ptr(scratch), L.stream()))
+    L.check(lib.splat_compact_scan(N, L.ptr(mask_u8), L.ptr(index), L.ptr(count), L.ptr(scratch), L.stream()))
     return mask_u8, index, int(count.item())
 
 
@@ -165,8 +164,8 @@ def _append(t: Tensor, mask_u8: Tensor, index: Tensor, n_sel: int, repeat: int, 
         tail.copy_(fill.reshape(tail.shape))
     else:
         row_words = src.numel() // N
-        L.check(L.lib().splat_gather_rows_repeat(L.ci(N), L.ptr(mask_u8), L.ptr(index), L.ci(n_sel), L.ci(repeat), L.ci(row_words),
-                                                 ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(tail.data_ptr()), L.stream()))
+        L.check(L.lib().splat_gather_rows_repeat(N, L.ptr(mask_u8), L.ptr(index), n_sel, repeat, row_words,
+                                                 src.data_ptr(), tail.data_ptr(), L.stream()))
     return out
 
 
@@ -218,7 +217,7 @@ def _split_children(position, scaling_raw, rotation_raw, mask_u8, index, n, spli
         if zn.numel() != split_num * n * 3:
             raise ValueError("unit_normals must be [split_num * n_selected, 3]")
     L.check(L.lib().splat_densify_split_sample(
-        L.ci(N), L.ptr(mask_u8), L.ptr(index), L.ci(n), L.ci(split_num), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)),
+        N, L.ptr(mask_u8), L.ptr(index), n, split_num, int(seed) & (2 ** 64 - 1),
         L.ptr(L.need(position.detach(), "position")), L.ptr(L.need(scaling_raw.detach(), "scaling")),
         L.ptr(L.need(rotation_raw.detach(), "rotation")), L.ptr(zn), L.ptr(new_pos), L.ptr(new_scl), L.stream()))
     return new_pos, new_scl
@@ -277,7 +276,7 @@ def spatial_order(uv: Tensor, W: int, H: int) -> Tensor:
     if uv.dim() != 2 or uv.shape[1] != 2:
         raise ValueError("uv must be [P, 2]")
     keys = torch.empty(P, dtype=torch.int32, device=uv.device)
-    L.check(L.lib().splat_morton_keys(L.ci(P), L.ptr(uv), L.ci(W), L.ci(H), L.ptr(keys), L.stream()))
+    L.check(L.lib().splat_morton_keys(P, L.ptr(uv), W, H, L.ptr(keys), L.stream()))
     return torch.sort(keys, stable=True).indices
 
 

@@ -122,7 +122,7 @@ class _DynamicEval(torch.autograd.Function):
         opa_t, scl_t = new(1, opacity is not None), new(3, scaling is not None)
         on = lambda t, flag: L.ptr(t if flag else None)
         L.check(L.lib().splat_dynamic_eval_forward(
-            L.ci(N), L.ci(I), L.ci(seg), L.cf(d), basis, L.ptr(position), L.ptr(cubic), L.ci(layout),
+            N, I, seg, d, basis, L.ptr(position), L.ptr(cubic), layout,
             L.ptr(rotation), L.ptr(rot_poly), L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), on(pos_t, want_pos),
             on(rot_t, want_rot), on(opa_t, opacity is not None), on(scl_t, scaling is not None), L.stream()))
         ctx.meta = (N, int(I), int(seg), float(d), basis, want_pos, cubic.shape if want_pos else None, int(layout))
@@ -163,9 +163,9 @@ class _DynamicEval(torch.autograd.Function):
             raise ValueError("grad_sink must cover every parameter that requires grad: "
                              "position, pos_cubic_node, rotation, opacity, scaling")
         L.check(L.lib().splat_dynamic_eval_backward(
-            L.ci(N), L.ci(I), L.ci(seg), L.cf(d), basis, L.ptr(rotation), L.ptr(rot_poly), L.ptr(rot_fourier),
-            L.ptr(opacity), L.ptr(scaling), L.ptr(g_pos), L.ptr(g_rot), L.ptr(g_opa), L.ptr(g_scl), L.ci(acc),
-            L.ci(layout), L.ptr(b_pos), L.ptr(b_cub), L.ptr(b_rot), L.ptr(b_opa), L.ptr(b_scl), L.stream()))
+            N, I, seg, d, basis, L.ptr(rotation), L.ptr(rot_poly), L.ptr(rot_fourier),
+            L.ptr(opacity), L.ptr(scaling), L.ptr(g_pos), L.ptr(g_rot), L.ptr(g_opa), L.ptr(g_scl), acc,
+            layout, L.ptr(b_pos), L.ptr(b_cub), L.ptr(b_rot), L.ptr(b_opa), L.ptr(b_scl), L.stream()))
         # rot_poly / rot_fourier: the reference detaches both sums (:195-197) -> no gradient
         return r_pos, r_cub, r_rot, None, None, r_opa, r_scl, None, None, None, None, None, None
 
@@ -222,9 +222,9 @@ class _FramePreprocess(torch.autograd.Function):
         radius = torch.empty(N, dtype=torch.int32, device=dev)
         tiles = torch.empty(N, dtype=torch.int32, device=dev)
         L.check(L.lib().splat_frame_preprocess_forward(
-            L.ci(N), L.ci(I), L.ci(seg), L.cf(d), basis, L.ptr(position), L.ptr(cubic), L.ci(layout), L.ptr(rotation),
-            L.ptr(rot_poly), L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c), L.ci(W), L.ci(H),
-            L.cf(nearest), L.cf(extent), L.ptr(uv), L.ptr(depth), L.ptr(conic), L.ptr(radius), L.ptr(tiles),
+            N, I, seg, d, basis, L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation),
+            L.ptr(rot_poly), L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c), W, H,
+            nearest, extent, L.ptr(uv), L.ptr(depth), L.ptr(conic), L.ptr(radius), L.ptr(tiles),
             L.ptr(opa_t), L.stream()))
         ctx.meta = (N, int(I), int(seg), float(d), basis, int(W), int(H), int(layout), cubic.shape)
         ctx.sink = sink
@@ -268,10 +268,10 @@ class _FramePreprocess(torch.autograd.Function):
                              "position, pos_cubic_node, rotation, opacity, scaling")
         if any(b is not None for b in bufs):
             L.check(L.lib().splat_frame_preprocess_backward(
-                L.ci(N), L.ci(I), L.ci(seg), L.cf(d), basis, L.ptr(position), L.ptr(cubic), L.ci(layout),
+                N, I, seg, d, basis, L.ptr(position), L.ptr(cubic), layout,
                 L.ptr(rotation), L.ptr(rot_poly), L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c),
-                L.ci(W), L.ci(H), L.ptr(depth), L.ptr(radius), L.ptr(g_uv), L.ptr(g_depth), L.ptr(g_conic), L.ptr(g_opa),
-                L.ci(1 if sinked else 0), L.ptr(b_pos), L.ptr(b_cub), L.ptr(b_rot), L.ptr(b_opa), L.ptr(b_scl),
+                W, H, L.ptr(depth), L.ptr(radius), L.ptr(g_uv), L.ptr(g_depth), L.ptr(g_conic), L.ptr(g_opa),
+                1 if sinked else 0, L.ptr(b_pos), L.ptr(b_cub), L.ptr(b_rot), L.ptr(b_opa), L.ptr(b_scl),
                 L.stream()))
         # rot_poly / rot_fourier: detached in the reference (:195-197) -> no gradient
         return (r_pos, r_cub, r_rot, None, None, r_opa, r_scl) + (None,) * 11
@@ -285,7 +285,7 @@ class _PositionPolyFourier(torch.autograd.Function):
         poly = _opt(pos_poly_feat, "pos_poly_feat", N, 12)
         four = _opt(pos_fourier_feat, "pos_fourier_feat", N, 24)
         out = torch.empty(N, 3, dtype=torch.float32, device=position.device)
-        L.check(L.lib().splat_position_poly_fourier_forward(L.ci(N), basis, L.ptr(position), L.ptr(poly), L.ptr(four), L.ptr(out),
+        L.check(L.lib().splat_position_poly_fourier_forward(N, basis, L.ptr(position), L.ptr(poly), L.ptr(four), L.ptr(out),
                                                             L.stream()))
         ctx.basis, ctx.shapes = basis, (position.shape, pos_poly_feat.shape, pos_fourier_feat.shape)
         return out
@@ -299,7 +299,7 @@ class _PositionPolyFourier(torch.autograd.Function):
         d_pos = torch.empty(ctx.shapes[0], dtype=torch.float32, device=dev) if need[0] else None
         d_poly = torch.empty(ctx.shapes[1], dtype=torch.float32, device=dev) if need[1] else None
         d_four = torch.empty(ctx.shapes[2], dtype=torch.float32, device=dev) if need[2] else None
-        L.check(L.lib().splat_position_poly_fourier_backward(L.ci(N), ctx.basis, L.ptr(g), L.ci(0), L.ptr(d_pos), L.ptr(d_poly),
+        L.check(L.lib().splat_position_poly_fourier_backward(N, ctx.basis, L.ptr(g), 0, L.ptr(d_pos), L.ptr(d_poly),
                                                              L.ptr(d_four), L.stream()))
         return d_pos, d_poly, d_four, None
 
@@ -377,8 +377,8 @@ def positions_batch_forward(tab: Tensor, position: Tensor, pos_cubic_node: Tenso
     elif tuple(out.shape) != (F, N, 3) or out.dtype != torch.float32 or not out.is_cuda or (N and (out.stride(1), out.stride(2)) != (3, 1)):
         raise ValueError(f"out must be a float32 GPU buffer [F={F}, N={N}, 3] with dense frames (any frame stride)")
     L.check(L.lib().splat_dynamic_positions_batch_forward(
-        L.ci(F), L.ci(N), L.ci(interval_num), L.ptr(tab), L.ptr(position), L.ptr(cubic), L.ci(cubic_layout), L.ptr(out),
-        ctypes.c_int64(out.stride(0) if F > 1 else N * 3), L.stream()))
+        F, N, interval_num, L.ptr(tab), L.ptr(position), L.ptr(cubic), cubic_layout, L.ptr(out),
+        out.stride(0) if F > 1 else N * 3, L.stream()))
     return out
 
 
@@ -392,7 +392,7 @@ def positions_batch_backward(tab: Tensor, g: Tensor, interval_num: int, cubic_la
     if tab.shape[0] != F:
         raise ValueError("one table entry per frame of g")
     L.check(L.lib().splat_dynamic_positions_batch_backward(
-        L.ci(F), L.ci(N), L.ci(interval_num), L.ptr(tab), L.ptr(g), ctypes.c_int64(g.stride(0) if F > 1 else N * 3), L.ci(cubic_layout),
+        F, N, interval_num, L.ptr(tab), L.ptr(g), g.stride(0) if F > 1 else N * 3, cubic_layout,
         L.ptr(d_position), L.ptr(d_pos_cubic_node), L.stream()))
 
 

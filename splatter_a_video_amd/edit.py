@@ -123,8 +123,8 @@ def blend_fit_color(uv: Tensor, conic: Tensor, opacity: Tensor, feature: Tensor,
         if n == 0:
             return      # (an empty tensor has no address to tell it from "every tile")
     L.check(L.lib().splat_blend_fit_color(
-        L.ci(P), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(idx_sorted), L.ptr(tile_range),
-        L.ptr(slot_sorted), ctypes.c_int64(M), L.cf(bg), L.ci(W), L.ci(H), L.ptr(target), L.ptr(pixel_weight), L.ci(n), L.ptr(at),
+        P, C, L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(idx_sorted), L.ptr(tile_range),
+        L.ptr(slot_sorted), M, bg, W, H, L.ptr(target), L.ptr(pixel_weight), n, L.ptr(at),
         L.ptr(tile_loss), L.ptr(pair_grad), L.ptr(out), L.ptr(ncontrib), L.stream()))
 
 
@@ -225,25 +225,25 @@ class AppearanceFit:
     def _iteration(self, target: Tensor, history: Tensor, slot: int, all_tiles: bool) -> None:
         lib, st = L.lib(), L.stream()
         S = self.S
-        L.check(lib.splat_compute_sh_forward(L.ci(S), L.ptr(self.shs_sel), L.ci(3), L.ptr(self.dirs), L.ptr(self.vis), L.ci(0),
+        L.check(lib.splat_compute_sh_forward(S, L.ptr(self.shs_sel), 3, L.ptr(self.dirs), L.ptr(self.vis), 0,
                                              L.ptr(self.colors_sel), L.ptr(self.clamped), st))
         if not self.all_selected:
             self.feature.index_copy_(0, self.sel_idx, self.colors_sel)
         at = None if all_tiles else self.active_tiles
         blend_fit_color(self.uv, self.conic, self.opacity, self.feature, self.idx_sorted, self.tile_range, self.slot_sorted, self.bg,
                         self.W, self.H, target, self.tile_loss, self.pair_grad, self.pixel_weight, at)
-        L.check(lib.splat_tile_loss_sum(L.ci(self.T), L.ptr(self.tile_loss), L.ptr(history), ctypes.c_int64(slot), st))
-        L.check(lib.splat_pair_records_segment_sum(L.ci(self.P), L.ci(4), L.ptr(self.pair_grad), L.ptr(self.goff), L.ptr(self.dcolor), st))
+        L.check(lib.splat_tile_loss_sum(self.T, L.ptr(self.tile_loss), L.ptr(history), slot, st))
+        L.check(lib.splat_pair_records_segment_sum(self.P, 4, L.ptr(self.pair_grad), L.ptr(self.goff), L.ptr(self.dcolor), st))
         torch.index_select(self.dcolor, 0, self.sel_idx, out=self.dcol_sel)
         self.g_col.copy_(self.dcol_sel[:, :3])
-        L.check(lib.splat_compute_sh_backward(L.ci(S), L.ptr(self.shs_sel), L.ci(3), L.ptr(self.dirs), L.ptr(self.vis),
-                                              L.ptr(self.clamped), L.ci(0), L.ptr(self.g_col), L.ci(0), L.ptr(self.dshs), L.ptr(None), st))
+        L.check(lib.splat_compute_sh_backward(S, L.ptr(self.shs_sel), 3, L.ptr(self.dirs), L.ptr(self.vis),
+                                              L.ptr(self.clamped), 0, L.ptr(self.g_col), 0, L.ptr(self.dshs), L.ptr(None), st))
         if self.dc:
             self.g_param.copy_(self.dshs[:, 0, :])
         self.step += 1
-        L.check(lib.splat_adam_step(ctypes.c_int64(self.param.numel()), L.ptr(self.param), L.ptr(self.g_param), L.ptr(self.exp_avg),
-                                    L.ptr(self.exp_avg_sq), L.ci(1), self.seg_end, self.seg_lr, L.cf(self.betas[0]),
-                                    L.cf(self.betas[1]), L.cf(self.eps), L.ci(self.step), L.cf(1.0), st))
+        L.check(lib.splat_adam_step(self.param.numel(), L.ptr(self.param), L.ptr(self.g_param), L.ptr(self.exp_avg),
+                                    L.ptr(self.exp_avg_sq), 1, self.seg_end, self.seg_lr, self.betas[0],
+                                    self.betas[1], self.eps, self.step, 1.0, st))
         if self.dc:
             self.shs_sel[:, 0, :].copy_(self.param)
 

@@ -28,29 +28,10 @@ from .gs.fused_ops import check_sink
 from .gs.point_ops import _extr12, _points
 
 
-_FRAMES_FIELDS = ([("struct_bytes", ctypes.c_size_t)]
-                  + [(n, ctypes.c_int32) for n in ("F", "P", "W", "H", "C", "want_abs", "accumulate")]
-                  + [("capacity", ctypes.c_int64)] + [(n, ctypes.c_float) for n in ("nearest", "extent", "bg")]
-                  + [("stream", ctypes.c_void_p)]
-                  + [(n, ctypes.c_void_p) for n in (
-                      "xyz", "offsets", "scales", "uquats", "opacity", "feature", "extr", "uv", "depth", "conic", "radius",
-                      "bin_scratch", "tile_range", "pairs", "overflow", "goff_incl", "owner", "idx_sorted", "slot_sorted", "keys",
-                      "pack", "out", "final_T", "ncontrib", "dL_dout", "pair_records", "d_xyz", "d_scales", "d_uquats",
-                      "d_opacity", "d_feature", "tap", "abs_tap", "radii_max", "dbg_T_front", "cull_flags")]
-                  + [("extr_frame_stride", ctypes.c_int64), ("intr_frame_stride", ctypes.c_int64), ("intr", ctypes.c_void_p),
-                     ("perspective", ctypes.c_int32), ("reach", ctypes.c_void_p)])
-
-
-class _SplatFrames(ctypes.Structure):
-    """mirror of splat_frames_t (include/splat_hip.h): every pointer of a batch, for the one-call entry points (the
-    library checks ``struct_bytes`` against its own sizeof)"""
-    _fields_ = _FRAMES_FIELDS
-
-
-class _SplatCamera(ctypes.Structure):
-    """mirror of splat_camera_t (include/splat_hip.h)"""
-    _fields_ = [("perspective", ctypes.c_int32), ("intr", ctypes.c_void_p), ("intr_frame_stride", ctypes.c_int64),
-                ("extr", ctypes.c_void_p), ("extr_frame_stride", ctypes.c_int64), ("offsets", ctypes.c_void_p)]
+# splat_frames_t carries every pointer of a batch for the one-call entry points (the library checks ``struct_bytes``
+# against its own sizeof); both structs are built from the header's text
+_SplatFrames = L.HEADER.structs["splat_frames_t"]
+_SplatCamera = L.HEADER.structs["splat_camera_t"]
 
 
 def _versions(*tensors):
@@ -260,8 +241,8 @@ class FrameBatch:
         lib, st = L.lib(), L.stream()
         F_, P_, W, H = self.F, self.P, self.W, self.H
         L.check(lib.splat_preprocess_forward_batch_cam(
-            L.ci(F_), L.ci(P_), L.ptr(xyz), L.ptr(offsets), L.ptr(scales), L.ptr(uquats), ctypes.byref(cam.struct()), L.ci(W),
-            L.ci(H), L.cf(nearest), L.cf(extent), L.ptr(self.uv), L.ptr(self.depth), L.ptr(self.conic), L.ptr(self.radius), st))
+            F_, P_, L.ptr(xyz), L.ptr(offsets), L.ptr(scales), L.ptr(uquats), ctypes.byref(cam.struct()), W,
+            H, nearest, extent, L.ptr(self.uv), L.ptr(self.depth), L.ptr(self.conic), L.ptr(self.radius), st))
         self._bin_and_sort(opacity, op_fs)
 
     def _bin_and_sort(self, opacity: Optional[Tensor] = None, op_fs: int = 0):
@@ -272,25 +253,25 @@ class FrameBatch:
         reach = opacity is not None and OPTIONS["reach"]
         if reach:
             L.check(lib.splat_bin_count_batch_reach(
-                L.ci(F_), L.ci(P_), L.ptr(self.uv), L.ptr(self.radius), L.ptr(self.conic), L.ptr(opacity), ctypes.c_int64(op_fs),
-                L.ci(W), L.ci(H), L.ptr(self.bin_scratch), L.ptr(self.tile_range), L.ptr(self.pairs), L.ptr(None),
+                F_, P_, L.ptr(self.uv), L.ptr(self.radius), L.ptr(self.conic), L.ptr(opacity), op_fs,
+                W, H, L.ptr(self.bin_scratch), L.ptr(self.tile_range), L.ptr(self.pairs), L.ptr(None),
                 L.ptr(self.reach), st))
         else:
-            L.check(lib.splat_bin_count_batch(L.ci(F_), L.ci(P_), L.ptr(self.uv), L.ptr(self.radius), L.ci(W), L.ci(H),
+            L.check(lib.splat_bin_count_batch(F_, P_, L.ptr(self.uv), L.ptr(self.radius), W, H,
                                               L.ptr(self.bin_scratch), L.ptr(self.tile_range), L.ptr(self.pairs), st))
         if self.capacity is None:      # first batch: size the pair buffers (the only host sync of the object's life)
             self._reserve(int(int(self.pairs.max().item()) * self.slack) + 1024)
         cap = self.capacity
         if reach:
             L.check(lib.splat_bin_sort_batch_reach(
-                L.ci(F_), L.ci(P_), L.ptr(self.uv), L.ptr(self.depth), L.ptr(self.radius), L.ptr(self.reach), L.ci(W), L.ci(H),
+                F_, P_, L.ptr(self.uv), L.ptr(self.depth), L.ptr(self.radius), L.ptr(self.reach), W, H,
                 L.ptr(self.bin_scratch), L.ptr(self.tile_range),
-                ctypes.c_int64(cap), L.ptr(self.keys), L.ptr(self.idx_sorted), L.ptr(self.overflow), L.ptr(self.goff),
+                cap, L.ptr(self.keys), L.ptr(self.idx_sorted), L.ptr(self.overflow), L.ptr(self.goff),
                 L.ptr(self.owner), L.ptr(self.slot_sorted), st))
         else:
             L.check(lib.splat_bin_sort_batch(
-                L.ci(F_), L.ci(P_), L.ptr(self.uv), L.ptr(self.depth), L.ptr(self.radius), L.ci(W), L.ci(H),
-                L.ptr(self.bin_scratch), L.ptr(self.tile_range), ctypes.c_int64(cap), L.ptr(self.keys), L.ptr(self.idx_sorted),
+                F_, P_, L.ptr(self.uv), L.ptr(self.depth), L.ptr(self.radius), W, H,
+                L.ptr(self.bin_scratch), L.ptr(self.tile_range), cap, L.ptr(self.keys), L.ptr(self.idx_sorted),
                 L.ptr(self.overflow), L.ptr(self.goff), L.ptr(self.owner), L.ptr(self.slot_sorted), st))
         self._note_overflow()
 
@@ -543,16 +524,16 @@ class _RenderDynamic(torch.autograd.Function):
         ctx.gen = fb._begin_forward()
         opa_t = torch.empty(P, 1, dtype=torch.float32, device=fb.dev)
         L.check(lib.splat_frame_preprocess_forward_batch(
-            L.ci(F), L.ci(P), L.ci(I), L.ptr(tab), L.ptr(position), L.ptr(cubic), L.ci(layout), L.ptr(rotation), L.ptr(rot_poly),
-            L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c), L.ci(W), L.ci(H), L.cf(nearest), L.cf(extent),
+            F, P, I, L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly),
+            L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c), W, H, nearest, extent,
             L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius), L.ptr(opa_t), st))
         fb._bin_and_sort(opa_t)
         cap = fb.capacity
         out = torch.empty(F, C, H, W, dtype=torch.float32, device=fb.dev)
         L.check(lib.splat_alpha_blending_forward_batch(
-            L.ci(F), L.ci(P), L.ci(C), L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opa_t), ctypes.c_int64(0), L.ptr(feature),
-            ctypes.c_int64(0), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), ctypes.c_int64(cap), L.cf(bg), L.ptr(None), L.ci(W),
-            L.ci(H), L.ci(0), L.ci(0), L.ptr(out), L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(None), L.ptr(fb.pack),
+            F, P, C, L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opa_t), 0, L.ptr(feature),
+            0, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), cap, bg, L.ptr(None), W,
+            H, 0, 0, L.ptr(out), L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(None), L.ptr(fb.pack),
             L.ptr(fb.cull_flags), st))
         ctx.fb, ctx.meta, ctx.sink = fb, (I, layout, bg), sink
         ctx.save_for_backward(position, cubic, rotation, opacity, scaling, feature, rot_poly, rot_fourier, extr_c, tab)
@@ -570,16 +551,16 @@ class _RenderDynamic(torch.autograd.Function):
         F, P, W, H, C, cap = fb.F, fb.P, fb.W, fb.H, fb.C, fb.capacity
         from .gs.raster_ops import _debug_T_front
         L.check(lib.splat_alpha_blending_backward_batch(
-            L.ci(F), L.ci(P), L.ci(C), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), ctypes.c_int64(cap), L.cf(bg), L.ci(W), L.ci(H),
-            L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(g), L.ci(1 if fb.want_abs else 0), L.ptr(fb.slot_sorted),
+            F, P, C, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), cap, bg, W, H,
+            L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(g), 1 if fb.want_abs else 0, L.ptr(fb.slot_sorted),
             L.ptr(fb.pair_records), L.ptr(fb.pack), L.ptr(fb.cull_flags), L.ptr(_debug_T_front(F * H, W, g.device)), st))
         like = {"position": position, "pos_cubic_node": cubic, "rotation": rotation, "opacity": opacity, "scaling": scaling,
                 "feature": feature}
         need = dict(zip(like, ctx.needs_input_grad[:6]))
         bufs = {k: (sink[k] if k in sink else (torch.zeros_like(v) if need[k] else None)) for k, v in like.items()}
         L.check(lib.splat_frames_gauss_backward_dynamic(
-            L.ci(F), L.ci(P), L.ci(I), L.ci(C), L.ci(W), L.ci(H), ctypes.c_int64(cap), L.ci(1 if fb.want_abs else 0),
-            L.ptr(fb.pair_records), L.ptr(fb.goff), L.ptr(fb.radius), L.ptr(tab), L.ptr(position), L.ptr(cubic), L.ci(layout),
+            F, P, I, C, W, H, cap, 1 if fb.want_abs else 0,
+            L.ptr(fb.pair_records), L.ptr(fb.goff), L.ptr(fb.radius), L.ptr(tab), L.ptr(position), L.ptr(cubic), layout,
             L.ptr(rotation), L.ptr(rot_poly), L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c),
             L.ptr(bufs["position"]), L.ptr(bufs["pos_cubic_node"]), L.ptr(bufs["rotation"]), L.ptr(bufs["opacity"]),
             L.ptr(bufs["scaling"]), L.ptr(bufs["feature"]), L.ptr(fb.tap), L.ptr(fb.abs_tap), L.ptr(fb.radii_max), st))
@@ -618,8 +599,8 @@ class _RenderDynamicSets(torch.autograd.Function):
         ctx.gen = fb._begin_forward()
         opa_t = torch.empty(P, 1, dtype=torch.float32, device=fb.dev)
         L.check(lib.splat_frame_preprocess_forward_batch(
-            L.ci(F), L.ci(P), L.ci(I), L.ptr(tab), L.ptr(position), L.ptr(cubic), L.ci(layout), L.ptr(rotation), L.ptr(rot_poly),
-            L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c), L.ci(W), L.ci(H), L.cf(nearest), L.cf(extent),
+            F, P, I, L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly),
+            L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c), W, H, nearest, extent,
             L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius), L.ptr(opa_t), st))
         fb._bin_and_sort(opa_t)
         if sources:
@@ -732,11 +713,11 @@ class _RenderDynamicSets(torch.autograd.Function):
                     c0 += cn
                     fi += 1
             L.check(lib.splat_frames_gauss_backward_dynamic_sources(
-                L.ci(F), L.ci(P), L.ci(I), L.ci(C), L.ci(W), L.ci(H), ctypes.c_int64(cap), L.ptr(rec), L.ptr(fb.goff),
-                L.ptr(fb.radius), L.ptr(tab), L.ptr(position), L.ptr(cubic), L.ci(layout), L.ptr(rotation), L.ptr(rot_poly),
+                F, P, I, C, W, H, cap, L.ptr(rec), L.ptr(fb.goff),
+                L.ptr(fb.radius), L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly),
                 L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c), L.ptr(bufs["position"]),
-                L.ptr(bufs["pos_cubic_node"]), L.ptr(bufs["rotation"]), L.ptr(bufs["opacity"]), L.ptr(bufs["scaling"]), L.ci(n),
-                table, L.ci(depth_ch), L.ptr(fb.tap if has_tap else None),
+                L.ptr(bufs["pos_cubic_node"]), L.ptr(bufs["rotation"]), L.ptr(bufs["opacity"]), L.ptr(bufs["scaling"]), n,
+                table, depth_ch, L.ptr(fb.tap if has_tap else None),
                 L.ptr(fb.abs_tap if (has_tap and want_abs) else None), L.ptr(fb.radii_max if has_tap else None), st))
             ret = tuple(None if k in sink else bufs[k] for k in like)
             return ret + (None,) * (NF - 5) + tuple(dfe) + d_pts + d_wide
@@ -756,11 +737,11 @@ class _RenderDynamicSets(torch.autograd.Function):
         i3 = ctypes.c_int32 * 3
         p3 = (ctypes.c_void_p * 3)(*[0 if d is None else d.data_ptr() for d in dfs])
         L.check(lib.splat_frames_gauss_backward_dynamic_sets(
-            L.ci(F), L.ci(P), L.ci(I), L.ci(C), L.ci(W), L.ci(H), ctypes.c_int64(cap), L.ptr(rec), L.ptr(fb.goff), L.ptr(fb.radius),
-            L.ptr(tab), L.ptr(position), L.ptr(cubic), L.ci(layout), L.ptr(rotation), L.ptr(rot_poly), L.ptr(rot_fourier),
+            F, P, I, C, W, H, cap, L.ptr(rec), L.ptr(fb.goff), L.ptr(fb.radius),
+            L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly), L.ptr(rot_fourier),
             L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c), L.ptr(bufs["position"]), L.ptr(bufs["pos_cubic_node"]),
             L.ptr(bufs["rotation"]), L.ptr(bufs["opacity"]), L.ptr(bufs["scaling"]), i3(*c0s), i3(*cns), p3, i3(*strides),
-            L.ci(depth_ch), L.ptr(fb.tap if has_tap else None), L.ptr(fb.abs_tap if (has_tap and want_abs) else None),
+            depth_ch, L.ptr(fb.tap if has_tap else None), L.ptr(fb.abs_tap if (has_tap and want_abs) else None),
             L.ptr(fb.radii_max if has_tap else None), st))
         ret = tuple(None if k in sink else bufs[k] for k in like)
         return ret + (None,) * (NF - 5) + tuple(dfe) + d_pts + d_wide
@@ -800,9 +781,9 @@ def _points_forward(fb, pts, pfeat, opacity):
     pts["corner_T"] = torch.empty(Q, 4, dtype=torch.float32, device=fb.dev)
     pts["corner_n"] = torch.empty(Q, 4, dtype=torch.int32, device=fb.dev)
     L.check(L.lib().splat_alpha_blending_points_forward_batch(
-        L.ci(fb.F), L.ci(fb.P), L.ci(c), L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), ctypes.c_int64(0), L.ptr(pfeat),
-        ctypes.c_int64(int(pfeat.stride(0)) if pts["per_frame"] else 0), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range),
-        ctypes.c_int64(fb.capacity), L.cf(pts["bg"]), L.ci(fb.W), L.ci(fb.H), ctypes.c_int64(Q), L.ptr(pts["offsets"]),
+        fb.F, fb.P, c, L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), 0, L.ptr(pfeat),
+        int(pfeat.stride(0)) if pts["per_frame"] else 0, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range),
+        fb.capacity, pts["bg"], fb.W, fb.H, Q, L.ptr(pts["offsets"]),
         L.ptr(pts["points"]), L.ptr(out), L.ptr(pts["corner_T"]), L.ptr(pts["corner_n"]), L.stream()))
     return out
 
@@ -818,25 +799,25 @@ def _points_backward(fb, pts, pfeat, opacity, g, rec, d_feature):
     if pts["ordered"]:
         # no float atomic, every sum in a fixed order (runs in deterministic mode too): the batch's pair map and a pooled scratch
         need = int(L.lib().splat_alpha_blending_points_backward_batch_ordered_scratch_bytes(
-            L.ci(fb.F), L.ci(c), L.ci(fb.W), L.ci(fb.H), ctypes.c_int64(Q), ctypes.c_int64(fb.capacity)))
+            fb.F, c, fb.W, fb.H, Q, fb.capacity))
         if need == 0:
             raise ValueError("the ordered sparse backward: sizes too large")
         scratch = fb._set_buffer(("points", "ordered"), (need + 3) // 4)
         L.check(L.lib().splat_alpha_blending_points_backward_batch_ordered(
-            L.ci(fb.F), L.ci(fb.P), L.ci(c), L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), ctypes.c_int64(0), L.ptr(pfeat),
-            ctypes.c_int64(int(pfeat.stride(0)) if pts["per_frame"] else 0), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range),
-            ctypes.c_int64(fb.capacity), L.cf(pts["bg"]), L.ci(fb.W), L.ci(fb.H), ctypes.c_int64(Q), L.ptr(pts["offsets"]),
+            fb.F, fb.P, c, L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), 0, L.ptr(pfeat),
+            int(pfeat.stride(0)) if pts["per_frame"] else 0, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range),
+            fb.capacity, pts["bg"], fb.W, fb.H, Q, L.ptr(pts["offsets"]),
             L.ptr(pts["points"]), L.ptr(pts["corner_T"]), L.ptr(pts["corner_n"]), L.ptr(g), L.ptr(fb.slot_sorted), L.ptr(rec),
-            L.ci(int(L.lib().splat_blend_sets_pair_stride(fb.C))), L.ci(1 if pts["detach_opacity"] else 0), L.ptr(d_feature),
-            ctypes.c_int64(dfs), L.ptr(fb.goff), L.ptr(scratch), ctypes.c_size_t(scratch.numel() * 4), L.stream()))
+            int(L.lib().splat_blend_sets_pair_stride(fb.C)), 1 if pts["detach_opacity"] else 0, L.ptr(d_feature),
+            dfs, L.ptr(fb.goff), L.ptr(scratch), scratch.numel() * 4, L.stream()))
         return
     L.check(L.lib().splat_alpha_blending_points_backward_batch(
-        L.ci(fb.F), L.ci(fb.P), L.ci(c), L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), ctypes.c_int64(0), L.ptr(pfeat),
-        ctypes.c_int64(int(pfeat.stride(0)) if pts["per_frame"] else 0), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range),
-        ctypes.c_int64(fb.capacity), L.cf(pts["bg"]), L.ci(fb.W), L.ci(fb.H), ctypes.c_int64(Q), L.ptr(pts["offsets"]),
+        fb.F, fb.P, c, L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), 0, L.ptr(pfeat),
+        int(pfeat.stride(0)) if pts["per_frame"] else 0, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range),
+        fb.capacity, pts["bg"], fb.W, fb.H, Q, L.ptr(pts["offsets"]),
         L.ptr(pts["points"]), L.ptr(pts["corner_T"]), L.ptr(pts["corner_n"]), L.ptr(g), L.ptr(fb.slot_sorted), L.ptr(rec),
-        L.ci(int(L.lib().splat_blend_sets_pair_stride(fb.C))), L.ci(1 if pts["detach_opacity"] else 0), L.ptr(d_feature),
-        ctypes.c_int64(dfs), L.stream()))
+        int(L.lib().splat_blend_sets_pair_stride(fb.C)), 1 if pts["detach_opacity"] else 0, L.ptr(d_feature),
+        dfs, L.stream()))
 
 
 def _parse_wide(wide, sink, P):
@@ -882,9 +863,9 @@ def _wide_forward(fb, wd, wfeat, opacity, op_fs):
         pack = fb._set_buffer(("wide", "pack", k), F * P * int(lib.splat_blend_pack_floats(cn)))
         cull = fb._set_buffer(("wide", "cull", k), F * cap)          # (raw 32-bit words)
         L.check(lib.splat_alpha_blending_forward_batch_set(
-            L.ci(F), L.ci(P), L.ci(c), L.ci(c0), L.ci(cn), L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), ctypes.c_int64(op_fs),
-            L.ptr(wfeat), ctypes.c_int64(0), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), ctypes.c_int64(cap), L.cf(wd["bg"]),
-            L.ci(W), L.ci(H), L.ptr(out), L.ptr(wd["final_T"][k]), L.ptr(wd["ncontrib"][k]), L.ptr(pack), L.ptr(cull), st))
+            F, P, c, c0, cn, L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), op_fs,
+            L.ptr(wfeat), 0, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), cap, wd["bg"],
+            W, H, L.ptr(out), L.ptr(wd["final_T"][k]), L.ptr(wd["ncontrib"][k]), L.ptr(pack), L.ptr(cull), st))
     return out
 
 
@@ -906,12 +887,12 @@ def _wide_backward(fb, wd, wfeat, opacity, op_fs, g, rec, d_feature):
         pack = fb._set_buffer(("wide", "pack", k), F * P * int(lib.splat_blend_pack_floats(cn)))
         cull = fb._set_buffer(("wide", "cull", k), F * cap)
         L.check(lib.splat_alpha_blending_backward_batch_set_packed(
-            L.ci(F), L.ci(P), L.ci(c), L.ci(c0), L.ci(cn), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), ctypes.c_int64(cap),
-            L.cf(wd["bg"]), L.ci(W), L.ci(H), L.ptr(wd["final_T"][k]), L.ptr(wd["ncontrib"][k]), L.ptr(g), L.ptr(fb.slot_sorted),
+            F, P, c, c0, cn, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), cap,
+            wd["bg"], W, H, L.ptr(wd["final_T"][k]), L.ptr(wd["ncontrib"][k]), L.ptr(g), L.ptr(fb.slot_sorted),
             L.ptr(tail), L.ptr(pack), L.ptr(cull), L.ptr(_debug_T_front(F * H, W, fb.dev)), st))
         L.check(lib.splat_frames_wide_fold(
-            L.ci(F), L.ci(P), L.ci(cn), ctypes.c_int64(cap), L.ptr(fb.goff), L.ptr(tail), L.ptr(rec), L.ci(row_stride),
-            L.ptr(d_feature), ctypes.c_int64(c), L.ci(c0), st))
+            F, P, cn, cap, L.ptr(fb.goff), L.ptr(tail), L.ptr(rec), row_stride,
+            L.ptr(d_feature), c, c0, st))
 
 
 def _parse_sets(sets, F, P):
@@ -991,8 +972,8 @@ def _blend_sources_forward(fb, meta, parts, feats, opacity, K):
     out = torch.empty(F, C, H, W, dtype=torch.float32, device=fb.dev)
     gs_idx = torch.empty(F, H, W, K, dtype=torch.int32, device=fb.dev) if K > 0 else None
     L.check(lib.splat_alpha_blending_forward_batch_sources(
-        L.ci(F), L.ci(P), L.ci(C), L.ci(n), table, L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), ctypes.c_int64(0),
-        L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), ctypes.c_int64(cap), L.ptr(bgc), L.ci(W), L.ci(H), L.ci(K), L.ci(0),
+        F, P, C, n, table, L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), 0,
+        L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), cap, L.ptr(bgc), W, H, K, 0,
         L.ptr(out), L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(gs_idx), L.ptr(fb.pack), L.ptr(fb.cull_flags), st))
     # (the forward-pack decision is taken HERE and kept in the autograd context: an option flipped between this forward and its
     #  backward must not change what the backward stages)
@@ -1028,16 +1009,16 @@ def _blend_sets_forward(fb, meta, feats, opacity, op_fs, K):
         row = torch.cat([t if m[0] == "depth" else t.unsqueeze(0).expand(F, P, t.shape[1]) for t, m in zip(tens, meta)],
                         dim=2).contiguous()
         L.check(lib.splat_alpha_blending_forward_batch(
-            L.ci(F), L.ci(P), L.ci(C), L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), ctypes.c_int64(op_fs), L.ptr(row),
-            ctypes.c_int64(P * C), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), ctypes.c_int64(cap), L.cf(0.0), L.ptr(bgc),
-            L.ci(W), L.ci(H), L.ci(K), L.ci(0), L.ptr(out), L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(gs_idx),
+            F, P, C, L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), op_fs, L.ptr(row),
+            P * C, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), cap, 0.0, L.ptr(bgc),
+            W, H, K, 0, L.ptr(out), L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(gs_idx),
             L.ptr(fb.pack), L.ptr(fb.cull_flags), st))
     else:
         tabs = _set_tables(meta, plan, tens, P)
         L.check(lib.splat_alpha_blending_forward_batch_sets(
-            L.ci(F), L.ci(P), L.ci(C), tabs["c0"], tabs["cn"], tabs["feat"], tabs["fs"], L.ptr(fb.uv), L.ptr(fb.conic),
-            L.ptr(opacity), ctypes.c_int64(op_fs), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), ctypes.c_int64(cap), L.ptr(bgc),
-            L.ci(W), L.ci(H), L.ci(K), L.ci(0), L.ptr(out), L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(gs_idx),
+            F, P, C, tabs["c0"], tabs["cn"], tabs["feat"], tabs["fs"], L.ptr(fb.uv), L.ptr(fb.conic),
+            L.ptr(opacity), op_fs, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), cap, L.ptr(bgc),
+            W, H, K, 0, L.ptr(out), L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(gs_idx),
             L.ptr(fb.pack), L.ptr(fb.cull_flags), st))
     return out, gs_idx, dict(plan=plan, tens=tens, row=row, widths=widths, std=_uses_forward_pack(plan, C), out_row=out)
 
@@ -1086,10 +1067,10 @@ def _blend_sets_backward_one_pass(fb, meta, state, grads, opacity, op_fs, want_a
         std = state["std"] if "std" in state else _uses_forward_pack(plan, C)
         pack = None if std else fb._set_buffer(("pack", "sets"), F * P * int(lib.splat_blend_sets_pack_floats()))
         L.check(lib.splat_alpha_blending_backward_batch_sets_l1(
-            L.ci(F), L.ci(P), L.ci(C), tabs["c0"], tabs["cn"], tabs["bg"], L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity),
-            ctypes.c_int64(op_fs), tabs["feat"], tabs["fs"], L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), ctypes.c_int64(cap),
-            L.ci(W), L.ci(H), L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(row), (ctypes.c_void_p * 3)(*dl),
-            (ctypes.c_float * 3)(*scale), L.ptr(sums), L.ci(want_abs), L.ptr(fb.slot_sorted), L.ptr(rec), L.ptr(pack),
+            F, P, C, tabs["c0"], tabs["cn"], tabs["bg"], L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity),
+            op_fs, tabs["feat"], tabs["fs"], L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), cap,
+            W, H, L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(row), (ctypes.c_void_p * 3)(*dl),
+            (ctypes.c_float * 3)(*scale), L.ptr(sums), want_abs, L.ptr(fb.slot_sorted), L.ptr(rec), L.ptr(pack),
             L.ptr(fb.cull_flags), L.ptr(_debug_T_front(F * H, W, fb.dev)), L.ptr(fb.pack if (std or tens is None) else None), st))
         # the slab order of the three groups: (tap set, second set, detached set) -> set index of the caller's list
         l1["group_of_set"] = list(groups)
@@ -1108,10 +1089,10 @@ def _blend_sets_backward_one_pass(fb, meta, state, grads, opacity, op_fs, want_a
     std = state["std"] if "std" in state else _uses_forward_pack(plan, C)     # decided at forward time
     pack = None if std else fb._set_buffer(("pack", "sets"), F * P * int(lib.splat_blend_sets_pack_floats()))
     L.check(lib.splat_alpha_blending_backward_batch_sets_packed(
-        L.ci(F), L.ci(P), L.ci(C), tabs["c0"], tabs["cn"], tabs["bg"], L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity),
-        ctypes.c_int64(op_fs), L.ptr(None), ctypes.c_int64(0), tabs["feat"], tabs["fs"], L.ptr(fb.idx_sorted),
-        L.ptr(fb.tile_range), ctypes.c_int64(cap), L.ci(W), L.ci(H), L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(None),
-        (ctypes.c_void_p * 3)(*dl), L.ci(want_abs), L.ptr(fb.slot_sorted), L.ptr(rec), L.ptr(pack), L.ptr(fb.cull_flags),
+        F, P, C, tabs["c0"], tabs["cn"], tabs["bg"], L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity),
+        op_fs, L.ptr(None), 0, tabs["feat"], tabs["fs"], L.ptr(fb.idx_sorted),
+        L.ptr(fb.tile_range), cap, W, H, L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(None),
+        (ctypes.c_void_p * 3)(*dl), want_abs, L.ptr(fb.slot_sorted), L.ptr(rec), L.ptr(pack), L.ptr(fb.cull_flags),
         L.ptr(_debug_T_front(F * H, W, fb.dev)), L.ptr(fb.pack if (std or tens is None) else None), st))
     return rec
 
@@ -1123,7 +1104,7 @@ def _uses_forward_pack(plan, C) -> bool:
     if plan is None or not RO["sets_fwdrec"]:
         return False
     i3 = ctypes.c_int32 * 3
-    return bool(L.lib().splat_blend_sets_uses_forward_pack(L.ci(C), i3(*plan[0]), i3(*plan[1]), L.ci(1)))
+    return bool(L.lib().splat_blend_sets_uses_forward_pack(C, i3(*plan[0]), i3(*plan[1]), 1))
 
 
 def _check_set_features(meta, feats, P):
@@ -1266,9 +1247,9 @@ class _RenderSets(torch.autograd.Function):
             p3 = (ctypes.c_void_p * 3)(*[0 if d is None else d.data_ptr() for d in dfs])
             has_tap = tap_set is not None
             L.check(lib.splat_frames_gauss_backward_static_sets_cam(
-                L.ci(F), L.ci(P), L.ci(C), L.ci(W), L.ci(H), ctypes.c_int64(cap), L.ptr(rec), L.ptr(fb.goff), L.ptr(fb.radius),
-                L.ptr(xyz), L.ptr(scales), L.ptr(uquats), ctypes.byref(camc), L.ci(1), L.ptr(bufs["xyz"]), L.ptr(bufs["scales"]),
-                L.ptr(bufs["uquats"]), L.ptr(bufs["opacity"]), i3(*c0s), i3(*cns), p3, i3(*strides), L.ci(depth_ch),
+                F, P, C, W, H, cap, L.ptr(rec), L.ptr(fb.goff), L.ptr(fb.radius),
+                L.ptr(xyz), L.ptr(scales), L.ptr(uquats), ctypes.byref(camc), 1, L.ptr(bufs["xyz"]), L.ptr(bufs["scales"]),
+                L.ptr(bufs["uquats"]), L.ptr(bufs["opacity"]), i3(*c0s), i3(*cns), p3, i3(*strides), depth_ch,
                 L.ptr(fb.tap if has_tap else None), L.ptr(fb.abs_tap if (has_tap and want_abs) else None),
                 L.ptr(fb.radii_max if has_tap else None), st))
             ret = tuple(None if k in sink else bufs[k] for k in ("xyz", "scales", "uquats", "opacity"))
@@ -1291,15 +1272,15 @@ class _RenderSets(torch.autograd.Function):
                 rec = fb._set_buffer(("rec", si), F * cap * ncp)
                 pack = fb._set_buffer(("pack", si), F * P * int(lib.splat_blend_pack_floats(cn)))
                 L.check(lib.splat_alpha_blending_backward_batch_set(
-                    L.ci(F), L.ci(P), L.ci(C), L.ci(c0), L.ci(cn), L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity),
-                    ctypes.c_int64(op_fs), L.ptr(row), ctypes.c_int64(P * C), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range),
-                    ctypes.c_int64(cap), L.cf(bg), L.ci(W), L.ci(H), L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(dL),
-                    L.ci(want_abs), L.ptr(fb.slot_sorted), L.ptr(rec), L.ptr(pack), L.ptr(_debug_T_front(F * H, W, dev)), st))
+                    F, P, C, c0, cn, L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity),
+                    op_fs, L.ptr(row), P * C, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range),
+                    cap, bg, W, H, L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(dL),
+                    want_abs, L.ptr(fb.slot_sorted), L.ptr(rec), L.ptr(pack), L.ptr(_debug_T_front(F * H, W, dev)), st))
                 L.check(lib.splat_frames_gauss_backward_static_cam(
-                    L.ci(F), L.ci(P), L.ci(cn), L.ci(W), L.ci(H), ctypes.c_int64(cap), L.ci(want_abs), L.ptr(rec), L.ptr(fb.goff),
-                    L.ptr(fb.radius), L.ptr(xyz), L.ptr(scales), L.ptr(uquats), ctypes.byref(camc), L.ci(1), L.ptr(bufs["xyz"]),
-                    L.ptr(bufs["scales"]), L.ptr(bufs["uquats"]), L.ptr(bufs["opacity"]), L.ptr(dfeat), L.ci(cn),
-                    L.ci(1 if detach else 0), L.ci(0 if is_depth else -1), L.ptr(fb.tap if taps else None),
+                    F, P, cn, W, H, cap, want_abs, L.ptr(rec), L.ptr(fb.goff),
+                    L.ptr(fb.radius), L.ptr(xyz), L.ptr(scales), L.ptr(uquats), ctypes.byref(camc), 1, L.ptr(bufs["xyz"]),
+                    L.ptr(bufs["scales"]), L.ptr(bufs["uquats"]), L.ptr(bufs["opacity"]), L.ptr(dfeat), cn,
+                    1 if detach else 0, 0 if is_depth else -1, L.ptr(fb.tap if taps else None),
                     L.ptr(fb.abs_tap if (taps and want_abs) else None), L.ptr(fb.radii_max if taps else None), st))
             c0 += cn
         ret = tuple(None if k in sink else bufs[k] for k in ("xyz", "scales", "uquats", "opacity"))

@@ -57,12 +57,12 @@ class _PreprocessOrtho(torch.autograd.Function):
         tiles = torch.empty(P, dtype=torch.int32, device=dev)
         if intr_c is None:
             L.check(L.lib().splat_preprocess_ortho_forward(
-                L.ci(P), L.ptr(xyz), L.ptr(off), L.ptr(scales), L.ptr(uquats), L.ptr(extr_c), L.ci(W), L.ci(H),
-                L.cf(nearest), L.cf(extent), L.ptr(uv), L.ptr(depth), L.ptr(conic), L.ptr(radius), L.ptr(tiles), L.stream()))
+                P, L.ptr(xyz), L.ptr(off), L.ptr(scales), L.ptr(uquats), L.ptr(extr_c), W, H,
+                nearest, extent, L.ptr(uv), L.ptr(depth), L.ptr(conic), L.ptr(radius), L.ptr(tiles), L.stream()))
         else:
             L.check(L.lib().splat_preprocess_persp_forward(
-                L.ci(P), L.ptr(xyz), L.ptr(off), L.ptr(scales), L.ptr(uquats), L.ptr(intr_c), L.ptr(extr_c), L.ci(W), L.ci(H),
-                L.cf(nearest), L.cf(extent), L.ptr(uv), L.ptr(depth), L.ptr(conic), L.ptr(radius), L.ptr(tiles), L.stream()))
+                P, L.ptr(xyz), L.ptr(off), L.ptr(scales), L.ptr(uquats), L.ptr(intr_c), L.ptr(extr_c), W, H,
+                nearest, extent, L.ptr(uv), L.ptr(depth), L.ptr(conic), L.ptr(radius), L.ptr(tiles), L.stream()))
         ctx.meta = (int(W), int(H))
         ctx.sink = sink
         ctx.intr = intr_c
@@ -105,13 +105,13 @@ class _PreprocessOrtho(torch.autograd.Function):
         if b_xyz is not None or b_s is not None or b_q is not None:
             if persp:
                 L.check(L.lib().splat_preprocess_persp_backward(
-                    L.ci(P), L.ptr(xyz), L.ptr(off), L.ptr(scales), L.ptr(uquats), L.ptr(ctx.intr), L.ptr(extr_c), L.ci(W),
-                    L.ci(H), L.ptr(depth), L.ptr(radius), L.ptr(g_uv), L.ptr(g_d), L.ptr(g_c), L.ci(1 if any(sinked) else 0),
+                    P, L.ptr(xyz), L.ptr(off), L.ptr(scales), L.ptr(uquats), L.ptr(ctx.intr), L.ptr(extr_c), W,
+                    H, L.ptr(depth), L.ptr(radius), L.ptr(g_uv), L.ptr(g_d), L.ptr(g_c), 1 if any(sinked) else 0,
                     L.ptr(b_xyz), L.ptr(b_s), L.ptr(b_q), L.stream()))
             else:
                 L.check(L.lib().splat_preprocess_ortho_backward(
-                    L.ci(P), L.ptr(xyz), L.ptr(off), L.ptr(scales), L.ptr(uquats), L.ptr(extr_c), L.ci(W), L.ci(H),
-                    L.ptr(depth), L.ptr(radius), L.ptr(g_uv), L.ptr(g_d), L.ptr(g_c), L.ci(1 if any(sinked) else 0),
+                    P, L.ptr(xyz), L.ptr(off), L.ptr(scales), L.ptr(uquats), L.ptr(extr_c), W, H,
+                    L.ptr(depth), L.ptr(radius), L.ptr(g_uv), L.ptr(g_d), L.ptr(g_c), 1 if any(sinked) else 0,
                     L.ptr(b_xyz), L.ptr(b_s), L.ptr(b_q), L.stream()))
         r_off = r_xyz if (off is not None and ctx.needs_input_grad[8]) else None
         return (r_xyz if ctx.needs_input_grad[0] else None), r_s, r_q, None, None, None, None, None, r_off, None, None

@@ -68,8 +68,8 @@ class _ProjectPoint(torch.autograd.Function):
         uv = torch.empty(P, 2, dtype=torch.float32, device=xyz.device)      # kernels write every element
         depth = torch.empty(P, 1, dtype=torch.float32, device=xyz.device)   # (zeros for culled points)
         L.check(L.lib().splat_project_point_forward(
-            L.ci(P), L.ptr(xyz), L.ptr(intr_c), L.ptr(extr_c), L.ci(W), L.ci(H), L.cf(nearest), L.cf(extent),
-            L.ci(1 if ortho else 0), L.ptr(uv), L.ptr(depth), L.stream()))
+            P, L.ptr(xyz), L.ptr(intr_c), L.ptr(extr_c), W, H, nearest, extent,
+            1 if ortho else 0, L.ptr(uv), L.ptr(depth), L.stream()))
         ctx.meta = (int(W), int(H), bool(ortho))
         ctx.save_for_backward(xyz, intr_c if intr_c is not None else extr_c, extr_c, depth)
         ctx.cam_grad = (False if ortho or not isinstance(intr, Tensor) else intr.requires_grad, extr.requires_grad)
@@ -88,8 +88,8 @@ class _ProjectPoint(torch.autograd.Function):
         dintr = torch.zeros(4, dtype=torch.float32, device=xyz.device) if g_intr else None
         dextr = torch.zeros(12, dtype=torch.float32, device=xyz.device) if g_extr else None
         L.check(L.lib().splat_project_point_backward(
-            L.ci(P), L.ptr(xyz), L.ptr(None if ortho else intr_c), L.ptr(extr_c), L.ci(W), L.ci(H),
-            L.ci(1 if ortho else 0), L.ptr(depth), L.ptr(dL_duv), L.ptr(dL_ddepth), L.ptr(dxyz), L.ptr(dintr),
+            P, L.ptr(xyz), L.ptr(None if ortho else intr_c), L.ptr(extr_c), W, H,
+            1 if ortho else 0, L.ptr(depth), L.ptr(dL_duv), L.ptr(dL_ddepth), L.ptr(dxyz), L.ptr(dintr),
             L.ptr(dextr), L.stream()))
         if dextr is not None:
             full = torch.zeros(ctx.extr_shape, dtype=torch.float32, device=xyz.device)
@@ -119,7 +119,7 @@ class _ComputeCov3D(torch.autograd.Function):
         P = scales.shape[0]
         vis = _visible(visible, P, scales.device)
         cov3d = torch.empty(P, 6, dtype=torch.float32, device=scales.device)
-        L.check(L.lib().splat_compute_cov3d_forward(L.ci(P), L.ptr(scales), L.ptr(uquats), L.ptr(vis), L.ptr(cov3d),
+        L.check(L.lib().splat_compute_cov3d_forward(P, L.ptr(scales), L.ptr(uquats), L.ptr(vis), L.ptr(cov3d),
                                                     L.stream()))
         ctx.save_for_backward(scales, uquats, vis)
         return cov3d
@@ -131,7 +131,7 @@ class _ComputeCov3D(torch.autograd.Function):
         g = L.need(dL_dcov3d, "dL_dcov3d")
         ds = torch.empty_like(scales)
         dq = torch.empty_like(uquats)
-        L.check(L.lib().splat_compute_cov3d_backward(L.ci(P), L.ptr(scales), L.ptr(uquats), L.ptr(vis), L.ptr(g),
+        L.check(L.lib().splat_compute_cov3d_backward(P, L.ptr(scales), L.ptr(uquats), L.ptr(vis), L.ptr(g),
                                                      L.ptr(ds), L.ptr(dq), L.stream()))
         return ds, dq, None
 
@@ -156,8 +156,8 @@ class _EWAProject(torch.autograd.Function):
         radius = torch.empty(P, dtype=torch.int32, device=xyz.device)
         tiles = torch.empty(P, dtype=torch.int32, device=xyz.device)
         L.check(L.lib().splat_ewa_project_forward(
-            L.ci(P), L.ptr(xyz), L.ptr(cov3d), L.ptr(intr_c), L.ptr(extr_c), L.ptr(uv), L.ci(W), L.ci(H), L.ptr(vis),
-            L.ci(1 if ortho else 0), L.ptr(conic), L.ptr(radius), L.ptr(tiles), L.stream()))
+            P, L.ptr(xyz), L.ptr(cov3d), L.ptr(intr_c), L.ptr(extr_c), L.ptr(uv), W, H, L.ptr(vis),
+            1 if ortho else 0, L.ptr(conic), L.ptr(radius), L.ptr(tiles), L.stream()))
         ctx.meta = (int(W), int(H), bool(ortho))
         ctx.save_for_backward(xyz, cov3d, intr_c if intr_c is not None else extr_c, extr_c, radius)
         ctx.cam_grad = (False if ortho or not isinstance(intr, Tensor) else intr.requires_grad, extr.requires_grad)
@@ -177,8 +177,8 @@ class _EWAProject(torch.autograd.Function):
         dintr = torch.zeros(4, dtype=torch.float32, device=xyz.device) if g_intr else None
         dextr = torch.zeros(12, dtype=torch.float32, device=xyz.device) if g_extr else None
         L.check(L.lib().splat_ewa_project_backward(
-            L.ci(P), L.ptr(xyz), L.ptr(cov3d), L.ptr(None if ortho else intr_c), L.ptr(extr_c), L.ci(W), L.ci(H),
-            L.ci(1 if ortho else 0), L.ptr(radius), L.ptr(g), L.ptr(dxyz), L.ptr(dcov), L.ptr(dintr), L.ptr(dextr),
+            P, L.ptr(xyz), L.ptr(cov3d), L.ptr(None if ortho else intr_c), L.ptr(extr_c), W, H,
+            1 if ortho else 0, L.ptr(radius), L.ptr(g), L.ptr(dxyz), L.ptr(dcov), L.ptr(dintr), L.ptr(dextr),
             L.stream()))
         if dextr is not None:
             full = torch.zeros(ctx.extr_shape, dtype=torch.float32, device=xyz.device)
@@ -216,8 +216,8 @@ class _ComputeSH(torch.autograd.Function):
         vis = _visible(visible, P, shs.device)
         colors = torch.empty(P, 3, dtype=torch.float32, device=shs.device)
         clamped = None if free else torch.empty(P, 3, dtype=torch.uint8, device=shs.device)
-        L.check(L.lib().splat_compute_sh_forward(L.ci(P), L.ptr(shs), L.ci(degree), L.ptr(dirs), L.ptr(vis),
-                                                 L.ci(1 if free else 0), L.ptr(colors), L.ptr(clamped), L.stream()))
+        L.check(L.lib().splat_compute_sh_forward(P, L.ptr(shs), degree, L.ptr(dirs), L.ptr(vis),
+                                                 1 if free else 0, L.ptr(colors), L.ptr(clamped), L.stream()))
         ctx.meta = (degree, bool(free))
         ctx.sink = sink
         if free:
@@ -240,9 +240,9 @@ class _ComputeSH(torch.autograd.Function):
         else:
             dshs = torch.zeros_like(shs) if shs.shape[1] != (degree + 1) ** 2 else torch.empty_like(shs)
         ddirs = torch.empty_like(dirs) if ctx.needs_input_grad[2] else None
-        L.check(L.lib().splat_compute_sh_backward(L.ci(P), L.ptr(shs), L.ci(degree), L.ptr(dirs), L.ptr(vis),
-                                                  L.ptr(clamped), L.ci(1 if free else 0), L.ptr(g),
-                                                  L.ci(1 if sink is not None else 0), L.ptr(dshs), L.ptr(ddirs),
+        L.check(L.lib().splat_compute_sh_backward(P, L.ptr(shs), degree, L.ptr(dirs), L.ptr(vis),
+                                                  L.ptr(clamped), 1 if free else 0, L.ptr(g),
+                                                  1 if sink is not None else 0, L.ptr(dshs), L.ptr(ddirs),
                                                   L.stream()))
         return (None if sink is not None else dshs), None, ddirs, None, None, None
 

@@ -147,11 +147,11 @@ def _sort(uv: Tensor, depth: Tensor, W: int, H: int, radius: Tensor, tiles: Opti
         if conic.numel() != 3 * P or opacity.numel() != P:
             raise ValueError("conic [P,3] and opacity [P] must agree with uv on P")
         reach = torch.empty(P, dtype=torch.int32, device=dev)
-        L.check(lib.splat_bin_count_batch_reach(L.ci(1), L.ci(P), L.ptr(uv), L.ptr(radius), L.ptr(conic), L.ptr(opacity),
-                                                ctypes.c_int64(0), L.ci(W), L.ci(H), L.ptr(scratch), L.ptr(tile_range), L.ptr(m_dev),
+        L.check(lib.splat_bin_count_batch_reach(1, P, L.ptr(uv), L.ptr(radius), L.ptr(conic), L.ptr(opacity),
+                                                0, W, H, L.ptr(scratch), L.ptr(tile_range), L.ptr(m_dev),
                                                 L.ptr(None), L.ptr(reach), L.stream()))
     else:
-        L.check(lib.splat_bin_count(L.ci(P), L.ptr(uv), L.ptr(radius), L.ci(W), L.ci(H), L.ptr(scratch),
+        L.check(lib.splat_bin_count(P, L.ptr(uv), L.ptr(radius), W, H, L.ptr(scratch),
                                     L.ptr(tile_range), L.ptr(m_dev), L.ptr(None), L.stream()))
     M = int(m_dev.item()) if capacity is None else int(capacity)   # the only host sync (none with a capacity)
     idx_sorted = torch.empty(M, dtype=torch.int32, device=dev)
@@ -163,13 +163,13 @@ def _sort(uv: Tensor, depth: Tensor, W: int, H: int, radius: Tensor, tiles: Opti
         slot_sorted = torch.empty(M, dtype=torch.int32, device=dev)
         goff = torch.empty(P, dtype=torch.int32, device=dev)   # inclusive tiles-per-Gaussian prefix, written by the sort
         if reach is not None:
-            L.check(lib.splat_bin_sort_batch_reach(L.ci(1), L.ci(P), L.ptr(uv), L.ptr(depth), L.ptr(radius), L.ptr(reach),
-                                                   L.ci(W), L.ci(H), L.ptr(scratch),
-                                                   L.ptr(tile_range), ctypes.c_int64(M), L.ptr(keys), L.ptr(idx_sorted),
+            L.check(lib.splat_bin_sort_batch_reach(1, P, L.ptr(uv), L.ptr(depth), L.ptr(radius), L.ptr(reach),
+                                                   W, H, L.ptr(scratch),
+                                                   L.ptr(tile_range), M, L.ptr(keys), L.ptr(idx_sorted),
                                                    L.ptr(overflow), L.ptr(goff), L.ptr(owner), L.ptr(slot_sorted), L.stream()))
         else:
-            L.check(lib.splat_bin_sort(L.ci(P), L.ptr(uv), L.ptr(depth), L.ptr(radius), L.ci(W), L.ci(H), L.ptr(scratch),
-                                       L.ptr(tile_range), ctypes.c_int64(M), L.ptr(keys), L.ptr(idx_sorted),
+            L.check(lib.splat_bin_sort(P, L.ptr(uv), L.ptr(depth), L.ptr(radius), W, H, L.ptr(scratch),
+                                       L.ptr(tile_range), M, L.ptr(keys), L.ptr(idx_sorted),
                                        L.ptr(overflow), L.ptr(goff), L.ptr(owner), L.ptr(slot_sorted), L.stream()))
         # companion of idx_sorted (the reference's signature has no room for it): lets alpha_blending's backward run
         # without global atomics; found again through the tensor's storage address and validated there
@@ -271,9 +271,9 @@ class _AlphaBlend(torch.autograd.Function):
         if ctx.pairmap is not None and idx_sorted.numel() > 0 and any(ctx.needs_input_grad[:5]):
             flags = torch.empty(idx_sorted.numel(), dtype=torch.int32, device=dev)
         L.check(L.lib().splat_alpha_blending_forward_flags(
-            L.ci(P), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(bias_c),
-            L.ptr(idx_sorted), L.ptr(tile_range), L.cf(bg), L.ptr(None), L.ci(W), L.ci(H), L.ci(K),
-            L.ci(1 if trunc else 0), L.ptr(out), L.ptr(final_T), L.ptr(ncontrib), L.ptr(gs_idx), L.ptr(pack), L.ptr(flags),
+            P, C, L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(bias_c),
+            L.ptr(idx_sorted), L.ptr(tile_range), bg, L.ptr(None), W, H, K,
+            1 if trunc else 0, L.ptr(out), L.ptr(final_T), L.ptr(ncontrib), L.ptr(gs_idx), L.ptr(pack), L.ptr(flags),
             L.stream()))
         ctx.flags = flags
         ctx.meta = (float(bg), int(W), int(H), bias is not None, ndc is not None, abs_ndc is not None)
@@ -325,10 +325,10 @@ class _AlphaBlend(torch.autograd.Function):
         dndc = alloc(P, 2, dtype=torch.float32, device=dev) if (has_ndc and in_kernel) else None
         dabs_ndc = alloc(P, 2, dtype=torch.float32, device=dev) if (has_abs and in_kernel) else None
         L.check(L.lib().splat_alpha_blending_backward_flags(
-            L.ci(P), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(bias), L.ptr(idx_sorted),
-            L.ptr(tile_range), L.cf(bg), L.ci(W), L.ci(H), L.ptr(final_T), L.ptr(ncontrib), L.ptr(g), L.ptr(duv),
+            P, C, L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(bias), L.ptr(idx_sorted),
+            L.ptr(tile_range), bg, W, H, L.ptr(final_T), L.ptr(ncontrib), L.ptr(g), L.ptr(duv),
             L.ptr(dabs), L.ptr(dconic), L.ptr(dop), L.ptr(dfeat), L.ptr(dbias), L.ptr(dndc), L.ptr(dabs_ndc), L.ptr(goff),
-            L.ptr(slot_sorted), L.ptr(scratch), L.ptr(pack), L.ci(1), L.ptr(_debug_T_front(H, W, dev)),
+            L.ptr(slot_sorted), L.ptr(scratch), L.ptr(pack), 1, L.ptr(_debug_T_front(H, W, dev)),
             L.ptr(ctx.flags if pm is not None else None), L.stream()))
         if (has_ndc or has_abs) and not in_kernel:
             half = _half_wh(W, H, dev)
@@ -406,8 +406,8 @@ def _points_forward(tensors, sizes, bg, corners: bool, live: bool = False):
     corner_n = torch.empty(Q, 4, dtype=torch.int32, device=dev) if corners else None
     fwd = L.lib().splat_alpha_blending_points_forward_live if live else L.lib().splat_alpha_blending_points_forward
     L.check(fwd(
-        L.ci(P), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(idx_sorted), L.ptr(tile_range), L.cf(bg),
-        L.ci(W), L.ci(H), L.ci(Q), L.ptr(points), L.ptr(out), L.ptr(corner_T), L.ptr(corner_n), L.stream()))
+        P, C, L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(idx_sorted), L.ptr(tile_range), bg,
+        W, H, Q, L.ptr(points), L.ptr(out), L.ptr(corner_T), L.ptr(corner_n), L.stream()))
     return out, corner_T, corner_n
 
 
@@ -440,19 +440,19 @@ class _BlendPoints(torch.autograd.Function):
         if pm is not None:   # the ordered route: no float atomic, every sum in a fixed order
             cap = int(pm.slot_sorted.numel())
             need = int(L.lib().splat_alpha_blending_points_backward_ordered_scratch_bytes(
-                L.ci(C), L.ci(W), L.ci(H), L.ci(Q), ctypes.c_int64(cap)))
+                C, W, H, Q, cap))
             if need == 0:
                 raise ValueError("alpha_blending_points(ordered=True): sizes too large")
             scratch = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
             L.check(L.lib().splat_alpha_blending_points_backward_ordered(
-                L.ci(P), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(idx_sorted), L.ptr(tile_range),
-                ctypes.c_int64(cap), L.cf(ctx.bg), L.ci(W), L.ci(H), L.ci(Q), L.ptr(points), L.ptr(corner_T), L.ptr(corner_n),
+                P, C, L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(idx_sorted), L.ptr(tile_range),
+                cap, ctx.bg, W, H, Q, L.ptr(points), L.ptr(corner_T), L.ptr(corner_n),
                 L.ptr(g_out), L.ptr(grads[0]), L.ptr(grads[1]), L.ptr(grads[2]), L.ptr(grads[3]), L.ptr(pm.goff),
-                L.ptr(pm.slot_sorted), L.ptr(scratch), ctypes.c_size_t(scratch.numel() * 4), L.stream()))
+                L.ptr(pm.slot_sorted), L.ptr(scratch), scratch.numel() * 4, L.stream()))
         else:
             L.check(L.lib().splat_alpha_blending_points_backward(
-                L.ci(P), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(idx_sorted), L.ptr(tile_range),
-                L.cf(ctx.bg), L.ci(W), L.ci(H), L.ci(Q), L.ptr(points), L.ptr(corner_T), L.ptr(corner_n), L.ptr(g_out),
+                P, C, L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(feature), L.ptr(idx_sorted), L.ptr(tile_range),
+                ctx.bg, W, H, Q, L.ptr(points), L.ptr(corner_T), L.ptr(corner_n), L.ptr(g_out),
                 L.ptr(grads[0]), L.ptr(grads[1]), L.ptr(grads[2]), L.ptr(grads[3]), L.stream()))
         return grads[0], grads[1], grads[2], grads[3], None, None, None, None, None, None, None, None
 
@@ -557,8 +557,8 @@ class _BlendShared(torch.autograd.Function):
         if ctx.pairmap is not None and idx_sorted.numel() > 0 and any(ctx.needs_input_grad):
             flags = torch.empty(idx_sorted.numel(), dtype=torch.int32, device=dev)
         L.check(L.lib().splat_alpha_blending_forward_flags(
-            L.ci(P), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(allf), L.ptr(None), L.ptr(idx_sorted),
-            L.ptr(tile_range), L.cf(0.0), L.ptr(bgc), L.ci(W), L.ci(H), L.ci(K), L.ci(0), L.ptr(out), L.ptr(final_T),
+            P, C, L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(allf), L.ptr(None), L.ptr(idx_sorted),
+            L.ptr(tile_range), 0.0, L.ptr(bgc), W, H, K, 0, L.ptr(out), L.ptr(final_T),
             L.ptr(ncontrib), L.ptr(gs_idx), L.ptr(pack), L.ptr(flags), L.stream()))
         ctx.flags = flags
         # the forward's packed records stay alive until the backward only when the one-pass backward will stage them (the
@@ -610,10 +610,10 @@ class _BlendShared(torch.autograd.Function):
             dfeat = alloc(P, C, dtype=torch.float32, device=dev)
             pack = torch.empty(max(P, 1) * lib.splat_blend_pack_floats(C), dtype=torch.float32, device=dev)
             L.check(lib.splat_alpha_blending_backward_flags(
-                L.ci(P), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(f), L.ptr(None), L.ptr(idx_sorted),
-                L.ptr(tile_range), L.cf(bgs[s]), L.ci(W), L.ci(H), L.ptr(final_T), L.ptr(ncontrib), L.ptr(g), L.ptr(duv),
+                P, C, L.ptr(uv), L.ptr(conic), L.ptr(opacity), L.ptr(f), L.ptr(None), L.ptr(idx_sorted),
+                L.ptr(tile_range), bgs[s], W, H, L.ptr(final_T), L.ptr(ncontrib), L.ptr(g), L.ptr(duv),
                 L.ptr(dabs), L.ptr(dconic), L.ptr(dop), L.ptr(dfeat), L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(goff),
-                L.ptr(slot_sorted), L.ptr(scratch), L.ptr(pack), L.ci(0), L.ptr(_debug_T_front(H, W, dev)),
+                L.ptr(slot_sorted), L.ptr(scratch), L.ptr(pack), 0, L.ptr(_debug_T_front(H, W, dev)),
                 L.ptr(ctx.flags if pm is not None else None), L.stream()))
             dfeats[s] = dfeat
             duv_t = duv if duv_t is None else duv_t + duv
@@ -683,12 +683,12 @@ def _blend_shared_one_pass(ctx, grads):
     i3, f3, p3, l3 = ctypes.c_int32 * 3, ctypes.c_float * 3, ctypes.c_void_p * 3, ctypes.c_int64 * 3
     pm = ctx.pairmap
     L.check(lib.splat_alpha_blending_backward_batch_sets_packed(
-        L.ci(1), L.ci(P), L.ci(C), i3(*c0s), i3(*cns), f3(*pbg), L.ptr(uv), L.ptr(conic), L.ptr(opacity), ctypes.c_int64(0),
-        L.ptr(None), ctypes.c_int64(0), p3(*fptr), l3(0, 0, 0), L.ptr(idx_sorted), L.ptr(tile_range), ctypes.c_int64(M), L.ci(W),
-        L.ci(H), L.ptr(final_T), L.ptr(ncontrib), L.ptr(None), p3(*dptr), L.ci(want_abs), L.ptr(pm.slot_sorted), L.ptr(rec),
+        1, P, C, i3(*c0s), i3(*cns), f3(*pbg), L.ptr(uv), L.ptr(conic), L.ptr(opacity), 0,
+        L.ptr(None), 0, p3(*fptr), l3(0, 0, 0), L.ptr(idx_sorted), L.ptr(tile_range), M, W,
+        H, L.ptr(final_T), L.ptr(ncontrib), L.ptr(None), p3(*dptr), want_abs, L.ptr(pm.slot_sorted), L.ptr(rec),
         L.ptr(pack), L.ptr(ctx.flags), L.ptr(_debug_T_front(H, W, dev)), L.ptr(ctx.fwd_pack if std else None), L.stream()))
     red = torch.empty(P, ncp, dtype=torch.float32, device=dev)
-    L.check(lib.splat_pair_records_segment_sum(L.ci(P), L.ci(ncp), L.ptr(rec), L.ptr(pm.goff), L.ptr(red), L.stream()))
+    L.check(lib.splat_pair_records_segment_sum(P, ncp, L.ptr(rec), L.ptr(pm.goff), L.ptr(red), L.stream()))
     half = _half_wh(W, H, dev)
     duv, dconic = red[:, 0:2].contiguous(), red[:, 2:5].contiguous()
     dop = red[:, 5].contiguous().reshape(opacity.shape)
@@ -721,7 +721,7 @@ def _uses_forward_pack(widths, detach, taps) -> bool:
     if plan is None:
         return False
     i3 = ctypes.c_int32 * 3
-    return bool(L.lib().splat_blend_sets_uses_forward_pack(L.ci(C), i3(*plan[0]), i3(*plan[1]), L.ci(1)))
+    return bool(L.lib().splat_blend_sets_uses_forward_pack(C, i3(*plan[0]), i3(*plan[1]), 1))
 
 
 def _offsets(widths):

@@ -9,7 +9,6 @@ require grad, as pytorch3d's do.  There is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes
 from collections import namedtuple
 from typing import Optional
 
@@ -29,22 +28,22 @@ def _knn_single(query: Tensor, points: Tensor, K: int):
     idx = torch.empty(N, K, dtype=torch.int32, device=dev)
     if N == 0:
         return dists, idx.long()
-    budget = int(lib.splat_knn_grid_cells(L.ci(M)))
+    budget = int(lib.splat_knn_grid_cells(M))
     plan = torch.empty(int(lib.splat_knn_plan_bytes()), dtype=torch.uint8, device=dev)
     cell_of = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
     count = torch.zeros(budget + 1, dtype=torch.int32, device=dev)
-    L.check(lib.splat_knn_build(L.ci(M), L.ptr(points), L.ci(budget), L.ptr(plan), L.ptr(cell_of), L.ptr(count), L.stream()))
+    L.check(lib.splat_knn_build(M, L.ptr(points), budget, L.ptr(plan), L.ptr(cell_of), L.ptr(count), L.stream()))
     cell_start = (torch.cumsum(count, 0, dtype=torch.int32) - count).contiguous()      # exclusive; entry [budget] = M
     fill = torch.zeros(budget, dtype=torch.int32, device=dev)
     sorted_pts = torch.empty(max(M, 1), 4, dtype=torch.float32, device=dev)
-    L.check(lib.splat_knn_scatter(L.ci(M), L.ptr(points), L.ptr(cell_of), L.ptr(cell_start), L.ptr(fill), L.ptr(sorted_pts),
+    L.check(lib.splat_knn_scatter(M, L.ptr(points), L.ptr(cell_of), L.ptr(cell_start), L.ptr(fill), L.ptr(sorted_pts),
                                   L.stream()))
     # walk the queries cell by cell (cache locality) when they are the point set itself
     order = None
     if query.data_ptr() == points.data_ptr() and N == M:
         order = sorted_pts[:, 3].contiguous().view(torch.int32)
-    L.check(lib.splat_knn_search(L.ci(N), L.ptr(query), L.ptr(order), L.ci(M), L.ptr(sorted_pts), L.ptr(cell_start),
-                                 L.ptr(plan), L.ci(K), L.ptr(dists), L.ptr(idx), L.stream()))
+    L.check(lib.splat_knn_search(N, L.ptr(query), L.ptr(order), M, L.ptr(sorted_pts), L.ptr(cell_start),
+                                 L.ptr(plan), K, L.ptr(dists), L.ptr(idx), L.stream()))
     return dists, idx.long()
 
 
@@ -100,7 +99,7 @@ def knn_brute_batch(points: Tensor, query_idx: Tensor, K: int):
     dists = torch.empty(B, S, K, dtype=torch.float32, device=dev)
     idx = torch.empty(B, S, K, dtype=torch.int32, device=dev)
     scratch = torch.empty(max(int(lib.splat_knn_brute_scratch_bytes(B, N, S)), 4), dtype=torch.uint8, device=dev)
-    L.check(lib.splat_knn_brute_batch(L.ci(B), L.ci(N), L.ci(S), L.ci(K), L.ptr(p), ctypes.c_int64(p.stride(0) if B > 1 else N * 3),
+    L.check(lib.splat_knn_brute_batch(B, N, S, K, L.ptr(p), p.stride(0) if B > 1 else N * 3,
                                       L.ptr(q), L.ptr(dists), L.ptr(idx), L.ptr(scratch), L.stream()))
     return dists, idx
 

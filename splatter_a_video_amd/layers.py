@@ -18,7 +18,6 @@ returns +-q up to rounding; the covariance does not see the sign.  Here the mode
 No CPU path, no gradients (the reference runs these edits under ``torch.no_grad()``)."""
 from __future__ import annotations
 
-import ctypes
 import math
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
@@ -264,7 +263,7 @@ class LayeredClip:
         lib = L.lib()
         self._centroid = {li: torch.empty(self.F, 3, dtype=torch.float32, device=dev)
                           for li, l_ in enumerate(self.layers) if l_.transformed}
-        nbytes = max([int(lib.splat_layer_centroids_scratch_bytes(L.ci(self.F), L.ci(self.S[li]))) for li in self._centroid] + [8])
+        nbytes = max([int(lib.splat_layer_centroids_scratch_bytes(self.F, self.S[li])) for li in self._centroid] + [8])
         self._scratch = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
         self._tables: Dict[tuple, Tensor] = {}
         self.table_builds = 0       # frame tables built so far (a later render of the same times builds none)
@@ -313,15 +312,15 @@ class LayeredClip:
             if l_.transformed:
                 cen = self._centroid[li]
                 L.check(lib.splat_layer_centroids(
-                    L.ci(F), L.ci(self.N), L.ci(self.S[li]), L.ci(self.I), L.ptr(tab), L.ptr(self.src[li]), L.ptr(p["position"]),
-                    L.ptr(p["pos_cubic_node"]), L.ci(self.layout), L.ptr(cen), L.ptr(self._scratch),
-                    ctypes.c_size_t(self._scratch.numel() * 8), st))
+                    F, self.N, self.S[li], self.I, L.ptr(tab), L.ptr(self.src[li]), L.ptr(p["position"]),
+                    L.ptr(p["pos_cubic_node"]), self.layout, L.ptr(cen), L.ptr(self._scratch),
+                    self._scratch.numel() * 8, st))
             L.check(lib.splat_frame_preprocess_layer_batch(
-                L.ci(F), L.ci(self.N), L.ci(self.S[li]), L.ci(self.Q), L.ci(self.q0[li]), L.ci(self.I), L.ptr(tab),
-                L.ptr(self.src[li]), L.ptr(p["position"]), L.ptr(p["pos_cubic_node"]), L.ci(self.layout), L.ptr(p["rotation"]),
+                F, self.N, self.S[li], self.Q, self.q0[li], self.I, L.ptr(tab),
+                L.ptr(self.src[li]), L.ptr(p["position"]), L.ptr(p["pos_cubic_node"]), self.layout, L.ptr(p["rotation"]),
                 L.ptr(p["rot_poly_feat"]), L.ptr(p["rot_fourier_feat"]), L.ptr(p["opacity"]), L.ptr(p["scaling"]), L.ptr(self.extr),
-                L.ci(self.W), L.ci(self.H), L.cf(self.nearest), L.cf(self.extent), L.ptr(cen), L.ptr(layer_deltas[li]),
-                L.cf(l_.scale), L.ci(1 if l_.scale_splats else 0), L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius),
+                self.W, self.H, self.nearest, self.extent, L.ptr(cen), L.ptr(layer_deltas[li]),
+                l_.scale, 1 if l_.scale_splats else 0, L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius),
                 L.ptr(self.opa_t), st))
         while True:
             fb._bin_and_sort(self.opa_t)

@@ -61,15 +61,15 @@ def _lift_chunks(F, P, D, uv, conic, opacity, op_fs, idx_sorted, tile_range, slo
     for c0, cn, last in _chunks(D):
         wd = 1 if (last and den is not None) else 0
         L.check(lib.splat_blend_lift_batch(
-            L.ci(F), L.ci(P), L.ci(D), L.ci(c0), L.ci(cn), L.ptr(uv), L.ptr(conic), L.ptr(opacity), ctypes.c_int64(op_fs),
-            L.ptr(idx_sorted), L.ptr(tile_range), L.ptr(slot_sorted), ctypes.c_int64(cap), L.ci(W), L.ci(H), L.ptr(maps),
-            L.ptr(pixel_weight), L.ci(wd), L.ptr(rec), st))
-        L.check(lib.splat_lift_fold(L.ci(F), L.ci(P), L.ci(cn), L.ci(wd), ctypes.c_int64(cap), L.ptr(goff), L.ptr(rec), L.ptr(num),
-                                    ctypes.c_int64(D), L.ci(c0), L.ptr(den if wd else None), st))
+            F, P, D, c0, cn, L.ptr(uv), L.ptr(conic), L.ptr(opacity), op_fs,
+            L.ptr(idx_sorted), L.ptr(tile_range), L.ptr(slot_sorted), cap, W, H, L.ptr(maps),
+            L.ptr(pixel_weight), wd, L.ptr(rec), st))
+        L.check(lib.splat_lift_fold(F, P, cn, wd, cap, L.ptr(goff), L.ptr(rec), L.ptr(num),
+                                    D, c0, L.ptr(den if wd else None), st))
 
 
 def _record_floats(D: int) -> int:
-    return int(L.lib().splat_lift_pair_stride(L.ci(min(D, CHUNK)), L.ci(1)))
+    return int(L.lib().splat_lift_pair_stride(min(D, CHUNK), 1))
 
 
 @torch.no_grad()
@@ -190,10 +190,10 @@ class FeatureLift:
             tab = self._tables[times] = frame_table(self.clock, list(times), fb.dev)
         fb._begin_forward()
         L.check(lib.splat_frame_preprocess_layer_batch(
-            L.ci(self.F), L.ci(self.N), L.ci(self.N), L.ci(self.N), L.ci(0), L.ci(self.I), L.ptr(tab), L.ptr(None),
-            L.ptr(p["position"]), L.ptr(p["pos_cubic_node"]), L.ci(self.layout), L.ptr(p["rotation"]), L.ptr(p["rot_poly_feat"]),
-            L.ptr(p["rot_fourier_feat"]), L.ptr(p["opacity"]), L.ptr(p["scaling"]), L.ptr(self.extr), L.ci(self.W), L.ci(self.H),
-            L.cf(self.nearest), L.cf(self.extent), L.ptr(None), L.ptr(None), L.cf(1.0), L.ci(0), L.ptr(fb.uv), L.ptr(fb.depth),
+            self.F, self.N, self.N, self.N, 0, self.I, L.ptr(tab), L.ptr(None),
+            L.ptr(p["position"]), L.ptr(p["pos_cubic_node"]), self.layout, L.ptr(p["rotation"]), L.ptr(p["rot_poly_feat"]),
+            L.ptr(p["rot_fourier_feat"]), L.ptr(p["opacity"]), L.ptr(p["scaling"]), L.ptr(self.extr), self.W, self.H,
+            self.nearest, self.extent, L.ptr(None), L.ptr(None), 1.0, 0, L.ptr(fb.uv), L.ptr(fb.depth),
             L.ptr(fb.conic), L.ptr(fb.radius), L.ptr(self.opa_t), st))
         while True:
             fb._bin_and_sort(self.opa_t)
@@ -251,9 +251,9 @@ class FeatureLift:
         for c0, cn, _ in _chunks(self.D):
             pack = fb._set_buffer(("lift", "pack"), self.F * self.N * int(lib.splat_blend_pack_floats(CHUNK)))
             L.check(lib.splat_alpha_blending_forward_batch_set(
-                L.ci(n), L.ci(self.N), L.ci(self.D), L.ci(c0), L.ci(cn), L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(self.opa_t),
-                ctypes.c_int64(0), L.ptr(feature), ctypes.c_int64(0), L.ptr(fb.idx_sorted), L.ptr(fb.tile_range),
-                ctypes.c_int64(fb.capacity), L.cf(0.0), L.ci(self.W), L.ci(self.H), L.ptr(out), L.ptr(final_T), L.ptr(ncontrib),
+                n, self.N, self.D, c0, cn, L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(self.opa_t),
+                0, L.ptr(feature), 0, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range),
+                fb.capacity, 0.0, self.W, self.H, L.ptr(out), L.ptr(final_T), L.ptr(ncontrib),
                 L.ptr(pack), L.ptr(cull), st))
         return out
 
@@ -322,8 +322,8 @@ class FeatureLift:
                 if len(batches) > 1:
                     self._geometry(bt, checked=False)
                 self._gradient_batch(n, f, maps[b0:b0 + n], None if pixel_weight is None else pixel_weight[b0:b0 + n], grad, loss)
-            L.check(lib.splat_adam_step(ctypes.c_int64(f.numel()), L.ptr(f), L.ptr(grad), L.ptr(m), L.ptr(v), L.ci(1), seg_end,
-                                        seg_lr, L.cf(betas[0]), L.cf(betas[1]), L.cf(eps), L.ci(it + 1), L.cf(1.0), L.stream()))
+            L.check(lib.splat_adam_step(f.numel(), L.ptr(f), L.ptr(grad), L.ptr(m), L.ptr(v), 1, seg_end,
+                                        seg_lr, betas[0], betas[1], eps, it + 1, 1.0, L.stream()))
         return f, history
 
 

@@ -111,8 +111,8 @@ def dssim_l1_grad(pred: torch.Tensor, target: torch.Tensor, w_l1: float, w_ssim:
         raise ValueError(f"dssim_l1: pred {tuple(pred.shape)}, target {tuple(target.shape)} and grad {tuple(grad.shape)} differ")
     p4, t4, g4 = planes(pred, layout), planes(target, layout), planes(grad, layout)
     N, Cp, Hp, Wp = p4.shape
-    L.check(L.lib().splat_dssim_l1_loss_grad(N, Cp, Hp, Wp, 11, L.ptr(p4), _strides(p4), L.ptr(t4), _strides(t4), L.cf(w_l1),
-                                             L.cf(w_ssim), L.ptr(g4), _strides(g4), L.ptr(l1_sum), L.ptr(ssim_sum),
+    L.check(L.lib().splat_dssim_l1_loss_grad(N, Cp, Hp, Wp, 11, L.ptr(p4), _strides(p4), L.ptr(t4), _strides(t4), w_l1,
+                                             w_ssim, L.ptr(g4), _strides(g4), L.ptr(l1_sum), L.ptr(ssim_sum),
                                              L.ptr(_scratch(N, Cp, Hp, Wp, 11, pred.device)), L.stream()))
 
 
@@ -184,7 +184,7 @@ def track_loss_grad(track: torch.Tensor, targets, frame_weights: torch.Tensor, q
         raise ValueError(f"track loss: unsupported sizes (F = {F}, Q = {targets.Q})")
     scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=track.device)
     L.check(lib.splat_track_loss_grad(F, H, W, C, L.ptr(track), _strides(track), L.ptr(targets.offsets), L.ptr(targets.pixels),
-                                      L.ptr(targets.targets), ctypes.c_int64(targets.Q), L.ptr(fw), L.cf(quantile), L.cf(scale),
+                                      L.ptr(targets.targets), targets.Q, L.ptr(fw), quantile, scale,
                                       L.ptr(grad), _strides(grad) if grad is not None else None, 1 if accumulate else 0,
                                       L.ptr(per_frame), L.ptr(loss_slot), L.ptr(counts), L.ptr(scratch), L.stream()))
 
@@ -227,7 +227,7 @@ def track_loss_points_grad(values: torch.Tensor, targets, frame_weights: torch.T
         raise ValueError(f"track loss: unsupported sizes (F = {F}, Q = {Q})")
     scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=values.device)
     L.check(lib.splat_track_loss_grad_points(F, H, W, C, L.ptr(values), L.ptr(targets.offsets), L.ptr(targets.pixels),
-                                             L.ptr(targets.targets), ctypes.c_int64(Q), L.ptr(fw), L.cf(quantile), L.cf(scale),
+                                             L.ptr(targets.targets), Q, L.ptr(fw), quantile, scale,
                                              L.ptr(grad), L.ptr(per_frame), L.ptr(loss_slot), L.ptr(counts), L.ptr(scratch),
                                              L.stream()))
 
@@ -362,7 +362,7 @@ def depth_dpt_loss_grad(pred: torch.Tensor, gt: torch.Tensor, scale: float = 1.0
     _depth_out(stats, "stats", 4 * F, dev)
     _depth_out(ties, "ties", F, dev, torch.int32)
     L.check(L.lib().splat_depth_dpt_loss_grad(F, H, W, L.ptr(pred), _strides(pred), L.ptr(gt), _strides(gt), L.ptr(gt_stats),
-                                              L.cf(scale), L.ptr(grad), _strides(grad) if grad is not None else None,
+                                              scale, L.ptr(grad), _strides(grad) if grad is not None else None,
                                               1 if accumulate else 0, L.ptr(per_frame), L.ptr(loss_slot), L.ptr(stats),
                                               L.ptr(ties), L.ptr(_depth_scratch(F, H, W, dev)), L.stream()))
 

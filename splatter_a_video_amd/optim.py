@@ -122,14 +122,14 @@ class FlatAdam:
         with torch.no_grad():
             if self.has_pattern:
                 L.check(L.lib().splat_adam_step_pattern(
-                    ctypes.c_int64(p.numel()), L.ptr(p), L.ptr(g), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                    L.ci(self.nseg), self.seg_end, self.seg_lr, self.seg_period, self.seg_head, self.seg_head_lr,
-                    L.cf(self.beta1), L.cf(self.beta2), L.cf(self.eps), L.ci(self.t), L.cf(grad_scale), L.stream()))
+                    p.numel(), L.ptr(p), L.ptr(g), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
+                    self.nseg, self.seg_end, self.seg_lr, self.seg_period, self.seg_head, self.seg_head_lr,
+                    self.beta1, self.beta2, self.eps, self.t, grad_scale, L.stream()))
             else:
                 L.check(L.lib().splat_adam_step(
-                    ctypes.c_int64(p.numel()), L.ptr(p), L.ptr(g), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                    L.ci(self.nseg), self.seg_end, self.seg_lr, L.cf(self.beta1), L.cf(self.beta2), L.cf(self.eps),
-                    L.ci(self.t), L.cf(grad_scale), L.stream()))
+                    p.numel(), L.ptr(p), L.ptr(g), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
+                    self.nseg, self.seg_end, self.seg_lr, self.beta1, self.beta2, self.eps,
+                    self.t, grad_scale, L.stream()))
 
 
 class OwnerShardedAdam:
@@ -214,13 +214,13 @@ class OwnerShardedAdam:
         c_ends, c_rates = (ctypes.c_int64 * n)(*ends), (ctypes.c_float * n)(*rates)
         if any(q[0] for q in pat):
             L.check(L.lib().splat_adam_step_pattern(
-                ctypes.c_int64(hi - lo), L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ci(n), c_ends, c_rates,
+                hi - lo, L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), n, c_ends, c_rates,
                 (ctypes.c_int32 * n)(*[q[0] for q in pat]), (ctypes.c_int32 * n)(*[q[1] for q in pat]),
-                (ctypes.c_float * n)(*[q[2] for q in pat]), L.cf(self.beta1), L.cf(self.beta2), L.cf(self.eps), L.ci(self.t),
-                L.cf(grad_scale), L.stream()))
+                (ctypes.c_float * n)(*[q[2] for q in pat]), self.beta1, self.beta2, self.eps, self.t,
+                grad_scale, L.stream()))
         else:
-            L.check(L.lib().splat_adam_step(ctypes.c_int64(hi - lo), L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ci(n), c_ends, c_rates,
-                                            L.cf(self.beta1), L.cf(self.beta2), L.cf(self.eps), L.ci(self.t), L.cf(grad_scale), L.stream()))
+            L.check(L.lib().splat_adam_step(hi - lo, L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), n, c_ends, c_rates,
+                                            self.beta1, self.beta2, self.eps, self.t, grad_scale, L.stream()))
 
     def step(self, grad_scale: float = 1.0) -> None:
         self.t += 1

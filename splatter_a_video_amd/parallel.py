@@ -88,7 +88,7 @@ class FlatGradBucket:
             import ctypes
 
             from . import _lib as L
-            L.check(L.lib().splat_fill_f32(L.ptr(g), ctypes.c_size_t(g.numel()), L.cf(0.0), L.stream()))
+            L.check(L.lib().splat_fill_f32(L.ptr(g), g.numel(), 0.0, L.stream()))
         else:
             g.zero_()
 

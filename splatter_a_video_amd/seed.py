@@ -50,7 +50,7 @@ def median_filter_2d(x: Tensor, kernel_size: int = 11) -> Tensor:
     if P > 0 and (H <= k // 2 or W <= k // 2):
         raise ValueError("H and W must exceed kernel_size // 2 (reflect padding)")
     out = torch.empty_like(xc)
-    L.check(L.lib().splat_median_filter_2d(L.ci(P), L.ci(H), L.ci(W), L.ci(k), L.ptr(xc), L.ptr(out), L.stream()))
+    L.check(L.lib().splat_median_filter_2d(P, H, W, k, L.ptr(xc), L.ptr(out), L.stream()))
     return out
 
 
@@ -97,8 +97,8 @@ def _lift(tracks_2d: Tensor, depths: Tensor, masks: Tensor, query_index: int, qu
     conf = torch.zeros(N, T, dtype=torch.float32, device=dev)
     inm = torch.zeros(N, T, dtype=torch.uint8, device=dev)
     cnt = torch.zeros(N, 2, dtype=torch.int32, device=dev)
-    L.check(L.lib().splat_lift_tracks(L.ci(N), L.ci(T), L.ci(H), L.ci(W), L.ptr(tr), L.ptr(dp), L.ptr(mk), L.ci(query_index),
-                                      L.ptr(im), L.ci(1 if grid_coords else 0), L.ptr(t3), L.ptr(col), L.ptr(vis), L.ptr(inv),
+    L.check(L.lib().splat_lift_tracks(N, T, H, W, L.ptr(tr), L.ptr(dp), L.ptr(mk), query_index,
+                                      L.ptr(im), 1 if grid_coords else 0, L.ptr(t3), L.ptr(col), L.ptr(vis), L.ptr(inv),
                                       L.ptr(conf), L.ptr(inm), L.ptr(cnt), L.stream()))
     return t3, col, vis.bool(), inv.bool(), conf, inm.bool(), cnt
 
@@ -195,7 +195,7 @@ def fit_cubic_nodes(tracks_3d: Tensor, clock: Optional[FrameClock] = None) -> Tu
     I = n - 1
     position = torch.empty(N, 3, dtype=torch.float32, device=tr.device)
     cubic = torch.empty(N, 4 * I * 3, dtype=torch.float32, device=tr.device)
-    L.check(L.lib().splat_fit_cubic_nodes(L.ci(N), L.ci(T), L.ci(n), knots.ctypes.data_as(ctypes.c_void_p),
+    L.check(L.lib().splat_fit_cubic_nodes(N, T, n, knots.ctypes.data_as(ctypes.c_void_p),
                                           frames.ctypes.data_as(ctypes.c_void_p), L.ptr(tr), L.ptr(position), L.ptr(cubic),
                                           L.stream()))
     return position, cubic, clock

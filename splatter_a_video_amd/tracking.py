@@ -137,8 +137,8 @@ def track_pixels(model: Union[Dict[str, Tensor], DynamicGaussians], clock: Frame
     rows = torch.empty(N, T, 3, dtype=torch.float32, device=dev)
     tab = frame_table(clock, times, dev)
     L.check(L.lib().splat_track_flow_rows(
-        L.ci(T), L.ci(N), L.ci(I), L.ptr(tab), L.ptr(position), L.ptr(cubic), L.ci(layout), L.ptr(extr_c), L.ci(W), L.ci(H),
-        L.cf(nearest), L.cf(extent), L.ptr(uv), L.ptr(rows), L.stream()))
+        T, N, I, L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(extr_c), W, H,
+        nearest, extent, L.ptr(uv), L.ptr(rows), L.stream()))
     pts = sample_coords(points_px, W, H)
     out = alpha_blending_points(uv, conic, opa, rows.view(N, 3 * T), idx_sorted, tile_range, 0.0, W, H, pts)
     out = out.view(Q, T, 3).permute(1, 0, 2)

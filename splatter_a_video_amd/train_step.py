@@ -273,7 +273,7 @@ class TrainingStep:
     @staticmethod
     def _fill(t: Tensor, v: float = 0.0) -> None:
         import ctypes
-        L.check(L.lib().splat_fill_f32(L.ptr(t), ctypes.c_size_t(t.numel()), L.cf(v), L.stream()))
+        L.check(L.lib().splat_fill_f32(L.ptr(t), t.numel(), v, L.stream()))
 
     def _l1(self, pred: Tensor, target: Tensor, weight: float, loss_slot: Tensor) -> Tensor:
         """gradient image of weight * mean |pred - target| over the step's GLOBAL batch share of this rank (mean over the local
@@ -287,8 +287,8 @@ class TrainingStep:
         if tuple(target.shape) != (F, c, H, W):
             raise ValueError(f"ground truth must be [{F}, {c}, {H}, {W}]")
         g = torch.empty(F, c, H, W, dtype=torch.float32, device=pred.device)
-        L.check(L.lib().splat_l1_loss_grad(L.ci(F), ctypes.c_int64(inner), L.ptr(pred), ctypes.c_int64(pred.stride(0)), L.ptr(target),
-                                           L.cf(weight / (F * inner)), L.ptr(g), L.ptr(loss_slot), L.stream()))
+        L.check(L.lib().splat_l1_loss_grad(F, inner, L.ptr(pred), pred.stride(0), L.ptr(target),
+                                           weight / (F * inner), L.ptr(g), L.ptr(loss_slot), L.stream()))
         return g
 
     def _rgb_loss_grad(self, pred: Tensor, target: Tensor, sums: Tensor) -> Tensor:
@@ -341,8 +341,8 @@ class TrainingStep:
             raise ValueError(f"ground truth must be [{F}, {c}, {H}, {W}]")
         lib = L.lib()
         for f in range(F):
-            L.check(lib.splat_l1_loss_grad(1, ctypes.c_int64(inner), L.ptr(pred[f, 3:]), ctypes.c_int64(inner), L.ptr(target[f, 3:]),
-                                           L.cf(self.w.attr / (F * inner)), L.ptr(grad[f, 3:]), L.ptr(loss_slot), L.stream()))
+            L.check(lib.splat_l1_loss_grad(1, inner, L.ptr(pred[f, 3:]), inner, L.ptr(target[f, 3:]),
+                                           self.w.attr / (F * inner), L.ptr(grad[f, 3:]), L.ptr(loss_slot), L.stream()))
 
     def _l1_channels(self, pred: Tensor, target: Tensor, t0: int, grad: Tensor, scale: float, loss_slot: Tensor) -> None:
         """L1 of the image ``pred`` [F, c, H, W] against channels [t0, t0 + c) of ``target``: grad = scale * sign(pred - target),
@@ -357,8 +357,8 @@ class TrainingStep:
             raise ValueError(f"ground truth must be [{F}, >= {t0 + c}, {H}, {W}]")
         lib = L.lib()
         for f in range(F):
-            L.check(lib.splat_l1_loss_grad(1, ctypes.c_int64(inner), L.ptr(pred[f]), ctypes.c_int64(inner), L.ptr(target[f, t0:t0 + c]),
-                                           L.cf(scale), L.ptr(grad[f]), L.ptr(loss_slot), L.stream()))
+            L.check(lib.splat_l1_loss_grad(1, inner, L.ptr(pred[f]), inner, L.ptr(target[f, t0:t0 + c]),
+                                           scale, L.ptr(grad[f]), L.ptr(loss_slot), L.stream()))
 
     # ------------------------------------------------------------------ the step
     def step(self, times1: Sequence[float], times2: Sequence[float], gt: Dict[str, Tensor]) -> Dict[str, Tensor]:

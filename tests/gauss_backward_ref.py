@@ -343,9 +343,9 @@ def camera_struct(extr, intr=None, offsets=None, per_frame=False):
 
 def _head(D, W, H, C, with_abs):
     L = lib()
-    a = [L.ci(D["F"]), L.ci(D["P"]), L.ci(C), L.ci(W), L.ci(H), ctypes.c_int64(D["cap"])]
+    a = [D["F"], D["P"], C, W, H, D["cap"]]
     if with_abs:
-        a.append(L.ci(1 if D["layout"]["want_abs"] else 0))
+        a.append(1 if D["layout"]["want_abs"] else 0)
     return a + [L.ptr(D["d_rec"]), L.ptr(D["d_goff"]), L.ptr(D["d_radius"])]
 
 
@@ -377,14 +377,14 @@ def _source_table(sources, o):
         buf = o.get(f"src{n}")
         table[n].d_feature = None if buf is None else buf.data_ptr()
         table[n].frame_stride = int(s.get("frame_stride", 0))
-    return [L.ci(len(sources)), table]
+    return [len(sources), table]
 
 
 def call_static(D, g, W, H, o, accumulate=0):
     L = lib()
     C = D["layout"]["C"]
     L.check(L.lib().splat_frames_gauss_backward_static(
-        *_head(D, W, H, C, True), L.ptr(g["xyz"]), L.ptr(g["scale"]), L.ptr(g["quat"]), L.ptr(g["extr"]), L.ci(accumulate),
+        *_head(D, W, H, C, True), L.ptr(g["xyz"]), L.ptr(g["scale"]), L.ptr(g["quat"]), L.ptr(g["extr"]), accumulate,
         *_sgrads(o), L.ptr(o["d_feature"]), *_tail(o)))
     _sync()
 
@@ -393,8 +393,8 @@ def call_static_set(D, g, W, H, o, accumulate=0, feature_stride=None, skip_opaci
     L = lib()
     C = D["layout"]["C"]
     L.check(L.lib().splat_frames_gauss_backward_static_set(
-        *_head(D, W, H, C, True), L.ptr(g["xyz"]), L.ptr(g["scale"]), L.ptr(g["quat"]), L.ptr(g["extr"]), L.ci(accumulate),
-        *_sgrads(o), L.ptr(o.get("d_feature")), L.ci(feature_stride or C), L.ci(skip_opacity), L.ci(depth_channel), *_tail(o)))
+        *_head(D, W, H, C, True), L.ptr(g["xyz"]), L.ptr(g["scale"]), L.ptr(g["quat"]), L.ptr(g["extr"]), accumulate,
+        *_sgrads(o), L.ptr(o.get("d_feature")), feature_stride or C, skip_opacity, depth_channel, *_tail(o)))
     _sync()
 
 
@@ -402,8 +402,8 @@ def call_static_cam(D, g, W, H, o, cam, accumulate=0, feature_stride=None, skip_
     L = lib()
     C = D["layout"]["C"]
     L.check(L.lib().splat_frames_gauss_backward_static_cam(
-        *_head(D, W, H, C, True), L.ptr(g["xyz"]), L.ptr(g["scale"]), L.ptr(g["quat"]), ctypes.byref(cam), L.ci(accumulate),
-        *_sgrads(o), L.ptr(o.get("d_feature")), L.ci(feature_stride or C), L.ci(skip_opacity), L.ci(depth_channel), *_tail(o)))
+        *_head(D, W, H, C, True), L.ptr(g["xyz"]), L.ptr(g["scale"]), L.ptr(g["quat"]), ctypes.byref(cam), accumulate,
+        *_sgrads(o), L.ptr(o.get("d_feature")), feature_stride or C, skip_opacity, depth_channel, *_tail(o)))
     _sync()
 
 
@@ -411,7 +411,7 @@ def call_static_sets(D, g, W, H, o, sets, accumulate=0, depth_channel=-1):
     L = lib()
     L.check(L.lib().splat_frames_gauss_backward_static_sets(
         *_head(D, W, H, D["layout"]["C"], False), L.ptr(g["xyz"]), L.ptr(g["scale"]), L.ptr(g["quat"]), L.ptr(g["extr"]),
-        L.ci(accumulate), *_sgrads(o), *_sets_tables(sets, o), L.ci(depth_channel), *_tail(o)))
+        accumulate, *_sgrads(o), *_sets_tables(sets, o), depth_channel, *_tail(o)))
     _sync()
 
 
@@ -419,7 +419,7 @@ def call_static_sets_cam(D, g, W, H, o, cam, sets, accumulate=0, depth_channel=-
     L = lib()
     L.check(L.lib().splat_frames_gauss_backward_static_sets_cam(
         *_head(D, W, H, D["layout"]["C"], False), L.ptr(g["xyz"]), L.ptr(g["scale"]), L.ptr(g["quat"]), ctypes.byref(cam),
-        L.ci(accumulate), *_sgrads(o), *_sets_tables(sets, o), L.ci(depth_channel), *_tail(o)))
+        accumulate, *_sgrads(o), *_sets_tables(sets, o), depth_channel, *_tail(o)))
     _sync()
 
 
@@ -427,15 +427,15 @@ def call_static_sources_cam(D, g, W, H, o, cam, sources, accumulate=0, depth_cha
     L = lib()
     L.check(L.lib().splat_frames_gauss_backward_static_sources_cam(
         *_head(D, W, H, D["layout"]["C"], False), L.ptr(g["xyz"]), L.ptr(g["scale"]), L.ptr(g["quat"]), ctypes.byref(cam),
-        L.ci(accumulate), *_sgrads(o), *_source_table(sources, o), L.ci(depth_channel), *_tail(o)))
+        accumulate, *_sgrads(o), *_source_table(sources, o), depth_channel, *_tail(o)))
     _sync()
 
 
 def _dyn_head(D, g, W, H, with_abs):
     L = lib()
     h = _head(D, W, H, D["layout"]["C"], with_abs)
-    h.insert(2, L.ci(g["I"]))
-    return h + [L.ptr(g["tab"]), L.ptr(g["position"]), L.ptr(g["cubic"]), L.ci(g["layout"]), L.ptr(g["rotation"]),
+    h.insert(2, g["I"])
+    return h + [L.ptr(g["tab"]), L.ptr(g["position"]), L.ptr(g["cubic"]), g["layout"], L.ptr(g["rotation"]),
                 L.ptr(g["rot_poly"]), L.ptr(g["rot_fourier"]), L.ptr(g["opacity"]), L.ptr(g["scaling"]), L.ptr(g["extr"])]
 
 
@@ -453,21 +453,21 @@ def call_dynamic(D, g, W, H, o):
 def call_dynamic_sets(D, g, W, H, o, sets, depth_channel=-1):
     L = lib()
     L.check(L.lib().splat_frames_gauss_backward_dynamic_sets(*_dyn_head(D, g, W, H, False), *_dgrads(o), *_sets_tables(sets, o),
-                                                             L.ci(depth_channel), *_tail(o)))
+                                                             depth_channel, *_tail(o)))
     _sync()
 
 
 def call_dynamic_sources(D, g, W, H, o, sources, depth_channel=-1):
     L = lib()
     L.check(L.lib().splat_frames_gauss_backward_dynamic_sources(*_dyn_head(D, g, W, H, False), *_dgrads(o),
-                                                                *_source_table(sources, o), L.ci(depth_channel), *_tail(o)))
+                                                                *_source_table(sources, o), depth_channel, *_tail(o)))
     _sync()
 
 
 def call_segment_sum(D, f, out):
     """splat_pair_records_segment_sum over frame f of the record set"""
     L = lib()
-    L.check(L.lib().splat_pair_records_segment_sum(L.ci(D["P"]), L.ci(D["layout"]["stride"]), L.ptr(D["d_rec"][f]),
+    L.check(L.lib().splat_pair_records_segment_sum(D["P"], D["layout"]["stride"], L.ptr(D["d_rec"][f]),
                                                    L.ptr(D["d_goff"][f]), L.ptr(out), L.stream()))
     _sync()
 

@@ -36,8 +36,8 @@ def test_abi_version_and_error_string(built_lib):
 def test_argument_validation_without_gpu(built_lib):
     """Bad sizes are rejected before any HIP call, so this runs on a CPU-only box."""
     lib = built_lib.lib()
-    rc = lib.splat_project_point_forward(ctypes.c_int(-1), None, None, None, 16, 16, ctypes.c_float(0.2),
-                                         ctypes.c_float(1.3), 0, None, None, None)
+    rc = lib.splat_project_point_forward(-1, None, None, None, 16, 16, 0.2,
+                                         1.3, 0, None, None, None)
     assert rc == -1
     assert b"bad sizes" in lib.splat_last_error()
     assert lib.splat_bin_scratch_bytes(1000, 64, 64) > 0
@@ -125,14 +125,14 @@ def test_extension_modules_refuse_cpu(built_lib):
 def test_new_entry_points_validate_arguments(built_lib):
     lib = built_lib.lib()
     f = ctypes.c_float
-    assert lib.splat_knn_search(ctypes.c_int(4), None, None, 4, None, None, None, ctypes.c_int(99), None, None, None) == -1
+    assert lib.splat_knn_search(4, None, None, 4, None, None, None, 99, None, None, None) == -1
     assert b"K must be" in lib.splat_last_error()
-    assert lib.splat_compact_rows(ctypes.c_int(4), None, None, ctypes.c_int(0), None, None, None) == -1
-    assert lib.splat_dynamic_eval_forward(ctypes.c_int(4), ctypes.c_int(2), ctypes.c_int(5), f(0.0), None, None, None, 0, None,
+    assert lib.splat_compact_rows(4, None, None, 0, None, None, None) == -1
+    assert lib.splat_dynamic_eval_forward(4, 2, 5, f(0.0), None, None, None, 0, None,
                                           None, None, None, None, None, None, None, None, None) == -1
     assert b"segment index" in lib.splat_last_error()
-    assert lib.splat_knn_grid_cells(ctypes.c_int(300000)) == 150000
-    assert lib.splat_compact_scratch_bytes(ctypes.c_int(1000)) >= 16
+    assert lib.splat_knn_grid_cells(300000) == 150000
+    assert lib.splat_compact_scratch_bytes(1000) >= 16
 
 
 def test_diff_gaussian_rasterization_shim_surface():
@@ -215,10 +215,105 @@ def test_sets_entry_points_validate_arguments(built_lib):
     assert L.splat_blend_sets_pair_stride(23) == 36 and L.splat_blend_sets_pair_stride(28) == 40
     # sets that do not tile the row / too wide / null tables: refused before any launch
     one = ctypes.c_void_p(8)
-    args = lambda c0, cn, C: (1, 10, C, i3(*c0), i3(*cn), f3(0, 0, 0), one, one, one, ctypes.c_int64(0), one, ctypes.c_int64(0), None,
-                              None, one, one, ctypes.c_int64(100), 32, 32, one, one, one, None, 0, one, one, one, None, None, None)
+    args = lambda c0, cn, C: (1, 10, C, i3(*c0), i3(*cn), f3(0, 0, 0), one, one, one, 0, one, 0, None,
+                              None, one, one, 100, 32, 32, one, one, one, None, 0, one, one, one, None, None, None)
     assert L.splat_alpha_blending_backward_batch_sets(*args([0, 3, 4], [3, 1, 18], 23)) == -1     # channel 22 uncovered
     assert b"cover" in L.splat_last_error()
     assert L.splat_alpha_blending_backward_batch_sets(*args([0, 3, 3], [3, 1, 19], 23)) == -1     # overlap
     assert L.splat_alpha_blending_backward_batch_sets(*args([0, 5, 6], [5, 1, 17], 23)) == -1     # tap set wider than 4
     assert L.splat_alpha_blending_backward_batch_sets(*args([0, 3, 4], [3, 1, 25], 29)) == -1     # C > 28
+
+
+# ---- the binding is read from the header (splatter_a_video_amd/_abi.py) ----
+
+_SYNTHETIC = """
+/* a header of every form include/splat_hip.h uses */
+#ifndef T_H
+#define T_H
+typedef void *t_stream_t; /* a handle */
+#define T_OK 0
+#define T_E_ARG (-1) /* bad argument */
+#define T_VERSION 7
+typedef struct t_batch_t {
+    size_t struct_bytes;
+    int32_t F, P;
+    int64_t capacity;      /* pairs */
+    float bg;
+    t_stream_t stream;
+    const float *xyz, *offsets, *extr;
+    uint64_t *keys;
+} t_batch_t;
+const char *t_last_error(void);
+size_t t_scratch_bytes(int P, int64_t capacity, uint64_t seed);
+void t_set(int on);
+int t_run(int P, const float *xyz /*[P,3]*/, float *out /*[P] or NULL*/, float *const *set_out,
+          const char *key, float bg, size_t n, const t_batch_t *batch, // trailing
+          t_stream_t stream);
+#endif
+"""
+
+
+def test_reader_on_a_synthetic_header():
+    from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
+    from splatter_a_video_amd import _abi
+    h = _abi.parse(_SYNTHETIC)
+    assert h.defines == {"T_OK": 0, "T_E_ARG": -1, "T_VERSION": 7}
+    assert list(h.functions) == ["t_last_error", "t_scratch_bytes", "t_set", "t_run"]
+    assert h.functions["t_last_error"] == (c_char_p, [])
+    assert h.functions["t_scratch_bytes"] == (c_size_t, [c_int, c_int64, c_uint64])
+    assert h.functions["t_set"] == (None, [c_int])
+    assert h.functions["t_run"] == (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_char_p, c_float, c_size_t, c_void_p, c_void_p])
+    S = h.structs["t_batch_t"]
+    assert list(h.structs) == ["t_batch_t"] and issubclass(S, ctypes.Structure)
+    assert S._fields_ == [("struct_bytes", c_size_t), ("F", c_int32), ("P", c_int32), ("capacity", c_int64), ("bg", c_float),
+                          ("stream", c_void_p), ("xyz", c_void_p), ("offsets", c_void_p), ("extr", c_void_p), ("keys", c_void_p)]
+    assert [getattr(S, n).offset for n, _ in S._fields_] == [0, 8, 12, 16, 24, 32, 40, 48, 56, 64]
+    assert ctypes.sizeof(S) == 72
+    # an unknown type is an error that names the function (and the parameter), never an int
+    with pytest.raises(_abi.HeaderError, match=r"t_bad, parameter 2 'mode'.*quux_t"):
+        _abi.parse("int t_bad(int P, quux_t mode);")
+    with pytest.raises(_abi.HeaderError, match="t_bad2, return type"):
+        _abi.parse("quux_t *t_bad2(void);")
+    with pytest.raises(_abi.HeaderError, match="t_bad3"):
+        _abi.parse("int t_bad3(unsigned int P);")
+    with pytest.raises(_abi.HeaderError, match="t_s.*field"):
+        _abi.parse("typedef struct t_s { int a; quux_t b; } t_s;")
+    with pytest.raises(_abi.HeaderError, match="cannot parse"):
+        _abi.parse("int t_ok(void); static int x = 3;")
+
+
+def test_whole_header_is_applied_to_every_function(built_lib):
+    from splatter_a_video_amd import frames
+    L = built_lib
+    lib = L.lib()
+    header = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "splat_hip.h")).read(), flags=re.S)
+    protos = re.findall(r"([\w \*]+?)\b(splat_\w+)\s*\(([^()]*)\)\s*;", header)
+    assert len(protos) == len(L.SYMBOLS) == 129
+    for ret, name, params in protos:
+        fn = getattr(lib, name)
+        n = 0 if params.strip() == "void" else params.count(",") + 1
+        assert fn.argtypes is not None and len(fn.argtypes) == n, name
+        ret = " ".join(ret.split())
+        want = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p, "void": None}[ret]
+        assert fn.restype is want, name
+    assert ctypes.sizeof(frames._SplatFrames) == 400
+    assert ctypes.sizeof(frames._SplatCamera) == 48
+    assert ctypes.sizeof(L.FeatureSource) == 32
+    assert L.ABI_VERSION == 22 and L.MAX_SOURCES == 8
+    assert L.HEADER.defines["SPLAT_E_ARG"] == -1 and L.HEADER.defines["SPLAT_E_CAPACITY"] == -3
+
+
+def test_crossings_of_the_abi_are_checked(built_lib):
+    """splat_bin_count_batch had no prototype on the Python side before the header was bound: a missing argument or a
+    wrong kind of scalar now raises instead of reaching the library"""
+    lib = built_lib.lib()
+    one = ctypes.c_void_p(8)
+    good = (-1, 10, one, one, 32, 32, one, one, one, None)
+    with pytest.raises(TypeError):
+        lib.splat_bin_count_batch(*good[:-1])
+    with pytest.raises(ctypes.ArgumentError):
+        lib.splat_bin_count_batch(ctypes.c_int64(-1), *good[1:])
+    with pytest.raises(ctypes.ArgumentError):
+        lib.splat_bin_count_batch(-1, 10.0, *good[2:])
+    assert lib.splat_bin_count_batch(*good) == -1
+    assert b"bad sizes" in lib.splat_last_error()

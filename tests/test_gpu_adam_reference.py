@@ -4,7 +4,6 @@ float4 body + scalar tail), group boundaries inside a float4, PatternLR periods 
 a buffer past one grid-stride trip; the blocks of ZeRO-1 (Zero1Shards, padded bucket) and of OwnerShards for every rank of a
 world emulated in one process (OwnerShardedAdam.step makes no collective); TrainingStep(zero1=True) with a padded bucket; and the
 bucket's zero fill (splat_fill_f32).  One GPU, no process group."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -291,7 +290,7 @@ def test_fill_at_every_alignment_leaves_its_neighbours_alone(n):
         assert buf.data_ptr() % 16 == 0
         want = buf.clone()
         want[off:off + n].fill_(1.25)
-        L.check(L.lib().splat_fill_f32(L.ptr(buf[off:]), ctypes.c_size_t(n), L.cf(1.25), L.stream()))
+        L.check(L.lib().splat_fill_f32(L.ptr(buf[off:]), n, 1.25, L.stream()))
         torch.cuda.synchronize()
         assert torch.equal(buf, want), (n, off)
 

@@ -69,8 +69,8 @@ def _dense(geom, feat, bg):
     nc = torch.empty(H, W, dtype=torch.int32, device="cuda")
     pack = torch.empty(max(N, 1) * lib.splat_blend_pack_floats(C), device="cuda")
     L.check(lib.splat_alpha_blending_forward(
-        L.ci(N), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(op), L.ptr(feat), L.ptr(None), L.ptr(idx), L.ptr(tr), L.cf(bg),
-        L.ptr(None), L.ci(W), L.ci(H), L.ci(0), L.ci(0), L.ptr(out), L.ptr(fT), L.ptr(nc), L.ptr(None), L.ptr(pack), L.stream()))
+        N, C, L.ptr(uv), L.ptr(conic), L.ptr(op), L.ptr(feat), L.ptr(None), L.ptr(idx), L.ptr(tr), bg,
+        L.ptr(None), W, H, 0, 0, L.ptr(out), L.ptr(fT), L.ptr(nc), L.ptr(None), L.ptr(pack), L.stream()))
     assert torch.equal(out, img)
     return img.cpu().numpy(), fT.cpu().numpy(), nc.cpu().numpy()
 

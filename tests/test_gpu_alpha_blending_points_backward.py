@@ -222,8 +222,8 @@ def test_forward_of_the_live_corners_reports_the_same_values_and_maps():
             out = torch.full((len(pts), C), 7.0, device="cuda")
             cT = torch.full((len(pts), 4), 7.0, device="cuda")
             cn = torch.full((len(pts), 4), 7, dtype=torch.int32, device="cuda")
-            L.check(fn(L.ci(N), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(op), L.ptr(feat), L.ptr(idx), L.ptr(tr), L.cf(0.75), L.ci(W),
-                       L.ci(H), L.ci(len(pts)), L.ptr(_t(pts)), L.ptr(out), L.ptr(cT), L.ptr(cn), L.stream()))
+            L.check(fn(N, C, L.ptr(uv), L.ptr(conic), L.ptr(op), L.ptr(feat), L.ptr(idx), L.ptr(tr), 0.75, W,
+                       H, len(pts), L.ptr(_t(pts)), L.ptr(out), L.ptr(cT), L.ptr(cn), L.stream()))
             res.append((out, cT.cpu().numpy(), cn.cpu().numpy()))
         (out_a, T_a, n_a), (out_b, T_b, n_b) = res
         assert torch.equal(out_a, out_b)

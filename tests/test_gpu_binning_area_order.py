@@ -10,7 +10,6 @@ and twice; all four runs must be equal.
 Reach masks: binning_ref has no cull test, so the reach WORDS are checked where the decision is clear (opacity below 1/255: no
 tile; a conic flat over the whole rectangle at opacity 1: every tile), must not depend on segment length or run, and everything
 else (counts, prefix, tile ranges, sorted ids and slots, owner) is derived from the words in numpy and compared exactly."""
-import ctypes
 import functools
 
 import numpy as np
@@ -211,21 +210,21 @@ def _run(frames, opacity, W, H, reach):
     scratch = torch.empty(F * lib.splat_bin_scratch_bytes(P, W, H), dtype=torch.uint8, device="cuda")
     tr, m, gcount, words = _full(F * T * 2).view(F, T, 2), _full(F), _full(F * P), _full(F * P)
     if reach:
-        L.check(lib.splat_bin_count_batch_reach(L.ci(F), L.ci(P), L.ptr(uv), L.ptr(radius), L.ptr(conic), L.ptr(op), ctypes.c_int64(0),
-                                                L.ci(W), L.ci(H), L.ptr(scratch), L.ptr(tr), L.ptr(m), L.ptr(gcount), L.ptr(words), st))
+        L.check(lib.splat_bin_count_batch_reach(F, P, L.ptr(uv), L.ptr(radius), L.ptr(conic), L.ptr(op), 0,
+                                                W, H, L.ptr(scratch), L.ptr(tr), L.ptr(m), L.ptr(gcount), L.ptr(words), st))
     else:
-        L.check(lib.splat_bin_count_batch(L.ci(F), L.ci(P), L.ptr(uv), L.ptr(radius), L.ci(W), L.ci(H), L.ptr(scratch), L.ptr(tr), L.ptr(m), st))
+        L.check(lib.splat_bin_count_batch(F, P, L.ptr(uv), L.ptr(radius), W, H, L.ptr(scratch), L.ptr(tr), L.ptr(m), st))
     Ms = _n(m).tolist()
     cap = max(max(Ms), 0) + 64
     keys, idx, owner, slot = _full(F * cap, torch.int64), _full(F * cap), _full(F * cap), _full(F * cap)
     goff, ovf = _full(F * P), torch.zeros(1, dtype=torch.int32, device="cuda")
     if reach:
-        L.check(lib.splat_bin_sort_batch_reach(L.ci(F), L.ci(P), L.ptr(uv), L.ptr(depth), L.ptr(radius), L.ptr(words), L.ci(W), L.ci(H),
-                                               L.ptr(scratch), L.ptr(tr), ctypes.c_int64(cap), L.ptr(keys), L.ptr(idx), L.ptr(ovf),
+        L.check(lib.splat_bin_sort_batch_reach(F, P, L.ptr(uv), L.ptr(depth), L.ptr(radius), L.ptr(words), W, H,
+                                               L.ptr(scratch), L.ptr(tr), cap, L.ptr(keys), L.ptr(idx), L.ptr(ovf),
                                                L.ptr(goff), L.ptr(owner), L.ptr(slot), st))
     else:
-        L.check(lib.splat_bin_sort_batch(L.ci(F), L.ci(P), L.ptr(uv), L.ptr(depth), L.ptr(radius), L.ci(W), L.ci(H), L.ptr(scratch),
-                                         L.ptr(tr), ctypes.c_int64(cap), L.ptr(keys), L.ptr(idx), L.ptr(ovf), L.ptr(goff), L.ptr(owner),
+        L.check(lib.splat_bin_sort_batch(F, P, L.ptr(uv), L.ptr(depth), L.ptr(radius), W, H, L.ptr(scratch),
+                                         L.ptr(tr), cap, L.ptr(keys), L.ptr(idx), L.ptr(ovf), L.ptr(goff), L.ptr(owner),
                                          L.ptr(slot), st))
     torch.cuda.synchronize()
     assert int(ovf.item()) == 0

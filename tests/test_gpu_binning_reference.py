@@ -6,7 +6,6 @@ and one render on both sides of the LDS / global boundary.  Every expected value
 
 The library is called two ways: through gs.sort_gaussian / gs.sort_gaussian_capped (pair-map mode: goff_incl, slot_sorted) and
 through the raw C ABI with goff_incl / owner / slot_sorted NULL (low key word = Gaussian id)."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -47,14 +46,14 @@ def _raw_sort(uv, depth, radius, W, H, capacity=None, pairmap=False, extra=0):
     gx, gy = R.grid(W, H)
     scratch = torch.empty(lib.splat_bin_scratch_bytes(P, W, H), dtype=torch.uint8, device="cuda")
     tr, m, gcount = _full(2 * gx * gy).view(-1, 2), _full(1), _full(P)
-    L.check(lib.splat_bin_count(L.ci(P), L.ptr(uv), L.ptr(radius), L.ci(W), L.ci(H), L.ptr(scratch), L.ptr(tr), L.ptr(m), L.ptr(gcount), st))
+    L.check(lib.splat_bin_count(P, L.ptr(uv), L.ptr(radius), W, H, L.ptr(scratch), L.ptr(tr), L.ptr(m), L.ptr(gcount), st))
     M = int(m.item())
     cap = M if capacity is None else int(capacity(M))
     n = max(M, cap) + extra
     keys, idx, ovf = _full(n, torch.int64), _full(n), torch.zeros(1, dtype=torch.int32, device="cuda")
     goff, owner, slot = (_full(P), _full(n), _full(n)) if pairmap else (None, None, None)
-    L.check(lib.splat_bin_sort(L.ci(P), L.ptr(uv), L.ptr(depth), L.ptr(radius), L.ci(W), L.ci(H), L.ptr(scratch), L.ptr(tr),
-                               ctypes.c_int64(cap), L.ptr(keys), L.ptr(idx), L.ptr(ovf), L.ptr(goff), L.ptr(owner), L.ptr(slot), st))
+    L.check(lib.splat_bin_sort(P, L.ptr(uv), L.ptr(depth), L.ptr(radius), W, H, L.ptr(scratch), L.ptr(tr),
+                               cap, L.ptr(keys), L.ptr(idx), L.ptr(ovf), L.ptr(goff), L.ptr(owner), L.ptr(slot), st))
     torch.cuda.synchronize()
     out = dict(idx=_n(idx), tr=_n(tr), M=int(m.item()), gcount=_n(gcount), ovf=int(ovf.item()), cap=cap, keys=_n(keys))
     if pairmap:
@@ -140,14 +139,14 @@ def _batch(F, P, W, H, rmax, seed):
     bytes_ = lib.splat_bin_scratch_bytes(P, W, H)
     scratch = torch.empty(F * bytes_, dtype=torch.uint8, device="cuda")
     tr, m = _full(F * T * 2).view(F, T, 2), _full(F)
-    L.check(lib.splat_bin_count_batch(L.ci(F), L.ci(P), L.ptr(uv), L.ptr(radius), L.ci(W), L.ci(H), L.ptr(scratch), L.ptr(tr), L.ptr(m), st))
+    L.check(lib.splat_bin_count_batch(F, P, L.ptr(uv), L.ptr(radius), W, H, L.ptr(scratch), L.ptr(tr), L.ptr(m), st))
     Ms = _n(m).tolist()
     assert Ms == [r.M for r in refs]
     cap = max(Ms) + 100
     keys, idx, owner, slot = _full(F * cap, torch.int64), _full(F * cap), _full(F * cap), _full(F * cap)
     goff, ovf = _full(F * P), torch.zeros(1, dtype=torch.int32, device="cuda")
-    L.check(lib.splat_bin_sort_batch(L.ci(F), L.ci(P), L.ptr(uv), L.ptr(depth), L.ptr(radius), L.ci(W), L.ci(H), L.ptr(scratch), L.ptr(tr),
-                                     ctypes.c_int64(cap), L.ptr(keys), L.ptr(idx), L.ptr(ovf), L.ptr(goff), L.ptr(owner), L.ptr(slot), st))
+    L.check(lib.splat_bin_sort_batch(F, P, L.ptr(uv), L.ptr(depth), L.ptr(radius), W, H, L.ptr(scratch), L.ptr(tr),
+                                     cap, L.ptr(keys), L.ptr(idx), L.ptr(ovf), L.ptr(goff), L.ptr(owner), L.ptr(slot), st))
     torch.cuda.synchronize()
     assert int(ovf.item()) == 0
     tr, idx, slot, goff, keys, owner = _n(tr), _n(idx).reshape(F, cap), _n(slot).reshape(F, cap), _n(goff).reshape(F, P), \
@@ -220,13 +219,13 @@ def _reach_sort(d, W, H):
     gx, gy = R.grid(W, H)
     scratch = torch.empty(lib.splat_bin_scratch_bytes(P, W, H), dtype=torch.uint8, device="cuda")
     tr, m, gcount, reach = _full(2 * gx * gy).view(-1, 2), _full(1), _full(P), _full(P)
-    L.check(lib.splat_bin_count_batch_reach(L.ci(1), L.ci(P), L.ptr(uv), L.ptr(radius), L.ptr(conic), L.ptr(op), ctypes.c_int64(0),
-                                            L.ci(W), L.ci(H), L.ptr(scratch), L.ptr(tr), L.ptr(m), L.ptr(gcount), L.ptr(reach), st))
+    L.check(lib.splat_bin_count_batch_reach(1, P, L.ptr(uv), L.ptr(radius), L.ptr(conic), L.ptr(op), 0,
+                                            W, H, L.ptr(scratch), L.ptr(tr), L.ptr(m), L.ptr(gcount), L.ptr(reach), st))
     M = int(m.item())
     keys, idx, owner, slot = _full(M, torch.int64), _full(M), _full(M), _full(M)
     goff, ovf = _full(P), torch.zeros(1, dtype=torch.int32, device="cuda")
-    L.check(lib.splat_bin_sort_batch_reach(L.ci(1), L.ci(P), L.ptr(uv), L.ptr(depth), L.ptr(radius), L.ptr(reach), L.ci(W), L.ci(H),
-                                           L.ptr(scratch), L.ptr(tr), ctypes.c_int64(M), L.ptr(keys), L.ptr(idx), L.ptr(ovf),
+    L.check(lib.splat_bin_sort_batch_reach(1, P, L.ptr(uv), L.ptr(depth), L.ptr(radius), L.ptr(reach), W, H,
+                                           L.ptr(scratch), L.ptr(tr), M, L.ptr(keys), L.ptr(idx), L.ptr(ovf),
                                            L.ptr(goff), L.ptr(owner), L.ptr(slot), st))
     torch.cuda.synchronize()
     assert int(ovf.item()) == 0

@@ -68,8 +68,8 @@ def test_single_frame_backward_with_and_without_the_forwards_cull_words(C, with_
         nc = torch.empty(H, W, dtype=torch.int32, device="cuda")
         pack = torch.empty(N * lib.splat_blend_pack_floats(C), device="cuda")
         flags = torch.empty(M, dtype=torch.int32, device="cuda") if use_flags else None
-        head = (L.ci(N), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opac), L.ptr(feat), L.ptr(None), L.ptr(idx), L.ptr(tr), L.cf(0.2),
-                L.ptr(None), L.ci(W), L.ci(H), L.ci(0), L.ci(0), L.ptr(out), L.ptr(fT), L.ptr(nc), L.ptr(None), L.ptr(pack))
+        head = (N, C, L.ptr(uv), L.ptr(conic), L.ptr(opac), L.ptr(feat), L.ptr(None), L.ptr(idx), L.ptr(tr), 0.2,
+                L.ptr(None), W, H, 0, 0, L.ptr(out), L.ptr(fT), L.ptr(nc), L.ptr(None), L.ptr(pack))
         if use_flags:
             L.check(lib.splat_alpha_blending_forward_flags(*head, L.ptr(flags), L.stream()))
         else:
@@ -77,9 +77,9 @@ def test_single_frame_backward_with_and_without_the_forwards_cull_words(C, with_
         duv = torch.empty(N, 2, device="cuda"); dabs = torch.empty(N, 2, device="cuda") if with_abs else None
         dcon = torch.empty(N, 3, device="cuda"); dop = torch.empty(N, 1, device="cuda"); dfe = torch.empty(N, C, device="cuda")
         scratch = torch.empty(M * lib.splat_blend_pair_floats(C, 0), device="cuda")
-        args = (L.ci(N), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opac), L.ptr(feat), L.ptr(None), L.ptr(idx), L.ptr(tr), L.cf(0.2),
-                L.ci(W), L.ci(H), L.ptr(fT), L.ptr(nc), L.ptr(g), L.ptr(duv), L.ptr(dabs), L.ptr(dcon), L.ptr(dop), L.ptr(dfe),
-                L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(pm.goff), L.ptr(pm.slot_sorted), L.ptr(scratch), L.ptr(pack), L.ci(1),
+        args = (N, C, L.ptr(uv), L.ptr(conic), L.ptr(opac), L.ptr(feat), L.ptr(None), L.ptr(idx), L.ptr(tr), 0.2,
+                W, H, L.ptr(fT), L.ptr(nc), L.ptr(g), L.ptr(duv), L.ptr(dabs), L.ptr(dcon), L.ptr(dop), L.ptr(dfe),
+                L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(pm.goff), L.ptr(pm.slot_sorted), L.ptr(scratch), L.ptr(pack), 1,
                 L.ptr(None))
         if use_flags:
             L.check(lib.splat_alpha_blending_backward_flags(*args, L.ptr(flags), L.stream()))

@@ -148,15 +148,15 @@ def test_block_level_kernel_gives_way_in_deterministic_mode():
         nc = torch.empty(H, W, dtype=torch.int32, device="cuda")
         pack = torch.empty(N * lib.splat_blend_pack_floats(C), device="cuda")
         L.check(lib.splat_alpha_blending_forward(
-            L.ci(N), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opac), L.ptr(feat), L.ptr(None), L.ptr(idx), L.ptr(tr), L.cf(0.2),
-            L.ptr(None), L.ci(W), L.ci(H), L.ci(0), L.ci(0), L.ptr(out), L.ptr(fT), L.ptr(nc), L.ptr(None), L.ptr(pack), L.stream()))
+            N, C, L.ptr(uv), L.ptr(conic), L.ptr(opac), L.ptr(feat), L.ptr(None), L.ptr(idx), L.ptr(tr), 0.2,
+            L.ptr(None), W, H, 0, 0, L.ptr(out), L.ptr(fT), L.ptr(nc), L.ptr(None), L.ptr(pack), L.stream()))
         duv = torch.empty(N, 2, device="cuda"); dcon = torch.empty(N, 3, device="cuda")
         dop = torch.empty(N, 1, device="cuda"); dfe = torch.empty(N, C, device="cuda")
         scratch = torch.empty(M * lib.splat_blend_pair_floats(C, 0), device="cuda")
         L.check(lib.splat_alpha_blending_backward(
-            L.ci(N), L.ci(C), L.ptr(uv), L.ptr(conic), L.ptr(opac), L.ptr(feat), L.ptr(None), L.ptr(idx), L.ptr(tr), L.cf(0.2),
-            L.ci(W), L.ci(H), L.ptr(fT), L.ptr(nc), L.ptr(g), L.ptr(duv), L.ptr(None), L.ptr(dcon), L.ptr(dop), L.ptr(dfe),
-            L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(pm.goff), L.ptr(pm.slot_sorted), L.ptr(scratch), L.ptr(pack), L.ci(1),
+            N, C, L.ptr(uv), L.ptr(conic), L.ptr(opac), L.ptr(feat), L.ptr(None), L.ptr(idx), L.ptr(tr), 0.2,
+            W, H, L.ptr(fT), L.ptr(nc), L.ptr(g), L.ptr(duv), L.ptr(None), L.ptr(dcon), L.ptr(dop), L.ptr(dfe),
+            L.ptr(None), L.ptr(None), L.ptr(None), L.ptr(pm.goff), L.ptr(pm.slot_sorted), L.ptr(scratch), L.ptr(pack), 1,
             L.ptr(None), L.stream()))
         torch.cuda.synchronize()
         return dict(duv=duv, dcon=dcon, dop=dop, dfe=dfe)

@@ -10,7 +10,6 @@ Scenes: synth.make_scene, 1500 Gaussians at 100 x 60 (no multiple of 16 either w
 right tile have radius 0 (culled: in no list), so every scene has an empty tile.  Every comparison asserts its own coverage from
 tile_range and ncontrib: an empty tile, a list longer than two staging batches of the kernel (2 x 64 entries), pixels whose last
 contributor lies below their list length."""
-import ctypes
 import functools
 
 import numpy as np
@@ -109,9 +108,9 @@ def _native(name, feature, target, pw=None, active=None, buffers=None, want_maps
     blend_fit_color(s["uv"], s["conic"], s["op"], feature, s["idx"], s["tr"], s["slot"], 0.0, W, H, target, tile_loss, pair_grad,
                     pw, active, None, out, nc)
     hist = torch.zeros(3, device="cuda")
-    L.check(L.lib().splat_tile_loss_sum(L.ci(T), L.ptr(tile_loss), L.ptr(hist), ctypes.c_int64(1), L.stream()))
+    L.check(L.lib().splat_tile_loss_sum(T, L.ptr(tile_loss), L.ptr(hist), 1, L.stream()))
     dcolor = torch.empty(N, 4, device="cuda")
-    L.check(L.lib().splat_pair_records_segment_sum(L.ci(N), L.ci(4), L.ptr(pair_grad), L.ptr(s["goff"]), L.ptr(dcolor), L.stream()))
+    L.check(L.lib().splat_pair_records_segment_sum(N, 4, L.ptr(pair_grad), L.ptr(s["goff"]), L.ptr(dcolor), L.stream()))
     assert hist[0] == 0 and hist[2] == 0                  # only history[slot] is written
     return hist[1:2], dcolor, out, nc, tile_loss, pair_grad
 
@@ -222,9 +221,9 @@ def test_active_tiles(gpu, name):
     # n_active == 0: success, nothing launched
     keep = tile_loss.clone()
     lib = L.lib()
-    rc = lib.splat_blend_fit_color(L.ci(N), L.ci(3), L.ptr(s["uv"]), L.ptr(s["conic"]), L.ptr(s["op"]), L.ptr(feat0), L.ptr(s["idx"]),
-                                   L.ptr(s["tr"]), L.ptr(s["slot"]), ctypes.c_int64(s["M"]), L.cf(0.0), L.ci(W), L.ci(H), L.ptr(target),
-                                   L.ptr(None), L.ci(0), L.ptr(active), L.ptr(tile_loss), L.ptr(pair_grad), L.ptr(None), L.ptr(None),
+    rc = lib.splat_blend_fit_color(N, 3, L.ptr(s["uv"]), L.ptr(s["conic"]), L.ptr(s["op"]), L.ptr(feat0), L.ptr(s["idx"]),
+                                   L.ptr(s["tr"]), L.ptr(s["slot"]), s["M"], 0.0, W, H, L.ptr(target),
+                                   L.ptr(None), 0, L.ptr(active), L.ptr(tile_loss), L.ptr(pair_grad), L.ptr(None), L.ptr(None),
                                    L.stream())
     assert rc == 0
     blend_fit_color(s["uv"], s["conic"], s["op"], feat0, s["idx"], s["tr"], s["slot"], 0.0, W, H, target, tile_loss, pair_grad,

@@ -5,7 +5,6 @@ the per-frame centroids against a float64 mean, the clip mechanics (batches, cap
 wrappers.  One scene for all tests: 2001 dynamic Gaussians, 30 frames, 96 x 64, six frame times (not a multiple of the
 kernel's four-frame trip); the foreground x^2 + y^2 < 0.25 selects 345, so a copy makes Q = 2346 instances (not a multiple of
 the 64-quad block)."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -230,7 +229,7 @@ def _centroids(scene, tab, src, S, layout, cubic):
     scratch = torch.empty(nbytes // 8, dtype=torch.float64, device="cuda")
     out = torch.full((F, 3), float("nan"), device="cuda")
     L.check(lib.splat_layer_centroids(F, N, S, scene.I, L.ptr(tab), L.ptr(src), L.ptr(scene.model["position"]), L.ptr(cubic), layout,
-                                      L.ptr(out), L.ptr(scratch), ctypes.c_size_t(nbytes), L.stream()))
+                                      L.ptr(out), L.ptr(scratch), nbytes, L.stream()))
     return out
 
 

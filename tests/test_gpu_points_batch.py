@@ -116,8 +116,8 @@ def _forward_batch(fb, op, feat, fs, bg, pts, off, nF=F, frame0=0):
     cn = torch.full((Q, 4), 7, dtype=torch.int32, device="cuda")
     i64 = ctypes.c_int64
     L.check(L.lib().splat_alpha_blending_points_forward_batch(
-        L.ci(nF), L.ci(N), L.ci(C), L.ptr(fb.uv[frame0:]), L.ptr(fb.conic[frame0:]), L.ptr(op), i64(0), L.ptr(feat), i64(fs),
-        L.ptr(fb.idx_sorted[frame0:]), L.ptr(fb.tile_range[frame0:]), i64(fb.capacity), L.cf(bg), L.ci(W), L.ci(H), i64(Q), L.ptr(off),
+        nF, N, C, L.ptr(fb.uv[frame0:]), L.ptr(fb.conic[frame0:]), L.ptr(op), i64(0), L.ptr(feat), i64(fs),
+        L.ptr(fb.idx_sorted[frame0:]), L.ptr(fb.tile_range[frame0:]), i64(fb.capacity), bg, W, H, i64(Q), L.ptr(off),
         L.ptr(pts), L.ptr(out), L.ptr(cT), L.ptr(cn), L.stream()))
     return out, cT, cn
 

@@ -2,7 +2,6 @@
 tile) pairs whose tile the splat can reach with alpha >= 1/255.  The reference creates a pair for every tile of the bounding
 square (include/utils.h:17-37) and skips per pixel (src/alpha_blending.cu:78-95): a dropped pair must not change a bit of the
 images or ids, and the gradients only by summation order."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -99,16 +98,16 @@ def test_reach_entry_points_raw():
     scratch = torch.empty(lib.splat_bin_scratch_bytes(N, W, H), dtype=torch.uint8, device="cuda")
     tr, m, gcount, reach = torch.empty(T, 2, **i32), torch.zeros(1, **i32), torch.empty(N, **i32), torch.empty(N, **i32)
     st = L.stream()
-    L.check(lib.splat_bin_count_batch_reach(L.ci(1), L.ci(N), L.ptr(uv), L.ptr(radius), L.ptr(conic), L.ptr(op), ctypes.c_int64(0),
-                                            L.ci(W), L.ci(H), L.ptr(scratch), L.ptr(tr), L.ptr(m), L.ptr(gcount), L.ptr(reach), st))
+    L.check(lib.splat_bin_count_batch_reach(1, N, L.ptr(uv), L.ptr(radius), L.ptr(conic), L.ptr(op), 0,
+                                            W, H, L.ptr(scratch), L.ptr(tr), L.ptr(m), L.ptr(gcount), L.ptr(reach), st))
     M = int(m.item())
     assert M == int(gcount.sum()) and 0 < M < int(tiles.sum())
     assert int((tiles.view(-1) >= 32).sum()) > 10 and int((reach < 0).sum()) > 10
     assert bool((gcount <= tiles.view(-1)).all())
     keys, idx, owner, slot = torch.empty(M, dtype=torch.int64, device="cuda"), torch.empty(M, **i32), torch.empty(M, **i32), torch.empty(M, **i32)
     goff, ovf = torch.empty(N, **i32), torch.zeros(1, **i32)
-    L.check(lib.splat_bin_sort_batch_reach(L.ci(1), L.ci(N), L.ptr(uv), L.ptr(depth), L.ptr(radius), L.ptr(reach), L.ci(W), L.ci(H),
-                                           L.ptr(scratch), L.ptr(tr), ctypes.c_int64(M),
+    L.check(lib.splat_bin_sort_batch_reach(1, N, L.ptr(uv), L.ptr(depth), L.ptr(radius), L.ptr(reach), W, H,
+                                           L.ptr(scratch), L.ptr(tr), M,
                                            L.ptr(keys), L.ptr(idx), L.ptr(ovf), L.ptr(goff), L.ptr(owner), L.ptr(slot), st))
     torch.cuda.synchronize()
     assert int(ovf.item()) == 0 and torch.equal(goff, torch.cumsum(gcount, 0).int())

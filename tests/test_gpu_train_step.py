@@ -118,8 +118,8 @@ def test_l1_loss_and_gradient_in_one_pass():
     g = torch.empty(F, C, H, W, device="cuda")
     s = torch.zeros(1, device="cuda")
     scale = 0.7 / (F * C * H * W)
-    L.check(L.lib().splat_l1_loss_grad(L.ci(F), ctypes.c_int64(C * H * W), L.ptr(pred), ctypes.c_int64(pred.stride(0)), L.ptr(tgt),
-                                       L.cf(scale), L.ptr(g), L.ptr(s), L.stream()))
+    L.check(L.lib().splat_l1_loss_grad(F, C * H * W, L.ptr(pred), pred.stride(0), L.ptr(tgt),
+                                       scale, L.ptr(g), L.ptr(s), L.stream()))
     p2 = pred.detach().clone().requires_grad_(True)
     (0.7 * (p2 - tgt).abs().mean()).backward()
     assert torch.allclose(g, p2.grad, rtol=1e-6, atol=0) and abs(float(s) - float((pred - tgt).abs().sum())) < 1e-3 * float(s)

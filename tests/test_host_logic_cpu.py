@@ -67,7 +67,7 @@ def test_library_options_through_the_abi(built_lib=None):
         L.set_option("bwd_kernel_dpp", 1)
     i3 = __import__("ctypes").c_int32 * 3
     q = L.lib().splat_blend_sets_uses_forward_pack
-    assert q(L.ci(23), i3(0, 3, 4), i3(3, 1, 19), L.ci(1)) == 1 and q(L.ci(23), i3(0, 3, 4), i3(3, 1, 19), L.ci(0)) == 0
-    assert q(L.ci(8), i3(0, 3, 4), i3(3, 1, 4), L.ci(1)) == 0
+    assert q(23, i3(0, 3, 4), i3(3, 1, 19), 1) == 1 and q(23, i3(0, 3, 4), i3(3, 1, 19), 0) == 0
+    assert q(8, i3(0, 3, 4), i3(3, 1, 4), 1) == 0
     with L.option("sets_std", 0):
-        assert q(L.ci(23), i3(0, 3, 4), i3(3, 1, 19), L.ci(1)) == 0
+        assert q(23, i3(0, 3, 4), i3(3, 1, 19), 1) == 0

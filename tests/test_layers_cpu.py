@@ -90,7 +90,7 @@ def _cen(lib, **k):
     a = dict(F=6, P=100, S=40, I=4, tab=ONE, src=ONE, position=ONE, cubic=ONE, layout=0, centroid=ONE, scratch=ONE, nbytes=1 << 20)
     a.update(k)
     return lib.splat_layer_centroids(a["F"], a["P"], a["S"], a["I"], a["tab"], a["src"], a["position"], a["cubic"], a["layout"],
-                                     a["centroid"], a["scratch"], ctypes.c_size_t(a["nbytes"]), None)
+                                     a["centroid"], a["scratch"], a["nbytes"], None)
 
 
 def test_layer_centroids_validates_before_hip(L):

@@ -41,7 +41,7 @@ def _call(lib, **k):
              g=one, duv=one, dconic=one, dop=one, dfeat=one)
     a.update(k)
     return lib.splat_alpha_blending_points_backward(a["P"], a["C"], a["uv"], a["conic"], a["op"], a["feat"], a["idx"], a["tr"],
-                                                    ctypes.c_float(a["bg"]), a["W"], a["H"], a["Q"], a["pts"], a["cT"], a["cn"],
+                                                    a["bg"], a["W"], a["H"], a["Q"], a["pts"], a["cT"], a["cn"],
                                                     a["g"], a["duv"], a["dconic"], a["dop"], a["dfeat"], None)
 
 

@@ -65,7 +65,7 @@ def test_track_entry_point_validates_before_hip(L):
 
     def call(F=2, H=48, W=64, C=3, track=one, ts=st, offs=one, pix=one, tgt=one, Q=10, fw=one, q=0.98, grad=None, gs=None,
              scr=one):
-        return lib.splat_track_loss_grad(F, H, W, C, track, ts, offs, pix, tgt, ctypes.c_int64(Q), fw, f(q), f(1.0), grad, gs, 0,
+        return lib.splat_track_loss_grad(F, H, W, C, track, ts, offs, pix, tgt, Q, fw, f(q), f(1.0), grad, gs, 0,
                                          None, None, None, scr, None)
     assert call(F=0) == -1 and b"sizes" in lib.splat_last_error()
     assert call(H=0) == -1 and call(W=-3) == -1 and call(C=1) == -1 and call(Q=-1) == -1

@@ -75,8 +75,6 @@ def _points_queries(W, H, hx, hy):
 
 
 def _points_family(record):
-    import ctypes
-
     import numpy as np
     import torch
     import dptr.gs as gs
@@ -189,7 +187,6 @@ def _points_family(record):
     with torch.no_grad():
         render(fb, {k: v.detach() for k, v in leaves().items()})
     opa = torch.sigmoid(p["opacity"]).reshape(Nb, 1).contiguous()
-    i64 = ctypes.c_int64
     for C in (1, 3, 65, 150, 300):
         for per_frame in (False, True):
             feat = t(np.random.default_rng(300 + C).uniform(-1, 1, size=(Fb, Nb, C) if per_frame else (Nb, C)))
@@ -197,8 +194,8 @@ def _points_family(record):
             cT = torch.full((Q, 4), 7.0, device="cuda")
             cn = torch.full((Q, 4), 7, dtype=torch.int32, device="cuda")
             L.check(L.lib().splat_alpha_blending_points_forward_batch(
-                L.ci(Fb), L.ci(Nb), L.ci(C), L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opa), i64(0), L.ptr(feat), i64(Nb * C if per_frame else 0),
-                L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), i64(fb.capacity), L.cf(0.75), L.ci(Wb), L.ci(Hb), i64(Q), L.ptr(off),
+                Fb, Nb, C, L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opa), 0, L.ptr(feat), Nb * C if per_frame else 0,
+                L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), fb.capacity, 0.75, Wb, Hb, Q, L.ptr(off),
                 L.ptr(pts), L.ptr(out), L.ptr(cT), L.ptr(cn), L.stream()))
             torch.cuda.synchronize()
             assert float(out[-1].abs().max()) == 0 and int(cn[-1].abs().max()) == 0 and int(cn.max()) > 64

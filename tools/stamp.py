@@ -3,7 +3,6 @@ gpurun -- the GPU box has no .git) and the build id of the library that actually
     python tools/stamp.py write      # in the build container, before gpurun: tools/.stamp.json (git-ignored, travels)
     from stamp import stamp          # on the box, in the tools that write profiles/*.json
 """
-import ctypes
 import json
 import os
 import subprocess
@@ -14,9 +13,10 @@ PATH = os.path.join(ROOT, "tools", ".stamp.json")
 
 
 def build_id() -> str:
-    lib = ctypes.CDLL(os.environ.get("SPLAT_LIB_PATH") or os.path.join(ROOT, "splatter_a_video_amd", "libsplat_hip.so"))
-    lib.splat_build_id.restype = ctypes.c_char_p
-    return lib.splat_build_id().decode()
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    from splatter_a_video_amd import _lib
+    return _lib.build_id()
 
 
 def stamp() -> dict:
