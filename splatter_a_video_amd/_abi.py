@@ -1,4 +1,5 @@
-"""Reader of the C ABI's header (include/splat_hip.h): prototypes, structs and integer #defines as ctypes types.
+"""Reader of the C ABI's headers (include/splat_hip.h and its extension include/splat_hip_views.h): prototypes, structs and
+integer #defines as ctypes types.
 
 The header is the only place a prototype is written; ``_lib.lib()`` applies what ``parse`` yields to every function.
 Anything the reader does not understand raises ``HeaderError`` -- it never guesses a type.
@@ -27,6 +28,7 @@ class Header(NamedTuple):
     functions: Dict[str, Tuple[Optional[type], List[type]]]     # name -> (restype, argtypes), in header order
     structs: Dict[str, type]                                    # typedef name -> ctypes.Structure
     defines: Dict[str, int]
+    handles: Tuple[str, ...] = ()                               # handle typedefs (void *), an extension's base included
 
 
 def _ctype(base: str, stars: int, known: set, where: str):
@@ -53,7 +55,10 @@ def _spec(spec: str, known: set, where: str):
     return _ctype(p[1], p[2].count("*"), known, where + (f" '{p[3]}'" if p[3] else ""))
 
 
-def parse(text: str) -> Header:
+def parse(text: str, base: Optional[Header] = None) -> Header:
+    """``base``: the header this one extends (an extension header includes it for its handles and structs; ``#include`` lines are
+    blanked here, so the names come in through this argument).  The result lists the extension's own functions, structs and
+    defines."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"//[^\n]*", " ", text)
     defines = {m[1]: int(m[2]) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, re.M)}
@@ -61,9 +66,12 @@ def parse(text: str) -> Header:
     text = re.sub(r'extern\s+"C"\s*\{', " ", text)
 
     handles = set(re.findall(r"typedef\s+void\s*\*\s*(\w+)\s*;", text))
+    if base is not None:
+        handles |= set(base.handles)
     text = re.sub(r"typedef\s+void\s*\*\s*\w+\s*;", " ", text)
 
-    structs: Dict[str, type] = {}
+    structs: Dict[str, type] = dict(base.structs) if base is not None else {}
+    inherited = set(structs)
     for m in re.finditer(r"typedef\s+struct\s+\w*\s*\{(.*?)\}\s*(\w+)\s*;", text, re.S):
         name, fields = m[2], []
         for decl in filter(None, (d.strip() for d in m[1].split(";"))):
@@ -89,9 +97,9 @@ def parse(text: str) -> Header:
         if None in args:
             raise HeaderError(f"{name}: a parameter of type void")
         functions[name] = (_spec(m[1], known, f"{name}, return type"), args)
-    return Header(functions, structs, defines)
+    return Header(functions, {k: v for k, v in structs.items() if k not in inherited}, defines, tuple(sorted(handles)))
 
 
-def load(path: str) -> Header:
+def load(path: str, base: Optional[Header] = None) -> Header:
     with open(path) as f:
-        return parse(f.read())
+        return parse(f.read(), base)

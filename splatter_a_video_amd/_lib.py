@@ -1,4 +1,4 @@
-"""ctypes binding of libsplat_hip.so (C ABI: include/splat_hip.h).
+"""ctypes binding of libsplat_hip.so (C ABI: include/splat_hip.h and its extension include/splat_hip_views.h).
 
 The product path has NO fallback: if the HIP library is missing or a tensor is not a contiguous
 float32/int32 CUDA tensor the call raises.  (The CPU oracle lives in ``oracle/`` and is never
@@ -25,6 +25,11 @@ ABI_VERSION = HEADER.defines["SPLAT_ABI_VERSION"]
 MAX_SOURCES = HEADER.defines["SPLAT_MAX_SOURCES"]
 SYMBOLS = list(HEADER.functions)
 FeatureSource = HEADER.structs["splat_feature_source_t"]
+# entry points added after the core header was frozen: a header of their own (it includes the core header for its handles and
+# structs), the same library, a version of their own
+VIEWS_HEADER = _abi.load(os.path.join(_HERE, os.pardir, "include", "splat_hip_views.h"), HEADER)
+VIEWS_ABI_VERSION = VIEWS_HEADER.defines["SPLAT_VIEWS_ABI_VERSION"]
+VIEWS_SYMBOLS = list(VIEWS_HEADER.functions)
 
 
 class SplatError(RuntimeError):
@@ -43,11 +48,17 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C splatter_a_video_amd/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in HEADER.functions.items():
-            fn = getattr(L, name)
+        for name, (restype, argtypes) in list(HEADER.functions.items()) + list(VIEWS_HEADER.functions.items()):
+            fn = getattr(L, name, None)
+            if fn is None:
+                where = "splat_hip_views.h" if name in VIEWS_HEADER.functions else "splat_hip.h"
+                raise SplatError(f"{LIB_PATH} lacks {name} (include/{where}: the library is older than the headers); rebuild it")
             fn.restype, fn.argtypes = restype, argtypes
         if L.splat_abi_version() != ABI_VERSION:
             raise SplatError(f"{LIB_PATH} has ABI version {L.splat_abi_version()}, include/splat_hip.h {ABI_VERSION}; rebuild it")
+        if L.splat_views_abi_version() != VIEWS_ABI_VERSION:
+            raise SplatError(f"{LIB_PATH} has views ABI version {L.splat_views_abi_version()}, include/splat_hip_views.h "
+                             f"{VIEWS_ABI_VERSION}; rebuild it")
         _lib = L
     return _lib
 

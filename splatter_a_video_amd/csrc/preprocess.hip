@@ -7,6 +7,7 @@
 #include "common.h"
 #include "pointwise_dev.h"
 #include "dynamics_dev.h"
+#include "../../include/splat_hip_views.h"
 
 namespace {
 
@@ -746,6 +747,71 @@ frame_preprocess_fwd_batch_kernel(int F, int P, int I, int layout, const DynTab 
             ewa_T<true>(c, m_pos, W, H, a, bb, tt, Jm);
             ewa_cov2d<true>(a, bb, c3, cov);
             ewa_finish_pt<true>(cov, make_float2(u, v), W, H, o[0], o[1], o[2], orad, otiles);
+        }
+        const size_t fn = (size_t)(f + j) * P + n;
+        *reinterpret_cast<float2 *>(uv + fn * 2) = make_float2(u, v);
+        conic[fn * 3] = o[0]; conic[fn * 3 + 1] = o[1]; conic[fn * 3 + 2] = o[2];
+        depth[fn] = dep;
+        radius[fn] = orad;
+    }
+}
+
+// The same batch under a camera PER FRAME (novel-view orbits, the two eyes of a stereo clip: src/trainer_fragGS.py:1123-1261)
+// and / or the pinhole camera (the renderer's enable_ortho_projection switch, dptr_ortho_enhanced.py:280-321).  CAM = 1:
+// orthographic cameras that differ from frame to frame; CAM = 2: pinhole.  The structure is the kernel's above; lane k of the
+// quad keeps frame f + k AND that frame's camera (extr + (f + k) * extr_fs, intr + (f + k) * intr_fs: all quads of a wave read
+// the same four 64-byte rows, cache hits after the first wave of a block).  The camera rows are requested at the top of the
+// trip, ahead of the spline segments, so their latency hides behind the evaluation.  CAM = 2 runs the chain of
+// preprocess_fwd_kernel<false>: the same device functions in the same order.  Forward only; no LDS, no atomics.
+template <int CAM>
+__global__ void __launch_bounds__(DYN_BLOCK)
+frame_preprocess_fwd_batch_cam_kernel(int F, int P, int I, int layout, const DynTab *__restrict__ tab,
+                                      const float *__restrict__ position, const float *__restrict__ cubic,
+                                      const float *__restrict__ rotation, const float4 *__restrict__ rot_poly,
+                                      const float4 *__restrict__ rot_fourier, const float *__restrict__ opacity,
+                                      const float *__restrict__ scaling, const float *__restrict__ intr,
+                                      const float *__restrict__ extr, long long intr_fs, long long extr_fs, int W, int H,
+                                      float nearest, float extent, float *__restrict__ uv, float *__restrict__ depth,
+                                      float *__restrict__ conic, int *__restrict__ radius, float *__restrict__ opa_t) {
+    constexpr bool ORTHO = CAM == 1;
+    const int t = blockIdx.x * DYN_BLOCK + threadIdx.x;
+    const int n = t >> 2, j = t & 3;
+    if (n >= P) return;  // whole quads leave together
+    const DynStatic stc = dyn_static(n, j, position, rotation, rot_poly, rot_fourier, scaling);
+    const int per = (F + gridDim.y - 1) / gridDim.y;
+    const int f0 = blockIdx.y * per, f1 = imin_(F, f0 + per);
+    if (blockIdx.y == 0 && j == 3) opa_t[n] = 1.0f / (1.0f + expf(-opacity[n]));  // frame independent
+    const float scl3[3] = {quad_bcast<0>(stc.scl_j), quad_bcast<1>(stc.scl_j), quad_bcast<2>(stc.scl_j)};
+    for (int f = f0; f < f1; f += 4) {
+        Cam c;
+        {   // this lane's frame (a lane past the slice reads the slice's last camera and does not store)
+            const size_t fc = (size_t)imin_(f + j, f1 - 1);
+            load_cam(ORTHO ? nullptr : intr + fc * intr_fs, extr + fc * extr_fs, c);
+        }
+        float m_pos[3] = {0.f, 0.f, 0.f}, m_q[4] = {1.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int ff = imin_(f + k, f1 - 1);  // (a repeated last frame: its lane does not store)
+            const CubicAddr ca = cubic_addr(layout, P, I, tab[ff].seg);
+            const DynFrame fr = dyn_frame_rows(n, j, ca, tab[ff].d, tab[ff].basis, stc, cubic);
+            if (j == k) {
+                m_pos[0] = fr.pos[0]; m_pos[1] = fr.pos[1]; m_pos[2] = fr.pos[2];
+                m_q[0] = fr.q[0]; m_q[1] = fr.q[1]; m_q[2] = fr.q[2]; m_q[3] = fr.q[3];
+            }
+        }
+        if (f + j >= f1) continue;
+        float u, v, dep;
+        const bool cull = ORTHO ? project_ortho_pt(c, m_pos[0], m_pos[1], m_pos[2], W, H, nearest, extent, u, v, dep)
+                                : project_persp_pt(c, m_pos[0], m_pos[1], m_pos[2], W, H, nearest, extent, u, v, dep);
+        u = cull ? 0.f : u; v = cull ? 0.f : v; dep = cull ? 0.f : dep;
+        float o[3] = {0.f, 0.f, 0.f};
+        int orad = 0, otiles = 0;
+        if (dep != 0.f) {
+            float c3[6], a[3], bb[3], tt[3], Jm[4], cov[3];
+            cov3d_pt(scl3, m_q, c3);
+            ewa_T<ORTHO>(c, m_pos, W, H, a, bb, tt, Jm);
+            ewa_cov2d<ORTHO>(a, bb, c3, cov);
+            ewa_finish_pt<ORTHO>(cov, make_float2(u, v), W, H, o[0], o[1], o[2], orad, otiles);
         }
         const size_t fn = (size_t)(f + j) * P + n;
         *reinterpret_cast<float2 *>(uv + fn * 2) = make_float2(u, v);
@@ -1668,6 +1734,44 @@ extern "C" int splat_frame_preprocess_forward_batch(int F, int P, int I, const v
     SPLAT_LAUNCH("frame_preprocess_fwd", frame_preprocess_fwd_batch_kernel, dim3(g.x, slices), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
                  F, P, I, cubic_layout, (const DynTab *)tab, position, cubic, rotation, (const float4 *)rot_poly,
                  (const float4 *)rot_fourier, opacity, scaling, extr, W, H, nearest, extent, uv, depth, conic, radius, opa_t);
+    SPLAT_POST_LAUNCH();
+    return SPLAT_OK;
+}
+
+// ---- the same batch under any camera (include/splat_hip_views.h): one orthographic camera IS the entry point above (its
+// kernel, its bits); cameras per frame and the pinhole camera run frame_preprocess_fwd_batch_cam_kernel.  Forward only.
+extern "C" int splat_frame_preprocess_forward_batch_cam(int F, int P, int I, const void *tab, const float *position,
+                                                        const float *cubic, int cubic_layout, const float *rotation,
+                                                        const float *rot_poly, const float *rot_fourier, const float *opacity,
+                                                        const float *scaling, const splat_camera_t *cam, int W, int H,
+                                                        float nearest, float extent, float *uv, float *depth, float *conic,
+                                                        int32_t *radius, float *opa_t, void *stream) {
+    SPLAT_CHECK_ARG(F >= 1 && F <= 65535 && P >= 1 && I >= 1 && W > 0 && H > 0, "bad sizes");
+    SPLAT_CHECK_ARG(cam && cam->extr, "null camera (cam and cam->extr are required)");
+    SPLAT_CHECK_ARG(!cam->perspective || cam->intr, "the perspective camera needs intr");
+    SPLAT_CHECK_ARG(cam->extr_frame_stride >= 0 && cam->intr_frame_stride >= 0, "negative camera stride");
+    if (!cam->perspective && (cam->extr_frame_stride == 0 || F == 1))
+        return splat_frame_preprocess_forward_batch(F, P, I, tab, position, cubic, cubic_layout, rotation, rot_poly, rot_fourier,
+                                                    opacity, scaling, cam->extr, W, H, nearest, extent, uv, depth, conic, radius,
+                                                    opa_t, stream);
+    SPLAT_CHECK_ARG(cubic_layout == SPLAT_CUBIC_GAUSSIAN_MAJOR || cubic_layout == SPLAT_CUBIC_SEGMENT_MAJOR, "unknown cubic_layout");
+    SPLAT_CHECK_ARG(tab && position && cubic && rotation && rot_poly && rot_fourier && opacity && scaling, "null input pointer");
+    SPLAT_CHECK_ARG(uv && depth && conic && radius && opa_t, "null output pointer");
+    const dim3 g = dyn_grid(P);
+    int slices = (int)((4096 + g.x - 1) / g.x);   // frames per thread: as in splat_frame_preprocess_forward_batch
+    if (slices < 1) slices = 1;
+    if (slices > F) slices = F;
+    if (cam->perspective)
+        SPLAT_LAUNCH("frame_preprocess_fwd_cam", frame_preprocess_fwd_batch_cam_kernel<2>, dim3(g.x, slices), dim3(DYN_BLOCK), 0,
+                     (hipStream_t)stream, F, P, I, cubic_layout, (const DynTab *)tab, position, cubic, rotation,
+                     (const float4 *)rot_poly, (const float4 *)rot_fourier, opacity, scaling, cam->intr, cam->extr,
+                     (long long)cam->intr_frame_stride, (long long)cam->extr_frame_stride, W, H, nearest, extent, uv, depth,
+                     conic, radius, opa_t);
+    else
+        SPLAT_LAUNCH("frame_preprocess_fwd_cam", frame_preprocess_fwd_batch_cam_kernel<1>, dim3(g.x, slices), dim3(DYN_BLOCK), 0,
+                     (hipStream_t)stream, F, P, I, cubic_layout, (const DynTab *)tab, position, cubic, rotation,
+                     (const float4 *)rot_poly, (const float4 *)rot_fourier, opacity, scaling, (const float *)nullptr, cam->extr,
+                     0ll, (long long)cam->extr_frame_stride, W, H, nearest, extent, uv, depth, conic, radius, opa_t);
     SPLAT_POST_LAUNCH();
     return SPLAT_OK;
 }

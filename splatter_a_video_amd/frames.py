@@ -396,7 +396,7 @@ class FrameBatch:
                             rotation: Tensor, rot_poly_feat: Tensor, rot_fourier_feat: Tensor, opacity: Tensor, scaling: Tensor,
                             cubic_layout: int = 1, K: int = 0, nearest: float = 0.01, extent: float = 1.3,
                             grad_sink: Optional[Dict[str, Tensor]] = None, points: Optional[dict] = None,
-                            wide: Optional[dict] = None):
+                            wide: Optional[dict] = None, intr: Optional[Tensor] = None):
         """The reference's real training frame, for all frames of the batch: its dynamic Gaussians (``render_dynamic``)
         through the three blends of ``render_iter`` (``render_sets``: same ``sets`` list, same return value).  The sets must
         fit the one-pass backward (one set per routing group, <= 4 / 4 / 20 channels).
@@ -429,8 +429,22 @@ class FrameBatch:
         parameters; not w.r.t. the opacity, and it feeds no taps.  Per 32-channel chunk its backward runs the tile kernels of the
         window and folds the chunk's records into the row's pair records before the Gaussian-side backward (no float atomics); the
         feature's gradient is ADDED to ``grad_sink["wide"]`` ([P, c]) when given, else returned through autograd.  A ``None``
-        gradient of the wide output launches nothing."""
+        gradient of the wide output launches nothing.
+
+        Cameras: ``extr`` [4,4] / [3,4] alone is the one orthographic camera of the video renderer -- the differentiable path
+        above.  ``extr`` [F,4,4] / [F,3,4] gives every frame its own camera (a novel-view orbit, the two eyes of a stereo clip)
+        and ``intr`` ((fx, fy, cx, cy), [4] or [F,4], as in ``render_sets``) selects the pinhole camera.  Per-frame and pinhole
+        cameras of a dynamic batch are FORWARD ONLY: the same tuple comes back with nothing requiring grad (``K``, ``wide`` as
+        above); under grad mode with a parameter or feature that requires grad the call raises, and so does ``points=``."""
         tab = self.frame_table(clock, times)
+        cam = None
+        if intr is not None or (isinstance(extr, Tensor) and extr.dim() == 3):
+            cam = _Camera(extr.detach(), None if intr is None else intr.detach(), self.F)
+            if points is not None:
+                raise ValueError("render_dynamic_sets: points= is not built for per-frame and pinhole cameras of a dynamic batch")
+            if grad_sink:
+                raise ValueError("render_dynamic_sets: per-frame and pinhole cameras of a dynamic batch are forward only "
+                                 "(grad_sink has no backward to feed)")
         meta, parts, feats = _parse_sets(sets, self.F, self.P)
         widths = [1 if m[0] == "depth" else m[0] for m in meta]
         if sum(widths) != self.C:
@@ -452,6 +466,18 @@ class FrameBatch:
             if not (0 <= i < len(feats)) or tuple(buf.shape) != tuple(feats[i].shape) or buf.dtype != torch.float32 \
                     or not buf.is_cuda or buf.stride(-1) != 1 or buf.stride(-2) != buf.shape[-1]:
                 raise ValueError(f"grad_sink[{k!r}] must be a float32 GPU buffer of the feature tensor's shape with dense rows")
+        if cam is not None:
+            every = [position, pos_cubic_node, rotation, opacity, scaling] + list(feats) + ([wide["feature"]] if wd is not None else [])
+            if torch.is_grad_enabled() and any(isinstance(t, Tensor) and t.requires_grad for t in every):
+                raise ValueError("render_dynamic_sets: per-frame and pinhole cameras of a dynamic batch are forward only (the "
+                                 "Gaussian-side backward under these cameras is not built); call it under torch.no_grad() or "
+                                 "with detached tensors")
+            with torch.no_grad():
+                st = _dynamic_sets_forward(self, position, pos_cubic_node, rotation, opacity, scaling, rot_poly_feat,
+                                           rot_fourier_feat, None, cam, tab, int(clock.interval_num), int(cubic_layout), meta,
+                                           int(K), float(nearest), float(extent), parts, None, wd,
+                                           tuple(feats) + ((wide["feature"],) if wd is not None else ()))
+            return st["outputs"]
         return _RenderDynamicSets.apply(position, pos_cubic_node, rotation, opacity, scaling, rot_poly_feat, rot_fourier_feat, extr,
                                         tab, self, int(clock.interval_num), int(cubic_layout), meta, int(K), float(nearest),
                                         float(extent), sink, parts, fsink or None, pts, wd,
@@ -568,73 +594,91 @@ class _RenderDynamic(torch.autograd.Function):
         return ret + (None,) * 11
 
 
+def _dynamic_sets_forward(fb, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr, cam, tab, I, layout, meta,
+                          K, nearest, extent, parts, pts, wd, feats):
+    """the forward of ``render_dynamic_sets``: batched dynamic preprocess, binning and sort, the sets' blends, the wide and the
+    sparse set.  ``cam`` None: the one orthographic camera ``extr`` (the differentiable path: ``_RenderDynamicSets``); a
+    ``_Camera``: cameras per frame and / or the pinhole camera through splat_frame_preprocess_forward_batch_cam (forward only)."""
+    P, F = fb.P, fb.F
+    pfeat = wfeat = None
+    if wd is not None:        # the wide set's feature rides last
+        feats, wfeat = feats[:-1], L.need(feats[-1], "wide feature")
+    if pts is not None:       # the sparse set's feature rides behind the sets' tensors
+        feats, pfeat = feats[:-1], feats[-1]
+    position = _points(position, "position", 3)
+    rotation = _points(rotation, "rotation", 4)
+    scaling = _points(scaling, "scaling", 3)
+    opacity = L.need(opacity, "opacity")
+    cubic = L.need(cubic, "pos_cubic_node")
+    rot_poly, rot_fourier = L.need(rot_poly, "rot_poly_feat"), L.need(rot_fourier, "rot_fourier_feat")
+    if cubic.numel() != P * 4 * I * 3 or rot_poly.numel() != P * 16 or rot_fourier.numel() != P * 32 or opacity.numel() != P:
+        raise ValueError("parameter shapes do not match the batch (P Gaussians, I spline segments)")
+    if position.shape[0] != P or rotation.shape[0] != P or scaling.shape[0] != P:
+        raise ValueError(f"the batch was built for {P} Gaussians")
+    sources = _has_sources(parts)
+    if not sources:
+        _check_set_features(meta, feats, P)
+    extr_c = _extr12(extr) if cam is None else cam.extr
+    lib, st = L.lib(), L.stream()
+    W, H = fb.W, fb.H
+    gen = fb._begin_forward()
+    opa_t = torch.empty(P, 1, dtype=torch.float32, device=fb.dev)
+    if cam is None:
+        L.check(lib.splat_frame_preprocess_forward_batch(
+            F, P, I, L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly),
+            L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c), W, H, nearest, extent,
+            L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius), L.ptr(opa_t), st))
+    else:
+        L.check(lib.splat_frame_preprocess_forward_batch_cam(
+            F, P, I, L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly),
+            L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), ctypes.byref(cam.struct()), W, H, nearest, extent,
+            L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius), L.ptr(opa_t), st))
+    fb._bin_and_sort(opa_t)
+    if sources:
+        feats = tuple(_source_tensor(t, pf, F, P) for t, (_, pf) in zip(feats, [p_ for pp in parts for p_ in pp]))
+        out, gs_idx, blend = _blend_sources_forward(fb, meta, parts, feats, opa_t, K)
+    else:
+        out, gs_idx, blend = _blend_sets_forward(fb, meta, feats, opa_t, 0, K)
+    if blend["plan"] is None:
+        raise ValueError("render_dynamic_sets needs sets that fit the one-pass backward")
+    sparse = ()
+    if pts is not None:
+        pfeat = _source_tensor(pfeat, pts["per_frame"], F, P)
+        sparse = (_points_forward(fb, pts, pfeat, opa_t),)
+        feats = tuple(feats) + (pfeat,)
+    wide_out = ()
+    if wd is not None:
+        wide_out = (_wide_forward(fb, wd, wfeat, opa_t, 0),)
+        feats = tuple(feats) + (wfeat,)
+    imgs, c0 = [], 0
+    for w, _, _, _ in meta:
+        w = 1 if w == "depth" else w
+        imgs.append(out[:, c0:c0 + w])
+        c0 += w
+    return dict(gen=gen, blend=blend, sources=sources, opa_t=opa_t,
+                saved=(position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr_c, tab) + tuple(feats),
+                outputs=tuple(imgs) + wide_out + sparse + (gs_idx,))
+
+
 class _RenderDynamicSets(torch.autograd.Function):
     N_FIXED = 21      # arguments in front of the feature tensors
 
     @staticmethod
     def forward(ctx, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr, tab, fb, I, layout, meta, K,
                 nearest, extent, sink, parts, fsink, pts, wd, *feats):
-        P, F = fb.P, fb.F
-        pfeat = wfeat = None
-        if wd is not None:        # the wide set's feature rides last
-            feats, wfeat = feats[:-1], L.need(feats[-1], "wide feature")
-        if pts is not None:       # the sparse set's feature rides behind the sets' tensors
-            feats, pfeat = feats[:-1], feats[-1]
-        position = _points(position, "position", 3)
-        rotation = _points(rotation, "rotation", 4)
-        scaling = _points(scaling, "scaling", 3)
-        opacity = L.need(opacity, "opacity")
-        cubic = L.need(cubic, "pos_cubic_node")
-        rot_poly, rot_fourier = L.need(rot_poly, "rot_poly_feat"), L.need(rot_fourier, "rot_fourier_feat")
-        if cubic.numel() != P * 4 * I * 3 or rot_poly.numel() != P * 16 or rot_fourier.numel() != P * 32 or opacity.numel() != P:
-            raise ValueError("parameter shapes do not match the batch (P Gaussians, I spline segments)")
-        if position.shape[0] != P or rotation.shape[0] != P or scaling.shape[0] != P:
-            raise ValueError(f"the batch was built for {P} Gaussians")
-        sources = _has_sources(parts)
-        if not sources:
-            _check_set_features(meta, feats, P)
-        extr_c = _extr12(extr)
-        lib, st = L.lib(), L.stream()
-        W, H, C = fb.W, fb.H, fb.C
-        ctx.gen = fb._begin_forward()
-        opa_t = torch.empty(P, 1, dtype=torch.float32, device=fb.dev)
-        L.check(lib.splat_frame_preprocess_forward_batch(
-            F, P, I, L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly),
-            L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c), W, H, nearest, extent,
-            L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius), L.ptr(opa_t), st))
-        fb._bin_and_sort(opa_t)
-        if sources:
-            feats = tuple(_source_tensor(t, pf, F, P) for t, (_, pf) in zip(feats, [p_ for pp in parts for p_ in pp]))
-            out, gs_idx, ctx.blend = _blend_sources_forward(fb, meta, parts, feats, opa_t, K)
-        else:
-            out, gs_idx, ctx.blend = _blend_sets_forward(fb, meta, feats, opa_t, 0, K)
-        if ctx.blend["plan"] is None:
-            raise ValueError("render_dynamic_sets needs sets that fit the one-pass backward")
+        st = _dynamic_sets_forward(fb, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr, None, tab, I,
+                                   layout, meta, K, nearest, extent, parts, pts, wd, feats)
+        ctx.gen, ctx.blend = st["gen"], st["blend"]
         ctx.fb, ctx.meta, ctx.sink, ctx.geo = fb, meta, sink, (I, layout)
-        ctx.parts, ctx.fsink, ctx.sources = parts, (fsink or {}), sources
-        ctx.opa_t = opa_t
-        ctx.pts = None
-        sparse = ()
-        if pts is not None:
-            pfeat = _source_tensor(pfeat, pts["per_frame"], F, P)
-            sparse = (_points_forward(fb, pts, pfeat, opa_t),)
-            ctx.pts = pts
-            feats = tuple(feats) + (pfeat,)
+        ctx.parts, ctx.fsink, ctx.sources = parts, (fsink or {}), st["sources"]
+        ctx.opa_t = st["opa_t"]
+        ctx.pts = pts
         ctx.wd = wd
-        wide_out = ()
-        if wd is not None:
-            wide_out = (_wide_forward(fb, wd, wfeat, opa_t, 0),)
-            feats = tuple(feats) + (wfeat,)
-        ctx.save_for_backward(position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr_c, tab, *feats)
+        ctx.save_for_backward(*st["saved"])
         ctx.set_materialize_grads(False)
-        imgs, c0 = [], 0
-        for w, _, _, _ in meta:
-            w = 1 if w == "depth" else w
-            imgs.append(out[:, c0:c0 + w])
-            c0 += w
-        if gs_idx is not None:
-            ctx.mark_non_differentiable(gs_idx)
-        return tuple(imgs) + wide_out + sparse + (gs_idx,)
+        if st["outputs"][-1] is not None:
+            ctx.mark_non_differentiable(st["outputs"][-1])
+        return st["outputs"]
 
     @staticmethod
     def backward(ctx, *grads):
