@@ -1,4 +1,5 @@
-"""ctypes binding of libsplat_hip.so (C ABI: include/splat_hip.h and its extension include/splat_hip_views.h).
+"""ctypes binding of libsplat_hip.so (C ABI: include/splat_hip.h and its extensions include/splat_hip_views.h and
+include/splat_hip_views_grad.h).
 
 The product path has NO fallback: if the HIP library is missing or a tensor is not a contiguous
 float32/int32 CUDA tensor the call raises.  (The CPU oracle lives in ``oracle/`` and is never
@@ -30,6 +31,11 @@ FeatureSource = HEADER.structs["splat_feature_source_t"]
 VIEWS_HEADER = _abi.load(os.path.join(_HERE, os.pardir, "include", "splat_hip_views.h"), HEADER)
 VIEWS_ABI_VERSION = VIEWS_HEADER.defines["SPLAT_VIEWS_ABI_VERSION"]
 VIEWS_SYMBOLS = list(VIEWS_HEADER.functions)
+# the second extension (training under those cameras).  It includes the views header, which brings no handle or struct of its
+# own: the names its prototypes use are the core header's
+VIEWS_GRAD_HEADER = _abi.load(os.path.join(_HERE, os.pardir, "include", "splat_hip_views_grad.h"), HEADER)
+VIEWS_GRAD_ABI_VERSION = VIEWS_GRAD_HEADER.defines["SPLAT_VIEWS_GRAD_ABI_VERSION"]
+VIEWS_GRAD_SYMBOLS = list(VIEWS_GRAD_HEADER.functions)
 
 
 class SplatError(RuntimeError):
@@ -48,10 +54,12 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C splatter_a_video_amd/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(HEADER.functions.items()) + list(VIEWS_HEADER.functions.items()):
+        for name, (restype, argtypes) in (list(HEADER.functions.items()) + list(VIEWS_HEADER.functions.items())
+                                          + list(VIEWS_GRAD_HEADER.functions.items())):
             fn = getattr(L, name, None)
             if fn is None:
-                where = "splat_hip_views.h" if name in VIEWS_HEADER.functions else "splat_hip.h"
+                where = ("splat_hip_views_grad.h" if name in VIEWS_GRAD_HEADER.functions
+                         else "splat_hip_views.h" if name in VIEWS_HEADER.functions else "splat_hip.h")
                 raise SplatError(f"{LIB_PATH} lacks {name} (include/{where}: the library is older than the headers); rebuild it")
             fn.restype, fn.argtypes = restype, argtypes
         if L.splat_abi_version() != ABI_VERSION:
@@ -59,6 +67,9 @@ def lib() -> ctypes.CDLL:
         if L.splat_views_abi_version() != VIEWS_ABI_VERSION:
             raise SplatError(f"{LIB_PATH} has views ABI version {L.splat_views_abi_version()}, include/splat_hip_views.h "
                              f"{VIEWS_ABI_VERSION}; rebuild it")
+        if L.splat_views_grad_abi_version() != VIEWS_GRAD_ABI_VERSION:
+            raise SplatError(f"{LIB_PATH} has views-grad ABI version {L.splat_views_grad_abi_version()}, "
+                             f"include/splat_hip_views_grad.h {VIEWS_GRAD_ABI_VERSION}; rebuild it")
         _lib = L
     return _lib
 

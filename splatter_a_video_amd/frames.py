@@ -89,6 +89,18 @@ class _Camera:
         return (self.extr,) if self.intr is None else (self.extr, self.intr)
 
 
+def _constant_camera(extr, intr, F: int, who: str) -> Optional[_Camera]:
+    """the camera of a differentiable dynamic batch: None for the one orthographic camera ([4,4] / [3,4] without intr: the path
+    that was always differentiable), else a ``_Camera``.  Cameras are constants -- one that requires grad raises instead of
+    being detached silently (camera-pose gradients are not built)."""
+    if any(isinstance(t, Tensor) and t.requires_grad for t in (extr, intr)):
+        raise ValueError(f"{who}: the cameras are constants (no gradient with respect to extr / intr is built); pass them "
+                         "detached")
+    if intr is None and not (isinstance(extr, Tensor) and extr.dim() == 3):
+        return None
+    return _Camera(extr, intr, F)
+
+
 # python-level switch of the multi-set paths (tests flip it in code -- no environment variable is read; the library's own
 # options: L.set_option)
 # "reach": create only the (Gaussian, tile) pairs whose tile the splat can reach with alpha >= 1/255 (splat_bin_*_batch_reach:
@@ -380,23 +392,32 @@ class FrameBatch:
     def render_dynamic(self, clock, times, extr: Tensor, feature: Tensor, *, position: Tensor, pos_cubic_node: Tensor,
                        rotation: Tensor, rot_poly_feat: Tensor, rot_fourier_feat: Tensor, opacity: Tensor, scaling: Tensor,
                        cubic_layout: int = 1, bg: float = 0.0, nearest: float = 0.01, extent: float = 1.3,
-                       grad_sink: Optional[Dict[str, Tensor]] = None) -> Tensor:
+                       grad_sink: Optional[Dict[str, Tensor]] = None, intr: Optional[Tensor] = None,
+                       differentiable: bool = False) -> Tensor:
         """images [F,C,H,W] of the reference's dynamic Gaussians (spline position, normalised rotation with the detached
         polynomial / Fourier sums, sigmoid opacity, exp scale: src/dynamic_gaussian_with_base_point_cloud.py:171-250) at the
         frame times ``times`` of ``clock``, evaluated inside the batched preprocess.  Differentiable w.r.t. position,
-        pos_cubic_node, rotation, opacity, scaling and feature; ``grad_sink`` as in ``render``."""
+        pos_cubic_node, rotation, opacity, scaling and feature; ``grad_sink`` as in ``render``.
+
+        ``differentiable=True`` (the opt-in of ``gs.alpha_blending_points``) opens the cameras of ``render_dynamic_sets``:
+        ``extr`` [F,4,4] / [F,3,4] gives every frame its own camera and ``intr`` ([4] or [F,4]) selects the pinhole camera, with
+        the same gradients; the cameras are constants (an ``extr`` / ``intr`` that requires grad raises).  One [4,4] camera is
+        the path above, with its bits.  Without it ``extr`` is ONE camera and ``intr`` raises."""
         tab = self.frame_table(clock, times)
         sink = check_sink(grad_sink, {"position": position, "pos_cubic_node": pos_cubic_node, "rotation": rotation,
                                       "opacity": opacity, "scaling": scaling, "feature": feature})
+        if intr is not None and not differentiable:
+            raise ValueError("render_dynamic: intr= (the pinhole camera) needs differentiable=True")
+        cam = _constant_camera(extr, intr, self.F, "render_dynamic") if differentiable else None
         return _RenderDynamic.apply(position, pos_cubic_node, rotation, opacity, scaling, feature, rot_poly_feat, rot_fourier_feat,
-                                    extr, tab, self, int(clock.interval_num), int(cubic_layout), float(bg), float(nearest),
-                                    float(extent), sink)
+                                    extr if cam is None else cam, tab, self, int(clock.interval_num), int(cubic_layout), float(bg),
+                                    float(nearest), float(extent), sink)
 
     def render_dynamic_sets(self, clock, times, extr: Tensor, sets, *, position: Tensor, pos_cubic_node: Tensor,
                             rotation: Tensor, rot_poly_feat: Tensor, rot_fourier_feat: Tensor, opacity: Tensor, scaling: Tensor,
                             cubic_layout: int = 1, K: int = 0, nearest: float = 0.01, extent: float = 1.3,
                             grad_sink: Optional[Dict[str, Tensor]] = None, points: Optional[dict] = None,
-                            wide: Optional[dict] = None, intr: Optional[Tensor] = None):
+                            wide: Optional[dict] = None, intr: Optional[Tensor] = None, differentiable: bool = False):
         """The reference's real training frame, for all frames of the batch: its dynamic Gaussians (``render_dynamic``)
         through the three blends of ``render_iter`` (``render_sets``: same ``sets`` list, same return value).  The sets must
         fit the one-pass backward (one set per routing group, <= 4 / 4 / 20 channels).
@@ -434,11 +455,21 @@ class FrameBatch:
         Cameras: ``extr`` [4,4] / [3,4] alone is the one orthographic camera of the video renderer -- the differentiable path
         above.  ``extr`` [F,4,4] / [F,3,4] gives every frame its own camera (a novel-view orbit, the two eyes of a stereo clip)
         and ``intr`` ((fx, fy, cx, cy), [4] or [F,4], as in ``render_sets``) selects the pinhole camera.  Per-frame and pinhole
-        cameras of a dynamic batch are FORWARD ONLY: the same tuple comes back with nothing requiring grad (``K``, ``wide`` as
-        above); under grad mode with a parameter or feature that requires grad the call raises, and so does ``points=``."""
+        cameras of a dynamic batch are FORWARD ONLY by default: the same tuple comes back with nothing requiring grad (``K``,
+        ``wide`` as above); under grad mode with a parameter or feature that requires grad the call raises, and so does
+        ``points=``.
+
+        ``differentiable=True`` (the opt-in of ``gs.alpha_blending_points``) trains under these cameras: the same autograd node
+        as the one-camera path, with the batched forward under the cameras and, behind the unchanged tile backward, the
+        Gaussian-side backward of include/splat_hip_views_grad.h -- every frame's records go back through that frame's camera.
+        Everything the one-camera path takes it takes (``grad_sink``, feature lists and per-frame tensors, ``K``, ``wide``,
+        ``points`` with ``ordered`` and the deterministic-mode rule).  The cameras are constants: an ``extr`` / ``intr`` that
+        requires grad raises instead of being detached.  One [4,4] camera with ``differentiable=True`` is the path above."""
         tab = self.frame_table(clock, times)
-        cam = None
-        if intr is not None or (isinstance(extr, Tensor) and extr.dim() == 3):
+        cam = dcam = None
+        if differentiable:
+            dcam = _constant_camera(extr, intr, self.F, "render_dynamic_sets")
+        elif intr is not None or (isinstance(extr, Tensor) and extr.dim() == 3):
             cam = _Camera(extr.detach(), None if intr is None else intr.detach(), self.F)
             if points is not None:
                 raise ValueError("render_dynamic_sets: points= is not built for per-frame and pinhole cameras of a dynamic batch")
@@ -478,8 +509,9 @@ class FrameBatch:
                                            int(K), float(nearest), float(extent), parts, None, wd,
                                            tuple(feats) + ((wide["feature"],) if wd is not None else ()))
             return st["outputs"]
-        return _RenderDynamicSets.apply(position, pos_cubic_node, rotation, opacity, scaling, rot_poly_feat, rot_fourier_feat, extr,
-                                        tab, self, int(clock.interval_num), int(cubic_layout), meta, int(K), float(nearest),
+        return _RenderDynamicSets.apply(position, pos_cubic_node, rotation, opacity, scaling, rot_poly_feat, rot_fourier_feat,
+                                        extr if dcam is None else dcam, tab, self, int(clock.interval_num),
+                                        int(cubic_layout), meta, int(K), float(nearest),
                                         float(extent), sink, parts, fsink or None, pts, wd,
                                         *(list(feats) + ([pts["feature"]] if pts is not None else [])
                                           + ([wide["feature"]] if wd is not None else [])))
@@ -544,15 +576,23 @@ class _RenderDynamic(torch.autograd.Function):
             raise ValueError("parameter shapes do not match the batch (P Gaussians, I spline segments)")
         if position.shape[0] != P or rotation.shape[0] != P or scaling.shape[0] != P or feature.shape[0] != P:
             raise ValueError(f"the batch was built for {P} Gaussians")
-        extr_c = _extr12(extr)
+        cam = extr if isinstance(extr, _Camera) else None     # cameras per frame / the pinhole camera (differentiable=True)
+        extr_c = _extr12(extr) if cam is None else cam.extr
         lib, st = L.lib(), L.stream()
         W, H, C = fb.W, fb.H, fb.C
         ctx.gen = fb._begin_forward()
         opa_t = torch.empty(P, 1, dtype=torch.float32, device=fb.dev)
-        L.check(lib.splat_frame_preprocess_forward_batch(
-            F, P, I, L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly),
-            L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c), W, H, nearest, extent,
-            L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius), L.ptr(opa_t), st))
+        if cam is None:
+            L.check(lib.splat_frame_preprocess_forward_batch(
+                F, P, I, L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly),
+                L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c), W, H, nearest, extent,
+                L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius), L.ptr(opa_t), st))
+        else:
+            L.check(lib.splat_frame_preprocess_forward_batch_cam(
+                F, P, I, L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly),
+                L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), ctypes.byref(cam.struct()), W, H, nearest, extent,
+                L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius), L.ptr(opa_t), st))
+        ctx.cam, ctx.cam_versions = cam, (_versions(*cam.tensors()) if cam is not None else ())
         fb._bin_and_sort(opa_t)
         cap = fb.capacity
         out = torch.empty(F, C, H, W, dtype=torch.float32, device=fb.dev)
@@ -584,21 +624,32 @@ class _RenderDynamic(torch.autograd.Function):
                 "feature": feature}
         need = dict(zip(like, ctx.needs_input_grad[:6]))
         bufs = {k: (sink[k] if k in sink else (torch.zeros_like(v) if need[k] else None)) for k, v in like.items()}
-        L.check(lib.splat_frames_gauss_backward_dynamic(
+        gauss_backward, cam_arg = _gauss_backward_entry(ctx, "splat_frames_gauss_backward_dynamic", extr_c)
+        L.check(gauss_backward(
             F, P, I, C, W, H, cap, 1 if fb.want_abs else 0,
             L.ptr(fb.pair_records), L.ptr(fb.goff), L.ptr(fb.radius), L.ptr(tab), L.ptr(position), L.ptr(cubic), layout,
-            L.ptr(rotation), L.ptr(rot_poly), L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c),
+            L.ptr(rotation), L.ptr(rot_poly), L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), cam_arg,
             L.ptr(bufs["position"]), L.ptr(bufs["pos_cubic_node"]), L.ptr(bufs["rotation"]), L.ptr(bufs["opacity"]),
             L.ptr(bufs["scaling"]), L.ptr(bufs["feature"]), L.ptr(fb.tap), L.ptr(fb.abs_tap), L.ptr(fb.radii_max), st))
         ret = tuple(None if (k in sink or bufs[k] is None) else bufs[k] for k in like)
         return ret + (None,) * 11
 
 
+def _gauss_backward_entry(ctx, name: str, extr_c: Tensor):
+    """the Gaussian-side entry point of a dynamic batch's backward and its camera argument: the core header's with the one
+    orthographic camera's 12 floats, or its ``_cam`` twin (include/splat_hip_views_grad.h) with the forward's cameras"""
+    if ctx.cam is None:
+        return getattr(L.lib(), name), L.ptr(extr_c)
+    _check_versions(ctx.cam_versions, "a camera tensor")
+    return getattr(L.lib(), name + "_cam"), ctypes.byref(ctx.cam.struct())
+
+
 def _dynamic_sets_forward(fb, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr, cam, tab, I, layout, meta,
                           K, nearest, extent, parts, pts, wd, feats):
     """the forward of ``render_dynamic_sets``: batched dynamic preprocess, binning and sort, the sets' blends, the wide and the
     sparse set.  ``cam`` None: the one orthographic camera ``extr`` (the differentiable path: ``_RenderDynamicSets``); a
-    ``_Camera``: cameras per frame and / or the pinhole camera through splat_frame_preprocess_forward_batch_cam (forward only)."""
+    ``_Camera``: cameras per frame and / or the pinhole camera through splat_frame_preprocess_forward_batch_cam (forward only
+    by default; ``_RenderDynamicSets`` with a ``_Camera`` in place of ``extr`` is the differentiable path under them)."""
     P, F = fb.P, fb.F
     pfeat = wfeat = None
     if wd is not None:        # the wide set's feature rides last
@@ -666,8 +717,11 @@ class _RenderDynamicSets(torch.autograd.Function):
     @staticmethod
     def forward(ctx, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr, tab, fb, I, layout, meta, K,
                 nearest, extent, sink, parts, fsink, pts, wd, *feats):
-        st = _dynamic_sets_forward(fb, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr, None, tab, I,
-                                   layout, meta, K, nearest, extent, parts, pts, wd, feats)
+        cam = extr if isinstance(extr, _Camera) else None     # cameras per frame / the pinhole camera (differentiable=True)
+        st = _dynamic_sets_forward(fb, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier,
+                                   extr if cam is None else None, cam, tab, I, layout, meta, K, nearest, extent, parts, pts,
+                                   wd, feats)
+        ctx.cam, ctx.cam_versions = cam, (_versions(*cam.tensors()) if cam is not None else ())
         ctx.gen, ctx.blend = st["gen"], st["blend"]
         ctx.fb, ctx.meta, ctx.sink, ctx.geo = fb, meta, sink, (I, layout)
         ctx.parts, ctx.fsink, ctx.sources = parts, (fsink or {}), st["sources"]
@@ -756,10 +810,11 @@ class _RenderDynamicSets(torch.autograd.Function):
                         n += 1
                     c0 += cn
                     fi += 1
-            L.check(lib.splat_frames_gauss_backward_dynamic_sources(
+            gauss_backward, cam_arg = _gauss_backward_entry(ctx, "splat_frames_gauss_backward_dynamic_sources", extr_c)
+            L.check(gauss_backward(
                 F, P, I, C, W, H, cap, L.ptr(rec), L.ptr(fb.goff),
                 L.ptr(fb.radius), L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly),
-                L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c), L.ptr(bufs["position"]),
+                L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), cam_arg, L.ptr(bufs["position"]),
                 L.ptr(bufs["pos_cubic_node"]), L.ptr(bufs["rotation"]), L.ptr(bufs["opacity"]), L.ptr(bufs["scaling"]), n,
                 table, depth_ch, L.ptr(fb.tap if has_tap else None),
                 L.ptr(fb.abs_tap if (has_tap and want_abs) else None), L.ptr(fb.radii_max if has_tap else None), st))
@@ -780,10 +835,11 @@ class _RenderDynamicSets(torch.autograd.Function):
         d_wide = wide_backward(rec)
         i3 = ctypes.c_int32 * 3
         p3 = (ctypes.c_void_p * 3)(*[0 if d is None else d.data_ptr() for d in dfs])
-        L.check(lib.splat_frames_gauss_backward_dynamic_sets(
+        gauss_backward, cam_arg = _gauss_backward_entry(ctx, "splat_frames_gauss_backward_dynamic_sets", extr_c)
+        L.check(gauss_backward(
             F, P, I, C, W, H, cap, L.ptr(rec), L.ptr(fb.goff), L.ptr(fb.radius),
             L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly), L.ptr(rot_fourier),
-            L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c), L.ptr(bufs["position"]), L.ptr(bufs["pos_cubic_node"]),
+            L.ptr(opacity), L.ptr(scaling), cam_arg, L.ptr(bufs["position"]), L.ptr(bufs["pos_cubic_node"]),
             L.ptr(bufs["rotation"]), L.ptr(bufs["opacity"]), L.ptr(bufs["scaling"]), i3(*c0s), i3(*cns), p3, i3(*strides),
             depth_ch, L.ptr(fb.tap if has_tap else None), L.ptr(fb.abs_tap if (has_tap and want_abs) else None),
             L.ptr(fb.radii_max if has_tap else None), st))
