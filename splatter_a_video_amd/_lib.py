@@ -1,5 +1,5 @@
-"""ctypes binding of libsplat_hip.so (C ABI: include/splat_hip.h and its extensions include/splat_hip_views.h and
-include/splat_hip_views_grad.h).
+"""ctypes binding of libsplat_hip.so (C ABI: include/splat_hip.h and its extensions include/splat_hip_views.h,
+include/splat_hip_views_grad.h and include/splat_hip_camera_grad.h).
 
 The product path has NO fallback: if the HIP library is missing or a tensor is not a contiguous
 float32/int32 CUDA tensor the call raises.  (The CPU oracle lives in ``oracle/`` and is never
@@ -36,6 +36,10 @@ VIEWS_SYMBOLS = list(VIEWS_HEADER.functions)
 VIEWS_GRAD_HEADER = _abi.load(os.path.join(_HERE, os.pardir, "include", "splat_hip_views_grad.h"), HEADER)
 VIEWS_GRAD_ABI_VERSION = VIEWS_GRAD_HEADER.defines["SPLAT_VIEWS_GRAD_ABI_VERSION"]
 VIEWS_GRAD_SYMBOLS = list(VIEWS_GRAD_HEADER.functions)
+# the third extension (the camera gradients of a dynamic batch), on the core header's names like the two before it
+CAMERA_GRAD_HEADER = _abi.load(os.path.join(_HERE, os.pardir, "include", "splat_hip_camera_grad.h"), HEADER)
+CAMERA_GRAD_ABI_VERSION = CAMERA_GRAD_HEADER.defines["SPLAT_CAMERA_GRAD_ABI_VERSION"]
+CAMERA_GRAD_SYMBOLS = list(CAMERA_GRAD_HEADER.functions)
 
 
 class SplatError(RuntimeError):
@@ -55,10 +59,12 @@ def lib() -> ctypes.CDLL:
                 "or `make -C splatter_a_video_amd/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
         L = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in (list(HEADER.functions.items()) + list(VIEWS_HEADER.functions.items())
-                                          + list(VIEWS_GRAD_HEADER.functions.items())):
+                                          + list(VIEWS_GRAD_HEADER.functions.items())
+                                          + list(CAMERA_GRAD_HEADER.functions.items())):
             fn = getattr(L, name, None)
             if fn is None:
-                where = ("splat_hip_views_grad.h" if name in VIEWS_GRAD_HEADER.functions
+                where = ("splat_hip_camera_grad.h" if name in CAMERA_GRAD_HEADER.functions
+                         else "splat_hip_views_grad.h" if name in VIEWS_GRAD_HEADER.functions
                          else "splat_hip_views.h" if name in VIEWS_HEADER.functions else "splat_hip.h")
                 raise SplatError(f"{LIB_PATH} lacks {name} (include/{where}: the library is older than the headers); rebuild it")
             fn.restype, fn.argtypes = restype, argtypes
@@ -70,6 +76,9 @@ def lib() -> ctypes.CDLL:
         if L.splat_views_grad_abi_version() != VIEWS_GRAD_ABI_VERSION:
             raise SplatError(f"{LIB_PATH} has views-grad ABI version {L.splat_views_grad_abi_version()}, "
                              f"include/splat_hip_views_grad.h {VIEWS_GRAD_ABI_VERSION}; rebuild it")
+        if L.splat_camera_grad_abi_version() != CAMERA_GRAD_ABI_VERSION:
+            raise SplatError(f"{LIB_PATH} has camera-grad ABI version {L.splat_camera_grad_abi_version()}, "
+                             f"include/splat_hip_camera_grad.h {CAMERA_GRAD_ABI_VERSION}; rebuild it")
         _lib = L
     return _lib
 

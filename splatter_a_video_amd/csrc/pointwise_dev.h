@@ -239,3 +239,78 @@ __device__ __forceinline__ void ewa_grad_cov_pt(const float a[3], const float b[
     o[4] = 2 * a[1] * a[2] * dcx + (a[1] * b[2] + b[1] * a[2]) * dcy + 2 * b[1] * b[2] * dcz;
     o[5] = a[2] * a[2] * dcx + a[2] * b[2] * dcy + b[2] * b[2] * dcz;
 }
+
+// ---- camera gradients of one Gaussian: cg[0..3] = dL/dintr (fx fy cx cy), cg[4..15] = dL/dextr rows; every function ADDS.
+//      The pinhole pair restates the CAMGRAD blocks of pointwise.hip (the per-operator kernels keep their own text and bits).
+
+// twin of project_point_bwd_kernel<false, true>'s CAMGRAD block (reference: src/project_point.cu:107-145)
+__device__ __forceinline__ void project_persp_camgrad_pt(const Cam &c, float x, float y, float z, float gu, float gv, float gd,
+                                                         float cg[16]) {
+    float tx, ty, tz;
+    cam_xform(c, x, y, z, tx, ty, tz);
+    const float n1 = (float)(1.0 / (double)tz);
+    const float n2 = (float)(1.0 / (double)(tz * tz));
+    cg[0] += tx * n1 * gu; cg[1] += ty * n1 * gv; cg[2] += gu; cg[3] += gv;
+    const float p[4] = {x, y, z, 1.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        cg[4 + j] += c.fx * p[j] * n1 * gu;
+        cg[8 + j] += c.fy * p[j] * n1 * gv;
+        cg[12 + j] += -c.fx * p[j] * tx * n2 * gu - c.fy * p[j] * ty * n2 * gv + p[j] * gd;
+    }
+}
+
+// twin of ewa_bwd_kernel<false, true>'s CAMGRAD block (reference: src/ewa_project.cu:207-252): p the world point, t its
+// camera-space image and Jm of ewa_T<false>, da / db / dt of ewa_grad_pos_persp_pt
+__device__ __forceinline__ void ewa_persp_camgrad_pt(const Cam &c, const float p[3], const float t[3], const float Jm[4],
+                                                     const float da[3], const float db[3], const float dt[3], float cg[16]) {
+    const float dJ00 = c.e[0] * da[0] + c.e[1] * da[1] + c.e[2] * da[2];
+    const float dJ02 = c.e[8] * da[0] + c.e[9] * da[1] + c.e[10] * da[2];
+    const float dJ11 = c.e[4] * db[0] + c.e[5] * db[1] + c.e[6] * db[2];
+    const float dJ12 = c.e[8] * db[0] + c.e[9] * db[1] + c.e[10] * db[2];
+    const float tz = 1.f / t[2], tz2 = tz * tz;
+    cg[0] += tz * dJ00 - t[0] * tz2 * dJ02;
+    cg[1] += tz * dJ11 - t[1] * tz2 * dJ12;
+    const float pp[4] = {p[0], p[1], p[2], 1.f};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        cg[4 + k] += pp[k] * dt[0] + (k < 3 ? Jm[0] * da[k] : 0.f);
+        cg[8 + k] += pp[k] * dt[1] + (k < 3 ? Jm[1] * db[k] : 0.f);
+        cg[12 + k] += pp[k] * dt[2] + (k < 3 ? Jm[2] * da[k] + Jm[3] * db[k] : 0.f);
+    }
+}
+
+// dL/da, dL/db of the rows a, b of T = J R from dL/dcov2d (the first loop of ewa_grad_pos_persp_pt)
+__device__ __forceinline__ void ewa_grad_rows_pt(const float a[3], const float b[3], const float c3[6], float dcx, float dcy,
+                                                 float dcz, float da[3], float db[3]) {
+    const float S[3][3] = {{c3[0], c3[1], c3[2]}, {c3[1], c3[3], c3[4]}, {c3[2], c3[4], c3[5]}};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float Sa = a[0] * S[0][k] + a[1] * S[1][k] + a[2] * S[2][k];
+        const float Sb = b[0] * S[0][k] + b[1] * S[1][k] + b[2] * S[2][k];
+        da[k] = 2 * Sa * dcx + Sb * dcy;
+        db[k] = Sa * dcy + 2 * Sb * dcz;
+    }
+}
+
+// orthographic projection: u = (e0 . p + 1) W / 2 - 0.5, v = (e1 . p + 1) H / 2 - 0.5, depth = e2 . p, p = (x, y, z, 1)
+__device__ __forceinline__ void project_ortho_camgrad_pt(float x, float y, float z, int W, int H, float gu, float gv, float gd,
+                                                         float cg[16]) {
+    const float gx = gu * ((float)W / 2.f), gy = gv * ((float)H / 2.f);
+    const float p[4] = {x, y, z, 1.f};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        cg[4 + k] += p[k] * gx;
+        cg[8 + k] += p[k] * gy;
+        cg[12 + k] += p[k] * gd;
+    }
+}
+
+// orthographic EWA: a = (W / 2) e0, b = (H / 2) e1 -- the conic reaches the first two rows of the rotation alone
+__device__ __forceinline__ void ewa_ortho_camgrad_pt(int W, int H, const float da[3], const float db[3], float cg[16]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        cg[4 + k] += ((float)W / 2.f) * da[k];
+        cg[8 + k] += ((float)H / 2.f) * db[k];
+    }
+}

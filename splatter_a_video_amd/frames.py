@@ -101,6 +101,74 @@ def _constant_camera(extr, intr, F: int, who: str) -> Optional[_Camera]:
     return _Camera(extr, intr, F)
 
 
+class _CameraGrad:
+    """``camera_grad=True`` of a differentiable dynamic batch: the cameras as the kernel of include/splat_hip_camera_grad.h reads
+    them (always a ``_Camera``, also for the one orthographic camera, whose parameter gradients stay with the core entry
+    point), the shapes the gradients go back in, and the ``grad_sink`` buffers of ``extr`` / ``intr``."""
+
+    def __init__(self, extr, intr, sink: Dict[str, Tensor], F: int, who: str):
+        if not isinstance(extr, Tensor) or tuple(extr.shape) not in ((4, 4), (3, 4), (F, 4, 4), (F, 3, 4)):
+            raise ValueError(f"{who}: camera_grad=True takes extr [4,4] / [3,4] / [F,4,4] / [F,3,4] (F = {F})")
+        if intr is not None and (not isinstance(intr, Tensor) or tuple(intr.shape) not in ((4,), (F, 4))):
+            raise ValueError(f"{who}: camera_grad=True takes intr [4] / [F,4] (F = {F})")
+        self.cam = _Camera(extr.detach(), None if intr is None else intr.detach(), F)
+        self.versions = _versions(*self.cam.tensors())
+        self.extr_shape, self.intr_shape = tuple(extr.shape), (None if intr is None else tuple(intr.shape))
+        self.sink_extr, self.sink_intr = sink.get("extr"), sink.get("intr")
+        for name, buf, shape in (("extr", self.sink_extr, self.extr_shape), ("intr", self.sink_intr, self.intr_shape)):
+            if buf is None:
+                continue
+            if shape is None or tuple(buf.shape) != shape or buf.dtype != torch.float32 or not buf.is_cuda or not buf.is_contiguous():
+                raise ValueError(f"{who}: grad_sink[{name!r}] must be a contiguous float32 GPU buffer of {name}'s shape")
+
+    def one_ortho(self) -> bool:
+        """the one orthographic camera: the parameters' backward is the core entry point (its bits)"""
+        return not self.cam.perspective and self.cam.extr_fs == 0
+
+    def backward(self, fb: "FrameBatch", rec: Tensor, stride: int, depth_column: int, tab, position, cubic, layout: int, I: int,
+                 rotation, rot_poly, rot_fourier, scaling, need_extr: bool, need_intr: bool):
+        """(dL/dextr, dL/dintr) in the tensors' shapes from the batch's pair records -- after the tile, sparse and wide backward
+        have filled them.  A sink receives its gradient by ADDITION and None goes back to autograd; a camera nobody asks about
+        launches nothing."""
+        want_e = need_extr or self.sink_extr is not None
+        want_i = self.cam.perspective and (need_intr or self.sink_intr is not None)
+        if not (want_e or want_i):
+            return None, None
+        _check_versions(self.versions, "a camera tensor")
+        lib, F = L.lib(), fb.F
+        de = torch.zeros(F if self.cam.extr_fs else 1, 12, dtype=torch.float32, device=fb.dev) if want_e else None
+        di = torch.zeros(F if self.cam.intr_fs else 1, 4, dtype=torch.float32, device=fb.dev) if want_i else None
+        part = fb._set_buffer(("camera_grad", "partials"), int(lib.splat_camera_grad_partials_floats(F, fb.P)))
+        L.check(lib.splat_frames_camera_backward_dynamic(
+            F, fb.P, I, fb.W, fb.H, fb.capacity, stride, depth_column, L.ptr(rec), L.ptr(fb.goff), L.ptr(tab), L.ptr(position),
+            L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly), L.ptr(rot_fourier), L.ptr(scaling),
+            ctypes.byref(self.cam.struct()), L.ptr(part), L.ptr(de), L.ptr(di), L.stream()))
+        g_e = g_i = None
+        if want_e:
+            if self.extr_shape[-2] == 4:                     # the bottom row of a 4x4 gets zeros
+                g_e = torch.zeros(self.extr_shape, dtype=torch.float32, device=fb.dev)
+                g_e[..., :3, :] = de.reshape(self.extr_shape[:-2] + (3, 4))
+            else:
+                g_e = de.reshape(self.extr_shape)
+            if self.sink_extr is not None:
+                self.sink_extr.add_(g_e)
+                g_e = None
+        if want_i:
+            g_i = di.reshape(self.intr_shape)
+            if self.sink_intr is not None:
+                self.sink_intr.add_(g_i)
+                g_i = None
+        return (g_e if need_extr else None), (g_i if need_intr else None)
+
+
+def _camera_grad(extr, intr, grad_sink, F: int, who: str):
+    """(``_CameraGrad``, the forward's camera -- None: the one orthographic camera --, grad_sink without the camera names)"""
+    sink = dict(grad_sink or {})
+    cams = {k: sink.pop(k) for k in ("extr", "intr") if k in sink}
+    cg = _CameraGrad(extr, intr, cams, F, who)
+    return cg, (None if cg.one_ortho() else cg.cam), (sink or None)
+
+
 # python-level switch of the multi-set paths (tests flip it in code -- no environment variable is read; the library's own
 # options: L.set_option)
 # "reach": create only the (Gaussian, tile) pairs whose tile the splat can reach with alpha >= 1/255 (splat_bin_*_batch_reach:
@@ -393,7 +461,7 @@ class FrameBatch:
                        rotation: Tensor, rot_poly_feat: Tensor, rot_fourier_feat: Tensor, opacity: Tensor, scaling: Tensor,
                        cubic_layout: int = 1, bg: float = 0.0, nearest: float = 0.01, extent: float = 1.3,
                        grad_sink: Optional[Dict[str, Tensor]] = None, intr: Optional[Tensor] = None,
-                       differentiable: bool = False) -> Tensor:
+                       differentiable: bool = False, camera_grad: bool = False) -> Tensor:
         """images [F,C,H,W] of the reference's dynamic Gaussians (spline position, normalised rotation with the detached
         polynomial / Fourier sums, sigmoid opacity, exp scale: src/dynamic_gaussian_with_base_point_cloud.py:171-250) at the
         frame times ``times`` of ``clock``, evaluated inside the batched preprocess.  Differentiable w.r.t. position,
@@ -402,22 +470,32 @@ class FrameBatch:
         ``differentiable=True`` (the opt-in of ``gs.alpha_blending_points``) opens the cameras of ``render_dynamic_sets``:
         ``extr`` [F,4,4] / [F,3,4] gives every frame its own camera and ``intr`` ([4] or [F,4]) selects the pinhole camera, with
         the same gradients; the cameras are constants (an ``extr`` / ``intr`` that requires grad raises).  One [4,4] camera is
-        the path above, with its bits.  Without it ``extr`` is ONE camera and ``intr`` raises."""
+        the path above, with its bits.  Without it ``extr`` is ONE camera and ``intr`` raises.
+
+        ``camera_grad=True`` (needs ``differentiable=True``) makes the cameras leaves as well, as in ``render_dynamic_sets``."""
         tab = self.frame_table(clock, times)
+        if camera_grad and not differentiable:
+            raise ValueError("render_dynamic: camera_grad=True needs differentiable=True")
+        cg = None
+        if camera_grad:
+            cg, cam, grad_sink = _camera_grad(extr, intr, grad_sink, self.F, "render_dynamic")
         sink = check_sink(grad_sink, {"position": position, "pos_cubic_node": pos_cubic_node, "rotation": rotation,
                                       "opacity": opacity, "scaling": scaling, "feature": feature})
         if intr is not None and not differentiable:
             raise ValueError("render_dynamic: intr= (the pinhole camera) needs differentiable=True")
-        cam = _constant_camera(extr, intr, self.F, "render_dynamic") if differentiable else None
+        if cg is None:
+            cam = _constant_camera(extr, intr, self.F, "render_dynamic") if differentiable else None
         return _RenderDynamic.apply(position, pos_cubic_node, rotation, opacity, scaling, feature, rot_poly_feat, rot_fourier_feat,
-                                    extr if cam is None else cam, tab, self, int(clock.interval_num), int(cubic_layout), float(bg),
-                                    float(nearest), float(extent), sink)
+                                    (extr.detach() if cg is not None else extr) if cam is None else cam, tab, self,
+                                    int(clock.interval_num), int(cubic_layout), float(bg), float(nearest), float(extent), sink,
+                                    cg, extr if cg is not None else None, intr if cg is not None else None)
 
     def render_dynamic_sets(self, clock, times, extr: Tensor, sets, *, position: Tensor, pos_cubic_node: Tensor,
                             rotation: Tensor, rot_poly_feat: Tensor, rot_fourier_feat: Tensor, opacity: Tensor, scaling: Tensor,
                             cubic_layout: int = 1, K: int = 0, nearest: float = 0.01, extent: float = 1.3,
                             grad_sink: Optional[Dict[str, Tensor]] = None, points: Optional[dict] = None,
-                            wide: Optional[dict] = None, intr: Optional[Tensor] = None, differentiable: bool = False):
+                            wide: Optional[dict] = None, intr: Optional[Tensor] = None, differentiable: bool = False,
+                            camera_grad: bool = False):
         """The reference's real training frame, for all frames of the batch: its dynamic Gaussians (``render_dynamic``)
         through the three blends of ``render_iter`` (``render_sets``: same ``sets`` list, same return value).  The sets must
         fit the one-pass backward (one set per routing group, <= 4 / 4 / 20 channels).
@@ -464,10 +542,24 @@ class FrameBatch:
         Gaussian-side backward of include/splat_hip_views_grad.h -- every frame's records go back through that frame's camera.
         Everything the one-camera path takes it takes (``grad_sink``, feature lists and per-frame tensors, ``K``, ``wide``,
         ``points`` with ``ordered`` and the deterministic-mode rule).  The cameras are constants: an ``extr`` / ``intr`` that
-        requires grad raises instead of being detached.  One [4,4] camera with ``differentiable=True`` is the path above."""
+        requires grad raises instead of being detached.  One [4,4] camera with ``differentiable=True`` is the path above.
+
+        ``camera_grad=True`` (needs ``differentiable=True``) makes the cameras leaves of the same autograd node: ``extr`` ([4,4] /
+        [3,4] / [F,4,4] / [F,3,4]) and ``intr`` ([4] / [F,4]) may require grad and receive gradients of their own shape -- zeros in
+        the bottom row of a 4x4, the sum over the frames for a camera the frames share -- or ``grad_sink["extr"]`` /
+        ``grad_sink["intr"]`` (float32 GPU buffers of the tensor's shape) receive them by ADDITION.  Behind the tile, sparse and
+        wide backward one more kernel sums the pair records per frame under that frame's camera
+        (include/splat_hip_camera_grad.h: orthographic cameras, per frame or one, and the pinhole camera; no float atomics,
+        bit-reproducible, allowed in deterministic mode); the parameter and feature gradients keep their bits, and a camera
+        that neither requires grad nor has a sink launches nothing.  ``views.pose_delta`` is the parameterisation a pose
+        refinement optimises.  Not differentiated: the cull / near / extent decisions and the radius."""
         tab = self.frame_table(clock, times)
-        cam = dcam = None
-        if differentiable:
+        cam = dcam = cg = None
+        if camera_grad:
+            if not differentiable:
+                raise ValueError("render_dynamic_sets: camera_grad=True needs differentiable=True")
+            cg, dcam, grad_sink = _camera_grad(extr, intr, grad_sink, self.F, "render_dynamic_sets")
+        elif differentiable:
             dcam = _constant_camera(extr, intr, self.F, "render_dynamic_sets")
         elif intr is not None or (isinstance(extr, Tensor) and extr.dim() == 3):
             cam = _Camera(extr.detach(), None if intr is None else intr.detach(), self.F)
@@ -510,9 +602,10 @@ class FrameBatch:
                                            tuple(feats) + ((wide["feature"],) if wd is not None else ()))
             return st["outputs"]
         return _RenderDynamicSets.apply(position, pos_cubic_node, rotation, opacity, scaling, rot_poly_feat, rot_fourier_feat,
-                                        extr if dcam is None else dcam, tab, self, int(clock.interval_num),
-                                        int(cubic_layout), meta, int(K), float(nearest),
+                                        (extr.detach() if cg is not None else extr) if dcam is None else dcam, tab, self,
+                                        int(clock.interval_num), int(cubic_layout), meta, int(K), float(nearest),
                                         float(extent), sink, parts, fsink or None, pts, wd,
+                                        cg, extr if cg is not None else None, intr if cg is not None else None,
                                         *(list(feats) + ([pts["feature"]] if pts is not None else [])
                                           + ([wide["feature"]] if wd is not None else [])))
 
@@ -563,8 +656,9 @@ class FrameBatch:
 class _RenderDynamic(torch.autograd.Function):
     @staticmethod
     def forward(ctx, position, cubic, rotation, opacity, scaling, feature, rot_poly, rot_fourier, extr, tab, fb, I, layout, bg,
-                nearest, extent, sink):
+                nearest, extent, sink, cg=None, cg_extr=None, cg_intr=None):
         P, F = fb.P, fb.F
+        ctx.cg = cg                                           # camera_grad=True: cg_extr / cg_intr are the camera leaves
         position = _points(position, "position", 3)
         rotation = _points(rotation, "rotation", 4)
         scaling = _points(scaling, "scaling", 3)
@@ -632,7 +726,11 @@ class _RenderDynamic(torch.autograd.Function):
             L.ptr(bufs["position"]), L.ptr(bufs["pos_cubic_node"]), L.ptr(bufs["rotation"]), L.ptr(bufs["opacity"]),
             L.ptr(bufs["scaling"]), L.ptr(bufs["feature"]), L.ptr(fb.tap), L.ptr(fb.abs_tap), L.ptr(fb.radii_max), st))
         ret = tuple(None if (k in sink or bufs[k] is None) else bufs[k] for k in like)
-        return ret + (None,) * 11
+        d_cam = (None, None)
+        if ctx.cg is not None:
+            d_cam = ctx.cg.backward(fb, fb.pair_records, fb.ncp, -1, tab, position, cubic, layout, I, rotation, rot_poly,
+                                    rot_fourier, scaling, ctx.needs_input_grad[18], ctx.needs_input_grad[19])
+        return ret + (None,) * 12 + d_cam
 
 
 def _gauss_backward_entry(ctx, name: str, extr_c: Tensor):
@@ -712,12 +810,13 @@ def _dynamic_sets_forward(fb, position, cubic, rotation, opacity, scaling, rot_p
 
 
 class _RenderDynamicSets(torch.autograd.Function):
-    N_FIXED = 21      # arguments in front of the feature tensors
+    N_FIXED = 24      # arguments in front of the feature tensors (the last two: the camera leaves of camera_grad=True)
 
     @staticmethod
     def forward(ctx, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr, tab, fb, I, layout, meta, K,
-                nearest, extent, sink, parts, fsink, pts, wd, *feats):
+                nearest, extent, sink, parts, fsink, pts, wd, cg, cg_extr, cg_intr, *feats):
         cam = extr if isinstance(extr, _Camera) else None     # cameras per frame / the pinhole camera (differentiable=True)
+        ctx.cg = cg
         st = _dynamic_sets_forward(fb, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier,
                                    extr if cam is None else None, cam, tab, I, layout, meta, K, nearest, extent, parts, pts,
                                    wd, feats)
@@ -783,6 +882,14 @@ class _RenderDynamicSets(torch.autograd.Function):
         want_abs = 1 if (tap_set is not None and fb.want_abs) else 0
         NF = _RenderDynamicSets.N_FIXED
         has_tap = tap_set is not None
+
+        def camera_backward(rec):
+            # the camera leaves (camera_grad=True): from the records every backward above has filled
+            if ctx.cg is None:
+                return (None, None)
+            return ctx.cg.backward(fb, rec, int(lib.splat_blend_sets_pair_stride(C)), 12 + depth_ch if depth_ch >= 0 else -1, tab,
+                                   position, cubic, layout, I, rotation, rot_poly, rot_fourier, scaling,
+                                   ctx.needs_input_grad[NF - 2], ctx.needs_input_grad[NF - 1])
         if ctx.sources:
             # the row by SOURCES: a shared tensor's gradient is the sum over the frames, a per-frame tensor gets every frame's own
             rec = _blend_sets_backward_one_pass(fb, meta, ctx.blend, grads[:len(meta)], ctx.opa_t, 0, want_abs)
@@ -819,7 +926,7 @@ class _RenderDynamicSets(torch.autograd.Function):
                 table, depth_ch, L.ptr(fb.tap if has_tap else None),
                 L.ptr(fb.abs_tap if (has_tap and want_abs) else None), L.ptr(fb.radii_max if has_tap else None), st))
             ret = tuple(None if k in sink else bufs[k] for k in like)
-            return ret + (None,) * (NF - 5) + tuple(dfe) + d_pts + d_wide
+            return ret + (None,) * (NF - 7) + camera_backward(rec) + tuple(dfe) + d_pts + d_wide
         group_of = _set_groups(meta)
         fi, dfe, dfs, strides = 0, [], [None, None, None], [0, 0, 0]
         for si, (w, _, _, _) in enumerate(meta):
@@ -844,7 +951,7 @@ class _RenderDynamicSets(torch.autograd.Function):
             depth_ch, L.ptr(fb.tap if has_tap else None), L.ptr(fb.abs_tap if (has_tap and want_abs) else None),
             L.ptr(fb.radii_max if has_tap else None), st))
         ret = tuple(None if k in sink else bufs[k] for k in like)
-        return ret + (None,) * (NF - 5) + tuple(dfe) + d_pts + d_wide
+        return ret + (None,) * (NF - 7) + camera_backward(rec) + tuple(dfe) + d_pts + d_wide
 
 
 def _parse_points(points, sink, F, P):

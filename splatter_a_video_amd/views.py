@@ -11,7 +11,8 @@ Here a clip is rendered in batches of frames with ONE camera PER FRAME of the ba
 frames' cameras, one binning, one sort, one compositing pass.  The two eyes of a stereo frame are two frames of the same
 batch at the same time.  ``to_uint8`` / the anaglyph mix turn the float images into display-ready bytes in one launch per
 batch (``splat_frames_present``): float32 arithmetic with every product and sum rounded once, restated in numpy by
-tests/views_ref.py.  No CPU path, no gradients (the reference runs these under ``torch.no_grad()``)."""
+tests/views_ref.py.  No CPU path, no gradients (the reference runs these under ``torch.no_grad()``).  ``pose_delta`` is the
+one differentiable helper: the pose parameterisation for ``FrameBatch.render_dynamic*(camera_grad=True)``."""
 from __future__ import annotations
 
 import ctypes
@@ -79,6 +80,19 @@ def stereo_cameras(radius: float = 0.05, at_z: float = 2.5, device="cpu") -> Ten
     pos = torch.tensor([[float(radius) * math.cos(p), float(radius) * math.sin(p), 0.0] for p in (0.0, math.pi)],
                        dtype=torch.float32)
     return _world_to_camera(pos, at_z, device)
+
+
+def pose_delta(extr: Tensor, xi: Tensor) -> Tensor:
+    """``exp(xi^) @ extr``: world-to-camera matrices ``extr`` ([F,4,4] or [4,4]) moved by the twists ``xi`` ([F,6] or [6],
+    ``(omega, v)``: rotation vector, then translation), the parameterisation a pose refinement optimises.  Pure torch
+    (``torch.linalg.matrix_exp`` of the 4x4 twist matrix) and differentiable w.r.t. both: the raw ``dL/dextr`` of
+    ``FrameBatch.render_dynamic*(camera_grad=True)`` chains into ``xi`` by autograd.  ``xi = 0`` returns ``extr``'s bits."""
+    if extr.shape[-2:] != (4, 4) or xi.shape[-1] != 6 or xi.shape[:-1] != extr.shape[:-2]:
+        raise ValueError(f"pose_delta: extr [F,4,4] with xi [F,6], or [4,4] with [6]; got {tuple(extr.shape)} and {tuple(xi.shape)}")
+    wx, wy, wz, vx, vy, vz = xi.unbind(-1)
+    o = torch.zeros_like(wx)
+    twist = torch.stack((o, -wz, wy, vx, wz, o, -wx, vy, -wy, wx, o, vz, o, o, o, o), dim=-1).reshape(*xi.shape[:-1], 4, 4)
+    return torch.linalg.matrix_exp(twist).to(extr.dtype) @ extr
 
 
 def canonical_intrinsics(W: int, H: int, device="cpu") -> Tensor:
