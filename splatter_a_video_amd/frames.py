@@ -316,18 +316,20 @@ class FrameBatch:
         return sum(t.numel() * t.element_size() for t in vars(self).values() if isinstance(t, Tensor))
 
     # ------------------------------------------------------------------ forward / backward launch sequences
-    def _geometry(self, xyz, scales, uquats, offsets, cam: "_Camera", nearest, extent, opacity=None, op_fs=0):
+    def _geometry(self, xyz, scales, uquats, offsets, cam: "_Camera", nearest, extent, opacity=None, op_fs=0, measure=False):
         """fused preprocess (projection + cov3d + EWA under the batch's camera) + tile binning + per-tile depth sort of all frames"""
         lib, st = L.lib(), L.stream()
         F_, P_, W, H = self.F, self.P, self.W, self.H
         L.check(lib.splat_preprocess_forward_batch_cam(
             F_, P_, L.ptr(xyz), L.ptr(offsets), L.ptr(scales), L.ptr(uquats), ctypes.byref(cam.struct()), W,
             H, nearest, extent, L.ptr(self.uv), L.ptr(self.depth), L.ptr(self.conic), L.ptr(self.radius), st))
-        self._bin_and_sort(opacity, op_fs)
+        self._bin_and_sort(opacity, op_fs, measure)
 
-    def _bin_and_sort(self, opacity: Optional[Tensor] = None, op_fs: int = 0):
+    def _bin_and_sort(self, opacity: Optional[Tensor] = None, op_fs: int = 0, measure: bool = False):
         """tile binning + per-tile depth sort of all frames.  With ``opacity`` ([P], or per frame [F,P] with ``op_fs`` = P) and
-        OPTIONS["reach"]: only the pairs whose tile the splat can reach with alpha >= 1/255 are created."""
+        OPTIONS["reach"]: only the pairs whose tile the splat can reach with alpha >= 1/255 are created.  ``measure``: read
+        the pair counts between the two steps (one host sync, as ``gs.sort_gaussian`` makes) and grow the pair buffers when a
+        frame holds more pairs than they were sized for -- no pair is dropped, no overflow is flagged."""
         lib, st = L.lib(), L.stream()
         F_, P_, W, H = self.F, self.P, self.W, self.H
         reach = opacity is not None and OPTIONS["reach"]
@@ -339,7 +341,11 @@ class FrameBatch:
         else:
             L.check(lib.splat_bin_count_batch(F_, P_, L.ptr(self.uv), L.ptr(self.radius), W, H,
                                               L.ptr(self.bin_scratch), L.ptr(self.tile_range), L.ptr(self.pairs), st))
-        if self.capacity is None:      # first batch: size the pair buffers (the only host sync of the object's life)
+        if measure:
+            m = int((self.pairs if F_ == 1 else self.pairs.max()).item())
+            if self.capacity is None or m > self.capacity:
+                self._reserve(int(m * self.slack) + 1024)
+        elif self.capacity is None:    # first batch: size the pair buffers (the only host sync of the object's life)
             self._reserve(int(int(self.pairs.max().item()) * self.slack) + 1024)
         cap = self.capacity
         if reach:
@@ -353,7 +359,8 @@ class FrameBatch:
                 F_, P_, L.ptr(self.uv), L.ptr(self.depth), L.ptr(self.radius), W, H,
                 L.ptr(self.bin_scratch), L.ptr(self.tile_range), cap, L.ptr(self.keys), L.ptr(self.idx_sorted),
                 L.ptr(self.overflow), L.ptr(self.goff), L.ptr(self.owner), L.ptr(self.slot_sorted), st))
-        self._note_overflow()
+        if not measure:                # (a measured batch fits: there is no flag to bring home)
+            self._note_overflow()
 
     def _struct(self, xyz, scales, uquats, opacity, feature, offsets, cam, bg, nearest=0.01, extent=1.3) -> _SplatFrames:
         b = _SplatFrames()
@@ -380,8 +387,18 @@ class FrameBatch:
         return b
 
     def _forward_onecall(self, xyz, scales, uquats, opacity, feature, offsets, cam, bg, nearest, extent):
-        """the whole forward of the batch behind ONE crossing of the C ABI (splat_frames_forward)"""
+        """the whole forward of the batch behind ONE crossing of the C ABI (splat_frames_forward).  A batch of
+        ``frame_rasterization``'s pool (``_measured``) runs the same launches step by step instead, with the pair counts read
+        in between (``_bin_and_sort(measure=True)``) -- except inside a stream capture, where nothing may synchronise."""
         lib = L.lib()
+        if getattr(self, "_measured", False) and not torch.cuda.is_current_stream_capturing():
+            self._geometry(xyz, scales, uquats, offsets, cam, nearest, extent, opacity, 0, measure=True)
+            out = torch.empty(self.F, self.C, self.H, self.W, dtype=torch.float32, device=self.dev)
+            L.check(lib.splat_alpha_blending_forward_batch(
+                self.F, self.P, self.C, L.ptr(self.uv), L.ptr(self.conic), L.ptr(opacity), 0, L.ptr(feature), 0,
+                L.ptr(self.idx_sorted), L.ptr(self.tile_range), self.capacity, bg, L.ptr(None), self.W, self.H, 0, 0, L.ptr(out),
+                L.ptr(self.final_T), L.ptr(self.ncontrib), L.ptr(None), L.ptr(self.pack), L.ptr(self.cull_flags), L.stream()))
+            return out
         if self.capacity is None:      # first batch: size the pair buffers (the only host sync of the object's life)
             L.check(lib.splat_frames_count(ctypes.byref(self._struct(xyz, scales, uquats, opacity, feature, offsets, cam, bg,
                                                                      nearest, extent))))
@@ -1544,25 +1561,45 @@ class _RenderFrames(torch.autograd.Function):
 # ------------------------------------------------------------------ ONE frame behind one call per direction
 # gs.rasterization's chain -- project_point -> compute_cov3d -> ewa_project -> sort_gaussian -> alpha_blending (reference:
 # src/submodules/dptr/dptr/gs/__init__.py:28-100) -- for a caller that wants the image of ONE frame: a FrameBatch of one frame
-# does it in one crossing of the C ABI per direction (splat_frames_forward / _backward: fused preprocess, binning with reach
-# masks, sort, compositing | tile backward, Gaussian-side backward with the projection chain), one autograd node, a dozen tensor
-# allocations less than the operator chain -- about 100 us of host time per frame instead of 220, which keeps a frame-by-frame
-# loop GPU-bound on a busy host.  The batches are pooled by shape: a batch whose forward still waits for its backward is not
+# does it with the launches of splat_frames_forward / _backward (fused preprocess, binning with reach masks, sort, compositing |
+# tile backward, Gaussian-side backward with the projection chain), one autograd node, a dozen tensor allocations less than the
+# operator chain.  The forward reads the frame's pair count between binning and sort (frame_rasterization's docstring: the ONE
+# host synchronisation sort_gaussian makes in the chain, so that a frame never loses pairs to buffers an earlier call sized), which
+# is why it enqueues its four steps itself; inside a stream capture it is the one crossing of the C ABI, and the backward always
+# is.  The batches are pooled by shape: a batch whose forward still waits for its backward is not
 # reused (two views rendered before one backward get two batches; at most POOL_MAX per shape, then the oldest is reused and ITS
-# late backward raises).
-_FRAME_POOL: Dict[tuple, list] = {}
+# late backward raises).  Over all shapes the pool holds at most POOL_TOTAL batches: a trainer that densifies renders a new P every
+# interval, and each batch owns keys, pair records, cull flags and bin scratch.  Beyond the total the least recently used shape
+# gives up its oldest batch -- the pool only drops its reference: a batch whose backward is pending lives on through its autograd
+# node and is freed with it.
+_FRAME_POOL: Dict[tuple, list] = {}     # shape -> its batches; the dict's order is the order of last use
 POOL_MAX = 4
+POOL_TOTAL = 8
+
+
+def clear_frame_pool() -> None:
+    """drop every pooled batch of ``frame_rasterization`` (their device memory goes back to the allocator once no pending
+    backward holds them); the next call builds a new batch"""
+    _FRAME_POOL.clear()
+    frame_rasterization.last = None
 
 
 def _pooled_batch(P: int, W: int, H: int, C: int, dev, needs_grad: bool) -> FrameBatch:
     key = (str(dev), int(P), int(W), int(H), int(C))
-    pool = _FRAME_POOL.setdefault(key, [])
+    pool = _FRAME_POOL.pop(key, [])
+    _FRAME_POOL[key] = pool                 # (most recently used: last)
     fb = next((b for b in pool if not getattr(b, "_pending", False)), None)
     if fb is None:
         if len(pool) >= POOL_MAX:
             fb = pool.pop(0)
         else:
+            while sum(len(v) for v in _FRAME_POOL.values()) >= POOL_TOTAL:
+                lru = next(iter(_FRAME_POOL))
+                _FRAME_POOL[lru].pop(0)
+                if not _FRAME_POOL[lru]:
+                    del _FRAME_POOL[lru]
             fb = FrameBatch(1, P, W, H, C, dev)
+            fb._measured = True             # sized per call from the frame's own pair count (_forward_onecall)
         pool.append(fb)
     fb._pending = bool(needs_grad)
     return fb
@@ -1574,7 +1611,17 @@ def frame_rasterization(xyz: Tensor, scale: Tensor, rotate: Tensor, opacity: Ten
     """image [C, H, W] of one frame: the orthographic camera ``extr`` -- or, with ``intr`` (fx, fy, cx, cy), the pinhole camera
     of ``gs.rasterization`` -- over ``xyz (+ offset)``; differentiable w.r.t. xyz, scale, rotate, opacity, feature (cameras are
     not differentiated).  ``grad_sink`` as in ``FrameBatch.render`` (names xyz, scales, uquats, opacity, feature).  The batch that
-    rendered the frame is ``frame_rasterization.last`` (its ``tap`` / ``radii_max`` after the backward: the densification taps)."""
+    rendered the frame is ``frame_rasterization.last`` (its ``tap`` / ``radii_max`` after the backward: the densification taps).
+
+    Pair capacity: the caller has no capacity knob, so no call returns an image with dropped pairs.  Every call reads the
+    frame's pair count between binning and sort -- ONE host synchronisation, the one ``gs.sort_gaussian`` makes in the operator
+    chain -- and grows the pooled batch's pair buffers (count * 1.25 + 1024) when another camera, a zoom or grown scales hold
+    more pairs than the buffers were sized for.  A batch whose backward is pending is not taken from the pool (also not by a
+    call under ``no_grad``), so a resize never touches lists a backward still reads; past ``POOL_MAX`` live forwards of one shape
+    the oldest batch is reused and its late backward raises before it reads anything.  INSIDE a stream capture (``torch.cuda.graph``) nothing is synchronised or
+    resized: the capacity is whatever the warm-up calls reserved, the whole forward is one ``splat_frames_forward``, and a
+    frame that outgrows the capacity at a replay drops its surplus pairs -- ``frame_rasterization.last.check()`` after the
+    replay raises then, as for an explicit ``FrameBatch``."""
     P, C = feature.shape
     needs = torch.is_grad_enabled() and any(t.requires_grad for t in (xyz, scale, rotate, opacity, feature))
     fb = _pooled_batch(P, W, H, C, xyz.device, needs)

@@ -43,10 +43,12 @@ class PairMap:
     """What ``sort_gaussian`` knows beyond the reference's two outputs: ``goff`` (inclusive prefix of tiles per Gaussian)
     and ``slot_sorted`` (Gaussian-major pair slot of every sorted entry).  ``alpha_blending*``'s backward uses it to run
     without global atomics.  The map is bound to the exact ``idx_sorted`` / ``tile_range`` tensors it was made with
-    (storage address, size and autograd version counter): ``match`` raises when either was modified in place since."""
+    (storage address, size and autograd version counter): ``match`` raises when either was modified in place since.
+    ``reach``: the lists were built with reach masks (``sort_gaussian_capped(conic=, opacity=)``) -- they lack the pairs whose
+    tile the splat cannot reach with alpha = opacity * G >= 1/255, which ``alpha_blending_with_bias`` may still need."""
 
-    def __init__(self, goff: Tensor, slot_sorted: Tensor, idx_sorted: Tensor, tile_range: Tensor):
-        self.goff, self.slot_sorted = goff, slot_sorted
+    def __init__(self, goff: Tensor, slot_sorted: Tensor, idx_sorted: Tensor, tile_range: Tensor, reach: bool = False):
+        self.goff, self.slot_sorted, self.reach = goff, slot_sorted, bool(reach)
         self.P, self.M = int(goff.numel()), int(idx_sorted.numel())
         self._idx = (idx_sorted.data_ptr(), idx_sorted._version)
         self._tr = (tile_range.data_ptr(), tile_range.numel(), tile_range._version)
@@ -103,10 +105,11 @@ def _overflow_sink(device) -> Tensor:
 
 class SortStatus:
     """Device-side outcome of a capacity-bounded sort: ``pairs`` (int32[1], the true number of tile-Gaussian
-    pairs M) and ``capacity``; ``overflow`` (bool[1], M exceeded the capacity and pairs were dropped) derives from them."""
+    pairs M) and ``capacity``; ``overflow`` (bool[1], M exceeded the capacity and pairs were dropped) derives from them.
+    ``reach``: the lists were built with reach masks (see ``PairMap``)."""
 
-    def __init__(self, pairs: Tensor, capacity: int, pairmap: Optional[PairMap] = None):
-        self.pairs, self.capacity, self.pairmap = pairs, int(capacity), pairmap
+    def __init__(self, pairs: Tensor, capacity: int, pairmap: Optional[PairMap] = None, reach: bool = False):
+        self.pairs, self.capacity, self.pairmap, self.reach = pairs, int(capacity), pairmap, bool(reach)
 
     @property
     def overflow(self) -> Tensor:
@@ -137,7 +140,7 @@ def _sort(uv: Tensor, depth: Tensor, W: int, H: int, radius: Tensor, tiles: Opti
     tile_range = torch.empty(T, 2, dtype=torch.int32, device=dev)
     if P == 0:
         z = torch.zeros(1, dtype=torch.int32, device=dev)
-        return torch.empty(0, dtype=torch.int32, device=dev), tile_range.zero_(), SortStatus(z, 0)
+        return torch.empty(0, dtype=torch.int32, device=dev), tile_range.zero_(), SortStatus(z, 0, reach=conic is not None)
     lib = L.lib()
     scratch = torch.empty(lib.splat_bin_scratch_bytes(P, W, H), dtype=torch.uint8, device=dev)
     m_dev = torch.empty(1, dtype=torch.int32, device=dev)
@@ -173,9 +176,9 @@ def _sort(uv: Tensor, depth: Tensor, W: int, H: int, radius: Tensor, tiles: Opti
                                        L.ptr(overflow), L.ptr(goff), L.ptr(owner), L.ptr(slot_sorted), L.stream()))
         # companion of idx_sorted (the reference's signature has no room for it): lets alpha_blending's backward run
         # without global atomics; found again through the tensor's storage address and validated there
-        pm = PairMap(goff, slot_sorted, idx_sorted, tile_range)
+        pm = PairMap(goff, slot_sorted, idx_sorted, tile_range, reach=reach is not None)
         _register_pairmap(idx_sorted, pm)
-    return idx_sorted, tile_range, SortStatus(m_dev, M, pm)
+    return idx_sorted, tile_range, SortStatus(m_dev, M, pm, reach=reach is not None)
 
 
 def sort_gaussian(uv: Tensor, depth: Tensor, W: int, H: int, radius: Tensor, tiles: Tensor) -> Tuple[Tensor, Tensor]:
@@ -197,8 +200,11 @@ def sort_gaussian_capped(uv: Tensor, depth: Tensor, W: int, H: int, radius: Tens
     blending such a result is memory-safe (and meaningless).  ``capacity`` None: sized exactly, with the one host sync.
     With ``conic`` [P,3] and ``opacity`` [P] the lists hold only the (Gaussian, tile) pairs whose tile the splat can reach with
     alpha >= 1/255 (reach masks, include/splat_hip.h): a third fewer entries on the bench scene for every kernel behind the sort;
-    ``alpha_blending*`` composites the same images, ids and gradients from them (list positions -- ncontrib -- differ from the
-    reference's, which is why ``sort_gaussian`` itself never drops a pair)."""
+    ``alpha_blending``, ``alpha_blending_enhanced``, ``alpha_blending_shared`` and ``alpha_blending_points`` composite the same
+    images, ids and gradients from them (list positions -- ncontrib -- differ from the reference's, which is why
+    ``sort_gaussian`` itself never drops a pair).  NOT ``alpha_blending_with_bias``: its alpha = opacity * G + bias can reach
+    1/255 in a tile the reach test (opacity * G alone) dropped, so the lists are tagged (``status.reach``, ``PairMap.reach``)
+    and that operator raises ``ValueError`` on them; build its lists without ``conic`` / ``opacity``."""
     if capacity is not None and capacity < 0:
         raise ValueError("capacity must be >= 0")
     if (conic is None) != (opacity is None):
@@ -362,9 +368,14 @@ def alpha_blending_enhanced(uv: Tensor, conic: Tensor, opacity: Tensor, feature:
 def alpha_blending_with_bias(uv: Tensor, conic: Tensor, opacity: Tensor, feature: Tensor, opacity_bias: Tensor,
                              idx_sorted: Tensor, title_bins: Tensor, bg: float, W: int, H: int,
                              ndc: Optional[Tensor] = None, abs_ndc: Optional[Tensor] = None) -> Tensor:
-    """alpha = min(0.99, opacity * G + opacity_bias[P,1])."""
+    """alpha = min(0.99, opacity * G + opacity_bias[P,1]).  Needs the full lists of ``sort_gaussian``: reach-masked lists
+    (``sort_gaussian_capped(conic=, opacity=)``) were cut by opacity * G alone and raise ``ValueError``."""
     if opacity_bias is None:
         raise ValueError("opacity_bias is required")
+    pm = _PAIRMAPS.get(idx_sorted.data_ptr()) if isinstance(idx_sorted, Tensor) else None
+    if pm is not None and pm.reach and idx_sorted.numel() == pm.M:
+        raise ValueError("alpha_blending_with_bias: idx_sorted was built with reach masks (sort_gaussian_capped(conic=, "
+                         "opacity=)), which drop the pairs a splat reaches only with its opacity bias; sort without them")
     return _AlphaBlend.apply(uv, conic, opacity, feature, opacity_bias, idx_sorted, title_bins, bg, W, H, ndc,
                              abs_ndc, 0, False)
 
@@ -763,8 +774,8 @@ def rasterization(xyz: Tensor, scale: Tensor, rotate: Tensor, opacity: Tensor, f
     (``preprocess_persp``: same arithmetic, no visible mask / cov3d round trips) unless the camera itself requires grad."""
     cam_grad = (isinstance(intr, Tensor) and intr.requires_grad) or (isinstance(extr, Tensor) and extr.requires_grad)
     if not cam_grad and ndc is None and OPTIONS["rasterization_one_call"] and feature.dim() == 2 and 1 <= feature.shape[1] <= 32:
-        # the whole chain behind ONE call of the C ABI per direction (a pooled one-frame batch: frames.frame_rasterization) -- half the
-        # host time of the operator chain; with a tap tensor (`ndc`) or a differentiable camera the operators below run
+        # the whole chain through a pooled one-frame batch (frames.frame_rasterization: one autograd node, one host synchronisation
+        # per call to size the lists, as sort_gaussian below); with a tap tensor (`ndc`) or a differentiable camera the operators run
         from ..frames import frame_rasterization
         return frame_rasterization(xyz, scale, rotate, opacity, feature, extr, W, H, bg, intr=intr, nearest=0.2, extent=1.3)
     if cam_grad:
@@ -783,8 +794,9 @@ def rasterization(xyz: Tensor, scale: Tensor, rotate: Tensor, opacity: Tensor, f
 def rasterization_ortho(xyz: Tensor, scale: Tensor, rotate: Tensor, opacity: Tensor, feature: Tensor, extr: Tensor, W: int, H: int,
                         bg: float, offset: Optional[Tensor] = None, nearest: float = 0.01, extent: float = 1.3, grad_sink=None) -> Tensor:
     """``rasterization`` for the ORTHOGRAPHIC camera of the reference's video renderer (dptr_ortho_enhanced.py:282-349: project_point,
-    compute_cov3d, the EWA projection, sort_gaussian, alpha_blending), one frame, behind one call of the C ABI per direction
-    (``frames.frame_rasterization``: a pooled one-frame batch).  ``offset`` [P, 3] is added to ``xyz`` inside the kernel;
+    compute_cov3d, the EWA projection, sort_gaussian, alpha_blending), one frame, through a pooled one-frame batch
+    (``frames.frame_rasterization``: one autograd node; every call reads its pair count -- one host synchronisation, as
+    ``sort_gaussian`` -- so no call loses pairs to an earlier call's sizes).  ``offset`` [P, 3] is added to ``xyz`` inside the kernel;
     ``grad_sink`` may hold buffers for "xyz", "scales", "uquats", "opacity", "feature"."""
     from ..frames import frame_rasterization
     return frame_rasterization(xyz, scale, rotate, opacity, feature, extr, W, H, bg, intr=None, offset=offset, nearest=nearest,
