@@ -167,7 +167,8 @@ __device__ __forceinline__ void philox4x32(unsigned c0, unsigned c1, unsigned c2
     }
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
-__device__ __forceinline__ float u01(unsigned x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }  // (0, 1)
+__device__ __forceinline__ float u01(unsigned x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+// [2^-25, 1]: from x >> 8 = 2^23 on the sum rounds (ties to even), so the top counter value gives exactly 1 (logf(1) = 0: r = 0)
 
 // new_pos_scale of the reference (atlas_gs_optimizer.py:255-287): samples ~ N(0, diag(scaling^2)) rotated by the
 // Gaussian's (normalised) rotation and added to its position; new scaling = log(scaling / (0.8 split_num)).

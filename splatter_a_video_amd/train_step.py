@@ -213,6 +213,7 @@ class TrainingStep:
         if spatial_order:
             self.initial_order = self._morton(p0)
             p0, _ = D.reorder_points(p0, None, self.initial_order)
+        self.last_order = None      # the permutation of the last densify()
         self._build(p0, None, 0)
 
     # ------------------------------------------------------------------ buffers at the current Gaussian count
@@ -694,7 +695,10 @@ class TrainingStep:
                                   c.size_threshold)
         p, m = D.prune_points(p, m, ~prune)
         N2 = p["position"].shape[0]
-        p, m = D.reorder_points(p, m, self._morton(p))
+        # ``last_order[i]`` = the row Gaussian i here had after clone / split / prune (the originals that survive in their old
+        # order, then the surviving clones, then the surviving children), as ``initial_order`` maps the set-up's rows
+        self.last_order = self._morton(p)
+        p, m = D.reorder_points(p, m, self.last_order)
         self.last_change = dict(cloned=n_clone, split=n_split, pruned=int(prune.sum()), N=N2)
         self._build(p, m, self.opt.t)
 
