@@ -1,5 +1,5 @@
 """ctypes binding of libsplat_hip.so (C ABI: include/splat_hip.h and its extensions include/splat_hip_views.h,
-include/splat_hip_views_grad.h and include/splat_hip_camera_grad.h).
+include/splat_hip_views_grad.h, include/splat_hip_camera_grad.h and include/splat_hip_layers_cam.h).
 
 The product path has NO fallback: if the HIP library is missing or a tensor is not a contiguous
 float32/int32 CUDA tensor the call raises.  (The CPU oracle lives in ``oracle/`` and is never
@@ -40,6 +40,10 @@ VIEWS_GRAD_SYMBOLS = list(VIEWS_GRAD_HEADER.functions)
 CAMERA_GRAD_HEADER = _abi.load(os.path.join(_HERE, os.pardir, "include", "splat_hip_camera_grad.h"), HEADER)
 CAMERA_GRAD_ABI_VERSION = CAMERA_GRAD_HEADER.defines["SPLAT_CAMERA_GRAD_ABI_VERSION"]
 CAMERA_GRAD_SYMBOLS = list(CAMERA_GRAD_HEADER.functions)
+# the fourth extension (layered scenes -- layer editing, feature lifting -- under those cameras), on the core header's names too
+LAYERS_CAM_HEADER = _abi.load(os.path.join(_HERE, os.pardir, "include", "splat_hip_layers_cam.h"), HEADER)
+LAYERS_CAM_ABI_VERSION = LAYERS_CAM_HEADER.defines["SPLAT_LAYERS_CAM_ABI_VERSION"]
+LAYERS_CAM_SYMBOLS = list(LAYERS_CAM_HEADER.functions)
 
 
 class SplatError(RuntimeError):
@@ -60,10 +64,12 @@ def lib() -> ctypes.CDLL:
         L = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in (list(HEADER.functions.items()) + list(VIEWS_HEADER.functions.items())
                                           + list(VIEWS_GRAD_HEADER.functions.items())
-                                          + list(CAMERA_GRAD_HEADER.functions.items())):
+                                          + list(CAMERA_GRAD_HEADER.functions.items())
+                                          + list(LAYERS_CAM_HEADER.functions.items())):
             fn = getattr(L, name, None)
             if fn is None:
-                where = ("splat_hip_camera_grad.h" if name in CAMERA_GRAD_HEADER.functions
+                where = ("splat_hip_layers_cam.h" if name in LAYERS_CAM_HEADER.functions
+                         else "splat_hip_camera_grad.h" if name in CAMERA_GRAD_HEADER.functions
                          else "splat_hip_views_grad.h" if name in VIEWS_GRAD_HEADER.functions
                          else "splat_hip_views.h" if name in VIEWS_HEADER.functions else "splat_hip.h")
                 raise SplatError(f"{LIB_PATH} lacks {name} (include/{where}: the library is older than the headers); rebuild it")
@@ -79,6 +85,9 @@ def lib() -> ctypes.CDLL:
         if L.splat_camera_grad_abi_version() != CAMERA_GRAD_ABI_VERSION:
             raise SplatError(f"{LIB_PATH} has camera-grad ABI version {L.splat_camera_grad_abi_version()}, "
                              f"include/splat_hip_camera_grad.h {CAMERA_GRAD_ABI_VERSION}; rebuild it")
+        if L.splat_layers_cam_abi_version() != LAYERS_CAM_ABI_VERSION:
+            raise SplatError(f"{LIB_PATH} has layers-cam ABI version {L.splat_layers_cam_abi_version()}, "
+                             f"include/splat_hip_layers_cam.h {LAYERS_CAM_ABI_VERSION}; rebuild it")
         _lib = L
     return _lib
 

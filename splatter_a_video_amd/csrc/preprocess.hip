@@ -9,6 +9,7 @@
 #include "dynamics_dev.h"
 #include "gauss_dyn_bwd.h"
 #include "../../include/splat_hip_views.h"
+#include "../../include/splat_hip_layers_cam.h"
 
 namespace {
 
@@ -845,6 +846,90 @@ frame_preprocess_fwd_layer_kernel(int F, int P, int S, int Q, int q0, int I, int
     }
 }
 
+// The layer kernel under a camera PER FRAME and / or the pinhole camera (include/splat_hip_layers_cam.h): the instance list and
+// the similarity transform of frame_preprocess_fwd_layer_kernel<XF> on the trip of frame_preprocess_fwd_batch_cam_kernel<CAM>
+// (CAM = 1: orthographic cameras that differ per frame; CAM = 2: pinhole).  Lane k of the quad keeps frame f + k and that
+// frame's camera; the camera rows are requested at the top of the trip, ahead of the spline segments.  The transform acts in
+// world space, before the projection, so the centroids (splat_layer_centroids) do not see the camera.  The same device functions
+// in the cam kernel's order; a fourth copy of the trip body instead of a shared __device__ function, so that the three kernels
+// above keep their code.  Forward only; no LDS, no atomics; a source id outside the model writes nothing.
+template <bool XF, int CAM>
+__global__ void __launch_bounds__(DYN_BLOCK)
+frame_preprocess_fwd_layer_cam_kernel(int F, int P, int S, int Q, int q0, int I, int layout, const DynTab *__restrict__ tab,
+                                      const int *__restrict__ src, const float *__restrict__ position,
+                                      const float *__restrict__ cubic, const float *__restrict__ rotation,
+                                      const float4 *__restrict__ rot_poly, const float4 *__restrict__ rot_fourier,
+                                      const float *__restrict__ opacity, const float *__restrict__ scaling,
+                                      const float *__restrict__ intr, const float *__restrict__ extr, long long intr_fs,
+                                      long long extr_fs, int W, int H, float nearest, float extent,
+                                      const float *__restrict__ centroid, const float *__restrict__ delta, float scale,
+                                      int scale_splats, float *__restrict__ uv, float *__restrict__ depth,
+                                      float *__restrict__ conic, int *__restrict__ radius, float *__restrict__ opa_t) {
+    constexpr bool ORTHO = CAM == 1;
+    const int t = blockIdx.x * DYN_BLOCK + threadIdx.x;
+    const int s = t >> 2, j = t & 3;
+    if (s >= S) return;  // whole quads leave together
+    const int n = src ? src[s] : s;
+    if ((unsigned)n >= (unsigned)P) return;  // (an id outside the model: the quad writes nothing instead of reading past the tables)
+    const DynStatic stc = dyn_static(n, j, position, rotation, rot_poly, rot_fourier, scaling);
+    const int per = (F + gridDim.y - 1) / gridDim.y;
+    const int f0 = blockIdx.y * per, f1 = imin_(F, f0 + per);
+    if (blockIdx.y == 0 && j == 3) opa_t[q0 + s] = 1.0f / (1.0f + expf(-opacity[n]));  // the source Gaussian's, frame independent
+    float scl3[3] = {quad_bcast<0>(stc.scl_j), quad_bcast<1>(stc.scl_j), quad_bcast<2>(stc.scl_j)};
+    if (XF && scale_splats) {
+        scl3[0] *= scale; scl3[1] *= scale; scl3[2] *= scale;
+    }
+    for (int f = f0; f < f1; f += 4) {
+        Cam c;
+        {   // this lane's frame (a lane past the slice reads the slice's last camera and does not store)
+            const size_t fc = (size_t)imin_(f + j, f1 - 1);
+            load_cam(ORTHO ? nullptr : intr + fc * intr_fs, extr + fc * extr_fs, c);
+        }
+        float m_pos[3] = {0.f, 0.f, 0.f}, m_q[4] = {1.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int ff = imin_(f + k, f1 - 1);  // (a repeated last frame: its lane does not store)
+            const CubicAddr ca = cubic_addr(layout, P, I, tab[ff].seg);
+            const DynFrame fr = dyn_frame_rows(n, j, ca, tab[ff].d, tab[ff].basis, stc, cubic);
+            if (j == k) {
+                m_pos[0] = fr.pos[0]; m_pos[1] = fr.pos[1]; m_pos[2] = fr.pos[2];
+                m_q[0] = fr.q[0]; m_q[1] = fr.q[1]; m_q[2] = fr.q[2]; m_q[3] = fr.q[3];
+            }
+        }
+        if (f + j >= f1) continue;
+        if (XF) {
+            if (centroid) {
+                const float *cf = centroid + (size_t)(f + j) * 3;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) m_pos[k] = layer_place(m_pos[k], cf[k], scale);
+            }
+            if (delta) {
+                const float *df = delta + (size_t)(f + j) * 3;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) m_pos[k] = layer_shift(m_pos[k], df[k]);
+            }
+        }
+        float u, v, dep;
+        const bool cull = ORTHO ? project_ortho_pt(c, m_pos[0], m_pos[1], m_pos[2], W, H, nearest, extent, u, v, dep)
+                                : project_persp_pt(c, m_pos[0], m_pos[1], m_pos[2], W, H, nearest, extent, u, v, dep);
+        u = cull ? 0.f : u; v = cull ? 0.f : v; dep = cull ? 0.f : dep;
+        float o[3] = {0.f, 0.f, 0.f};
+        int orad = 0, otiles = 0;
+        if (dep != 0.f) {
+            float c3[6], a[3], bb[3], tt[3], Jm[4], cov[3];
+            cov3d_pt(scl3, m_q, c3);
+            ewa_T<ORTHO>(c, m_pos, W, H, a, bb, tt, Jm);
+            ewa_cov2d<ORTHO>(a, bb, c3, cov);
+            ewa_finish_pt<ORTHO>(cov, make_float2(u, v), W, H, o[0], o[1], o[2], orad, otiles);
+        }
+        const size_t fn = (size_t)(f + j) * Q + q0 + s;
+        *reinterpret_cast<float2 *>(uv + fn * 2) = make_float2(u, v);
+        conic[fn * 3] = o[0]; conic[fn * 3 + 1] = o[1]; conic[fn * 3 + 2] = o[2];
+        depth[fn] = dep;
+        radius[fn] = orad;
+    }
+}
+
 // centroid[f] = mean over the layer's S selected Gaussians of position(t_f) (add_fg's fg_pos.mean, :1359-1360), the spline
 // expression of the preprocess in float32, the sum in float64 in a FIXED order: a wave of 64 lanes sums CEN_ITEMS strided
 // elements per lane and folds the lanes with xor shuffles into partial[f][block][3]; a second launch sums a frame's partials
@@ -1414,6 +1499,62 @@ extern "C" int splat_frame_preprocess_layer_batch(int F, int P, int S, int Q, in
                      (hipStream_t)stream, F, P, S, Q, q0, I, cubic_layout, (const DynTab *)tab, src, position, cubic, rotation,
                      (const float4 *)rot_poly, (const float4 *)rot_fourier, opacity, scaling, extr, W, H, nearest, extent, centroid,
                      delta, scale, scale_splats, uv, depth, conic, radius, opa_t);
+    SPLAT_POST_LAUNCH();
+    return SPLAT_OK;
+}
+
+// ---- the same layer under any camera (include/splat_hip_layers_cam.h): one orthographic camera IS the entry point above (its
+// kernels, its bits); cameras per frame and the pinhole camera run frame_preprocess_fwd_layer_cam_kernel.  Forward only.
+extern "C" int splat_layers_cam_abi_version(void) { return SPLAT_LAYERS_CAM_ABI_VERSION; }
+
+extern "C" int splat_frame_preprocess_layer_batch_cam(int F, int P, int S, int Q, int q0, int I, const void *tab,
+                                                      const int32_t *src, const float *position, const float *cubic,
+                                                      int cubic_layout, const float *rotation, const float *rot_poly,
+                                                      const float *rot_fourier, const float *opacity, const float *scaling,
+                                                      const splat_camera_t *cam, int W, int H, float nearest, float extent,
+                                                      const float *centroid, const float *delta, float scale, int scale_splats,
+                                                      float *uv, float *depth, float *conic, int32_t *radius, float *opa_t,
+                                                      void *stream) {
+    SPLAT_CHECK_ARG(F >= 0 && F <= 65535 && P >= 1 && S >= 0 && Q >= 1 && q0 >= 0 && I >= 1 && W > 0 && H > 0, "bad sizes");
+    SPLAT_CHECK_ARG(cam && cam->extr, "null camera (cam and cam->extr are required)");
+    SPLAT_CHECK_ARG(!cam->perspective || cam->intr, "the perspective camera needs intr");
+    SPLAT_CHECK_ARG((cam->extr_frame_stride == 0 || cam->extr_frame_stride >= 12) &&
+                        (cam->intr_frame_stride == 0 || cam->intr_frame_stride >= 4),
+                    "negative camera stride, or rows that overlap (extr: 0 or >= 12 floats, intr: 0 or >= 4)");
+    if (!cam->perspective && (cam->extr_frame_stride == 0 || F == 1))
+        return splat_frame_preprocess_layer_batch(F, P, S, Q, q0, I, tab, src, position, cubic, cubic_layout, rotation, rot_poly,
+                                                  rot_fourier, opacity, scaling, cam->extr, W, H, nearest, extent, centroid, delta,
+                                                  scale, scale_splats, uv, depth, conic, radius, opa_t, stream);
+    SPLAT_CHECK_ARG(S <= P, "a layer selects at most P Gaussians (src: ascending ids)");
+    SPLAT_CHECK_ARG((long long)q0 + S <= (long long)Q, "q0 + S exceeds the batch's Q instances");
+    SPLAT_CHECK_ARG(cubic_layout == SPLAT_CUBIC_GAUSSIAN_MAJOR || cubic_layout == SPLAT_CUBIC_SEGMENT_MAJOR, "unknown cubic_layout");
+    SPLAT_CHECK_ARG(std::isfinite(scale), "scale must be finite");
+    SPLAT_CHECK_ARG(scale == 1.0f || centroid, "scale != 1 needs the layer's centroid");
+    SPLAT_CHECK_ARG(src || S == P, "src == NULL means every Gaussian in place: S must be P");
+    if (S == 0 || F == 0) return SPLAT_OK;
+    SPLAT_CHECK_ARG(tab && position && cubic && rotation && rot_poly && rot_fourier && opacity && scaling, "null input pointer");
+    SPLAT_CHECK_ARG(uv && depth && conic && radius && opa_t, "null output pointer");
+    const dim3 g = dyn_grid(S);
+    int slices = (int)((4096 + g.x - 1) / g.x);   // frames per thread: as in splat_frame_preprocess_forward_batch
+    if (slices < 1) slices = 1;
+    if (slices > F) slices = F;
+    const bool xf = centroid || delta || (scale_splats && scale != 1.0f);
+    const float *intr = cam->perspective ? cam->intr : nullptr;
+    const long long intr_fs = cam->perspective ? (long long)cam->intr_frame_stride : 0ll;
+    const long long extr_fs = (long long)cam->extr_frame_stride;
+#define SPLAT_LAYER_CAM(XF_, CAM_)                                                                                              \
+    SPLAT_LAUNCH("frame_preprocess_fwd_layer_cam", (frame_preprocess_fwd_layer_cam_kernel<XF_, CAM_>), dim3(g.x, slices),       \
+                 dim3(DYN_BLOCK), 0, (hipStream_t)stream, F, P, S, Q, q0, I, cubic_layout, (const DynTab *)tab, src, position,  \
+                 cubic, rotation, (const float4 *)rot_poly, (const float4 *)rot_fourier, opacity, scaling, intr, cam->extr,     \
+                 intr_fs, extr_fs, W, H, nearest, extent, centroid, delta, scale, scale_splats, uv, depth, conic, radius, opa_t)
+    if (cam->perspective) {
+        if (xf) SPLAT_LAYER_CAM(true, 2);
+        else SPLAT_LAYER_CAM(false, 2);
+    } else {
+        if (xf) SPLAT_LAYER_CAM(true, 1);
+        else SPLAT_LAYER_CAM(false, 1);
+    }
+#undef SPLAT_LAYER_CAM
     SPLAT_POST_LAUNCH();
     return SPLAT_OK;
 }

@@ -176,6 +176,16 @@ def _camera_grad(extr, intr, grad_sink, F: int, who: str):
 OPTIONS = {"sets_one_pass": True, "reach": True}
 
 
+def _set_tensors(sets, points, wide) -> list:
+    """every feature tensor a render call was handed (sets, the sparse and the wide set), before any parsing: what autograd could
+    attach a backward to"""
+    out = []
+    for s_ in list(sets or []) + [points, wide]:
+        f = s_.get("feature") if isinstance(s_, dict) else None
+        out += list(f) if isinstance(f, (list, tuple)) else [f]
+    return [t for t in out if isinstance(t, Tensor)]
+
+
 def _tiles(W: int, H: int) -> int:
     return ((W + 15) // 16) * ((H + 15) // 16)
 
@@ -187,10 +197,15 @@ class FrameBatch:
     host synchronises anyway, e.g. once per optimiser step) raises if a frame outgrew it; without ``check()`` the next
     forward raises, a step or a few late (the flag travels to pinned host memory behind the binning kernels; the error is
     raised once and the flag cleared, so batches that fit keep running afterwards).  An overflow of the LAST batches of a run
-    is only seen by ``check()``: call it after the final step."""
+    is only seen by ``check()``: call it after the final step.
+
+    ``records=False``: a FORWARD-ONLY batch.  The backward's pair-record buffer ([F, capacity, stride] floats, half of a
+    batch's memory at video sizes) is never allocated -- no forward launch reads or writes it -- and every differentiable render
+    (``differentiable=True`` / ``camera_grad=True``, or grad mode with an input that requires grad) raises ``ValueError`` before
+    a launch.  The forward-only clip renderers (``layers.LayeredClip``, ``lift.FeatureLift``, ``views``) build theirs this way."""
 
     def __init__(self, F: int, P: int, W: int, H: int, C: int, device, capacity: Optional[int] = None,
-                 want_abs: bool = False, slack: float = 1.25):
+                 want_abs: bool = False, slack: float = 1.25, records: bool = True):
         dev = torch.device(device)
         if dev.type != "cuda":
             raise ValueError("FrameBatch lives on the GPU (there is no CPU path)")
@@ -199,6 +214,7 @@ class FrameBatch:
         self.F, self.P, self.W, self.H, self.C = int(F), int(P), int(W), int(H), int(C)
         self.T = _tiles(W, H)
         self.dev, self.want_abs, self.slack = dev, bool(want_abs), float(slack)
+        self.records = bool(records)
         lib = L.lib()
         f32, i32 = torch.float32, torch.int32
         F_, P_, T_ = self.F, self.P, self.T
@@ -238,7 +254,8 @@ class FrameBatch:
         self.owner = torch.empty(F_, capacity, dtype=torch.int32, device=dev)
         self.idx_sorted = torch.empty(F_, capacity, dtype=torch.int32, device=dev)
         self.slot_sorted = torch.empty(F_, capacity, dtype=torch.int32, device=dev)
-        self.pair_records = torch.empty(F_ * capacity * self.ncp, dtype=torch.float32, device=dev)
+        # read and written by the backward alone (the tile backward fills it, the Gaussian-side backward folds it)
+        self.pair_records = torch.empty(F_ * capacity * self.ncp, dtype=torch.float32, device=dev) if self.records else None
         self.cull_flags = torch.empty(F_, capacity, dtype=torch.int32, device=dev)   # the forward's cull, for the backward
 
     def _set_buffer(self, key, numel: int) -> Tensor:
@@ -314,6 +331,16 @@ class FrameBatch:
 
     def memory_bytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in vars(self).values() if isinstance(t, Tensor))
+
+    def _forward_only_guard(self, who: str, tensors, asked: bool = False) -> None:
+        """a batch without the pair-record buffer (``records=False``) has no backward: refuse, before any launch, a render that
+        asks for one (``asked``) or that autograd would attach one to"""
+        if getattr(self, "records", True):
+            return
+        if asked or (torch.is_grad_enabled() and any(isinstance(t, Tensor) and t.requires_grad for t in tensors)):
+            raise ValueError(f"{who}: this FrameBatch was built with records=False (forward only: it holds no pair-record buffer "
+                             "for a backward); render under torch.no_grad() with detached tensors, or build the batch with "
+                             "records=True")
 
     # ------------------------------------------------------------------ forward / backward launch sequences
     def _geometry(self, xyz, scales, uquats, offsets, cam: "_Camera", nearest, extent, opacity=None, op_fs=0, measure=False):
@@ -432,6 +459,7 @@ class FrameBatch:
         then sees no gradient for them), the others are returned to autograd.  After
         the backward, ``tap`` / ``abs_tap`` hold the batch's summed densification taps and ``radii_max`` the largest
         screen radius of every Gaussian over the frames."""
+        self._forward_only_guard("render", (xyz, scales, uquats, opacity, feature, offsets), bool(grad_sink))
         sink = check_sink(grad_sink, {"xyz": xyz, "scales": scales, "uquats": uquats, "opacity": opacity, "feature": feature})
         return _RenderFrames.apply(xyz, scales, uquats, opacity, feature, offsets, extr, self, float(bg), float(nearest),
                                    float(extent), sink, intr)
@@ -490,6 +518,8 @@ class FrameBatch:
         the path above, with its bits.  Without it ``extr`` is ONE camera and ``intr`` raises.
 
         ``camera_grad=True`` (needs ``differentiable=True``) makes the cameras leaves as well, as in ``render_dynamic_sets``."""
+        self._forward_only_guard("render_dynamic", (position, pos_cubic_node, rotation, opacity, scaling, feature, extr, intr),
+                                 bool(differentiable or camera_grad or grad_sink))
         tab = self.frame_table(clock, times)
         if camera_grad and not differentiable:
             raise ValueError("render_dynamic: camera_grad=True needs differentiable=True")
@@ -570,6 +600,8 @@ class FrameBatch:
         bit-reproducible, allowed in deterministic mode); the parameter and feature gradients keep their bits, and a camera
         that neither requires grad nor has a sink launches nothing.  ``views.pose_delta`` is the parameterisation a pose
         refinement optimises.  Not differentiated: the cull / near / extent decisions and the radius."""
+        self._forward_only_guard("render_dynamic_sets", [position, pos_cubic_node, rotation, opacity, scaling, extr, intr]
+                                 + _set_tensors(sets, points, wide), bool(differentiable or camera_grad or grad_sink))
         tab = self.frame_table(clock, times)
         cam = dcam = cg = None
         if camera_grad:
@@ -640,6 +672,8 @@ class FrameBatch:
         ``wide``: one more detached feature set of any width outside the row, as in ``render_dynamic_sets`` (its image [F,c,H,W]
         comes behind the sets' images, in front of ``gs_idx``; ``grad_sink["wide"]``); the sets must then fit the one-pass
         backward."""
+        self._forward_only_guard("render_sets", [xyz, scales, uquats, opacity, offsets] + _set_tensors(sets, None, wide),
+                                 bool(grad_sink))
         def one(f):
             # a list of shared tensors = their concatenation along the channels, as the reference's renderer concatenates its
             # attributes (RenderFeatures.combine); per-frame tensors belong to the dynamic renderer (render_dynamic_sets)

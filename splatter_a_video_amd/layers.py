@@ -13,11 +13,18 @@ per batch of frames every layer takes ONE launch of the batched dynamic preproce
 one more pair of launches for its per-frame centroids (``splat_layer_centroids``) -- and binning, sort and compositing are the
 frame batch's.  Features and opacity belong to the source Gaussian and are gathered per instance.
 
+Cameras: the clip's default camera is the constructor's ``extr`` (one camera) and ``intr`` (None: orthographic; [4]: pinhole).
+``render(times, extr=, intr=)`` sets the cameras of one call -- one per clip frame ([T_clip,4,4], [T_clip,4]: an orbit about the
+edited scene, the two eyes of a stereo clip) or one for all -- and the layers then go through
+``splat_frame_preprocess_layer_batch_cam`` (include/splat_hip_layers_cam.h).  The transform is applied in world space, so the
+centroids do not depend on the camera.
+
 Rotation: the reference sends the copy's quaternion through quaternion -> matrix -> quaternion -> normalise (:1365-1371), which
 returns +-q up to rounding; the covariance does not see the sign.  Here the model's normalised rotation is used directly.
 No CPU path, no gradients (the reference runs these edits under ``torch.no_grad()``)."""
 from __future__ import annotations
 
+import ctypes
 import math
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
@@ -151,7 +158,7 @@ def _forward_meta(meta, C):
     return tuple(meta)
 
 
-def _check_clip_args(p, clock, layers, extr, W, H, sets, frames_per_batch, capacity, K):
+def _check_clip_args(p, clock, layers, extr, W, H, sets, frames_per_batch, capacity, K, intr=None):
     """every argument check of a layered clip, on tensors of any device, before any GPU work"""
     if int(K) != 0:
         raise ValueError("LayeredClip: contributor ids (K > 0) are not built for layered scenes")
@@ -178,6 +185,8 @@ def _check_clip_args(p, clock, layers, extr, W, H, sets, frames_per_batch, capac
             raise ValueError(f"model {k} does not hold {n} values (N = {N} Gaussians, {I} spline segments)")
     if not isinstance(extr, Tensor) or tuple(extr.shape) not in ((4, 4), (3, 4)):
         raise ValueError("extr must be one camera, [4, 4] or [3, 4]")
+    if intr is not None and (not isinstance(intr, Tensor) or intr.dtype != torch.float32 or tuple(intr.shape) != (4,)):
+        raise ValueError("intr must be None or one pinhole camera, float32 (fx, fy, cx, cy) [4] (per-frame cameras: render(...))")
     for li, l_ in enumerate(layers):
         if l_.select is not None:
             if l_.select.shape[0] != N:
@@ -211,18 +220,20 @@ def clip_layer_inputs(layers: Sequence[Layer], times):
 
 class LayeredClip:
     """A clip rendered from the layers ``layers`` of ``model`` (a parameter dict or a ``DynamicGaussians``, as
-    ``tracking.track_pixels`` and ``edit.fit_appearance`` take it) under the orthographic video camera ``extr`` ([4,4] / [3,4]).
+    ``tracking.track_pixels`` and ``edit.fit_appearance`` take it) under the clip's default camera: ``extr`` ([4,4] / [3,4], one
+    camera) and ``intr`` (None: the orthographic video camera; (fx, fy, cx, cy) [4]: the pinhole camera).
 
     ``sets``: the feature sets of ``FrameBatch.render_dynamic_sets`` (dicts ``feature`` [N, c] or ``"depth"``, ``bg``,
     ``detach_opacity``), features indexed by SOURCE Gaussian; ``"depth"`` is the instance's own projected depth.  The constructor
     builds the instance list, gathers the features per instance once and owns one ``FrameBatch(frames_per_batch, Q, W, H, C)``.
-    ``render(times)`` returns one image tensor [T_clip, c, H, W] per set.  Contributor ids (``K > 0``) are not built."""
+    ``render(times, extr=None, intr=None)`` returns one image tensor [T_clip, c, H, W] per set, under the default camera or the
+    cameras of that call.  Contributor ids (``K > 0``) are not built."""
 
     def __init__(self, model, clock, layers: Sequence[Layer], extr: Tensor, W: int, H: int, sets, frames_per_batch: int = 8,
                  shs: Optional[Tensor] = None, cubic_layout: Optional[int] = None, nearest: float = 0.01, extent: float = 1.3,
-                 capacity: Optional[int] = None, K: int = 0):
+                 capacity: Optional[int] = None, K: int = 0, intr: Optional[Tensor] = None):
         p, layout = _params(model, shs, cubic_layout, need_shs=False)
-        N, I, meta, feats, C = _check_clip_args(p, clock, layers, extr, W, H, sets, frames_per_batch, capacity, K)
+        N, I, meta, feats, C = _check_clip_args(p, clock, layers, extr, W, H, sets, frames_per_batch, capacity, K, intr)
         pos = p["position"]
         dev = pos.device
         if dev.type != "cuda":
@@ -236,6 +247,8 @@ class LayeredClip:
         self.p = {k: L.need(p[k], k) for k in ("position", "pos_cubic_node", "rotation", "rot_poly_feat", "rot_fourier_feat",
                                                 "opacity", "scaling")}
         self.extr = _extr12(extr.detach())
+        # the default camera as ``render`` takes one: None without ``intr`` (the one orthographic camera: today's launches)
+        self.camera = None if intr is None else (extr.detach().to(dev).contiguous(), intr.detach().to(dev).contiguous())
         # the instance list: layer by layer, ascending source ids inside a layer
         self.src: List[Optional[Tensor]] = []
         self.q0: List[int] = []
@@ -258,7 +271,7 @@ class LayeredClip:
             self.feats = [L.need(f, "feature").index_select(0, gather) for f in feats]
         self.meta = _forward_meta(meta, C)
         self.widths = [1 if m[0] == "depth" else m[0] for m in self.meta]
-        self.fb = FrameBatch(self.F, self.Q, self.W, self.H, C, dev, capacity=capacity)
+        self.fb = FrameBatch(self.F, self.Q, self.W, self.H, C, dev, capacity=capacity, records=False)    # forward only
         self.opa_t = torch.empty(self.Q, 1, dtype=torch.float32, device=dev)
         lib = L.lib()
         self._centroid = {li: torch.empty(self.F, 3, dtype=torch.float32, device=dev)
@@ -280,28 +293,51 @@ class LayeredClip:
         return tab
 
     @torch.no_grad()
-    def render(self, times: Sequence[float]) -> List[Tensor]:
+    def render(self, times: Sequence[float], extr: Optional[Tensor] = None, intr: Optional[Tensor] = None) -> List[Tensor]:
         """the clip at the frame times ``times``: one detached image tensor [T_clip, c, H, W] per set.  The clip is worked through
         in batches of ``frames_per_batch`` frames (a short last batch is padded with its last frame, the padding dropped).  A
         batch whose tile-Gaussian pairs outgrow the pair capacity is never returned: the capacity is raised and the batch
-        rendered again (one host synchronisation per batch reads the pair counts)."""
+        rendered again (one host synchronisation per batch reads the pair counts).
+
+        ``extr`` / ``intr``: the cameras of this call in place of the clip's default camera -- ``extr`` [4,4] / [3,4] or one per
+        clip frame [T_clip,4,4] / [T_clip,3,4]; ``intr`` None (orthographic), (fx, fy, cx, cy) [4] or [T_clip,4] (pinhole).  An
+        ``extr`` alone keeps the default ``intr``, an ``intr`` alone the default ``extr``.  A ``"depth"`` set is the instance's
+        depth under its frame's camera.  Without either, a clip built without ``intr`` issues the launches of the one
+        orthographic camera."""
         times, lt, ld = clip_layer_inputs(self.layers, times)
         T = len(times)
         F, dev = self.F, self.fb.dev
         padded = [min(i, T - 1) for i in range(((T + F - 1) // F) * F)]    # a short last batch repeats the last frame
+        cams = None
+        if extr is not None or intr is not None or self.camera is not None:
+            from .views import _clip_cameras
+            e = extr if extr is not None else (self.camera[0] if self.camera is not None else self.extr)
+            i_ = intr if intr is not None else (self.camera[1] if self.camera is not None else None)
+            e, i_ = _clip_cameras(e, i_, T, dev, "T_clip")
+            if e.dim() == 3 or (i_ is not None and i_.dim() == 2):
+                pidx = torch.tensor(padded, device=dev)
+                e = e.index_select(0, pidx) if e.dim() == 3 else e
+                i_ = i_.index_select(0, pidx) if i_ is not None and i_.dim() == 2 else i_
+            cams = (e, i_)
         deltas = [None if d is None else d[padded].contiguous().to(dev) for d in ld]
         outs = [torch.empty(T, w, self.H, self.W, dtype=torch.float32, device=dev) for w in self.widths]
         for b0 in range(0, T, F):
             idx = padded[b0:b0 + F]
             n = min(F, T - b0)
-            row = self._render_batch([tuple(t_[i] for i in idx) for t_ in lt], [None if d is None else d[b0:b0 + F] for d in deltas])
+            cam = None
+            if cams is not None:
+                from .frames import _Camera
+                e, i_ = cams
+                cam = _Camera(e[b0:b0 + F] if e.dim() == 3 else e, i_[b0:b0 + F] if i_ is not None and i_.dim() == 2 else i_, F)
+            row = self._render_batch([tuple(t_[i] for i in idx) for t_ in lt], [None if d is None else d[b0:b0 + F] for d in deltas],
+                                     cam)
             c0 = 0
             for o, w in zip(outs, self.widths):
                 o[b0:b0 + n].copy_(row[:n, c0:c0 + w])
                 c0 += w
         return outs
 
-    def _render_batch(self, layer_times, layer_deltas) -> Tensor:
+    def _render_batch(self, layer_times, layer_deltas, cam=None) -> Tensor:
         from .frames import _blend_sets_forward
         fb, lib, st, p = self.fb, L.lib(), L.stream(), self.p
         F = self.F
@@ -315,10 +351,13 @@ class LayeredClip:
                     F, self.N, self.S[li], self.I, L.ptr(tab), L.ptr(self.src[li]), L.ptr(p["position"]),
                     L.ptr(p["pos_cubic_node"]), self.layout, L.ptr(cen), L.ptr(self._scratch),
                     self._scratch.numel() * 8, st))
-            L.check(lib.splat_frame_preprocess_layer_batch(
+            # one orthographic camera: the core entry point; the cameras of a call: its twin of include/splat_hip_layers_cam.h
+            pre = lib.splat_frame_preprocess_layer_batch if cam is None else lib.splat_frame_preprocess_layer_batch_cam
+            L.check(pre(
                 F, self.N, self.S[li], self.Q, self.q0[li], self.I, L.ptr(tab),
                 L.ptr(self.src[li]), L.ptr(p["position"]), L.ptr(p["pos_cubic_node"]), self.layout, L.ptr(p["rotation"]),
-                L.ptr(p["rot_poly_feat"]), L.ptr(p["rot_fourier_feat"]), L.ptr(p["opacity"]), L.ptr(p["scaling"]), L.ptr(self.extr),
+                L.ptr(p["rot_poly_feat"]), L.ptr(p["rot_fourier_feat"]), L.ptr(p["opacity"]), L.ptr(p["scaling"]),
+                L.ptr(self.extr) if cam is None else ctypes.byref(cam.struct()),
                 self.W, self.H, self.nearest, self.extent, L.ptr(cen), L.ptr(layer_deltas[li]),
                 l_.scale, 1 if l_.scale_splats else 0, L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius),
                 L.ptr(self.opa_t), st))
@@ -366,39 +405,49 @@ def _edit_sets(rgb, mask, bg):
             dict(feature=mask, bg=0.0, detach_opacity=True)]
 
 
-def _edit_clip(p, layout, m, clock, layers, times, extr, W, H, bg, frames_per_batch, nearest, extent, capacity) -> Dict[str, Tensor]:
+def _edit_clip(p, layout, m, clock, layers, times, extr, W, H, bg, frames_per_batch, nearest, extent, capacity, intr=None
+               ) -> Dict[str, Tensor]:
     # every argument check first (the DC rows stand in for the colours: a view, no launch), then the colours, then the clip
-    _check_clip_args(p, clock, layers, extr, W, H, _edit_sets(p["shs"][:, 0, :], m, bg), frames_per_batch, capacity, 0)
-    clip_layer_inputs(layers, times)
-    clip = LayeredClip(p, clock, layers, extr, W, H, _edit_sets(_colors(p["shs"]), m, bg), frames_per_batch, cubic_layout=layout,
+    per_frame = isinstance(extr, Tensor) and extr.dim() == 3 and extr.shape[0] >= 1
+    one = extr[0] if per_frame else extr        # the clip's default camera is one camera; the call's cameras go to render()
+    _check_clip_args(p, clock, layers, one, W, H, _edit_sets(p["shs"][:, 0, :], m, bg), frames_per_batch, capacity, 0)
+    ts, _, _ = clip_layer_inputs(layers, times)
+    if per_frame or intr is not None:
+        from .views import _clip_cameras
+        _clip_cameras(extr, intr, len(ts), extr.device, "T")
+    clip = LayeredClip(p, clock, layers, one, W, H, _edit_sets(_colors(p["shs"]), m, bg), frames_per_batch, cubic_layout=layout,
                        nearest=nearest, extent=extent, capacity=capacity)
-    return dict(zip(("rgb", "depth", "mask_attribute"), clip.render(times)))
+    images = clip.render(times, extr, intr) if (per_frame or intr is not None) else clip.render(times)
+    return dict(zip(("rgb", "depth", "mask_attribute"), images))
 
 
 def render_part(model, clock, times, extr: Tensor, W: int, H: int, fg: bool = True, threshold: float = 0.5, bg: float = 1.0,
                 mask_attribute: Optional[Tensor] = None, shs: Optional[Tensor] = None, cubic_layout: Optional[int] = None,
-                frames_per_batch: int = 8, nearest: float = 0.01, extent: float = 1.3, capacity: Optional[int] = None
-                ) -> Dict[str, Tensor]:
+                frames_per_batch: int = 8, nearest: float = 0.01, extent: float = 1.3, capacity: Optional[int] = None,
+                intr: Optional[Tensor] = None) -> Dict[str, Tensor]:
     """The reference's ``render_part`` (:1310-1341): the clip from only the Gaussians whose ``mask_attribute`` is above (``fg``)
     or not above ``threshold`` -- a foreground-only or background-only video on the background colour ``bg`` (the reference: 1).
     Colours from the SH coefficients (``model["shs"]`` or ``shs=``), the mask from ``model["mask_attribute"]`` or
-    ``mask_attribute=``.  Returns ``rgb`` [T, 3, H, W], ``depth`` and ``mask_attribute`` [T, 1, H, W]."""
+    ``mask_attribute=``.  ``extr`` one camera or one per frame time [T,4,4]; ``intr`` None, [4] or [T,4]: the pinhole camera (as
+    ``LayeredClip.render`` takes them).  Returns ``rgb`` [T, 3, H, W], ``depth`` and ``mask_attribute`` [T, 1, H, W]."""
     p, layout, m = _wrapper_model(model, shs, cubic_layout, mask_attribute)
     sel = foreground_mask(m, threshold, fg)
     if not bool(sel.any()):
         raise ValueError("render_part: the selection is empty")
-    return _edit_clip(p, layout, m, clock, [Layer(select=sel)], times, extr, W, H, bg, frames_per_batch, nearest, extent, capacity)
+    return _edit_clip(p, layout, m, clock, [Layer(select=sel)], times, extr, W, H, bg, frames_per_batch, nearest, extent, capacity,
+                      intr)
 
 
 def add_foreground(model, clock, times, extr: Tensor, W: int, H: int, delta, scale: float, fg_threshold: float = 0.5,
                    delay: float = 0, drift=None, bg: float = 0.0, scale_splats: bool = False,
                    mask_attribute: Optional[Tensor] = None, shs: Optional[Tensor] = None, cubic_layout: Optional[int] = None,
-                   frames_per_batch: int = 8, nearest: float = 0.01, extent: float = 1.3, capacity: Optional[int] = None
-                   ) -> Dict[str, Tensor]:
+                   frames_per_batch: int = 8, nearest: float = 0.01, extent: float = 1.3, capacity: Optional[int] = None,
+                   intr: Optional[Tensor] = None) -> Dict[str, Tensor]:
     """The reference's ``add_fg`` (:1344-1405): every frame from the whole model plus a copy of the foreground
     (``mask_attribute > fg_threshold``) evaluated at ``max(0, t - delay)`` (the reference's commented "for cow" line: 2), scaled
     by ``scale`` about the copy's centroid at that time and shifted by ``delta + drift * max(0, t - delay)`` ([3] each; the
-    reference's per-frame drift of ``delta_pos``).  Returns ``rgb``, ``depth`` and ``mask_attribute`` images as ``render_part``."""
+    reference's per-frame drift of ``delta_pos``).  ``extr`` / ``intr``: cameras as in ``render_part``.  Returns ``rgb``, ``depth``
+    and ``mask_attribute`` images as ``render_part``."""
     p, layout, m = _wrapper_model(model, shs, cubic_layout, mask_attribute)
     times = [float(t) for t in times]
     if not math.isfinite(float(delay)) or float(delay) < 0:
@@ -417,4 +466,4 @@ def add_foreground(model, clock, times, extr: Tensor, W: int, H: int, delta, sca
     if not bool(sel.any()):
         raise ValueError("add_foreground: the foreground selection is empty")
     layers = [Layer(), Layer(select=sel, times=ltimes, scale=scale, delta=d, scale_splats=scale_splats)]
-    return _edit_clip(p, layout, m, clock, layers, times, extr, W, H, bg, frames_per_batch, nearest, extent, capacity)
+    return _edit_clip(p, layout, m, clock, layers, times, extr, W, H, bg, frames_per_batch, nearest, extent, capacity, intr)

@@ -119,15 +119,18 @@ class FeatureLift:
     """Per-Gaussian features of a dynamic model from per-frame maps.
 
     ``model``: a parameter dict (position, pos_cubic_node, rotation, rot_poly_feat, rot_fourier_feat, opacity (logit), scaling
-    (log)) or a ``DynamicGaussians``, as ``edit.fit_appearance`` and ``layers.LayeredClip`` take it; ``extr`` the orthographic video
-    camera ([4, 4] / [3, 4]); ``D`` the width of the maps.  The object holds ONE ``FrameBatch`` of ``frames_per_batch`` frames for
+    (log)) or a ``DynamicGaussians``, as ``edit.fit_appearance`` and ``layers.LayeredClip`` take it; ``extr`` ([4, 4] / [3, 4], one
+    camera) and ``intr`` (None: the orthographic video camera; (fx, fy, cx, cy) [4]: the pinhole camera) the default camera;
+    ``D`` the width of the maps.  ``add`` / ``gradient`` / ``refine`` take ``extr=`` / ``intr=`` for the cameras the call's frames
+    were taken by: one for all, or one per frame time ([T,4,4] / [T,3,4], [T,4] -- a video from a moving, known camera); they
+    then go through ``splat_frame_preprocess_layer_batch_cam`` (include/splat_hip_layers_cam.h).  The object holds ONE ``FrameBatch`` of ``frames_per_batch`` frames for
     geometry, binning and sort (the batch's composited row is never used) and the sums ``num`` [N, D] / ``den`` [N].
 
     ``add(times, maps, pixel_weight=None)`` accumulates over any number of calls; ``result()`` returns
     ``(feature [N, D] = where(den > 0, num / den, 0), weight [N] = den)``; ``refine`` runs the least-squares fit from a start."""
 
     def __init__(self, model, clock, extr: Tensor, W: int, H: int, D: int, frames_per_batch: int = 8, capacity: Optional[int] = None,
-                 cubic_layout: Optional[int] = None, nearest: float = 0.01, extent: float = 1.3):
+                 cubic_layout: Optional[int] = None, nearest: float = 0.01, extent: float = 1.3, intr: Optional[Tensor] = None):
         from .layers import _params
         from .tracking import _NAMES, _cull_args
         p, layout = _params(model, None, cubic_layout, need_shs=False)
@@ -151,6 +154,8 @@ class FeatureLift:
                 raise ValueError(f"model {k} does not hold {n} values (N = {N} Gaussians, {I} spline segments)")
         if not isinstance(extr, Tensor) or tuple(extr.shape) not in ((4, 4), (3, 4)):
             raise ValueError("extr must be one camera, [4, 4] or [3, 4]")
+        if intr is not None and (not isinstance(intr, Tensor) or intr.dtype != torch.float32 or tuple(intr.shape) != (4,)):
+            raise ValueError("intr must be None or one pinhole camera, float32 (fx, fy, cx, cy) [4] (per-frame cameras: add(...))")
         src = model if isinstance(model, dict) else {k: getattr(model, k) for k in _NAMES}
         self.model_requires_grad = any(isinstance(src.get(k), Tensor) and src[k].requires_grad for k in _NAMES)
         dev = pos.device
@@ -163,7 +168,10 @@ class FeatureLift:
         self.nearest, self.extent = _cull_args(nearest, extent)
         self.p = {k: L.need(p[k], k) for k in _NAMES}
         self.extr = _extr12(extr.detach())
-        self.fb = FrameBatch(self.F, N, W, H, 1, dev, capacity=None if capacity is None else int(capacity))
+        # the default camera as a call takes one: None without ``intr`` (the one orthographic camera: the core entry point)
+        self.camera = None if intr is None else (extr.detach().to(dev).contiguous(), intr.detach().to(dev).contiguous())
+        self.fb = FrameBatch(self.F, N, W, H, 1, dev, capacity=None if capacity is None else int(capacity),
+                             records=False)     # forward only: the lift keeps its own ("lift", "rec") records
         self.opa_t = torch.empty(N, 1, dtype=torch.float32, device=dev)
         self.num = torch.zeros(N, D, dtype=torch.float32, device=dev)
         self.den = torch.zeros(N, dtype=torch.float32, device=dev)
@@ -171,28 +179,49 @@ class FeatureLift:
         self.regrows = 0            # batches binned again after their pairs outgrew the capacity
 
     # ------------------------------------------------------------------
-    def _batches(self, times: Sequence[float]):
-        """(first frame, frames, the batch's F frame times: a short last batch repeats its last frame)"""
+    def _batches(self, times: Sequence[float], cams=None):
+        """(first frame, frames, the batch's F frame times: a short last batch repeats its last frame, the batch's ``_Camera``
+        -- None without ``cams``, the result of ``_cameras``)"""
         times = [float(t) for t in times]
         T, F = len(times), self.F
         for b0 in range(0, T, F):
             n = min(F, T - b0)
-            yield b0, n, tuple(times[min(b0 + i, T - 1)] for i in range(F))
+            cam = None
+            if cams is not None:
+                from .frames import _Camera
+                e, i_ = cams
+                cam = _Camera(e[b0:b0 + F] if e.dim() == 3 else e, i_[b0:b0 + F] if i_ is not None and i_.dim() == 2 else i_, F)
+            yield b0, n, tuple(times[min(b0 + i, T - 1)] for i in range(F)), cam
 
-    def _geometry(self, times: tuple, checked: bool) -> None:
+    def _cameras(self, T: int, extr, intr):
+        """the cameras of a call over T frame times, padded like the frame times: None for the one orthographic camera of the
+        constructor, else (extr, intr) on the device with per-frame tensors of ceil(T / F) * F rows"""
+        if extr is None and intr is None and self.camera is None:
+            return None
+        from .views import _clip_cameras, _padded
+        e = extr if extr is not None else (self.camera[0] if self.camera is not None else self.extr)
+        i_ = intr if intr is not None else (self.camera[1] if self.camera is not None else None)
+        e, i_ = _clip_cameras(e, i_, T, self.fb.dev, "T")
+        pidx = torch.tensor(_padded(T, self.F), device=self.fb.dev)
+        return e.index_select(0, pidx) if e.dim() == 3 else e, i_.index_select(0, pidx) if i_ is not None and i_.dim() == 2 else i_
+
+    def _geometry(self, times: tuple, checked: bool, cam=None) -> None:
         """the batch's preprocess, binning and sort.  ``checked``: a batch whose tile-Gaussian pairs outgrow the pair capacity
         is binned again with a larger one -- nothing is ever folded in from truncated lists (one host synchronisation per batch
-        reads the pair counts)"""
+        reads the pair counts).  ``cam``: the batch's ``_Camera``; None: the one orthographic camera of the constructor"""
         from .dynamics import frame_table
         fb, lib, st, p = self.fb, L.lib(), L.stream(), self.p
         tab = self._tables.get(times)
         if tab is None:
             tab = self._tables[times] = frame_table(self.clock, list(times), fb.dev)
         fb._begin_forward()
-        L.check(lib.splat_frame_preprocess_layer_batch(
+        # one orthographic camera: the core entry point; the cameras of a call: its twin of include/splat_hip_layers_cam.h
+        pre = lib.splat_frame_preprocess_layer_batch if cam is None else lib.splat_frame_preprocess_layer_batch_cam
+        L.check(pre(
             self.F, self.N, self.N, self.N, 0, self.I, L.ptr(tab), L.ptr(None),
             L.ptr(p["position"]), L.ptr(p["pos_cubic_node"]), self.layout, L.ptr(p["rotation"]), L.ptr(p["rot_poly_feat"]),
-            L.ptr(p["rot_fourier_feat"]), L.ptr(p["opacity"]), L.ptr(p["scaling"]), L.ptr(self.extr), self.W, self.H,
+            L.ptr(p["rot_fourier_feat"]), L.ptr(p["opacity"]), L.ptr(p["scaling"]),
+            L.ptr(self.extr) if cam is None else ctypes.byref(cam.struct()), self.W, self.H,
             self.nearest, self.extent, L.ptr(None), L.ptr(None), 1.0, 0, L.ptr(fb.uv), L.ptr(fb.depth),
             L.ptr(fb.conic), L.ptr(fb.radius), L.ptr(self.opa_t), st))
         while True:
@@ -225,11 +254,14 @@ class FeatureLift:
         return times, maps, pixel_weight
 
     @torch.no_grad()
-    def add(self, times: Sequence[float], maps: Tensor, pixel_weight: Optional[Tensor] = None) -> "FeatureLift":
-        """accumulate ``num`` / ``den`` over the frames ``times`` with the maps ``maps`` [F, D, H, W] (``pixel_weight`` [F, H, W])"""
+    def add(self, times: Sequence[float], maps: Tensor, pixel_weight: Optional[Tensor] = None, extr: Optional[Tensor] = None,
+            intr: Optional[Tensor] = None) -> "FeatureLift":
+        """accumulate ``num`` / ``den`` over the frames ``times`` with the maps ``maps`` [F, D, H, W] (``pixel_weight`` [F, H, W]);
+        ``extr`` / ``intr``: the cameras the frames were taken by (one, or one per frame time) in place of the default camera"""
         times, maps, pixel_weight = self._inputs(times, maps, pixel_weight)
-        for b0, n, bt in self._batches(times):
-            self._geometry(bt, checked=True)
+        cams = self._cameras(len(times), extr, intr)
+        for b0, n, bt, cam in self._batches(times, cams):
+            self._geometry(bt, checked=True, cam=cam)
             self._lift(n, maps[b0:b0 + n], None if pixel_weight is None else pixel_weight[b0:b0 + n], self.num, self.den)
         return self
 
@@ -271,14 +303,16 @@ class FeatureLift:
 
     @torch.no_grad()
     def gradient(self, times: Sequence[float], maps: Tensor, feature: Tensor, pixel_weight: Optional[Tensor] = None,
-                 _checked: bool = True) -> Tuple[Tensor, Tensor]:
-        """(d loss / d feature [N, D], loss [1]) of ``loss = 1/2 sum pw (A f - maps)^2`` over the frames ``times``"""
+                 _checked: bool = True, extr: Optional[Tensor] = None, intr: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        """(d loss / d feature [N, D], loss [1]) of ``loss = 1/2 sum pw (A f - maps)^2`` over the frames ``times`` (``extr`` /
+        ``intr``: the call's cameras, as in ``add``)"""
         times, maps, pixel_weight = self._inputs(times, maps, pixel_weight)
+        cams = self._cameras(len(times), extr, intr)
         feature = self._feature(feature)
         grad = torch.zeros(self.N, self.D, dtype=torch.float32, device=self.fb.dev)
         loss = torch.zeros(1, dtype=torch.float32, device=self.fb.dev)
-        for b0, n, bt in self._batches(times):
-            self._geometry(bt, checked=_checked)
+        for b0, n, bt, cam in self._batches(times, cams):
+            self._geometry(bt, checked=_checked, cam=cam)
             self._gradient_batch(n, feature, maps[b0:b0 + n], None if pixel_weight is None else pixel_weight[b0:b0 + n], grad, loss)
         return grad, loss
 
@@ -289,12 +323,14 @@ class FeatureLift:
 
     @torch.no_grad()
     def refine(self, times: Sequence[float], maps: Tensor, feature: Tensor, iters: int, lr: float = 0.01,
-               pixel_weight: Optional[Tensor] = None, betas=(0.9, 0.999), eps: float = 1e-8) -> Tuple[Tensor, Tensor]:
+               pixel_weight: Optional[Tensor] = None, betas=(0.9, 0.999), eps: float = 1e-8, extr: Optional[Tensor] = None,
+               intr: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
         """(feature [N, D], loss history [iters]): ``iters`` Adam steps on ``1/2 sum pw (A f - maps)^2`` from ``feature`` (the
         lifted start).  Per iteration and chunk: the forward A f (background 0), one elementwise residual, the lift kernel as
         A^T; then the project's Adam launch on [N, D].  ``history[i]`` is the loss of iteration i's feature, before its step; it
         stays on the device, and nothing synchronises with the host inside the loop (the pair capacity is settled in one pass
-        over the batches before it).  Forward-only with respect to the model: refused when a model tensor requires grad."""
+        over the batches before it).  Forward-only with respect to the model: refused when a model tensor requires grad.
+        ``extr`` / ``intr``: the call's cameras, as in ``add``."""
         if self.model_requires_grad:
             raise ValueError("refine is forward-only with respect to the model: detach the model tensors that require grad")
         if isinstance(iters, bool) or int(iters) != iters or int(iters) < 1:
@@ -308,9 +344,9 @@ class FeatureLift:
         times, maps, pixel_weight = self._inputs(times, maps, pixel_weight)
         f = self._feature(feature).clone()
         lib, dev = L.lib(), self.fb.dev
-        batches = list(self._batches(times))
-        for _, _, bt in batches:                 # settles the pair capacity; a single batch keeps its lists for every iteration
-            self._geometry(bt, checked=True)
+        batches = list(self._batches(times, self._cameras(len(times), extr, intr)))
+        for _, _, bt, cam in batches:            # settles the pair capacity; a single batch keeps its lists for every iteration
+            self._geometry(bt, checked=True, cam=cam)
         m, v = torch.zeros_like(f), torch.zeros_like(f)
         grad = torch.empty_like(f)
         history = torch.zeros(int(iters), dtype=torch.float32, device=dev)
@@ -318,9 +354,9 @@ class FeatureLift:
         for it in range(int(iters)):
             grad.zero_()
             loss = history[it:it + 1]
-            for b0, n, bt in batches:
+            for b0, n, bt, cam in batches:
                 if len(batches) > 1:
-                    self._geometry(bt, checked=False)
+                    self._geometry(bt, checked=False, cam=cam)
                 self._gradient_batch(n, f, maps[b0:b0 + n], None if pixel_weight is None else pixel_weight[b0:b0 + n], grad, loss)
             L.check(lib.splat_adam_step(f.numel(), L.ptr(f), L.ptr(grad), L.ptr(m), L.ptr(v), 1, seg_end,
                                         seg_lr, betas[0], betas[1], eps, it + 1, 1.0, L.stream()))
@@ -328,11 +364,19 @@ class FeatureLift:
 
 
 def lift_features(model, clock, times: Sequence[float], extr: Tensor, W: int, H: int, maps: Tensor,
-                  pixel_weight: Optional[Tensor] = None, **opts) -> Tuple[Tensor, Tensor]:
+                  pixel_weight: Optional[Tensor] = None, intr: Optional[Tensor] = None, **opts) -> Tuple[Tensor, Tensor]:
     """The one-call form: (feature [N, D], weight [N]) of ``FeatureLift(model, clock, extr, W, H, D, **opts)`` after one ``add``
-    of the frames ``times`` with ``maps`` [F, D, H, W] and ``pixel_weight`` [F, H, W] (None: ones)."""
+    of the frames ``times`` with ``maps`` [F, D, H, W] and ``pixel_weight`` [F, H, W] (None: ones).  ``extr`` [4,4] / [3,4] or
+    one camera per frame time [T,4,4] / [T,3,4]; ``intr`` None, [4] or [T,4]: the pinhole camera."""
     W, H = int(W), int(H)
     if W < 1 or H < 1:
         raise ValueError("W and H must be >= 1")
-    _, D = _check_maps(maps, pixel_weight, len(list(times)), None, W, H)
-    return FeatureLift(model, clock, extr, W, H, D, **opts).add(times, maps, pixel_weight).result()
+    times = list(times)
+    _, D = _check_maps(maps, pixel_weight, len(times), None, W, H)
+    per_frame = isinstance(extr, Tensor) and extr.dim() == 3 and extr.shape[0] >= 1
+    if not (per_frame or intr is not None):
+        return FeatureLift(model, clock, extr, W, H, D, **opts).add(times, maps, pixel_weight).result()
+    from .views import _clip_cameras
+    _clip_cameras(extr, intr, len(times), extr.device if isinstance(extr, Tensor) else "cpu", "T")     # before any GPU work
+    lift = FeatureLift(model, clock, extr[0] if per_frame else extr, W, H, D, **opts)
+    return lift.add(times, maps, pixel_weight, extr=extr, intr=intr).result()

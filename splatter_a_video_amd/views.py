@@ -220,7 +220,7 @@ class _Clip:
         self.F, self.W, self.H, self.K = int(frames_per_batch), int(W), int(H), int(K)
         self.nearest, self.extent = float(nearest), float(extent)
         self.fb = FrameBatch(self.F, int(pos.shape[0]), self.W, self.H, sum(self.widths), self.dev,
-                             capacity=None if capacity is None else int(capacity))
+                             capacity=None if capacity is None else int(capacity), records=False)      # forward only
         self.regrows = 0            # batches rendered again after their pairs outgrew the capacity
 
     def batch(self, times, extr: Tensor, intr: Optional[Tensor]):
@@ -250,11 +250,39 @@ def _padded(T: int, F: int) -> List[int]:
     return [min(i, T - 1) for i in range(((T + F - 1) // F) * F)]     # a short last batch repeats the last frame
 
 
+def _no_layers_with(K, wide, who: str) -> None:
+    if int(K) != 0 or wide is not None:
+        raise ValueError(f"{who}: neither contributor ids (K > 0) nor wide= is built for layered scenes (layers=)")
+
+
+def _layered_clip(model, clock, layers, W, H, sets, frames_per_batch, nearest, extent, bg, shs, cubic_layout, capacity, extr):
+    """the ``layers.LayeredClip`` of a viewed layered scene and its set names: the model and the ``sets`` default of ``_Clip``
+    (``_video_sets``), the clip's batches and regrow rule; ``extr``: the call's cameras (the clip's default is the first)"""
+    from .layers import LayeredClip, _params
+    p, layout = _params(model, shs, cubic_layout, need_shs=sets is None)
+    if not isinstance(model, dict) and "mask_attribute" not in p and isinstance(getattr(model, "mask_attribute", None), Tensor):
+        p["mask_attribute"] = model.mask_attribute
+    if sets is None:
+        if not (isinstance(p["shs"], Tensor) and p["shs"].is_cuda):
+            raise ValueError("the model must hold CUDA (ROCm) tensors (there is no CPU path)")
+        sets = _video_sets(p, bg)
+    sets = [dict(s_) for s_ in sets]
+    names = [s_.pop("name", None) or f"set{i}" for i, s_ in enumerate(sets)]
+    if len(set(names)) != len(names) or any(n_ in ("wide", "gs_idx") for n_ in names):
+        raise ValueError(f"set names must be distinct and none of 'wide', 'gs_idx': {names}")
+    one = extr[0] if isinstance(extr, Tensor) and extr.dim() == 3 and extr.shape[0] >= 1 else extr
+    if isinstance(one, Tensor) and isinstance(p["position"], Tensor):
+        one = one.to(p["position"].device)
+    clip = LayeredClip(p, clock, layers, one, W, H, sets, frames_per_batch, cubic_layout=layout, nearest=nearest, extent=extent,
+                       capacity=capacity)
+    return clip, names
+
+
 @torch.no_grad()
 def render_views(model, clock, times, extr: Tensor, W: int, H: int, intr: Optional[Tensor] = None, sets=None,
                  frames_per_batch: int = 8, K: int = 0, nearest: float = 0.01, extent: float = 1.3, bg: float = 1.0,
                  shs: Optional[Tensor] = None, cubic_layout: Optional[int] = None, capacity: Optional[int] = None,
-                 wide: Optional[dict] = None, stats: Optional[dict] = None) -> Dict[str, Tensor]:
+                 wide: Optional[dict] = None, stats: Optional[dict] = None, layers=None) -> Dict[str, Tensor]:
     """The clip at the frame times ``times`` (fractional times: the interpolated clip) seen from ``extr``: one world-to-camera
     matrix [4,4] for the whole clip (``render_video``) or one per time [T,4,4] (``orbit_cameras``: the novel-view clip).
     ``intr`` None: the orthographic camera of the video renderer; (fx, fy, cx, cy) as [4] or [T,4]: the pinhole camera
@@ -270,11 +298,27 @@ def render_views(model, clock, times, extr: Tensor, W: int, H: int, intr: Option
     measured on the first batch) is never returned: the capacity is raised and the batch rendered again (one host
     synchronisation per batch reads the pair counts; ``stats["regrows"]`` counts them).  One orthographic camera runs the
     single-camera kernel of the training path; per-frame cameras and the pinhole camera a kernel of their own, whose conic may
-    differ from the former's in the last bit."""
+    differ from the former's in the last bit.
+
+    ``layers``: a list of ``layers.Layer`` -- the clip is the LAYERED scene (an object removed, duplicated, moved or resized)
+    seen from these cameras: a ``layers.LayeredClip`` with the same ``sets`` default, batches, regrow rule and ``stats``, a set's
+    feature indexed by source Gaussian.  Neither ``K > 0`` nor ``wide=`` is built for layered scenes."""
     times = [float(t) for t in times]
     T = len(times)
     if T < 1:
         raise ValueError("a clip needs at least one frame time")
+    if layers is not None:
+        _no_layers_with(K, wide, "render_views")
+        from .layers import clip_layer_inputs
+        clip_layer_inputs(layers, times)
+        if isinstance(extr, Tensor):
+            _clip_cameras(extr, intr, T, extr.device, "T")                   # before any GPU work
+        lclip, names = _layered_clip(model, clock, layers, W, H, sets, frames_per_batch, nearest, extent, bg, shs, cubic_layout,
+                                     capacity, extr)
+        out = dict(zip(names, lclip.render(times, extr, intr)))
+        if stats is not None:
+            stats.update(regrows=lclip.regrows, capacity=lclip.fb.capacity, frame_batch_bytes=lclip.fb.memory_bytes())
+        return out
     clip = _Clip(model, clock, W, H, sets, frames_per_batch, K, nearest, extent, bg, shs, cubic_layout, capacity, wide)
     extr, intr = _clip_cameras(extr, intr, T, clip.dev, "T")
     F = clip.F
@@ -303,7 +347,7 @@ def render_views(model, clock, times, extr: Tensor, W: int, H: int, intr: Option
 def render_stereo(model, clock, times, W: int, H: int, cameras: Optional[Tensor] = None, intr: Optional[Tensor] = None,
                   mode="optimized", frames_per_batch: int = 8, nearest: float = 0.01, extent: float = 1.3, bg: float = 1.0,
                   shs: Optional[Tensor] = None, cubic_layout: Optional[int] = None, capacity: Optional[int] = None,
-                  return_eyes: bool = False):
+                  return_eyes: bool = False, layers=None):
     """The reference's stereo clip (:1158-1261): every frame time of ``times`` from the two eyes ``cameras`` ([2,4,4] world to
     camera; None: ``stereo_cameras()``), mixed into an anaglyph by ``mode`` (a name of ``ANAGLYPH`` or a 3 x 6 tensor); uint8
     [T,H,W,3].  ``intr`` None: orthographic eyes; [4]: pinhole eyes.
@@ -312,7 +356,8 @@ def render_stereo(model, clock, times, W: int, H: int, cameras: Optional[Tensor]
     the right eyes, so that each eye's images are one dense block --: the frame table repeats every time, one batch evaluates
     the model for both eyes, and one launch mixes the batch's images into bytes.  Only the colours are composited.
     ``return_eyes``: also return the two eyes' float images [T,3,H,W] (left, right).  Batches and the pair capacity as in
-    ``render_views``."""
+    ``render_views``.  ``layers``: a list of ``layers.Layer`` -- the stereo clip of the layered scene; each layer's times and
+    per-frame deltas are repeated for the two eyes the way the clip's times are."""
     times = [float(t) for t in times]
     T = len(times)
     if T < 1:
@@ -325,24 +370,40 @@ def render_stereo(model, clock, times, W: int, H: int, cameras: Optional[Tensor]
     p, layout = _params(model, shs, cubic_layout, need_shs=True)
     if not (isinstance(p["shs"], Tensor) and p["shs"].is_cuda):
         raise ValueError("the model must hold CUDA (ROCm) tensors (there is no CPU path)")
-    clip = _Clip(p, clock, W, H, _video_sets(p, bg)[:1], frames_per_batch, 0, nearest, extent, bg, None, layout, capacity, None)
-    cams = stereo_cameras(device=clip.dev) if cameras is None else cameras
-    cams, intr = _clip_cameras(cams, intr, 2, clip.dev, "eyes")
+    dev = p["shs"].device
+    lt = ld = None
+    if layers is not None:
+        from .layers import LayeredClip, clip_layer_inputs
+        _, lt, ld = clip_layer_inputs(layers, times)
+        # (the clip's default camera is never used: every batch is rendered under the two eyes)
+        clip = LayeredClip(p, clock, layers, torch.eye(4, device=dev), W, H, _video_sets(p, bg)[:1], frames_per_batch,
+                           cubic_layout=layout, nearest=nearest, extent=extent, capacity=capacity)
+    else:
+        clip = _Clip(p, clock, W, H, _video_sets(p, bg)[:1], frames_per_batch, 0, nearest, extent, bg, None, layout, capacity, None)
+    cams = stereo_cameras(device=dev) if cameras is None else cameras
+    cams, intr = _clip_cameras(cams, intr, 2, dev, "eyes")
     if cams.dim() != 3:
         raise ValueError("cameras must hold the two eyes: [2, 4, 4] or [2, 3, 4]")
     if intr is not None and intr.dim() != 1:
         raise ValueError("render_stereo: intr is one (fx, fy, cx, cy) for both eyes")
     h = clip.F // 2
     eyes = cams.repeat_interleave(h, dim=0).contiguous()          # [L x h, R x h]
-    out = torch.empty(T, H, W, 3, dtype=torch.uint8, device=clip.dev)
+    out = torch.empty(T, H, W, 3, dtype=torch.uint8, device=dev)
     left = right = None
     if return_eyes:
-        left, right = (torch.empty(T, 3, H, W, dtype=torch.float32, device=clip.dev) for _ in range(2))
+        left, right = (torch.empty(T, 3, H, W, dtype=torch.float32, device=dev) for _ in range(2))
     padded = _padded(T, h)
     for b0 in range(0, T, h):
         n = min(h, T - b0)
-        bt = [times[i] for i in padded[b0:b0 + h]]
-        rgb = clip.batch(bt + bt, eyes, intr)[0]                  # [2h,3,H,W]: the whole row of the batch, dense
+        idx = padded[b0:b0 + h]
+        bt = [times[i] for i in idx]
+        if layers is not None:                                    # each layer's times and deltas: left block, then right block
+            from .frames import _Camera
+            rgb = clip._render_batch([tuple(t_[i] for i in idx) * 2 for t_ in lt],
+                                     [None if d is None else d[idx + idx].contiguous().to(dev) for d in ld],
+                                     _Camera(eyes, intr, clip.F))
+        else:
+            rgb = clip.batch(bt + bt, eyes, intr)[0]              # [2h,3,H,W]: the whole row of the batch, dense
         _present(rgb[:n], rgb[h:h + n], mix, out=out[b0:b0 + n])
         if return_eyes:
             left[b0:b0 + n].copy_(rgb[:n])

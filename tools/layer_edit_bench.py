@@ -130,7 +130,7 @@ stat = lambda v: {"median_ms_per_frame": round(float(np.median(v)), 3), "min": r
 rec = {"bench": "layer_edit", **stamp(), "build_id": L.build_id(), "device": torch.cuda.get_device_name(0), "gaussians": N, "W": W, "H": H,
        "clip_frames": T, "frames_per_batch": args.frames_per_batch, "foreground": S, "Q": Q, "delay": DELAY, "scale": SCALE,
        "max_pairs_per_frame": int(clip.fb.check()), "regrows": clip.regrows, "frame_batch_bytes": clip.fb.memory_bytes(),
-       "pair_record_bytes": int(clip.fb.pair_records.numel() * 4), "routes_worst_share_outside_image_rule": worst,
+       "pair_record_bytes": 0 if clip.fb.pair_records is None else int(clip.fb.pair_records.numel() * 4), "routes_worst_share_outside_image_rule": worst,
        "legs": {name: stat(v) for name, v in ms.items()}}
 rec["per_frame_over_layered"] = round(rec["legs"]["per_frame"]["median_ms_per_frame"] / rec["legs"]["layered"]["median_ms_per_frame"], 3)
 # per-kernel times of one more layered clip from the library's own events (a pass of its own)
