@@ -20,30 +20,32 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPLAT_LIB_PATH") or os.path.join(_HERE, "libsplat_hip.so")
 _lib: Optional[ctypes.CDLL] = None
 
+
+def _load(file: str, base=None):
+    return _abi.load(os.path.join(_HERE, os.pardir, "include", file), base)
+
+
 # the header is the only place a prototype, a struct or a constant of the ABI is written (_abi.py reads it)
-HEADER = _abi.load(os.path.join(_HERE, os.pardir, "include", "splat_hip.h"))
-ABI_VERSION = HEADER.defines["SPLAT_ABI_VERSION"]
+CORE = ("splat_hip.h", "SPLAT_ABI_VERSION", "splat_abi_version")
+HEADER = _load(CORE[0])
+ABI_VERSION = HEADER.defines[CORE[1]]
 MAX_SOURCES = HEADER.defines["SPLAT_MAX_SOURCES"]
 SYMBOLS = list(HEADER.functions)
 FeatureSource = HEADER.structs["splat_feature_source_t"]
 # entry points added after the core header was frozen: a header of their own (it includes the core header for its handles and
-# structs), the same library, a version of their own
-VIEWS_HEADER = _abi.load(os.path.join(_HERE, os.pardir, "include", "splat_hip_views.h"), HEADER)
-VIEWS_ABI_VERSION = VIEWS_HEADER.defines["SPLAT_VIEWS_ABI_VERSION"]
-VIEWS_SYMBOLS = list(VIEWS_HEADER.functions)
-# the second extension (training under those cameras).  It includes the views header, which brings no handle or struct of its
-# own: the names its prototypes use are the core header's
-VIEWS_GRAD_HEADER = _abi.load(os.path.join(_HERE, os.pardir, "include", "splat_hip_views_grad.h"), HEADER)
-VIEWS_GRAD_ABI_VERSION = VIEWS_GRAD_HEADER.defines["SPLAT_VIEWS_GRAD_ABI_VERSION"]
-VIEWS_GRAD_SYMBOLS = list(VIEWS_GRAD_HEADER.functions)
-# the third extension (the camera gradients of a dynamic batch), on the core header's names like the two before it
-CAMERA_GRAD_HEADER = _abi.load(os.path.join(_HERE, os.pardir, "include", "splat_hip_camera_grad.h"), HEADER)
-CAMERA_GRAD_ABI_VERSION = CAMERA_GRAD_HEADER.defines["SPLAT_CAMERA_GRAD_ABI_VERSION"]
-CAMERA_GRAD_SYMBOLS = list(CAMERA_GRAD_HEADER.functions)
-# the fourth extension (layered scenes -- layer editing, feature lifting -- under those cameras), on the core header's names too
-LAYERS_CAM_HEADER = _abi.load(os.path.join(_HERE, os.pardir, "include", "splat_hip_layers_cam.h"), HEADER)
-LAYERS_CAM_ABI_VERSION = LAYERS_CAM_HEADER.defines["SPLAT_LAYERS_CAM_ABI_VERSION"]
-LAYERS_CAM_SYMBOLS = list(LAYERS_CAM_HEADER.functions)
+# structs and brings none of its own: the names its prototypes use are the core header's), the same library, a version of their
+# own.  One row per extension: (file name, version define, version function) -- the cameras per frame and the pinhole camera of a
+# dynamic batch; training under those cameras; the camera gradients of a dynamic batch; layered scenes (layer editing, feature
+# lifting) under those cameras
+EXTENSIONS = (("splat_hip_views.h", "SPLAT_VIEWS_ABI_VERSION", "splat_views_abi_version"),
+              ("splat_hip_views_grad.h", "SPLAT_VIEWS_GRAD_ABI_VERSION", "splat_views_grad_abi_version"),
+              ("splat_hip_camera_grad.h", "SPLAT_CAMERA_GRAD_ABI_VERSION", "splat_camera_grad_abi_version"),
+              ("splat_hip_layers_cam.h", "SPLAT_LAYERS_CAM_ABI_VERSION", "splat_layers_cam_abi_version"))
+_EXT = tuple(_load(file, HEADER) for file, _, _ in EXTENSIONS)
+VIEWS_HEADER, VIEWS_GRAD_HEADER, CAMERA_GRAD_HEADER, LAYERS_CAM_HEADER = _EXT
+VIEWS_ABI_VERSION, VIEWS_GRAD_ABI_VERSION, CAMERA_GRAD_ABI_VERSION, LAYERS_CAM_ABI_VERSION = (
+    h.defines[define] for h, (_, define, _) in zip(_EXT, EXTENSIONS))
+VIEWS_SYMBOLS, VIEWS_GRAD_SYMBOLS, CAMERA_GRAD_SYMBOLS, LAYERS_CAM_SYMBOLS = (list(h.functions) for h in _EXT)
 
 
 class SplatError(RuntimeError):
@@ -62,32 +64,19 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C splatter_a_video_amd/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in (list(HEADER.functions.items()) + list(VIEWS_HEADER.functions.items())
-                                          + list(VIEWS_GRAD_HEADER.functions.items())
-                                          + list(CAMERA_GRAD_HEADER.functions.items())
-                                          + list(LAYERS_CAM_HEADER.functions.items())):
-            fn = getattr(L, name, None)
-            if fn is None:
-                where = ("splat_hip_layers_cam.h" if name in LAYERS_CAM_HEADER.functions
-                         else "splat_hip_camera_grad.h" if name in CAMERA_GRAD_HEADER.functions
-                         else "splat_hip_views_grad.h" if name in VIEWS_GRAD_HEADER.functions
-                         else "splat_hip_views.h" if name in VIEWS_HEADER.functions else "splat_hip.h")
-                raise SplatError(f"{LIB_PATH} lacks {name} (include/{where}: the library is older than the headers); rebuild it")
-            fn.restype, fn.argtypes = restype, argtypes
-        if L.splat_abi_version() != ABI_VERSION:
-            raise SplatError(f"{LIB_PATH} has ABI version {L.splat_abi_version()}, include/splat_hip.h {ABI_VERSION}; rebuild it")
-        if L.splat_views_abi_version() != VIEWS_ABI_VERSION:
-            raise SplatError(f"{LIB_PATH} has views ABI version {L.splat_views_abi_version()}, include/splat_hip_views.h "
-                             f"{VIEWS_ABI_VERSION}; rebuild it")
-        if L.splat_views_grad_abi_version() != VIEWS_GRAD_ABI_VERSION:
-            raise SplatError(f"{LIB_PATH} has views-grad ABI version {L.splat_views_grad_abi_version()}, "
-                             f"include/splat_hip_views_grad.h {VIEWS_GRAD_ABI_VERSION}; rebuild it")
-        if L.splat_camera_grad_abi_version() != CAMERA_GRAD_ABI_VERSION:
-            raise SplatError(f"{LIB_PATH} has camera-grad ABI version {L.splat_camera_grad_abi_version()}, "
-                             f"include/splat_hip_camera_grad.h {CAMERA_GRAD_ABI_VERSION}; rebuild it")
-        if L.splat_layers_cam_abi_version() != LAYERS_CAM_ABI_VERSION:
-            raise SplatError(f"{LIB_PATH} has layers-cam ABI version {L.splat_layers_cam_abi_version()}, "
-                             f"include/splat_hip_layers_cam.h {LAYERS_CAM_ABI_VERSION}; rebuild it")
+        headers = ((CORE, HEADER),) + tuple(zip(EXTENSIONS, _EXT))
+        for (file, _, _), h in headers:
+            for name, (restype, argtypes) in h.functions.items():
+                fn = getattr(L, name, None)
+                if fn is None:
+                    raise SplatError(f"{LIB_PATH} lacks {name} (include/{file}: the library is older than the headers); rebuild it")
+                fn.restype, fn.argtypes = restype, argtypes
+        for (file, define, version), h in headers:
+            have = getattr(L, version)()
+            if have != h.defines[define]:
+                kind = "-".join(define.split("_")[1:-2]).lower()      # "", "views", "views-grad", ...
+                raise SplatError(f"{LIB_PATH} has {kind + ' ' if kind else ''}ABI version {have}, include/{file} "
+                                 f"{h.defines[define]}; rebuild it")
         _lib = L
     return _lib
 

@@ -16,6 +16,7 @@ No CPU fallback.
 from __future__ import annotations
 
 import ctypes
+import inspect
 import os
 import warnings
 from typing import Dict, Optional
@@ -258,6 +259,27 @@ class FrameBatch:
         self.pair_records = torch.empty(F_ * capacity * self.ncp, dtype=torch.float32, device=dev) if self.records else None
         self.cull_flags = torch.empty(F_, capacity, dtype=torch.int32, device=dev)   # the forward's cull, for the backward
 
+    def _grow(self, pairs: int) -> None:
+        """size the pair buffers for a fullest frame of ``pairs`` tile-Gaussian pairs: the one place of the capacity rule"""
+        self._reserve(int(pairs * self.slack) + 1024)
+
+    def _bin_and_sort_fitting(self, opacity: Tensor, checked: bool = True) -> int:
+        """``_bin_and_sort`` until the lists fit (the forward-only clips: the sort drops surplus pairs, and nothing may be
+        composited or folded in from truncated lists): ``check()`` reads the pair counts -- one host synchronisation per batch --
+        and a batch that outgrew the capacity is binned again with a larger one.  Returns the number of regrows.  ``checked``
+        False: one pass, nothing is read."""
+        regrows = 0
+        while True:
+            self._bin_and_sort(opacity)
+            if not checked:
+                return regrows
+            try:
+                self.check()
+                return regrows
+            except L.SplatError:
+                self._grow(int(self.pairs.max().item()))
+                regrows += 1
+
     def _set_buffer(self, key, numel: int) -> Tensor:
         """scratch of the multi-set backward (pair records / packed records per feature set), kept across steps"""
         cache = self.__dict__.setdefault("_set_buffers", {})
@@ -371,9 +393,9 @@ class FrameBatch:
         if measure:
             m = int((self.pairs if F_ == 1 else self.pairs.max()).item())
             if self.capacity is None or m > self.capacity:
-                self._reserve(int(m * self.slack) + 1024)
+                self._grow(m)
         elif self.capacity is None:    # first batch: size the pair buffers (the only host sync of the object's life)
-            self._reserve(int(int(self.pairs.max().item()) * self.slack) + 1024)
+            self._grow(int(self.pairs.max().item()))
         cap = self.capacity
         if reach:
             L.check(lib.splat_bin_sort_batch_reach(
@@ -429,7 +451,7 @@ class FrameBatch:
         if self.capacity is None:      # first batch: size the pair buffers (the only host sync of the object's life)
             L.check(lib.splat_frames_count(ctypes.byref(self._struct(xyz, scales, uquats, opacity, feature, offsets, cam, bg,
                                                                      nearest, extent))))
-            self._reserve(int(int(self.pairs.max().item()) * self.slack) + 1024)
+            self._grow(int(self.pairs.max().item()))
         out = torch.empty(self.F, self.C, self.H, self.W, dtype=torch.float32, device=self.dev)
         b = self._struct(xyz, scales, uquats, opacity, feature, offsets, cam, bg, nearest, extent)
         b.out = out.data_ptr()
@@ -646,7 +668,7 @@ class FrameBatch:
                                  "with detached tensors")
             with torch.no_grad():
                 st = _dynamic_sets_forward(self, position, pos_cubic_node, rotation, opacity, scaling, rot_poly_feat,
-                                           rot_fourier_feat, None, cam, tab, int(clock.interval_num), int(cubic_layout), meta,
+                                           rot_fourier_feat, cam, tab, int(clock.interval_num), int(cubic_layout), meta,
                                            int(K), float(nearest), float(extent), parts, None, wd,
                                            tuple(feats) + ((wide["feature"],) if wd is not None else ()))
             return st["outputs"]
@@ -704,107 +726,39 @@ class FrameBatch:
         return res
 
 
-class _RenderDynamic(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, position, cubic, rotation, opacity, scaling, feature, rot_poly, rot_fourier, extr, tab, fb, I, layout, bg,
-                nearest, extent, sink, cg=None, cg_extr=None, cg_intr=None):
-        P, F = fb.P, fb.F
-        ctx.cg = cg                                           # camera_grad=True: cg_extr / cg_intr are the camera leaves
-        position = _points(position, "position", 3)
-        rotation = _points(rotation, "rotation", 4)
-        scaling = _points(scaling, "scaling", 3)
-        opacity = L.need(opacity, "opacity")
-        cubic = L.need(cubic, "pos_cubic_node")
-        feature = _points(feature, "feature", fb.C)
-        rot_poly, rot_fourier = L.need(rot_poly, "rot_poly_feat"), L.need(rot_fourier, "rot_fourier_feat")
-        if cubic.numel() != P * 4 * I * 3 or rot_poly.numel() != P * 16 or rot_fourier.numel() != P * 32 or opacity.numel() != P:
-            raise ValueError("parameter shapes do not match the batch (P Gaussians, I spline segments)")
-        if position.shape[0] != P or rotation.shape[0] != P or scaling.shape[0] != P or feature.shape[0] != P:
-            raise ValueError(f"the batch was built for {P} Gaussians")
-        cam = extr if isinstance(extr, _Camera) else None     # cameras per frame / the pinhole camera (differentiable=True)
-        extr_c = _extr12(extr) if cam is None else cam.extr
-        lib, st = L.lib(), L.stream()
-        W, H, C = fb.W, fb.H, fb.C
-        ctx.gen = fb._begin_forward()
-        opa_t = torch.empty(P, 1, dtype=torch.float32, device=fb.dev)
-        if cam is None:
-            L.check(lib.splat_frame_preprocess_forward_batch(
-                F, P, I, L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly),
-                L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c), W, H, nearest, extent,
-                L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius), L.ptr(opa_t), st))
-        else:
-            L.check(lib.splat_frame_preprocess_forward_batch_cam(
-                F, P, I, L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly),
-                L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), ctypes.byref(cam.struct()), W, H, nearest, extent,
-                L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius), L.ptr(opa_t), st))
-        ctx.cam, ctx.cam_versions = cam, (_versions(*cam.tensors()) if cam is not None else ())
-        fb._bin_and_sort(opa_t)
-        cap = fb.capacity
-        out = torch.empty(F, C, H, W, dtype=torch.float32, device=fb.dev)
-        L.check(lib.splat_alpha_blending_forward_batch(
-            F, P, C, L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opa_t), 0, L.ptr(feature),
-            0, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), cap, bg, L.ptr(None), W,
-            H, 0, 0, L.ptr(out), L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(None), L.ptr(fb.pack),
-            L.ptr(fb.cull_flags), st))
-        ctx.fb, ctx.meta, ctx.sink = fb, (I, layout, bg), sink
-        ctx.save_for_backward(position, cubic, rotation, opacity, scaling, feature, rot_poly, rot_fourier, extr_c, tab)
-        return out
-
-    @staticmethod
-    def backward(ctx, dL_dout):
-        fb: FrameBatch = ctx.fb
-        fb._check_generation(ctx.gen)
-        position, cubic, rotation, opacity, scaling, feature, rot_poly, rot_fourier, extr_c, tab = ctx.saved_tensors
-        I, layout, bg = ctx.meta
-        sink = ctx.sink or {}
-        g = L.need(dL_dout, "dL_dout")
-        lib, st = L.lib(), L.stream()
-        F, P, W, H, C, cap = fb.F, fb.P, fb.W, fb.H, fb.C, fb.capacity
-        from .gs.raster_ops import _debug_T_front
-        L.check(lib.splat_alpha_blending_backward_batch(
-            F, P, C, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), cap, bg, W, H,
-            L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(g), 1 if fb.want_abs else 0, L.ptr(fb.slot_sorted),
-            L.ptr(fb.pair_records), L.ptr(fb.pack), L.ptr(fb.cull_flags), L.ptr(_debug_T_front(F * H, W, g.device)), st))
-        like = {"position": position, "pos_cubic_node": cubic, "rotation": rotation, "opacity": opacity, "scaling": scaling,
-                "feature": feature}
-        need = dict(zip(like, ctx.needs_input_grad[:6]))
-        bufs = {k: (sink[k] if k in sink else (torch.zeros_like(v) if need[k] else None)) for k, v in like.items()}
-        gauss_backward, cam_arg = _gauss_backward_entry(ctx, "splat_frames_gauss_backward_dynamic", extr_c)
-        L.check(gauss_backward(
-            F, P, I, C, W, H, cap, 1 if fb.want_abs else 0,
-            L.ptr(fb.pair_records), L.ptr(fb.goff), L.ptr(fb.radius), L.ptr(tab), L.ptr(position), L.ptr(cubic), layout,
-            L.ptr(rotation), L.ptr(rot_poly), L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), cam_arg,
-            L.ptr(bufs["position"]), L.ptr(bufs["pos_cubic_node"]), L.ptr(bufs["rotation"]), L.ptr(bufs["opacity"]),
-            L.ptr(bufs["scaling"]), L.ptr(bufs["feature"]), L.ptr(fb.tap), L.ptr(fb.abs_tap), L.ptr(fb.radii_max), st))
-        ret = tuple(None if (k in sink or bufs[k] is None) else bufs[k] for k in like)
-        d_cam = (None, None)
-        if ctx.cg is not None:
-            d_cam = ctx.cg.backward(fb, fb.pair_records, fb.ncp, -1, tab, position, cubic, layout, I, rotation, rot_poly,
-                                    rot_fourier, scaling, ctx.needs_input_grad[18], ctx.needs_input_grad[19])
-        return ret + (None,) * 12 + d_cam
+def _args_of(forward, *leaves) -> tuple:
+    """the argument table of an autograd node: the names of its ``forward``'s parameters behind ``ctx`` (a ``*feats`` last, so that
+    ``index("feats")`` is the number of fixed arguments), read ONCE, at import.  Every position and every ``None`` padding of the
+    node's ``backward`` comes from this table: an argument added to a ``forward`` moves them with it.  ``leaves``: the
+    differentiable parameters, which lead the table in this order (a ``backward`` returns their gradients first)."""
+    names = tuple(inspect.signature(forward.__func__).parameters)[1:]
+    assert names[:len(leaves)] == leaves, (names, leaves)
+    return names
 
 
-def _gauss_backward_entry(ctx, name: str, extr_c: Tensor):
-    """the Gaussian-side entry point of a dynamic batch's backward and its camera argument: the core header's with the one
-    orthographic camera's 12 floats, or its ``_cam`` twin (include/splat_hip_views_grad.h) with the forward's cameras"""
-    if ctx.cam is None:
-        return getattr(L.lib(), name), L.ptr(extr_c)
-    _check_versions(ctx.cam_versions, "a camera tensor")
-    return getattr(L.lib(), name + "_cam"), ctypes.byref(ctx.cam.struct())
+def _entry(name: str, cam: Optional[_Camera], extr: Tensor):
+    """an entry point that takes a camera, and its camera argument: the core header's ``name`` with the 12 floats ``extr`` of the
+    one orthographic camera when ``cam`` is None, else its ``_cam`` twin (include/splat_hip_views.h, splat_hip_views_grad.h,
+    splat_hip_layers_cam.h) with the ``_Camera``'s struct"""
+    if cam is None:
+        return getattr(L.lib(), name), L.ptr(extr)
+    return getattr(L.lib(), name + "_cam"), ctypes.byref(cam.struct())
 
 
-def _dynamic_sets_forward(fb, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr, cam, tab, I, layout, meta,
-                          K, nearest, extent, parts, pts, wd, feats):
-    """the forward of ``render_dynamic_sets``: batched dynamic preprocess, binning and sort, the sets' blends, the wide and the
-    sparse set.  ``cam`` None: the one orthographic camera ``extr`` (the differentiable path: ``_RenderDynamicSets``); a
-    ``_Camera``: cameras per frame and / or the pinhole camera through splat_frame_preprocess_forward_batch_cam (forward only
-    by default; ``_RenderDynamicSets`` with a ``_Camera`` in place of ``extr`` is the differentiable path under them)."""
-    P, F = fb.P, fb.F
-    pfeat = wfeat = None
-    if wd is not None:        # the wide set's feature rides last
-        feats, wfeat = feats[:-1], L.need(feats[-1], "wide feature")
-    if pts is not None:       # the sparse set's feature rides behind the sets' tensors
-        feats, pfeat = feats[:-1], feats[-1]
+def _backward_entry(ctx, name: str, extr_c: Tensor):
+    """``_entry`` for the Gaussian-side backward of a dynamic batch: it re-reads the forward's cameras through raw pointers, so
+    they must not have been edited in place since"""
+    if ctx.cam is not None:
+        _check_versions(ctx.cam_versions, "a camera tensor")
+    return _entry(name, ctx.cam, extr_c)
+
+
+def _dynamic_geometry(fb, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr, tab, I, layout, nearest, extent):
+    """the geometry of a dynamic batch's forward: the raw parameters normalised and checked against the batch, the batched dynamic
+    preprocess (splat_frame_preprocess_forward_batch[_cam]) under ``extr`` -- the tensor of the one orthographic camera, or a
+    ``_Camera`` (cameras per frame / the pinhole camera) --, tile binning and sort.  Returns (the seven normalised parameters in the order of the arguments, ``opa_t`` [P, 1]:
+    the activated opacity, ``extr_c``: the camera tensor a backward saves, the generation of this forward)."""
+    P = fb.P
     position = _points(position, "position", 3)
     rotation = _points(rotation, "rotation", 4)
     scaling = _points(scaling, "scaling", 3)
@@ -815,25 +769,97 @@ def _dynamic_sets_forward(fb, position, cubic, rotation, opacity, scaling, rot_p
         raise ValueError("parameter shapes do not match the batch (P Gaussians, I spline segments)")
     if position.shape[0] != P or rotation.shape[0] != P or scaling.shape[0] != P:
         raise ValueError(f"the batch was built for {P} Gaussians")
+    cam = extr if isinstance(extr, _Camera) else None
+    extr_c = _extr12(extr) if cam is None else cam.extr
+    gen = fb._begin_forward()
+    opa_t = torch.empty(P, 1, dtype=torch.float32, device=fb.dev)
+    preprocess, cam_arg = _entry("splat_frame_preprocess_forward_batch", cam, extr_c)
+    L.check(preprocess(
+        fb.F, P, I, L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly),
+        L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), cam_arg, fb.W, fb.H, nearest, extent,
+        L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius), L.ptr(opa_t), L.stream()))
+    fb._bin_and_sort(opa_t)
+    return (position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier), opa_t, extr_c, gen
+
+
+class _RenderDynamic(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, position, cubic, rotation, opacity, scaling, feature, rot_poly, rot_fourier, extr, tab, fb, I, layout, bg,
+                nearest, extent, sink, cg=None, cg_extr=None, cg_intr=None):
+        F, P, W, H, C = fb.F, fb.P, fb.W, fb.H, fb.C
+        ctx.cg = cg                                           # camera_grad=True: cg_extr / cg_intr are the camera leaves
+        feature = _points(feature, "feature", C)
+        if feature.shape[0] != P:
+            raise ValueError(f"the batch was built for {P} Gaussians")
+        (position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier), opa_t, extr_c, ctx.gen = _dynamic_geometry(
+            fb, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr, tab, I, layout, nearest, extent)
+        ctx.cam = cam = extr if isinstance(extr, _Camera) else None     # cameras per frame / the pinhole camera (differentiable=True)
+        ctx.cam_versions = _versions(*cam.tensors()) if cam is not None else ()
+        out = torch.empty(F, C, H, W, dtype=torch.float32, device=fb.dev)
+        L.check(L.lib().splat_alpha_blending_forward_batch(
+            F, P, C, L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opa_t), 0, L.ptr(feature),
+            0, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), fb.capacity, bg, L.ptr(None), W,
+            H, 0, 0, L.ptr(out), L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(None), L.ptr(fb.pack),
+            L.ptr(fb.cull_flags), L.stream()))
+        ctx.fb, ctx.meta, ctx.sink = fb, (I, layout, bg), sink
+        ctx.save_for_backward(position, cubic, rotation, opacity, scaling, feature, rot_poly, rot_fourier, extr_c, tab)
+        return out
+
+    ARGS = _args_of(forward, "position", "cubic", "rotation", "opacity", "scaling", "feature")
+    CG_EXTR, CG_INTR = ARGS.index("cg_extr"), ARGS.index("cg_intr")
+
+    @staticmethod
+    def backward(ctx, dL_dout):
+        A, fb = _RenderDynamic, ctx.fb
+        fb._check_generation(ctx.gen)
+        position, cubic, rotation, opacity, scaling, feature, rot_poly, rot_fourier, extr_c, tab = ctx.saved_tensors
+        I, layout, bg = ctx.meta
+        sink, nig = ctx.sink or {}, ctx.needs_input_grad
+        g = L.need(dL_dout, "dL_dout")
+        lib, st = L.lib(), L.stream()
+        F, P, W, H, C, cap = fb.F, fb.P, fb.W, fb.H, fb.C, fb.capacity
+        from .gs.raster_ops import _debug_T_front
+        L.check(lib.splat_alpha_blending_backward_batch(
+            F, P, C, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range), cap, bg, W, H,
+            L.ptr(fb.final_T), L.ptr(fb.ncontrib), L.ptr(g), 1 if fb.want_abs else 0, L.ptr(fb.slot_sorted),
+            L.ptr(fb.pair_records), L.ptr(fb.pack), L.ptr(fb.cull_flags), L.ptr(_debug_T_front(F * H, W, g.device)), st))
+        like = {"position": position, "pos_cubic_node": cubic, "rotation": rotation, "opacity": opacity, "scaling": scaling,
+                "feature": feature}
+        need = dict(zip(like, nig))                           # (the leaves lead the argument table)
+        bufs = {k: (sink[k] if k in sink else (torch.zeros_like(v) if need[k] else None)) for k, v in like.items()}
+        gauss_backward, cam_arg = _backward_entry(ctx, "splat_frames_gauss_backward_dynamic", extr_c)
+        L.check(gauss_backward(
+            F, P, I, C, W, H, cap, 1 if fb.want_abs else 0,
+            L.ptr(fb.pair_records), L.ptr(fb.goff), L.ptr(fb.radius), L.ptr(tab), L.ptr(position), L.ptr(cubic), layout,
+            L.ptr(rotation), L.ptr(rot_poly), L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), cam_arg,
+            L.ptr(bufs["position"]), L.ptr(bufs["pos_cubic_node"]), L.ptr(bufs["rotation"]), L.ptr(bufs["opacity"]),
+            L.ptr(bufs["scaling"]), L.ptr(bufs["feature"]), L.ptr(fb.tap), L.ptr(fb.abs_tap), L.ptr(fb.radii_max), st))
+        ret = [None] * len(A.ARGS)
+        ret[:len(like)] = [None if k in sink else bufs[k] for k in like]
+        if ctx.cg is not None:
+            ret[A.CG_EXTR], ret[A.CG_INTR] = ctx.cg.backward(
+                fb, fb.pair_records, fb.ncp, -1, tab, position, cubic, layout, I, rotation, rot_poly, rot_fourier, scaling,
+                nig[A.CG_EXTR], nig[A.CG_INTR])
+        return tuple(ret)
+
+
+def _dynamic_sets_forward(fb, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr, tab, I, layout, meta,
+                          K, nearest, extent, parts, pts, wd, feats):
+    """the forward of ``render_dynamic_sets``: the dynamic geometry (``_dynamic_geometry``), the sets' blends, the wide and the
+    sparse set.  ``extr``: the tensor of the one orthographic camera (the differentiable path: ``_RenderDynamicSets``), or a
+    ``_Camera``: cameras per frame and / or the pinhole camera (forward only by default; ``_RenderDynamicSets`` with a
+    ``_Camera`` is the differentiable path under them)."""
+    P, F = fb.P, fb.F
+    pfeat = wfeat = None
+    if wd is not None:        # the wide set's feature rides last
+        feats, wfeat = feats[:-1], L.need(feats[-1], "wide feature")
+    if pts is not None:       # the sparse set's feature rides behind the sets' tensors
+        feats, pfeat = feats[:-1], feats[-1]
     sources = _has_sources(parts)
     if not sources:
         _check_set_features(meta, feats, P)
-    extr_c = _extr12(extr) if cam is None else cam.extr
-    lib, st = L.lib(), L.stream()
-    W, H = fb.W, fb.H
-    gen = fb._begin_forward()
-    opa_t = torch.empty(P, 1, dtype=torch.float32, device=fb.dev)
-    if cam is None:
-        L.check(lib.splat_frame_preprocess_forward_batch(
-            F, P, I, L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly),
-            L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), L.ptr(extr_c), W, H, nearest, extent,
-            L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius), L.ptr(opa_t), st))
-    else:
-        L.check(lib.splat_frame_preprocess_forward_batch_cam(
-            F, P, I, L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly),
-            L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), ctypes.byref(cam.struct()), W, H, nearest, extent,
-            L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius), L.ptr(opa_t), st))
-    fb._bin_and_sort(opa_t)
+    geo, opa_t, extr_c, gen = _dynamic_geometry(fb, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr, tab,
+                                                I, layout, nearest, extent)
     if sources:
         feats = tuple(_source_tensor(t, pf, F, P) for t, (_, pf) in zip(feats, [p_ for pp in parts for p_ in pp]))
         out, gs_idx, blend = _blend_sources_forward(fb, meta, parts, feats, opa_t, K)
@@ -850,28 +876,85 @@ def _dynamic_sets_forward(fb, position, cubic, rotation, opacity, scaling, rot_p
     if wd is not None:
         wide_out = (_wide_forward(fb, wd, wfeat, opa_t, 0),)
         feats = tuple(feats) + (wfeat,)
+    return dict(gen=gen, blend=blend, sources=sources, opa_t=opa_t, saved=geo + (extr_c, tab) + tuple(feats),
+                outputs=tuple(_split_row(out, meta)) + wide_out + sparse + (gs_idx,))
+
+
+def _split_row(out: Tensor, meta) -> list:
+    """the composited row [F, C, H, W] by the sets' widths: one image [F, c, H, W] per set (views)"""
     imgs, c0 = [], 0
     for w, _, _, _ in meta:
         w = 1 if w == "depth" else w
         imgs.append(out[:, c0:c0 + w])
         c0 += w
-    return dict(gen=gen, blend=blend, sources=sources, opa_t=opa_t,
-                saved=(position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr_c, tab) + tuple(feats),
-                outputs=tuple(imgs) + wide_out + sparse + (gs_idx,))
+    return imgs
+
+
+def _side_backward(wanted: bool, sink: Optional[Tensor], feature: Tensor, run) -> tuple:
+    """the backward of a set beside the row (the wide set, the sparse set) whose output received a gradient: ``run(buffer)`` puts
+    its geometry terms into the pair records and ADDS its feature's gradient to ``buffer`` -- the ``sink``, else zeros of the
+    feature's shape when autograd wants it (``wanted``), else None.  Returns the 1-tuple for autograd: a sink keeps its
+    gradient from it."""
+    buf, ret = sink, None
+    want = wanted or sink is not None
+    if want and buf is None:
+        buf = ret = torch.zeros(feature.shape, dtype=torch.float32, device=feature.device)
+    run(buf if want else None)
+    return (ret,)
+
+
+def _group_grads(meta, plan, feats, grads, wanted):
+    """the feature gradients of a one-pass plan whose sets are one tensor each: (per tensor zeros of its shape, or None where its
+    set received no gradient or autograd does not want it (``wanted``: per tensor); the ``c0 / cn / d_feature / stride`` arguments
+    of the three routing groups for the Gaussian-side entry points)"""
+    group_of = _set_groups(meta)
+    fi, dfe, dfs, strides = 0, [], [0, 0, 0], [0, 0, 0]
+    for si, (w, _, _, _) in enumerate(meta):
+        if w == "depth":
+            continue
+        dfeat = torch.zeros_like(feats[fi]) if grads[si] is not None and wanted[fi] else None
+        dfe.append(dfeat)
+        dfs[group_of[si]], strides[group_of[si]] = (0 if dfeat is None else dfeat.data_ptr()), int(feats[fi].shape[1])
+        fi += 1
+    i3 = ctypes.c_int32 * 3
+    return tuple(dfe), (i3(*plan[0]), i3(*plan[1]), (ctypes.c_void_p * 3)(*dfs), i3(*strides))
+
+
+def _source_grads(meta, parts, feats, grads, wanted, fsink):
+    """the feature gradients of a row by SOURCES -- a shared tensor's is the sum over the frames, a per-frame tensor gets every
+    frame's own --: (per tensor zeros of its shape for autograd, or None; the ``n, table`` arguments of the Gaussian-side entry
+    point: the sources whose gradient autograd (``wanted``: per tensor) or a ``grad_sink["feature:k"]`` buffer receives)"""
+    table = (L.FeatureSource * L.MAX_SOURCES)()
+    dfe, n, fi, c0 = [], 0, 0, 0
+    for si, ((w, _, _, _), pp) in enumerate(zip(meta, parts)):
+        if w == "depth":
+            c0 += 1
+            continue
+        for cn, per_frame in pp:
+            t, buf, ret = feats[fi], fsink.get(f"feature:{fi}"), None
+            need = grads[si] is not None and (wanted[fi] or buf is not None)
+            if need and buf is None:
+                buf = ret = torch.zeros(t.shape, dtype=torch.float32, device=t.device)
+            dfe.append(ret)
+            if need:
+                table[n].c0, table[n].cn, table[n].feature = c0, cn, t.data_ptr()
+                table[n].d_feature = buf.data_ptr()
+                table[n].frame_stride = int(buf.stride(0)) if per_frame else 0
+                n += 1
+            c0 += cn
+            fi += 1
+    return tuple(dfe), (n, table)
 
 
 class _RenderDynamicSets(torch.autograd.Function):
-    N_FIXED = 24      # arguments in front of the feature tensors (the last two: the camera leaves of camera_grad=True)
-
     @staticmethod
     def forward(ctx, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr, tab, fb, I, layout, meta, K,
                 nearest, extent, sink, parts, fsink, pts, wd, cg, cg_extr, cg_intr, *feats):
-        cam = extr if isinstance(extr, _Camera) else None     # cameras per frame / the pinhole camera (differentiable=True)
-        ctx.cg = cg
-        st = _dynamic_sets_forward(fb, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier,
-                                   extr if cam is None else None, cam, tab, I, layout, meta, K, nearest, extent, parts, pts,
-                                   wd, feats)
-        ctx.cam, ctx.cam_versions = cam, (_versions(*cam.tensors()) if cam is not None else ())
+        ctx.cg = cg                                           # camera_grad=True: cg_extr / cg_intr are the camera leaves
+        st = _dynamic_sets_forward(fb, position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr, tab, I, layout,
+                                   meta, K, nearest, extent, parts, pts, wd, feats)
+        ctx.cam = cam = extr if isinstance(extr, _Camera) else None     # cameras per frame / the pinhole camera (differentiable=True)
+        ctx.cam_versions = _versions(*cam.tensors()) if cam is not None else ()
         ctx.gen, ctx.blend = st["gen"], st["blend"]
         ctx.fb, ctx.meta, ctx.sink, ctx.geo = fb, meta, sink, (I, layout)
         ctx.parts, ctx.fsink, ctx.sources = parts, (fsink or {}), st["sources"]
@@ -884,19 +967,19 @@ class _RenderDynamicSets(torch.autograd.Function):
             ctx.mark_non_differentiable(st["outputs"][-1])
         return st["outputs"]
 
+    ARGS = _args_of(forward, "position", "cubic", "rotation", "opacity", "scaling")
+    CG_EXTR, CG_INTR, FEATS = ARGS.index("cg_extr"), ARGS.index("cg_intr"), ARGS.index("feats")
+
     @staticmethod
     def backward(ctx, *grads):
-        fb: FrameBatch = ctx.fb
+        A, fb = _RenderDynamicSets, ctx.fb
         fb._check_generation(ctx.gen)
         position, cubic, rotation, opacity, scaling, rot_poly, rot_fourier, extr_c, tab = ctx.saved_tensors[:9]
         feats = ctx.saved_tensors[9:]
-        meta, sink = ctx.meta, (ctx.sink or {})
+        meta, sink, nig = ctx.meta, (ctx.sink or {}), ctx.needs_input_grad
         I, layout = ctx.geo
-        lib, st = L.lib(), L.stream()
         F, P, W, H, C, cap = fb.F, fb.P, fb.W, fb.H, fb.C, fb.capacity
-        dev = fb.dev
-        widths = ctx.blend["widths"]
-        pts, pfeat, g_pts, d_pts = ctx.pts, None, None, ()
+        pts, pfeat, g_pts = ctx.pts, None, None
         wd, wfeat, g_wide = ctx.wd, None, None
         if wd is not None:
             feats, wfeat = feats[:-1], feats[-1]
@@ -904,105 +987,40 @@ class _RenderDynamicSets(torch.autograd.Function):
         if pts is not None:
             feats, pfeat = feats[:-1], feats[-1]
             g_pts = grads[len(meta) + (1 if wd is not None else 0)]
-            d_pts = (None,)
-
-        def wide_backward(rec):
-            # the wide set's chunks: their geometry terms into the pair records, their feature sums into the feature's gradient
-            if g_wide is None:
-                return (None,) if wd is not None else ()
-            want = ctx.needs_input_grad[NF + len(feats) + (1 if pts is not None else 0)] or wd["sink"] is not None
-            buf, ret = wd["sink"], None
-            if want and buf is None:
-                buf = ret = torch.zeros(wfeat.shape, dtype=torch.float32, device=dev)
-            _wide_backward(fb, wd, wfeat, ctx.opa_t, 0, g_wide, rec, buf if want else None)
-            return (ret,)
-
-        def sparse_backward(rec):
-            # the sparse set's gradient: into the pair records the tile backward has just written, before the Gaussian-side walk
-            if g_pts is None:
-                return (None,) if pts is not None else ()
-            want = ctx.needs_input_grad[NF + len(feats)] or pts["sink"] is not None
-            buf, ret = pts["sink"], None
-            if want and buf is None:
-                buf = ret = torch.zeros(pfeat.shape, dtype=torch.float32, device=dev)
-            _points_backward(fb, pts, pfeat, ctx.opa_t, g_pts, rec, buf if want else None)
-            return (ret,)
         like = {"position": position, "pos_cubic_node": cubic, "rotation": rotation, "opacity": opacity, "scaling": scaling}
         bufs = {k: (sink[k] if k in sink else torch.zeros_like(v)) for k, v in like.items()}
-        c0s, cns, bgs, depth_ch, tap_set = _one_pass_plan(meta, widths, C)
-        want_abs = 1 if (tap_set is not None and fb.want_abs) else 0
-        NF = _RenderDynamicSets.N_FIXED
-        has_tap = tap_set is not None
-
-        def camera_backward(rec):
-            # the camera leaves (camera_grad=True): from the records every backward above has filled
-            if ctx.cg is None:
-                return (None, None)
-            return ctx.cg.backward(fb, rec, int(lib.splat_blend_sets_pair_stride(C)), 12 + depth_ch if depth_ch >= 0 else -1, tab,
-                                   position, cubic, layout, I, rotation, rot_poly, rot_fourier, scaling,
-                                   ctx.needs_input_grad[NF - 2], ctx.needs_input_grad[NF - 1])
+        plan = _one_pass_plan(meta, ctx.blend["widths"], C)
+        depth_ch, has_tap = plan[3], plan[4] is not None
+        want_abs = 1 if (has_tap and fb.want_abs) else 0
+        wanted = nig[A.FEATS:]                                # per feature tensor: the sets' tensors, the sparse, the wide set's
+        # the sets' tensors: by SOURCES (a feature list, a per-frame tensor), or one tensor per routing group -- two entry points
+        # that differ in these arguments alone
         if ctx.sources:
-            # the row by SOURCES: a shared tensor's gradient is the sum over the frames, a per-frame tensor gets every frame's own
-            rec = _blend_sets_backward_one_pass(fb, meta, ctx.blend, grads[:len(meta)], ctx.opa_t, 0, want_abs)
-            d_pts = sparse_backward(rec)
-            d_wide = wide_backward(rec)
-            table = (L.FeatureSource * L.MAX_SOURCES)()
-            dfe, n, fi, c0 = [], 0, 0, 0
-            for si, ((w, _, _, _), pp) in enumerate(zip(meta, ctx.parts)):
-                if w == "depth":
-                    c0 += 1
-                    continue
-                for cn, per_frame in pp:
-                    t = feats[fi]
-                    key = f"feature:{fi}"
-                    need = grads[si] is not None and (ctx.needs_input_grad[NF + fi] or key in ctx.fsink)
-                    buf = ctx.fsink.get(key)
-                    ret = None
-                    if need and buf is None:
-                        buf = ret = torch.zeros(t.shape, dtype=torch.float32, device=dev)
-                    dfe.append(ret)
-                    if need:
-                        table[n].c0, table[n].cn, table[n].feature = c0, cn, t.data_ptr()
-                        table[n].d_feature = buf.data_ptr()
-                        table[n].frame_stride = int(buf.stride(0)) if per_frame else 0
-                        n += 1
-                    c0 += cn
-                    fi += 1
-            gauss_backward, cam_arg = _gauss_backward_entry(ctx, "splat_frames_gauss_backward_dynamic_sources", extr_c)
-            L.check(gauss_backward(
-                F, P, I, C, W, H, cap, L.ptr(rec), L.ptr(fb.goff),
-                L.ptr(fb.radius), L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly),
-                L.ptr(rot_fourier), L.ptr(opacity), L.ptr(scaling), cam_arg, L.ptr(bufs["position"]),
-                L.ptr(bufs["pos_cubic_node"]), L.ptr(bufs["rotation"]), L.ptr(bufs["opacity"]), L.ptr(bufs["scaling"]), n,
-                table, depth_ch, L.ptr(fb.tap if has_tap else None),
-                L.ptr(fb.abs_tap if (has_tap and want_abs) else None), L.ptr(fb.radii_max if has_tap else None), st))
-            ret = tuple(None if k in sink else bufs[k] for k in like)
-            return ret + (None,) * (NF - 7) + camera_backward(rec) + tuple(dfe) + d_pts + d_wide
-        group_of = _set_groups(meta)
-        fi, dfe, dfs, strides = 0, [], [None, None, None], [0, 0, 0]
-        for si, (w, _, _, _) in enumerate(meta):
-            if w == "depth":
-                continue
-            need = grads[si] is not None and ctx.needs_input_grad[NF + fi]
-            dfeat = torch.zeros_like(feats[fi]) if need else None
-            dfe.append(dfeat)
-            dfs[group_of[si]], strides[group_of[si]] = dfeat, int(feats[fi].shape[1])
-            fi += 1
+            name, (dfe, features) = "splat_frames_gauss_backward_dynamic_sources", _source_grads(meta, ctx.parts, feats, grads, wanted,
+                                                                                                   ctx.fsink)
+        else:
+            name, (dfe, features) = "splat_frames_gauss_backward_dynamic_sets", _group_grads(meta, plan, feats, grads, wanted)
         rec = _blend_sets_backward_one_pass(fb, meta, ctx.blend, grads[:len(meta)], ctx.opa_t, 0, want_abs)
-        d_pts = sparse_backward(rec)
-        d_wide = wide_backward(rec)
-        i3 = ctypes.c_int32 * 3
-        p3 = (ctypes.c_void_p * 3)(*[0 if d is None else d.data_ptr() for d in dfs])
-        gauss_backward, cam_arg = _gauss_backward_entry(ctx, "splat_frames_gauss_backward_dynamic_sets", extr_c)
+        # the sparse, then the wide set: into the pair records the tile backward has just written, before the Gaussian-side walk
+        d_pts = () if pts is None else (None,) if g_pts is None else _side_backward(
+            wanted[len(feats)], pts["sink"], pfeat, lambda buf: _points_backward(fb, pts, pfeat, ctx.opa_t, g_pts, rec, buf))
+        d_wide = () if wd is None else (None,) if g_wide is None else _side_backward(
+            wanted[len(feats) + len(d_pts)], wd["sink"], wfeat, lambda buf: _wide_backward(fb, wd, wfeat, ctx.opa_t, 0, g_wide, rec, buf))
+        gauss_backward, cam_arg = _backward_entry(ctx, name, extr_c)
         L.check(gauss_backward(
             F, P, I, C, W, H, cap, L.ptr(rec), L.ptr(fb.goff), L.ptr(fb.radius),
             L.ptr(tab), L.ptr(position), L.ptr(cubic), layout, L.ptr(rotation), L.ptr(rot_poly), L.ptr(rot_fourier),
             L.ptr(opacity), L.ptr(scaling), cam_arg, L.ptr(bufs["position"]), L.ptr(bufs["pos_cubic_node"]),
-            L.ptr(bufs["rotation"]), L.ptr(bufs["opacity"]), L.ptr(bufs["scaling"]), i3(*c0s), i3(*cns), p3, i3(*strides),
+            L.ptr(bufs["rotation"]), L.ptr(bufs["opacity"]), L.ptr(bufs["scaling"]), *features,
             depth_ch, L.ptr(fb.tap if has_tap else None), L.ptr(fb.abs_tap if (has_tap and want_abs) else None),
-            L.ptr(fb.radii_max if has_tap else None), st))
-        ret = tuple(None if k in sink else bufs[k] for k in like)
-        return ret + (None,) * (NF - 7) + camera_backward(rec) + tuple(dfe) + d_pts + d_wide
+            L.ptr(fb.radii_max if has_tap else None), L.stream()))
+        ret = [None] * A.FEATS
+        ret[:len(like)] = [None if k in sink else bufs[k] for k in like]
+        if ctx.cg is not None:        # the camera leaves (camera_grad=True): from the records every backward above has filled
+            ret[A.CG_EXTR], ret[A.CG_INTR] = ctx.cg.backward(
+                fb, rec, int(L.lib().splat_blend_sets_pair_stride(C)), 12 + depth_ch if depth_ch >= 0 else -1, tab, position, cubic,
+                layout, I, rotation, rot_poly, rot_fourier, scaling, nig[A.CG_EXTR], nig[A.CG_INTR])
+        return tuple(ret) + dfe + d_pts + d_wide
 
 
 def _parse_points(points, sink, F, P):
@@ -1054,28 +1072,21 @@ def _points_backward(fb, pts, pfeat, opacity, g, rec, d_feature):
     if tuple(g.shape) != (Q, c):
         raise ValueError(f"the gradient of the sparse output must be [{Q}, {c}]")
     dfs = 0 if d_feature is None or not pts["per_frame"] else int(d_feature.stride(0))
+    lib, name, tail = L.lib(), "splat_alpha_blending_points_backward_batch", ()
     if pts["ordered"]:
         # no float atomic, every sum in a fixed order (runs in deterministic mode too): the batch's pair map and a pooled scratch
-        need = int(L.lib().splat_alpha_blending_points_backward_batch_ordered_scratch_bytes(
-            fb.F, c, fb.W, fb.H, Q, fb.capacity))
+        need = int(lib.splat_alpha_blending_points_backward_batch_ordered_scratch_bytes(fb.F, c, fb.W, fb.H, Q, fb.capacity))
         if need == 0:
             raise ValueError("the ordered sparse backward: sizes too large")
         scratch = fb._set_buffer(("points", "ordered"), (need + 3) // 4)
-        L.check(L.lib().splat_alpha_blending_points_backward_batch_ordered(
-            fb.F, fb.P, c, L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), 0, L.ptr(pfeat),
-            int(pfeat.stride(0)) if pts["per_frame"] else 0, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range),
-            fb.capacity, pts["bg"], fb.W, fb.H, Q, L.ptr(pts["offsets"]),
-            L.ptr(pts["points"]), L.ptr(pts["corner_T"]), L.ptr(pts["corner_n"]), L.ptr(g), L.ptr(fb.slot_sorted), L.ptr(rec),
-            int(L.lib().splat_blend_sets_pair_stride(fb.C)), 1 if pts["detach_opacity"] else 0, L.ptr(d_feature),
-            dfs, L.ptr(fb.goff), L.ptr(scratch), scratch.numel() * 4, L.stream()))
-        return
-    L.check(L.lib().splat_alpha_blending_points_backward_batch(
+        name, tail = name + "_ordered", (L.ptr(fb.goff), L.ptr(scratch), scratch.numel() * 4)
+    L.check(getattr(lib, name)(
         fb.F, fb.P, c, L.ptr(fb.uv), L.ptr(fb.conic), L.ptr(opacity), 0, L.ptr(pfeat),
         int(pfeat.stride(0)) if pts["per_frame"] else 0, L.ptr(fb.idx_sorted), L.ptr(fb.tile_range),
         fb.capacity, pts["bg"], fb.W, fb.H, Q, L.ptr(pts["offsets"]),
         L.ptr(pts["points"]), L.ptr(pts["corner_T"]), L.ptr(pts["corner_n"]), L.ptr(g), L.ptr(fb.slot_sorted), L.ptr(rec),
-        int(L.lib().splat_blend_sets_pair_stride(fb.C)), 1 if pts["detach_opacity"] else 0, L.ptr(d_feature),
-        dfs, L.stream()))
+        int(lib.splat_blend_sets_pair_stride(fb.C)), 1 if pts["detach_opacity"] else 0, L.ptr(d_feature),
+        dfs, *tail, L.stream()))
 
 
 def _parse_wide(wide, sink, P):
@@ -1404,33 +1415,39 @@ def _one_pass_plan(meta, widths, C):
     return c0s, cns, bgs, depth_ch, tap_set
 
 
+def _static_geometry(fb, xyz, scales, uquats, opacity, offsets, extr, intr):
+    """the static geometry of ``render`` / ``render_sets`` normalised and checked against the batch: (xyz, scales, uquats, opacity,
+    offsets [F, P, 3] or None, the batch's ``_Camera``); the opacity's size is the caller's check"""
+    xyz = _points(xyz, "xyz", 3)
+    scales = _points(scales, "scales", 3)
+    uquats = _points(uquats, "uquats", 4)
+    opacity = L.need(opacity, "opacity")
+    P, F = fb.P, fb.F
+    cam = _Camera(extr, intr, F)
+    if xyz.shape[0] != P or scales.shape[0] != P or uquats.shape[0] != P:
+        raise ValueError(f"the batch was built for {P} Gaussians")
+    off = L.need(offsets, "offsets") if offsets is not None else None
+    if off is not None and tuple(off.shape) != (F, P, 3):
+        raise ValueError(f"offsets must be [F={F}, P={P}, 3]")
+    if off is None and F > 1 and cam.extr_fs == 0:
+        raise ValueError("several frames of static Gaussians need per-frame offsets or per-frame cameras")
+    return xyz, scales, uquats, opacity, off, cam
+
+
 class _RenderSets(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, scales, uquats, opacity, offsets, extr, fb, meta, K, nearest, extent, sink, intr, wd, *feats):
         wfeat = None
         if wd is not None:        # the wide set's feature rides last
             feats, wfeat = feats[:-1], L.need(feats[-1], "wide feature")
-        xyz = _points(xyz, "xyz", 3)
-        scales = _points(scales, "scales", 3)
-        uquats = _points(uquats, "uquats", 4)
-        opacity = L.need(opacity, "opacity")
-        P, F = fb.P, fb.F
-        cam = _Camera(extr, intr, F)
-        if xyz.shape[0] != P or scales.shape[0] != P or uquats.shape[0] != P:
-            raise ValueError(f"the batch was built for {P} Gaussians")
-        if opacity.numel() != P:
+        xyz, scales, uquats, opacity, off, cam = _static_geometry(fb, xyz, scales, uquats, opacity, offsets, extr, intr)
+        if opacity.numel() != fb.P:
             # (the Gaussian-side backward sums the opacity gradient over the frames: a per-frame opacity [F,P,1] has no entry point)
-            raise ValueError(f"opacity must hold one value per Gaussian ({P}), shared by the frames; got {tuple(opacity.shape)}")
-        _check_set_features(meta, feats, P)
-        off = L.need(offsets, "offsets") if offsets is not None else None
-        if off is not None and tuple(off.shape) != (F, P, 3):
-            raise ValueError(f"offsets must be [F={F}, P={P}, 3]")
-        if off is None and F > 1 and cam.extr_fs == 0:
-            raise ValueError("several frames of static Gaussians need per-frame offsets or per-frame cameras")
+            raise ValueError(f"opacity must hold one value per Gaussian ({fb.P}), shared by the frames; got {tuple(opacity.shape)}")
+        _check_set_features(meta, feats, fb.P)
         ctx.gen = fb._begin_forward()
         fb._geometry(xyz, scales, uquats, off, cam, nearest, extent, opacity)
         op_fs = 0
-        C = fb.C
         out, gs_idx, ctx.blend = _blend_sets_forward(fb, meta, feats, opacity, op_fs, K)
         if wd is not None and ctx.blend["plan"] is None:
             raise ValueError("render_sets(wide=...) needs sets that fit the one-pass backward")
@@ -1444,26 +1461,25 @@ class _RenderSets(torch.autograd.Function):
             feats = tuple(feats) + (wfeat,)
         ctx.save_for_backward(xyz, scales, uquats, opacity, *feats)
         ctx.set_materialize_grads(False)
-        imgs, c0 = [], 0
-        for w, _, _, _ in meta:
-            w = 1 if w == "depth" else w
-            imgs.append(out[:, c0:c0 + w])
-            c0 += w
         if gs_idx is not None:
             ctx.mark_non_differentiable(gs_idx)
-            return tuple(imgs) + wide_out + (gs_idx,)
-        return tuple(imgs) + wide_out + (None,)
+        return tuple(_split_row(out, meta)) + wide_out + (gs_idx,)
+
+    LEAVES = ("xyz", "scales", "uquats", "opacity")
+    ARGS = _args_of(forward, *LEAVES)
+    FEATS = ARGS.index("feats")
+    PAD = (None,) * (FEATS - len(LEAVES))
 
     @staticmethod
     def backward(ctx, *grads):
-        fb: FrameBatch = ctx.fb
+        A, fb = _RenderSets, ctx.fb
         fb._check_generation(ctx.gen)
         xyz, scales, uquats, opacity = ctx.saved_tensors[:4]
         feats = ctx.saved_tensors[4:]
-        wd, wfeat, g_wide, d_wide = ctx.wd, None, None, ()
+        wd, wfeat, g_wide = ctx.wd, None, None
         if wd is not None:
             feats, wfeat = feats[:-1], feats[-1]
-            g_wide, d_wide = grads[len(ctx.meta)], (None,)
+            g_wide = grads[len(ctx.meta)]
         _check_versions(ctx.cam_versions, "a camera / offset tensor")
         camc = ctx.cam.struct(ctx.off)
         meta, sink = ctx.meta, (ctx.sink or {})
@@ -1473,46 +1489,29 @@ class _RenderSets(torch.autograd.Function):
         widths = ctx.blend["widths"]
         like = {"xyz": xyz, "scales": scales, "uquats": uquats, "opacity": opacity}
         bufs = {k: (sink[k] if k in sink else torch.zeros_like(v)) for k, v in like.items()}   # every set accumulates
-        dfe = []
+        ret = tuple(None if k in sink else bufs[k] for k in A.LEAVES)
+        wanted = ctx.needs_input_grad[A.FEATS:]               # per feature tensor: the sets' tensors, then the wide set's
         op_fs = 0
         from .gs.raster_ops import _debug_T_front
         plan = ctx.blend["plan"]
         if plan is not None:
             # the sets share the alpha / transmittance replay: ONE pass of the tile kernels and ONE Gaussian-side reduction
             # route dL/dalpha of every set where the reference's three autograd nodes would
-            c0s, cns, bgs, depth_ch, tap_set = plan
-            want_abs = 1 if (tap_set is not None and fb.want_abs) else 0
-            fi, dfs, strides = 0, [None, None, None], [0, 0, 0]
-            group_of = _set_groups(meta)
-            for si, (w, _, _, _) in enumerate(meta):
-                if w == "depth":
-                    continue
-                need = grads[si] is not None and ctx.needs_input_grad[14 + fi]
-                dfeat = torch.zeros_like(feats[fi]) if need else None
-                dfe.append(dfeat)
-                dfs[group_of[si]], strides[group_of[si]] = dfeat, int(feats[fi].shape[1])
-                fi += 1
+            depth_ch, has_tap = plan[3], plan[4] is not None
+            want_abs = 1 if (has_tap and fb.want_abs) else 0
+            dfe, features = _group_grads(meta, plan, feats, grads, wanted)
             rec = _blend_sets_backward_one_pass(fb, meta, ctx.blend, grads[:len(meta)], opacity, op_fs, want_abs)
-            if g_wide is not None:
-                # the wide set's chunks: their geometry terms into the pair records, their feature sums into the feature's gradient
-                want = ctx.needs_input_grad[14 + len(feats)] or wd["sink"] is not None
-                buf, wret = wd["sink"], None
-                if want and buf is None:
-                    buf = wret = torch.zeros(wfeat.shape, dtype=torch.float32, device=dev)
-                _wide_backward(fb, wd, wfeat, opacity, op_fs, g_wide, rec, buf if want else None)
-                d_wide = (wret,)
-            i3 = ctypes.c_int32 * 3
-            p3 = (ctypes.c_void_p * 3)(*[0 if d is None else d.data_ptr() for d in dfs])
-            has_tap = tap_set is not None
+            # the wide set's chunks: their geometry terms into the pair records, their feature sums into the feature's gradient
+            d_wide = () if wd is None else (None,) if g_wide is None else _side_backward(
+                wanted[len(feats)], wd["sink"], wfeat, lambda buf: _wide_backward(fb, wd, wfeat, opacity, op_fs, g_wide, rec, buf))
             L.check(lib.splat_frames_gauss_backward_static_sets_cam(
                 F, P, C, W, H, cap, L.ptr(rec), L.ptr(fb.goff), L.ptr(fb.radius),
                 L.ptr(xyz), L.ptr(scales), L.ptr(uquats), ctypes.byref(camc), 1, L.ptr(bufs["xyz"]), L.ptr(bufs["scales"]),
-                L.ptr(bufs["uquats"]), L.ptr(bufs["opacity"]), i3(*c0s), i3(*cns), p3, i3(*strides), depth_ch,
+                L.ptr(bufs["uquats"]), L.ptr(bufs["opacity"]), *features, depth_ch,
                 L.ptr(fb.tap if has_tap else None), L.ptr(fb.abs_tap if (has_tap and want_abs) else None),
                 L.ptr(fb.radii_max if has_tap else None), st))
-            ret = tuple(None if k in sink else bufs[k] for k in ("xyz", "scales", "uquats", "opacity"))
-            return ret + (None,) * 10 + tuple(dfe) + d_wide
-        row = ctx.blend["row"]
+            return ret + A.PAD + dfe + d_wide
+        row, dfe = ctx.blend["row"], []
         dL = torch.cat([(g if g is not None else torch.zeros(F, w, H, W, dtype=torch.float32, device=dev))
                         for g, w in zip(grads[:len(meta)], widths)], dim=1).contiguous()
         c0, fi = 0, 0
@@ -1521,7 +1520,7 @@ class _RenderSets(torch.autograd.Function):
             is_depth = w == "depth"
             dfeat = None
             if not is_depth:
-                dfeat = torch.zeros_like(feats[fi]) if g is not None and ctx.needs_input_grad[14 + fi] else None
+                dfeat = torch.zeros_like(feats[fi]) if g is not None and wanted[fi] else None
                 dfe.append(dfeat)
                 fi += 1
             if g is not None:
@@ -1541,29 +1540,16 @@ class _RenderSets(torch.autograd.Function):
                     1 if detach else 0, 0 if is_depth else -1, L.ptr(fb.tap if taps else None),
                     L.ptr(fb.abs_tap if (taps and want_abs) else None), L.ptr(fb.radii_max if taps else None), st))
             c0 += cn
-        ret = tuple(None if k in sink else bufs[k] for k in ("xyz", "scales", "uquats", "opacity"))
-        return ret + (None,) * 10 + tuple(dfe) + d_wide
+        return ret + A.PAD + tuple(dfe) + (() if wd is None else (None,))
 
 
 class _RenderFrames(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, scales, uquats, opacity, feature, offsets, extr, fb: FrameBatch, bg, nearest, extent, sink, intr=None):
-        xyz = _points(xyz, "xyz", 3)
-        scales = _points(scales, "scales", 3)
-        uquats = _points(uquats, "uquats", 4)
-        opacity = L.need(opacity, "opacity")
+        xyz, scales, uquats, opacity, off, cam = _static_geometry(fb, xyz, scales, uquats, opacity, offsets, extr, intr)
         feature = _points(feature, "feature", fb.C)
-        P, F = fb.P, fb.F
-        cam = _Camera(extr, intr, F)
-        if xyz.shape[0] != P or scales.shape[0] != P or uquats.shape[0] != P or opacity.numel() != P or feature.shape[0] != P:
-            raise ValueError(f"the batch was built for {P} Gaussians")
-        off = None
-        if offsets is not None:
-            off = L.need(offsets, "offsets")
-            if tuple(off.shape) != (F, P, 3):
-                raise ValueError(f"offsets must be [F={F}, P={P}, 3]")
-        elif F > 1 and cam.extr_fs == 0:
-            raise ValueError("several frames of static Gaussians need per-frame offsets or per-frame cameras")
+        if opacity.numel() != fb.P or feature.shape[0] != fb.P:
+            raise ValueError(f"the batch was built for {fb.P} Gaussians")
         ctx.gen = fb._begin_forward()
         out = fb._forward_onecall(xyz, scales, uquats, opacity, feature, off, cam, bg, nearest, extent)
         ctx.fb, ctx.bg, ctx.sink = fb, bg, sink
@@ -1572,9 +1558,13 @@ class _RenderFrames(torch.autograd.Function):
         ctx.save_for_backward(xyz, scales, uquats, opacity, feature)
         return out
 
+    LEAVES = ("xyz", "scales", "uquats", "opacity", "feature")
+    ARGS = _args_of(forward, *LEAVES)
+    PAD = (None,) * (len(ARGS) - len(LEAVES))
+
     @staticmethod
     def backward(ctx, dL_dout):
-        fb: FrameBatch = ctx.fb
+        A, fb = _RenderFrames, ctx.fb
         fb._check_generation(ctx.gen)
         xyz, scales, uquats, opacity, feature = ctx.saved_tensors
         _check_versions(ctx.cam_versions, "a camera / offset tensor")
@@ -1584,12 +1574,11 @@ class _RenderFrames(torch.autograd.Function):
         # one accumulate flag for the launch: with a sink in play the buffers autograd receives start from zero
         fresh = torch.zeros_like if sink else torch.empty_like
         bufs = {k: (sink[k] if k in sink else fresh(v)) for k, v in like.items()}
-        ret = tuple(None if k in sink else bufs[k] for k in ("xyz", "scales", "uquats", "opacity", "feature"))
         from .gs.raster_ops import _debug_T_front
         dbg = _debug_T_front(fb.F * fb.H, fb.W, g.device)
         fb._backward_onecall(g, xyz, scales, uquats, ctx.off, ctx.cam, ctx.bg, bufs, accumulate=bool(sink), dbg=dbg)
         fb._pending = False        # (frame_rasterization's pool: the batch's forward has had its backward)
-        return ret + (None,) * 8
+        return tuple(None if k in sink else bufs[k] for k in A.LEAVES) + A.PAD
 
 
 # ------------------------------------------------------------------ ONE frame behind one call per direction

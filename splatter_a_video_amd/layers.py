@@ -24,7 +24,6 @@ returns +-q up to rounding; the covariance does not see the sign.  Here the mode
 No CPU path, no gradients (the reference runs these edits under ``torch.no_grad()``)."""
 from __future__ import annotations
 
-import ctypes
 import math
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
@@ -307,30 +306,16 @@ class LayeredClip:
         times, lt, ld = clip_layer_inputs(self.layers, times)
         T = len(times)
         F, dev = self.F, self.fb.dev
-        padded = [min(i, T - 1) for i in range(((T + F - 1) // F) * F)]    # a short last batch repeats the last frame
-        cams = None
-        if extr is not None or intr is not None or self.camera is not None:
-            from .views import _clip_cameras
-            e = extr if extr is not None else (self.camera[0] if self.camera is not None else self.extr)
-            i_ = intr if intr is not None else (self.camera[1] if self.camera is not None else None)
-            e, i_ = _clip_cameras(e, i_, T, dev, "T_clip")
-            if e.dim() == 3 or (i_ is not None and i_.dim() == 2):
-                pidx = torch.tensor(padded, device=dev)
-                e = e.index_select(0, pidx) if e.dim() == 3 else e
-                i_ = i_.index_select(0, pidx) if i_ is not None and i_.dim() == 2 else i_
-            cams = (e, i_)
+        from .views import _batch_cameras, _padded
+        padded = _padded(T, F)
+        cams = _batch_cameras(extr, intr, self.camera or (self.extr, None), T, F, dev, "T_clip")
         deltas = [None if d is None else d[padded].contiguous().to(dev) for d in ld]
         outs = [torch.empty(T, w, self.H, self.W, dtype=torch.float32, device=dev) for w in self.widths]
         for b0 in range(0, T, F):
             idx = padded[b0:b0 + F]
             n = min(F, T - b0)
-            cam = None
-            if cams is not None:
-                from .frames import _Camera
-                e, i_ = cams
-                cam = _Camera(e[b0:b0 + F] if e.dim() == 3 else e, i_[b0:b0 + F] if i_ is not None and i_.dim() == 2 else i_, F)
             row = self._render_batch([tuple(t_[i] for i in idx) for t_ in lt], [None if d is None else d[b0:b0 + F] for d in deltas],
-                                     cam)
+                                     None if cams is None else cams[b0 // F])
             c0 = 0
             for o, w in zip(outs, self.widths):
                 o[b0:b0 + n].copy_(row[:n, c0:c0 + w])
@@ -338,7 +323,7 @@ class LayeredClip:
         return outs
 
     def _render_batch(self, layer_times, layer_deltas, cam=None) -> Tensor:
-        from .frames import _blend_sets_forward
+        from .frames import _blend_sets_forward, _entry
         fb, lib, st, p = self.fb, L.lib(), L.stream(), self.p
         F = self.F
         fb._begin_forward()
@@ -351,26 +336,16 @@ class LayeredClip:
                     F, self.N, self.S[li], self.I, L.ptr(tab), L.ptr(self.src[li]), L.ptr(p["position"]),
                     L.ptr(p["pos_cubic_node"]), self.layout, L.ptr(cen), L.ptr(self._scratch),
                     self._scratch.numel() * 8, st))
-            # one orthographic camera: the core entry point; the cameras of a call: its twin of include/splat_hip_layers_cam.h
-            pre = lib.splat_frame_preprocess_layer_batch if cam is None else lib.splat_frame_preprocess_layer_batch_cam
+            pre, cam_arg = _entry("splat_frame_preprocess_layer_batch", cam, self.extr)
             L.check(pre(
                 F, self.N, self.S[li], self.Q, self.q0[li], self.I, L.ptr(tab),
                 L.ptr(self.src[li]), L.ptr(p["position"]), L.ptr(p["pos_cubic_node"]), self.layout, L.ptr(p["rotation"]),
-                L.ptr(p["rot_poly_feat"]), L.ptr(p["rot_fourier_feat"]), L.ptr(p["opacity"]), L.ptr(p["scaling"]),
-                L.ptr(self.extr) if cam is None else ctypes.byref(cam.struct()),
+                L.ptr(p["rot_poly_feat"]), L.ptr(p["rot_fourier_feat"]), L.ptr(p["opacity"]), L.ptr(p["scaling"]), cam_arg,
                 self.W, self.H, self.nearest, self.extent, L.ptr(cen), L.ptr(layer_deltas[li]),
                 l_.scale, 1 if l_.scale_splats else 0, L.ptr(fb.uv), L.ptr(fb.depth), L.ptr(fb.conic), L.ptr(fb.radius),
                 L.ptr(self.opa_t), st))
-        while True:
-            fb._bin_and_sort(self.opa_t)
-            try:
-                fb.check()          # the pair counts are on the device: one synchronisation per batch
-                break
-            except L.SplatError:
-                # the sort dropped the surplus pairs: no image is composited from these lists
-                m = int(fb.pairs.max().item())
-                fb._reserve(int(m * fb.slack) + 1024)
-                self.regrows += 1
+        # the sort drops surplus pairs: no image is composited from lists that did not fit (one synchronisation per batch)
+        self.regrows += fb._bin_and_sort_fitting(self.opa_t)
         out, _, _ = _blend_sets_forward(fb, self.meta, self.feats, self.opa_t, 0, 0)
         return out
 

@@ -185,56 +185,33 @@ class FeatureLift:
         times = [float(t) for t in times]
         T, F = len(times), self.F
         for b0 in range(0, T, F):
-            n = min(F, T - b0)
-            cam = None
-            if cams is not None:
-                from .frames import _Camera
-                e, i_ = cams
-                cam = _Camera(e[b0:b0 + F] if e.dim() == 3 else e, i_[b0:b0 + F] if i_ is not None and i_.dim() == 2 else i_, F)
-            yield b0, n, tuple(times[min(b0 + i, T - 1)] for i in range(F)), cam
+            yield b0, min(F, T - b0), tuple(times[min(b0 + i, T - 1)] for i in range(F)), None if cams is None else cams[b0 // F]
 
     def _cameras(self, T: int, extr, intr):
-        """the cameras of a call over T frame times, padded like the frame times: None for the one orthographic camera of the
-        constructor, else (extr, intr) on the device with per-frame tensors of ceil(T / F) * F rows"""
-        if extr is None and intr is None and self.camera is None:
-            return None
-        from .views import _clip_cameras, _padded
-        e = extr if extr is not None else (self.camera[0] if self.camera is not None else self.extr)
-        i_ = intr if intr is not None else (self.camera[1] if self.camera is not None else None)
-        e, i_ = _clip_cameras(e, i_, T, self.fb.dev, "T")
-        pidx = torch.tensor(_padded(T, self.F), device=self.fb.dev)
-        return e.index_select(0, pidx) if e.dim() == 3 else e, i_.index_select(0, pidx) if i_ is not None and i_.dim() == 2 else i_
+        """the ``_Camera`` of every batch of a call over T frame times (``views._batch_cameras``); None for the one orthographic
+        camera of the constructor"""
+        from .views import _batch_cameras
+        return _batch_cameras(extr, intr, self.camera or (self.extr, None), T, self.F, self.fb.dev, "T")
 
     def _geometry(self, times: tuple, checked: bool, cam=None) -> None:
         """the batch's preprocess, binning and sort.  ``checked``: a batch whose tile-Gaussian pairs outgrow the pair capacity
         is binned again with a larger one -- nothing is ever folded in from truncated lists (one host synchronisation per batch
         reads the pair counts).  ``cam``: the batch's ``_Camera``; None: the one orthographic camera of the constructor"""
         from .dynamics import frame_table
-        fb, lib, st, p = self.fb, L.lib(), L.stream(), self.p
+        from .frames import _entry
+        fb, st, p = self.fb, L.stream(), self.p
         tab = self._tables.get(times)
         if tab is None:
             tab = self._tables[times] = frame_table(self.clock, list(times), fb.dev)
         fb._begin_forward()
-        # one orthographic camera: the core entry point; the cameras of a call: its twin of include/splat_hip_layers_cam.h
-        pre = lib.splat_frame_preprocess_layer_batch if cam is None else lib.splat_frame_preprocess_layer_batch_cam
+        pre, cam_arg = _entry("splat_frame_preprocess_layer_batch", cam, self.extr)
         L.check(pre(
             self.F, self.N, self.N, self.N, 0, self.I, L.ptr(tab), L.ptr(None),
             L.ptr(p["position"]), L.ptr(p["pos_cubic_node"]), self.layout, L.ptr(p["rotation"]), L.ptr(p["rot_poly_feat"]),
-            L.ptr(p["rot_fourier_feat"]), L.ptr(p["opacity"]), L.ptr(p["scaling"]),
-            L.ptr(self.extr) if cam is None else ctypes.byref(cam.struct()), self.W, self.H,
+            L.ptr(p["rot_fourier_feat"]), L.ptr(p["opacity"]), L.ptr(p["scaling"]), cam_arg, self.W, self.H,
             self.nearest, self.extent, L.ptr(None), L.ptr(None), 1.0, 0, L.ptr(fb.uv), L.ptr(fb.depth),
             L.ptr(fb.conic), L.ptr(fb.radius), L.ptr(self.opa_t), st))
-        while True:
-            fb._bin_and_sort(self.opa_t)
-            if not checked:
-                return
-            try:
-                fb.check()
-                return
-            except L.SplatError:
-                m = int(fb.pairs.max().item())
-                fb._reserve(int(m * fb.slack) + 1024)
-                self.regrows += 1
+        self.regrows += fb._bin_and_sort_fitting(self.opa_t, checked)
 
     def _records(self) -> Tensor:
         return self.fb._set_buffer(("lift", "rec"), self.F * self.fb.capacity * _record_floats(self.D))

@@ -233,7 +233,7 @@ class _Clip:
                 return res
             except L.SplatError:
                 # the sort dropped the surplus pairs: nothing composited from these lists is returned
-                fb._reserve(int(int(fb.pairs.max().item()) * fb.slack) + 1024)
+                fb._grow(int(fb.pairs.max().item()))
                 self.regrows += 1
 
     def outputs(self, T: int) -> Dict[str, Tensor]:
@@ -248,6 +248,23 @@ class _Clip:
 
 def _padded(T: int, F: int) -> List[int]:
     return [min(i, T - 1) for i in range(((T + F - 1) // F) * F)]     # a short last batch repeats the last frame
+
+
+def _batch_cameras(extr, intr, default, T: int, F: int, dev, what: str):
+    """the ``_Camera`` of every batch of ``F`` frames of a call over ``T`` frame times (``layers.LayeredClip``, ``lift.FeatureLift``):
+    the call's ``extr`` / ``intr``, each falling back to the object's ``default`` (extr, intr or None), checked and brought to the
+    device (``_clip_cameras``), per-frame tensors padded like the frame times (``_padded``) and sliced per batch.  None: neither
+    the call nor the object names a camera -- the one orthographic camera of the core entry point."""
+    if extr is None and intr is None and default[1] is None:
+        return None
+    from .frames import _Camera
+    e, i_ = _clip_cameras(default[0] if extr is None else extr, default[1] if intr is None else intr, T, dev, what)
+    per_e, per_i = e.dim() == 3, i_ is not None and i_.dim() == 2
+    if per_e or per_i:
+        pidx = torch.tensor(_padded(T, F), device=dev)
+        e = e.index_select(0, pidx) if per_e else e
+        i_ = i_.index_select(0, pidx) if per_i else i_
+    return [_Camera(e[b0:b0 + F] if per_e else e, i_[b0:b0 + F] if per_i else i_, F) for b0 in range(0, T, F)]
 
 
 def _no_layers_with(K, wide, who: str) -> None:

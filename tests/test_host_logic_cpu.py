@@ -28,6 +28,26 @@ def test_parse_sets_flattens_feature_lists_and_marks_per_frame_tensors():
         FR._parse_sets([dict(feature="colour")], F, P)
 
 
+def test_autograd_nodes_take_their_argument_positions_from_the_forward_signature():
+    """every position a backward uses (first feature tensor, the camera leaves, the None padding) is the one ``forward`` declares"""
+    import inspect
+    for node in (FR._RenderFrames, FR._RenderSets, FR._RenderDynamic, FR._RenderDynamicSets):
+        params = list(inspect.signature(node.forward).parameters.values())
+        names = tuple(p.name for p in params)
+        assert names[0] == "ctx" and node.ARGS == names[1:]
+        variadic = [p.name for p in params if p.kind is inspect.Parameter.VAR_POSITIONAL]
+        assert variadic in ([], ["feats"]) and (not variadic or names[-1] == "feats")
+        if variadic:
+            assert node.FEATS == names.index("feats") - 1 == len(names) - 2
+        if "cg_extr" in names:
+            assert (node.CG_EXTR, node.CG_INTR) == (names.index("cg_extr") - 1, names.index("cg_intr") - 1)
+    assert FR._RenderDynamicSets.ARGS[:5] == ("position", "cubic", "rotation", "opacity", "scaling")
+    assert FR._RenderDynamic.ARGS[:6] == ("position", "cubic", "rotation", "opacity", "scaling", "feature")
+    for node in (FR._RenderFrames, FR._RenderSets):          # the leaves lead, Nones up to the features (or the end)
+        fixed = getattr(node, "FEATS", len(node.ARGS))
+        assert node.ARGS[:len(node.LEAVES)] == node.LEAVES and node.PAD == (None,) * (fixed - len(node.LEAVES))
+
+
 def test_source_tensor_keeps_a_strided_per_frame_view_only_on_the_device():
     F, P = 2, 5
     pairs = torch.rand(F, 2, P, 3)
