@@ -3957,34 +3957,59 @@ blend_bwd_atomic_kernel(const BlendArgs B) {
 }
 
 // ================================================================== launch tables
+#include <type_traits>
+
+// Runtime value -> template argument, once per axis.  dispatch_bools(fn, b0, b1, ..) calls the generic lambda fn with one
+// std::bool_constant per bool (the first bool outermost, true before false); a kernel's template argument is then
+// decltype(B)::value, and fn's result is handed back.  Everything is resolved at compile time: what remains at run time is the
+// ladder of ifs written out.
+template <class Fn>
+static auto dispatch_bools(Fn &&fn) { return fn(); }
+template <class Fn, class... Rest>
+static auto dispatch_bools(Fn &&fn, bool b, Rest... rest) {
+    if (b) return dispatch_bools([&](auto... r) { return fn(std::true_type{}, r...); }, rest...);
+    return dispatch_bools([&](auto... r) { return fn(std::false_type{}, r...); }, rest...);
+}
+
+// channel-chunk width -> kernel instantiation: chunk_ch is the width table, dispatch_chunk hands the width to a generic lambda
+// as std::integral_constant<int, CH> and returns what the lambda returns
+static inline int chunk_ch(int cn) { return cn <= 1 ? 1 : cn <= 3 ? 3 : cn <= 8 ? 8 : cn <= 16 ? 16 : cn <= 20 ? 20 : cn <= 24 ? 24 : 32; }
+
+template <int N> using int_c = std::integral_constant<int, N>;
+template <class Fn>
+static int dispatch_chunk(int cn, Fn &&fn) {
+    switch (chunk_ch(cn)) {
+        case 1: return fn(int_c<1>{});
+        case 3: return fn(int_c<3>{});
+        case 8: return fn(int_c<8>{});
+        case 16: return fn(int_c<16>{});
+        case 20: return fn(int_c<20>{});
+        case 24: return fn(int_c<24>{});
+        default: return fn(int_c<32>{});
+    }
+}
+
 template <int CH>
 static int launch_pack(const BlendArgs &A, bool bias, hipStream_t s) {
     if (A.P == 0) return SPLAT_OK;
     const dim3 grid((unsigned)((A.P + 255) / 256), (unsigned)A.F), block(256);
-    const bool exact = A.cn == CH;
-    if (bias) { if (exact) SPLAT_LAUNCH("blend_pack", (pack_kernel<CH, true, true>), grid, block, 0, s, A); else SPLAT_LAUNCH("blend_pack", (pack_kernel<CH, true, false>), grid, block, 0, s, A); }
-    else { if (exact) SPLAT_LAUNCH("blend_pack", (pack_kernel<CH, false, true>), grid, block, 0, s, A); else SPLAT_LAUNCH("blend_pack", (pack_kernel<CH, false, false>), grid, block, 0, s, A); }
+    dispatch_bools([&](auto B, auto X) {
+        SPLAT_LAUNCH("blend_pack", (pack_kernel<CH, decltype(B)::value, decltype(X)::value>), grid, block, 0, s, A);
+    }, bias, A.cn == CH);
     SPLAT_POST_LAUNCH();
     return SPLAT_OK;
 }
 
 template <int CH>
-static int launch_fwd(const BlendArgs &A, int T, bool enh, bool bias, hipStream_t s) {
-    const dim3 grid((unsigned)(T * A.F)), block(256);
-    const bool exact = A.cn == CH;
+static int launch_fwd(const BlendArgs &A, bool enh, bool bias, hipStream_t s) {
+    const dim3 grid((unsigned)(A.T * A.F)), block(256);
     {
         const int rc = launch_pack<CH>(A, bias, s);
         if (rc != SPLAT_OK) return rc;
     }
-#define FWD(E, B, X) SPLAT_LAUNCH("blend_fwd", (blend_fwd_kernel<CH, E, B, X>), grid, block, 0, s, A)
-    if (enh) {
-        if (bias) { if (exact) FWD(true, true, true); else FWD(true, true, false); }
-        else { if (exact) FWD(true, false, true); else FWD(true, false, false); }
-    } else {
-        if (bias) { if (exact) FWD(false, true, true); else FWD(false, true, false); }
-        else { if (exact) FWD(false, false, true); else FWD(false, false, false); }
-    }
-#undef FWD
+    dispatch_bools([&](auto E, auto B, auto X) {
+        SPLAT_LAUNCH("blend_fwd", (blend_fwd_kernel<CH, decltype(E)::value, decltype(B)::value, decltype(X)::value>), grid, block, 0, s, A);
+    }, enh, bias, A.cn == CH);
     SPLAT_POST_LAUNCH();
     return SPLAT_OK;
 }
@@ -3994,34 +4019,38 @@ static bool bwd_use_quarters() { return splat_option(SPLAT_OPT_BWD_QUARTERS) != 
 static bool sets_std_plan_enabled() { return splat_option(SPLAT_OPT_SETS_STD) != 0; }     // 0: generic slot -> channel routing
 
 template <int CH, bool ABS, bool BIAS>
-static int launch_bwd_ab(const BlendArgs &A, int T, bool pair, hipStream_t s) {
-    const dim3 grid((unsigned)(T * A.F)), block(256);
+static int launch_bwd_ab(const BlendArgs &A, bool pair, hipStream_t s) {
+    const dim3 grid((unsigned)(A.T * A.F)), block(256);
     const bool exact = A.cn == CH;
-    if (pair && !BIAS && CH <= 3 && A.cull_flags && bwd_use_quarters()) {
-        // narrow row with the forward's cull words: one survivor list per 4x4 quarter
-        constexpr int QC = CH <= 3 ? CH : 3;
-        if (exact) SPLAT_LAUNCH("blend_bwd", (blend_bwd_quarter_kernel<QC, ABS, true>), grid, block, 0, s, A);
-        else SPLAT_LAUNCH("blend_bwd", (blend_bwd_quarter_kernel<QC, ABS, false>), grid, block, 0, s, A);
-    } else if (pair && !BIAS && !ABS && CH >= 16 && A.cull_flags && !A.rec_stride && bwd_use_quarters()) {
-        // frame batch, wide row without |taps|: quarter lists
-        constexpr int WC = CH >= 16 ? CH : 16;
-        if (exact) SPLAT_LAUNCH("blend_bwd", (blend_bwd_wide_quarter_kernel<WC, true>), grid, block, 0, s, A);
-        else SPLAT_LAUNCH("blend_bwd", (blend_bwd_wide_quarter_kernel<WC, false>), grid, block, 0, s, A);
-    } else if (pair && !BIAS && !splat_deterministic()) {   // (its carried survivors add into pair_buf with float atomics)
-        if (exact) SPLAT_LAUNCH("blend_bwd", (blend_bwd_mfma_kernel<CH, ABS, true>), grid, block, 0, s, A);
-        else SPLAT_LAUNCH("blend_bwd", (blend_bwd_mfma_kernel<CH, ABS, false>), grid, block, 0, s, A);
-    } else if (pair) {
-        if (exact) SPLAT_LAUNCH("blend_bwd", (blend_bwd_pair_kernel<CH, ABS, BIAS, true>), grid, block, 0, s, A);
-        else SPLAT_LAUNCH("blend_bwd", (blend_bwd_pair_kernel<CH, ABS, BIAS, false>), grid, block, 0, s, A);
-    } else {
-        if (splat_deterministic()) {
-            splat_set_error("deterministic mode: the backward needs this library's pair map (goff_incl, slot_sorted, pair_scratch); "
-                            "a foreign idx_sorted would take the float-atomic kernel");
-            return SPLAT_E_ARG;
+    [&] {   // the tile kernel: the first route that serves the call
+        if constexpr (CH <= 3) {
+            // narrow row with the forward's cull words: one survivor list per 4x4 quarter
+            if (pair && !BIAS && A.cull_flags && bwd_use_quarters())
+                return dispatch_bools([&](auto X) {
+                    SPLAT_LAUNCH("blend_bwd", (blend_bwd_quarter_kernel<CH, ABS, decltype(X)::value>), grid, block, 0, s, A);
+                }, exact);
         }
-        if (exact) SPLAT_LAUNCH("blend_bwd", (blend_bwd_atomic_kernel<CH, ABS, BIAS, true>), grid, block, 0, s, A);
-        else SPLAT_LAUNCH("blend_bwd", (blend_bwd_atomic_kernel<CH, ABS, BIAS, false>), grid, block, 0, s, A);
-    }
+        // frame batch, wide row without |taps|: quarter lists.  (CH >= 16 is not an `if constexpr` and the clamp stays: without
+        // it the narrow instantiations of this function no longer name the 16-channel kernel, and the kernels change places in
+        // the code object, which is compared byte for byte with earlier builds.  The same holds for !BIAS and !ABS.)
+        constexpr int WC = CH >= 16 ? CH : 16;
+        if (pair && !BIAS && !ABS && CH >= 16 && A.cull_flags && !A.rec_stride && bwd_use_quarters())
+            return dispatch_bools([&](auto X) {
+                SPLAT_LAUNCH("blend_bwd", (blend_bwd_wide_quarter_kernel<WC, decltype(X)::value>), grid, block, 0, s, A);
+            }, exact);
+        if (pair && !BIAS && !splat_deterministic())   // (its carried survivors add into pair_buf with float atomics)
+            return dispatch_bools([&](auto X) {
+                SPLAT_LAUNCH("blend_bwd", (blend_bwd_mfma_kernel<CH, ABS, decltype(X)::value>), grid, block, 0, s, A);
+            }, exact);
+        if (pair)
+            return dispatch_bools([&](auto X) {
+                SPLAT_LAUNCH("blend_bwd", (blend_bwd_pair_kernel<CH, ABS, BIAS, decltype(X)::value>), grid, block, 0, s, A);
+            }, exact);
+        // a foreign idx_sorted: float atomics (blend_backward_impl has refused that in deterministic mode)
+        return dispatch_bools([&](auto X) {
+            SPLAT_LAUNCH("blend_bwd", (blend_bwd_atomic_kernel<CH, ABS, BIAS, decltype(X)::value>), grid, block, 0, s, A);
+        }, exact);
+    }();
     SPLAT_POST_LAUNCH();
     if (pair && !A.tile_only) {  // frame batches reduce their records in the Gaussian-side backward (preprocess.hip)
         const dim3 rgrid((unsigned)(((size_t)A.P * 4 + 255) / 256));
@@ -4032,41 +4061,22 @@ static int launch_bwd_ab(const BlendArgs &A, int T, bool pair, hipStream_t s) {
 }
 
 template <int CH>
-static int launch_bwd(const BlendArgs &A, int T, bool bias, bool pair, hipStream_t s) {
+static int launch_bwd(const BlendArgs &A, bool bias, bool pair, hipStream_t s) {
     if (!A.pack_valid) {
         const int rc = launch_pack<CH>(A, bias, s);
         if (rc != SPLAT_OK) return rc;
     }
-    const bool abs_ = A.dL_dabs_uv != nullptr;  // |d uv| sums are only produced when the caller asks for them
-    if (abs_) return bias ? launch_bwd_ab<CH, true, true>(A, T, pair, s) : launch_bwd_ab<CH, true, false>(A, T, pair, s);
-    return bias ? launch_bwd_ab<CH, false, true>(A, T, pair, s) : launch_bwd_ab<CH, false, false>(A, T, pair, s);
+    return dispatch_bools([&](auto ABS, auto B) { return launch_bwd_ab<CH, decltype(ABS)::value, decltype(B)::value>(A, pair, s); },
+                          A.dL_dabs_uv != nullptr, bias);   // |d uv| sums are only produced when the caller asks for them
 }
 
-// channel-chunk width -> kernel instantiation
-static inline int chunk_ch(int cn) { return cn <= 1 ? 1 : cn <= 3 ? 3 : cn <= 8 ? 8 : cn <= 16 ? 16 : cn <= 20 ? 20 : cn <= 24 ? 24 : 32; }
-
-static int fwd_chunk(const BlendArgs &A, int T, bool enh, bool bias, hipStream_t s) {
-    switch (chunk_ch(A.cn)) {
-        case 1: return launch_fwd<1>(A, T, enh, bias, s);
-        case 3: return launch_fwd<3>(A, T, enh, bias, s);
-        case 8: return launch_fwd<8>(A, T, enh, bias, s);
-        case 16: return launch_fwd<16>(A, T, enh, bias, s);
-        case 20: return launch_fwd<20>(A, T, enh, bias, s);
-        case 24: return launch_fwd<24>(A, T, enh, bias, s);
-        default: return launch_fwd<32>(A, T, enh, bias, s);
-    }
+// one channel chunk [A.c0, A.c0 + A.cn) over the A.F * A.T tiles
+static int fwd_chunk(const BlendArgs &A, bool enh, bool bias, hipStream_t s) {
+    return dispatch_chunk(A.cn, [&](auto CH) { return launch_fwd<decltype(CH)::value>(A, enh, bias, s); });
 }
 
-static int bwd_chunk(const BlendArgs &A, int T, bool bias, bool pair, hipStream_t s) {
-    switch (chunk_ch(A.cn)) {
-        case 1: return launch_bwd<1>(A, T, bias, pair, s);
-        case 3: return launch_bwd<3>(A, T, bias, pair, s);
-        case 8: return launch_bwd<8>(A, T, bias, pair, s);
-        case 16: return launch_bwd<16>(A, T, bias, pair, s);
-        case 20: return launch_bwd<20>(A, T, bias, pair, s);
-        case 24: return launch_bwd<24>(A, T, bias, pair, s);
-        default: return launch_bwd<32>(A, T, bias, pair, s);
-    }
+static int bwd_chunk(const BlendArgs &A, bool bias, bool pair, hipStream_t s) {
+    return dispatch_chunk(A.cn, [&](auto CH) { return launch_bwd<decltype(CH)::value>(A, bias, pair, s); });
 }
 
 extern "C" size_t splat_blend_pack_floats(int C) {
@@ -4080,32 +4090,72 @@ extern "C" size_t splat_blend_pair_floats(int C, int has_bias) {
 }
 
 // ================================================================== C ABI
-static int blend_forward_impl(int P, int C, const float *uv, const float *conic, const float *opacity,
-                              const float *feature, const float *opacity_bias,
-                              const int32_t *idx_sorted, const int32_t *tile_range, float bg,
-                              const float *bg_channels, int W, int H, int K, int enable_truncation,
-                              float *out, float *final_T, int32_t *ncontrib, int32_t *gs_idx,
-                              float *pack_scratch, uint32_t *cull_flags, splat_stream_t stream) {
+// Every entry point below is its SPLAT_CHECK_ARG lines, blend_args(), the setters of the groups it uses and what is its own
+// (background, bias, the chunk, gradient outputs, the sets); a field no call names stays zero.
+static BlendArgs blend_args(int F, int P, int C, int W, int H, long long capacity) {
+    BlendArgs A;
+    memset(&A, 0, sizeof(A));
+    A.P = P; A.C = C; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
+    A.F = F; A.T = A.gx * ((H + TILE - 1) / TILE); A.cap = capacity;
+    return A;
+}
+// workgroup index -> (frame, tile) is an int: every frame-batch entry refuses more tiles with "too many tiles"
+static bool tiles_fit(const BlendArgs &A) { return (long long)A.F * A.T < (1ll << 31); }
+
+// the Gaussians' geometry and features; the strides are floats between two frames (0: shared by the frames)
+static void set_geometry(BlendArgs &A, const float *uv, const float *conic, const float *opacity, long long opacity_fs,
+                         const float *feature, long long feature_fs) {
+    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
+    A.opacity_fs = opacity_fs; A.feature_fs = feature_fs;
+}
+static void set_lists(BlendArgs &A, const int32_t *idx_sorted, const int32_t *tile_range) {
+    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
+}
+// what the forward writes; the enhanced forward (A.K > 0) needs both gs_idx and K
+static void set_forward_outputs(BlendArgs &A, float *out, float *final_T, int32_t *ncontrib, int32_t *gs_idx, int K,
+                                int enable_truncation, uint32_t *cull_flags) {
+    A.out = out; A.final_T = final_T; A.ncontrib = ncontrib; A.gs_idx = gs_idx;
+    A.K = (gs_idx != nullptr && K > 0) ? K : 0; A.trunc = enable_truncation ? 1 : 0;
+    A.cull_flags = cull_flags;
+}
+// what the tile backward reads of its forward and where its pair records go (the kernels write none of the const inputs)
+static void set_tile_backward(BlendArgs &A, const float *final_T, const int32_t *ncontrib, const float *dL_dout,
+                              const int32_t *slot_sorted, float *pair_buf, float *dbg_T_front, const uint32_t *cull_flags,
+                              int tile_only) {
+    A.final_T = const_cast<float *>(final_T); A.ncontrib = const_cast<int32_t *>(ncontrib);
+    A.dL_dout = dL_dout;
+    A.slot_sorted = slot_sorted; A.pair_buf = pair_buf;
+    A.dbg_T_front = dbg_T_front;
+    A.cull_flags = const_cast<uint32_t *>(cull_flags);
+    A.tile_only = tile_only;
+}
+// the packed records: a scratch the packing launch fills (pack_valid = 0) or the records a forward left (1: no packing launch,
+// nothing writes them); pack_fs = floats between two frames
+static void set_pack(BlendArgs &A, const float *pack, long long pack_fs, int pack_valid) {
+    A.pack = const_cast<float *>(pack); A.pack_fs = pack_fs; A.pack_valid = pack_valid;
+}
+static long long pack_frame_floats(int P, int width) { return (long long)P * (long long)splat_blend_pack_floats(width); }
+
+extern "C" int splat_alpha_blending_forward_flags(int P, int C, const float *uv, const float *conic, const float *opacity,
+                                                  const float *feature, const float *opacity_bias,
+                                                  const int32_t *idx_sorted, const int32_t *tile_range, float bg,
+                                                  const float *bg_channels, int W, int H, int K, int enable_truncation,
+                                                  float *out, float *final_T, int32_t *ncontrib, int32_t *gs_idx,
+                                                  float *pack_scratch, uint32_t *cull_flags, splat_stream_t stream) {
     SPLAT_CHECK_ARG(P >= 0 && C >= 1 && W > 0 && H > 0, "bad sizes");
     SPLAT_CHECK_ARG(tile_range && out && final_T && ncontrib, "null pointer");
     SPLAT_CHECK_ARG(P == 0 || (uv && conic && opacity && feature && pack_scratch), "null pointer");
-    const bool enh = (gs_idx != nullptr) && K > 0;
-    BlendArgs A;
-    memset(&A, 0, sizeof(A));
-    A.P = P; A.C = C;
-    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature; A.bias = opacity_bias;
-    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
-    A.bg = bg; A.bgc = bg_channels; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
-    A.K = enh ? K : 0; A.trunc = enable_truncation ? 1 : 0;
-    A.out = out; A.final_T = final_T; A.ncontrib = ncontrib; A.gs_idx = gs_idx;
-    A.pack = pack_scratch;
-    A.cull_flags = cull_flags;   // optional: the cull's keep words of every sorted entry, for the backward
-    const int T = A.gx * ((H + TILE - 1) / TILE);
-    A.F = 1; A.T = T;
+    BlendArgs A = blend_args(1, P, C, W, H, 0);
+    set_geometry(A, uv, conic, opacity, 0, feature, 0);
+    set_lists(A, idx_sorted, tile_range);
+    // (cull_flags, optional: the cull's keep words of every sorted entry, for the backward)
+    set_forward_outputs(A, out, final_T, ncontrib, gs_idx, K, enable_truncation, cull_flags);
+    set_pack(A, pack_scratch, 0, 0);
+    A.bias = opacity_bias; A.bg = bg; A.bgc = bg_channels;
     for (int c0 = 0; c0 < C; c0 += 32) {  // reference chunking: src/alpha_blending.cu:287-394
         A.c0 = c0;
         A.cn = C - c0 > 32 ? 32 : C - c0;
-        const int rc = fwd_chunk(A, T, enh, opacity_bias != nullptr, (hipStream_t)stream);
+        const int rc = fwd_chunk(A, A.K > 0, opacity_bias != nullptr, (hipStream_t)stream);
         if (rc != SPLAT_OK) return rc;
     }
     return SPLAT_OK;
@@ -4117,29 +4167,21 @@ extern "C" int splat_alpha_blending_forward(int P, int C, const float *uv, const
                                             const float *bg_channels, int W, int H, int K, int enable_truncation,
                                             float *out, float *final_T, int32_t *ncontrib, int32_t *gs_idx,
                                             float *pack_scratch, splat_stream_t stream) {
-    return blend_forward_impl(P, C, uv, conic, opacity, feature, opacity_bias, idx_sorted, tile_range, bg, bg_channels, W, H, K,
-                              enable_truncation, out, final_T, ncontrib, gs_idx, pack_scratch, nullptr, stream);
+    // the same without the cull words (a refusal carries the _flags entry's name)
+    return splat_alpha_blending_forward_flags(P, C, uv, conic, opacity, feature, opacity_bias, idx_sorted, tile_range, bg, bg_channels,
+                                              W, H, K, enable_truncation, out, final_T, ncontrib, gs_idx, pack_scratch, nullptr, stream);
 }
 
-extern "C" int splat_alpha_blending_forward_flags(int P, int C, const float *uv, const float *conic, const float *opacity,
-                                                  const float *feature, const float *opacity_bias,
-                                                  const int32_t *idx_sorted, const int32_t *tile_range, float bg,
-                                                  const float *bg_channels, int W, int H, int K, int enable_truncation,
-                                                  float *out, float *final_T, int32_t *ncontrib, int32_t *gs_idx,
-                                                  float *pack_scratch, uint32_t *cull_flags, splat_stream_t stream) {
-    return blend_forward_impl(P, C, uv, conic, opacity, feature, opacity_bias, idx_sorted, tile_range, bg, bg_channels, W, H, K,
-                              enable_truncation, out, final_T, ncontrib, gs_idx, pack_scratch, cull_flags, stream);
-}
-
-static int blend_backward_impl(int P, int C, const float *uv, const float *conic, const float *opacity,
-                               const float *feature, const float *opacity_bias,
-                               const int32_t *idx_sorted, const int32_t *tile_range, float bg, int W,
-                               int H, const float *final_T, const int32_t *ncontrib,
-                               const float *dL_dout, float *dL_duv, float *dL_dabs_uv, float *dL_dconic,
-                               float *dL_dopacity, float *dL_dfeature, float *dL_dopacity_bias,
-                               float *dL_dndc, float *dL_dabs_ndc, const int32_t *goff_incl,
-                               const int32_t *slot_sorted, float *pair_scratch, float *pack_scratch,
-                               int pack_is_valid, float *dbg_T_front, const uint32_t *cull_flags, splat_stream_t stream) {
+extern "C" int splat_alpha_blending_backward_flags(int P, int C, const float *uv, const float *conic, const float *opacity,
+                                                   const float *feature, const float *opacity_bias,
+                                                   const int32_t *idx_sorted, const int32_t *tile_range, float bg, int W,
+                                                   int H, const float *final_T, const int32_t *ncontrib,
+                                                   const float *dL_dout, float *dL_duv, float *dL_dabs_uv, float *dL_dconic,
+                                                   float *dL_dopacity, float *dL_dfeature, float *dL_dopacity_bias,
+                                                   float *dL_dndc, float *dL_dabs_ndc, const int32_t *goff_incl,
+                                                   const int32_t *slot_sorted, float *pair_scratch, float *pack_scratch,
+                                                   int pack_is_valid, float *dbg_T_front, const uint32_t *cull_flags,
+                                                   splat_stream_t stream) {
     SPLAT_CHECK_ARG(P >= 0 && C >= 1 && W > 0 && H > 0, "bad sizes");
     if (P == 0) return SPLAT_OK;
     // idx_sorted may be NULL when no Gaussian touches any tile (M = 0: every tile range is empty, nothing dereferences it)
@@ -4157,29 +4199,22 @@ static int blend_backward_impl(int P, int C, const float *uv, const float *conic
     }
     SPLAT_CHECK_ARG(pair_mode || (!dL_dndc && !dL_dabs_ndc), "the tap outputs need the pair-mode backward");
     SPLAT_CHECK_ARG(!dL_dabs_ndc || dL_dabs_uv, "dL_dabs_ndc needs dL_dabs_uv");
-    BlendArgs A;
-    memset(&A, 0, sizeof(A));
-    A.P = P; A.C = C;
-    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature; A.bias = opacity_bias;
-    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
-    A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
-    A.final_T = const_cast<float *>(final_T); A.ncontrib = const_cast<int *>(ncontrib);
-    A.dL_dout = dL_dout;
+    BlendArgs A = blend_args(1, P, C, W, H, 0);
+    set_geometry(A, uv, conic, opacity, 0, feature, 0);
+    set_lists(A, idx_sorted, tile_range);
+    // (the forward's keep words serve the quarter-list kernels, which need the pair map; the Gaussian-side reduce runs: not tile_only)
+    set_tile_backward(A, final_T, ncontrib, dL_dout, slot_sorted, pair_scratch, dbg_T_front, pair_mode ? cull_flags : nullptr, 0);
+    set_pack(A, pack_scratch, 0, (pack_is_valid && C <= 32) ? 1 : 0);  // one chunk only: later chunks overwrite the scratch
+    A.bias = opacity_bias; A.bg = bg;
     A.dL_duv = dL_duv; A.dL_dabs_uv = dL_dabs_uv; A.dL_dconic = dL_dconic; A.dL_dopacity = dL_dopacity;
     A.dL_dfeature = dL_dfeature; A.dL_dbias = dL_dopacity_bias;
     A.dL_dndc = dL_dndc; A.dL_dabs_ndc = dL_dabs_ndc;
-    A.goff_incl = goff_incl; A.slot_sorted = slot_sorted; A.pair_buf = pair_scratch;
-    A.pack = pack_scratch;
-    A.dbg_T_front = dbg_T_front;
-    A.cull_flags = pair_mode ? const_cast<uint32_t *>(cull_flags) : nullptr;   // (the forward's keep words: quarter-list kernels)
-    A.pack_valid = (pack_is_valid && C <= 32) ? 1 : 0;  // one chunk only: later chunks overwrite the scratch
-    const int T = A.gx * ((H + TILE - 1) / TILE);
-    A.F = 1; A.T = T;
+    A.goff_incl = goff_incl;
     for (int c0 = 0; c0 < C; c0 += 32) {  // reference chunking: src/alpha_blending.cu:440-577
         A.c0 = c0;
         A.cn = C - c0 > 32 ? 32 : C - c0;
         A.accumulate = c0 > 0;
-        const int rc = bwd_chunk(A, T, opacity_bias != nullptr, pair_mode, (hipStream_t)stream);
+        const int rc = bwd_chunk(A, opacity_bias != nullptr, pair_mode, (hipStream_t)stream);
         if (rc != SPLAT_OK) return rc;
     }
     return SPLAT_OK;
@@ -4194,28 +4229,12 @@ extern "C" int splat_alpha_blending_backward(int P, int C, const float *uv, cons
                                              float *dL_dndc, float *dL_dabs_ndc, const int32_t *goff_incl,
                                              const int32_t *slot_sorted, float *pair_scratch, float *pack_scratch,
                                              int pack_is_valid, float *dbg_T_front, splat_stream_t stream) {
-    return blend_backward_impl(P, C, uv, conic, opacity, feature, opacity_bias, idx_sorted, tile_range, bg, W, H, final_T, ncontrib,
-                               dL_dout, dL_duv, dL_dabs_uv, dL_dconic, dL_dopacity, dL_dfeature, dL_dopacity_bias, dL_dndc,
-                               dL_dabs_ndc, goff_incl, slot_sorted, pair_scratch, pack_scratch, pack_is_valid, dbg_T_front, nullptr,
-                               stream);
+    // the same without the cull words (a refusal carries the _flags entry's name)
+    return splat_alpha_blending_backward_flags(P, C, uv, conic, opacity, feature, opacity_bias, idx_sorted, tile_range, bg, W, H, final_T,
+                                               ncontrib, dL_dout, dL_duv, dL_dabs_uv, dL_dconic, dL_dopacity, dL_dfeature,
+                                               dL_dopacity_bias, dL_dndc, dL_dabs_ndc, goff_incl, slot_sorted, pair_scratch, pack_scratch,
+                                               pack_is_valid, dbg_T_front, nullptr, stream);
 }
-
-extern "C" int splat_alpha_blending_backward_flags(int P, int C, const float *uv, const float *conic, const float *opacity,
-                                                   const float *feature, const float *opacity_bias,
-                                                   const int32_t *idx_sorted, const int32_t *tile_range, float bg, int W,
-                                                   int H, const float *final_T, const int32_t *ncontrib,
-                                                   const float *dL_dout, float *dL_duv, float *dL_dabs_uv, float *dL_dconic,
-                                                   float *dL_dopacity, float *dL_dfeature, float *dL_dopacity_bias,
-                                                   float *dL_dndc, float *dL_dabs_ndc, const int32_t *goff_incl,
-                                                   const int32_t *slot_sorted, float *pair_scratch, float *pack_scratch,
-                                                   int pack_is_valid, float *dbg_T_front, const uint32_t *cull_flags,
-                                                   splat_stream_t stream) {
-    return blend_backward_impl(P, C, uv, conic, opacity, feature, opacity_bias, idx_sorted, tile_range, bg, W, H, final_T, ncontrib,
-                               dL_dout, dL_duv, dL_dabs_uv, dL_dconic, dL_dopacity, dL_dfeature, dL_dopacity_bias, dL_dndc,
-                               dL_dabs_ndc, goff_incl, slot_sorted, pair_scratch, pack_scratch, pack_is_valid, dbg_T_front,
-                               cull_flags, stream);
-}
-
 
 // ================================================================== frame batch (F frames of one Gaussian set per launch)
 // The tile kernels take workgroup b -> (frame, tile) through the same XCD-aware mapping over the F * T tiles; per-frame
@@ -4225,6 +4244,22 @@ extern "C" size_t splat_blend_pair_stride(int C, int want_abs, int has_bias) {
     // exact record stride (floats) the backward kernels use for this configuration
     const int ng = 6 + (want_abs ? 2 : 0) + (has_bias ? 1 : 0);
     return (size_t)PAIR_STRIDE(ng + chunk_ch(C > 32 ? 32 : C));
+}
+
+// Do the channel ranges [c0[g], c0[g] + cn[g]) (cn = 0: no such range) tile the row's channels [0, C), C <= 32, each channel
+// once?  Else the first thing wrong, in the order the entries report it: range g itself (with its pointer, where the ranges
+// carry pointers), then its overlap with the ranges before it; a channel nobody covers comes last.
+enum RowCover { COVER_OK, COVER_OUTSIDE, COVER_OVERLAP, COVER_HOLE };
+static RowCover row_cover(int C, int n, const int32_t *c0, const int32_t *cn, const float *const *ptr) {
+    unsigned long long covered = 0ull;
+    for (int g = 0; g < n; ++g) {
+        if (cn[g] < 0 || (cn[g] > 0 && (c0[g] < 0 || c0[g] + cn[g] > C || (ptr && !ptr[g])))) return COVER_OUTSIDE;
+        for (int k = 0; k < cn[g]; ++k) {
+            if (covered & (1ull << (c0[g] + k))) return COVER_OVERLAP;
+            covered |= 1ull << (c0[g] + k);
+        }
+    }
+    return covered == (1ull << C) - 1ull ? COVER_OK : COVER_HOLE;
 }
 
 extern "C" int splat_alpha_blending_forward_batch(int F, int P, int C, const float *uv, const float *conic,
@@ -4239,24 +4274,15 @@ extern "C" int splat_alpha_blending_forward_batch(int F, int P, int C, const flo
     SPLAT_CHECK_ARG(uv && conic && opacity && feature && idx_sorted && tile_range && out && final_T && ncontrib &&
                         pack_scratch,
                     "null pointer");
-    const bool enh = (gs_idx != nullptr) && K > 0;
-    BlendArgs A;
-    memset(&A, 0, sizeof(A));
-    A.P = P; A.C = C;
-    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
-    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
-    A.bg = bg; A.bgc = bg_channels; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
-    A.K = enh ? K : 0; A.trunc = enable_truncation ? 1 : 0;
-    A.out = out; A.final_T = final_T; A.ncontrib = ncontrib; A.gs_idx = gs_idx;
-    A.pack = pack_scratch;
-    A.cull_flags = cull_flags;
-    const int T = A.gx * ((H + TILE - 1) / TILE);
-    SPLAT_CHECK_ARG((long long)F * T < (1ll << 31), "too many tiles");
-    A.F = F; A.T = T; A.cap = capacity;
-    A.pack_fs = (long long)P * (long long)splat_blend_pack_floats(C);
-    A.opacity_fs = opacity_frame_stride; A.feature_fs = feature_frame_stride;
+    BlendArgs A = blend_args(F, P, C, W, H, capacity);
+    SPLAT_CHECK_ARG(tiles_fit(A), "too many tiles");
+    set_geometry(A, uv, conic, opacity, opacity_frame_stride, feature, feature_frame_stride);
+    set_lists(A, idx_sorted, tile_range);
+    set_forward_outputs(A, out, final_T, ncontrib, gs_idx, K, enable_truncation, cull_flags);
+    set_pack(A, pack_scratch, pack_frame_floats(P, C), 0);
+    A.bg = bg; A.bgc = bg_channels;
     A.c0 = 0; A.cn = C;
-    return fwd_chunk(A, T, enh, false, (hipStream_t)stream);
+    return fwd_chunk(A, A.K > 0, false, (hipStream_t)stream);
 }
 
 // splat_alpha_blending_forward_batch over a row whose channels come from several SOURCES (no concatenated [F,P,C] row):
@@ -4273,38 +4299,23 @@ extern "C" int splat_alpha_blending_forward_batch_sources(int F, int P, int C, i
     SPLAT_CHECK_ARG(F >= 1 && P >= 1 && C >= 1 && C <= 32 && W > 0 && H > 0 && capacity >= 1, "bad sizes (C <= 32)");
     SPLAT_CHECK_ARG(src && nsrc >= 1 && nsrc <= SPLAT_MAX_SOURCES && bg_channels, "null / oversized source table");
     SPLAT_CHECK_ARG(uv && conic && opacity && idx_sorted && tile_range && out && final_T && ncontrib && pack_scratch, "null pointer");
-    BlendArgs A;
-    memset(&A, 0, sizeof(A));
-    {
-        unsigned long long covered = 0ull;
-        for (int g = 0; g < nsrc; ++g) {
-            SPLAT_CHECK_ARG(src[g].cn >= 0 && (src[g].cn == 0 || (src[g].c0 >= 0 && src[g].c0 + src[g].cn <= C && src[g].feature)),
-                            "source outside the row / null source pointer");
-            for (int k = 0; k < src[g].cn; ++k) {
-                SPLAT_CHECK_ARG(!(covered & (1ull << (src[g].c0 + k))), "the sources overlap");
-                covered |= 1ull << (src[g].c0 + k);
-            }
-            A.src_c0[g] = src[g].c0; A.src_cn[g] = src[g].cn; A.src_f[g] = src[g].feature; A.src_fs[g] = src[g].frame_stride;
-        }
-        SPLAT_CHECK_ARG(covered == (1ull << C) - 1ull, "the sources do not cover the row's channels");
-    }
+    BlendArgs A = blend_args(F, P, C, W, H, capacity);
     A.nsrc = nsrc;
-    const bool enh = (gs_idx != nullptr) && K > 0;
-    A.P = P; A.C = C;
-    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity;
-    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
-    A.bgc = bg_channels; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
-    A.K = enh ? K : 0; A.trunc = enable_truncation ? 1 : 0;
-    A.out = out; A.final_T = final_T; A.ncontrib = ncontrib; A.gs_idx = gs_idx;
-    A.pack = pack_scratch;
-    A.cull_flags = cull_flags;
-    const int T = A.gx * ((H + TILE - 1) / TILE);
-    SPLAT_CHECK_ARG((long long)F * T < (1ll << 31), "too many tiles");
-    A.F = F; A.T = T; A.cap = capacity;
-    A.pack_fs = (long long)P * (long long)splat_blend_pack_floats(C);
-    A.opacity_fs = opacity_frame_stride;
+    for (int g = 0; g < nsrc; ++g) {
+        A.src_c0[g] = src[g].c0; A.src_cn[g] = src[g].cn; A.src_f[g] = src[g].feature; A.src_fs[g] = src[g].frame_stride;
+    }
+    const RowCover cover = row_cover(C, nsrc, A.src_c0, A.src_cn, A.src_f);
+    SPLAT_CHECK_ARG(cover != COVER_OUTSIDE, "source outside the row / null source pointer");
+    SPLAT_CHECK_ARG(cover != COVER_OVERLAP, "the sources overlap");
+    SPLAT_CHECK_ARG(cover != COVER_HOLE, "the sources do not cover the row's channels");
+    SPLAT_CHECK_ARG(tiles_fit(A), "too many tiles");
+    set_geometry(A, uv, conic, opacity, opacity_frame_stride, nullptr, 0);   // (the features are the sources')
+    set_lists(A, idx_sorted, tile_range);
+    set_forward_outputs(A, out, final_T, ncontrib, gs_idx, K, enable_truncation, cull_flags);
+    set_pack(A, pack_scratch, pack_frame_floats(P, C), 0);
+    A.bgc = bg_channels;   // (required above: no scalar background)
     A.c0 = 0; A.cn = C;
-    return fwd_chunk(A, T, enh, false, (hipStream_t)stream);
+    return fwd_chunk(A, A.K > 0, false, (hipStream_t)stream);
 }
 
 // The same with (at most) three sets given as parallel HOST arrays of three entries (set_cn[g] = 0: no such set).
@@ -4338,24 +4349,16 @@ extern "C" int splat_alpha_blending_backward_batch(int F, int P, int C, const in
     SPLAT_CHECK_ARG(F >= 1 && P >= 1 && C >= 1 && C <= 32 && W > 0 && H > 0 && capacity >= 1, "bad sizes (C <= 32)");
     SPLAT_CHECK_ARG(idx_sorted && tile_range && final_T && ncontrib && dL_dout && slot_sorted && pair_records && pack,
                     "null pointer");
-    BlendArgs A;
-    memset(&A, 0, sizeof(A));
-    A.P = P; A.C = C;
-    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
-    A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
-    A.final_T = const_cast<float *>(final_T); A.ncontrib = const_cast<int *>(ncontrib);
-    A.dL_dout = dL_dout;
-    A.slot_sorted = slot_sorted; A.pair_buf = pair_records;
-    A.pack = const_cast<float *>(pack); A.pack_valid = 1;
-    A.dbg_T_front = dbg_T_front;
-    A.cull_flags = const_cast<uint32_t *>(cull_flags);
-    const int T = A.gx * ((H + TILE - 1) / TILE);
-    A.F = F; A.T = T; A.cap = capacity; A.tile_only = 1;
-    A.pack_fs = (long long)P * (long long)splat_blend_pack_floats(C);
+    BlendArgs A = blend_args(F, P, C, W, H, capacity);
+    SPLAT_CHECK_ARG(tiles_fit(A), "too many tiles");
+    set_lists(A, idx_sorted, tile_range);
+    set_tile_backward(A, final_T, ncontrib, dL_dout, slot_sorted, pair_records, dbg_T_front, cull_flags, 1);
+    set_pack(A, pack, pack_frame_floats(P, C), 1);
+    A.bg = bg;
     A.c0 = 0; A.cn = C;
     // tile kernels only: the abs sums are requested through a non-null marker (nothing is written through it here)
     A.dL_dabs_uv = want_abs ? pair_records : nullptr;
-    return bwd_chunk(A, T, false, true, (hipStream_t)stream);
+    return bwd_chunk(A, false, true, (hipStream_t)stream);
 }
 
 // One feature SET [c0, c0 + cn) of a wider composited row (the reference's renderer blends rgb / depth / attributes of one
@@ -4376,24 +4379,16 @@ extern "C" int splat_alpha_blending_backward_batch_set(int F, int P, int C, int 
     SPLAT_CHECK_ARG(uv && conic && opacity && feature && idx_sorted && tile_range && final_T && ncontrib && dL_dout &&
                         slot_sorted && pair_records && pack_scratch,
                     "null pointer");
-    BlendArgs A;
-    memset(&A, 0, sizeof(A));
-    A.P = P; A.C = C;
-    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
-    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
-    A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
-    A.final_T = const_cast<float *>(final_T); A.ncontrib = const_cast<int *>(ncontrib);
-    A.dL_dout = dL_dout;
-    A.slot_sorted = slot_sorted; A.pair_buf = pair_records;
-    A.pack = pack_scratch; A.pack_valid = 0;
-    A.dbg_T_front = dbg_T_front;
-    const int T = A.gx * ((H + TILE - 1) / TILE);
-    A.F = F; A.T = T; A.cap = capacity; A.tile_only = 1;
-    A.pack_fs = (long long)P * (long long)splat_blend_pack_floats(cn);
-    A.opacity_fs = opacity_frame_stride; A.feature_fs = feature_frame_stride;
+    BlendArgs A = blend_args(F, P, C, W, H, capacity);
+    SPLAT_CHECK_ARG(tiles_fit(A), "too many tiles");
+    set_geometry(A, uv, conic, opacity, opacity_frame_stride, feature, feature_frame_stride);
+    set_lists(A, idx_sorted, tile_range);
+    set_tile_backward(A, final_T, ncontrib, dL_dout, slot_sorted, pair_records, dbg_T_front, nullptr, 1);   // (no cull words: block-level kernels)
+    set_pack(A, pack_scratch, pack_frame_floats(P, cn), 0);   // the set's own records, one set wide
+    A.bg = bg;
     A.c0 = c0; A.cn = cn;
     A.dL_dabs_uv = want_abs ? pair_records : nullptr;
-    return bwd_chunk(A, T, false, true, (hipStream_t)stream);
+    return bwd_chunk(A, false, true, (hipStream_t)stream);
 }
 
 // The forward twin of splat_alpha_blending_backward_batch_set: channels [c0, c0 + cn) of a feature set [P, C] of ANY width into
@@ -4412,22 +4407,15 @@ extern "C" int splat_alpha_blending_forward_batch_set(int F, int P, int C, int c
     SPLAT_CHECK_ARG(c0 >= 0 && cn >= 1 && cn <= 32 && (long long)c0 + cn <= C, "the chunk must be 1..32 channels inside the set");
     SPLAT_CHECK_ARG(uv && conic && opacity && feature && idx_sorted && tile_range && out && final_T && ncontrib && pack_scratch,
                     "null pointer");
-    BlendArgs A;
-    memset(&A, 0, sizeof(A));
-    A.P = P; A.C = C;
-    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
-    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
-    A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
-    A.out = out; A.final_T = final_T; A.ncontrib = ncontrib;
-    A.pack = pack_scratch;
-    A.cull_flags = cull_flags;
-    const int T = A.gx * ((H + TILE - 1) / TILE);
-    SPLAT_CHECK_ARG((long long)F * T < (1ll << 31), "too many tiles");
-    A.F = F; A.T = T; A.cap = capacity;
-    A.pack_fs = (long long)P * (long long)splat_blend_pack_floats(cn);
-    A.opacity_fs = opacity_frame_stride; A.feature_fs = feature_frame_stride;
+    BlendArgs A = blend_args(F, P, C, W, H, capacity);
+    SPLAT_CHECK_ARG(tiles_fit(A), "too many tiles");
+    set_geometry(A, uv, conic, opacity, opacity_frame_stride, feature, feature_frame_stride);
+    set_lists(A, idx_sorted, tile_range);
+    set_forward_outputs(A, out, final_T, ncontrib, nullptr, 0, 0, cull_flags);   // (no gs_idx, no truncation)
+    set_pack(A, pack_scratch, pack_frame_floats(P, cn), 0);   // the chunk's own records, one chunk wide
+    A.bg = bg;
     A.c0 = c0; A.cn = cn;
-    return fwd_chunk(A, T, false, false, (hipStream_t)stream);
+    return fwd_chunk(A, false, false, (hipStream_t)stream);
 }
 
 // ... and the chunk's tile backward from what that forward left: its packed records (`pack`, untouched since) and, optionally,
@@ -4445,23 +4433,14 @@ extern "C" int splat_alpha_blending_backward_batch_set_packed(int F, int P, int 
     SPLAT_CHECK_ARG(c0 >= 0 && cn >= 1 && cn <= 32 && (long long)c0 + cn <= C, "the chunk must be 1..32 channels inside the set");
     SPLAT_CHECK_ARG(idx_sorted && tile_range && final_T && ncontrib && dL_dout && slot_sorted && pair_records && pack,
                     "null pointer");
-    BlendArgs A;
-    memset(&A, 0, sizeof(A));
-    A.P = P; A.C = C;
-    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
-    A.bg = bg; A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
-    A.final_T = const_cast<float *>(final_T); A.ncontrib = const_cast<int *>(ncontrib);
-    A.dL_dout = dL_dout;
-    A.slot_sorted = slot_sorted; A.pair_buf = pair_records;
-    A.pack = const_cast<float *>(pack); A.pack_valid = 1;
-    A.dbg_T_front = dbg_T_front;
-    A.cull_flags = const_cast<uint32_t *>(cull_flags);
-    const int T = A.gx * ((H + TILE - 1) / TILE);
-    SPLAT_CHECK_ARG((long long)F * T < (1ll << 31), "too many tiles");
-    A.F = F; A.T = T; A.cap = capacity; A.tile_only = 1;
-    A.pack_fs = (long long)P * (long long)splat_blend_pack_floats(cn);
+    BlendArgs A = blend_args(F, P, C, W, H, capacity);
+    SPLAT_CHECK_ARG(tiles_fit(A), "too many tiles");
+    set_lists(A, idx_sorted, tile_range);
+    set_tile_backward(A, final_T, ncontrib, dL_dout, slot_sorted, pair_records, dbg_T_front, cull_flags, 1);
+    set_pack(A, pack, pack_frame_floats(P, cn), 1);   // the chunk forward's records, one chunk wide
+    A.bg = bg;
     A.c0 = c0; A.cn = cn;
-    return bwd_chunk(A, T, false, true, (hipStream_t)stream);
+    return bwd_chunk(A, false, true, (hipStream_t)stream);
 }
 
 // Backward tile pass of up to three feature sets of one geometry in ONE launch (blend_bwd_sets_kernel): set 0 = the tap set
@@ -4473,13 +4452,17 @@ extern "C" int splat_alpha_blending_backward_batch_set_packed(int F, int P, int 
 extern "C" size_t splat_blend_sets_pair_stride(int C) { return (size_t)PAIR_STRIDE(SetsCfg::NG + C); }
 extern "C" size_t splat_blend_sets_pack_floats(void) { return (size_t)Rec<SetsCfg::CH>::RS; }
 
+// the renderer's own plan (rgb 0-2 | depth 3 | 19 attributes 4-22), unless the option asks for the generic routing
+static bool is_std_plan(int C, const int32_t *set_c0, const int32_t *set_cn) {
+    return C == 23 && set_c0[0] == 0 && set_cn[0] == 3 && set_c0[1] == 3 && set_cn[1] == 1 && set_c0[2] == 4 && set_cn[2] == 19 &&
+           sets_std_plan_enabled();
+}
+
 // Does splat_alpha_blending_backward_batch_sets_packed stage the FORWARD's packed records for this plan (no packing launch, no
 // pack_scratch needed)?  The one place the condition lives: callers ask instead of re-deriving it.
 extern "C" int splat_blend_sets_uses_forward_pack(int C, const int32_t *set_c0, const int32_t *set_cn, int has_cull_flags) {
     if (!set_c0 || !set_cn) return 0;
-    const bool std_plan = C == 23 && set_c0[0] == 0 && set_cn[0] == 3 && set_c0[1] == 3 && set_cn[1] == 1 && set_c0[2] == 4 &&
-                          set_cn[2] == 19 && sets_std_plan_enabled();
-    return (std_plan && has_cull_flags && bwd_use_quarters()) ? 1 : 0;
+    return (is_std_plan(C, set_c0, set_cn) && has_cull_flags && bwd_use_quarters()) ? 1 : 0;
 }
 
 static int backward_batch_sets_impl(int F, int P, int C, const int32_t *set_c0, const int32_t *set_cn,
@@ -4506,34 +4489,18 @@ static int backward_batch_sets_impl(int F, int P, int C, const int32_t *set_c0, 
     SPLAT_CHECK_ARG(dL_dout || set_dL, "image gradient: the row [F,C,H,W] or the sets' own tensors");
     SPLAT_CHECK_ARG(set_cn[0] >= 0 && set_cn[0] <= 4 && set_cn[1] >= 0 && set_cn[1] <= 4 && set_cn[2] >= 0 && set_cn[2] <= 20,
                     "set widths: tap set <= 4, second set <= 4, detached set <= 20 channels");
-    {   // the sets tile [0, C): every row channel has exactly one slot (every record component is written)
-        unsigned covered = 0u;
-        for (int g = 0; g < 3; ++g) {
-            SPLAT_CHECK_ARG(set_cn[g] == 0 || (set_c0[g] >= 0 && set_c0[g] + set_cn[g] <= C), "set outside the row");
-            for (int k = 0; k < set_cn[g]; ++k) {
-                SPLAT_CHECK_ARG(!(covered & (1u << (set_c0[g] + k))), "the sets overlap");
-                covered |= 1u << (set_c0[g] + k);
-            }
-        }
-        SPLAT_CHECK_ARG(covered == (C == 32 ? 0xffffffffu : (1u << C) - 1u), "the sets do not cover the row's channels");
-    }
-    BlendArgs A;
-    memset(&A, 0, sizeof(A));
-    A.P = P; A.C = C;
-    A.uv = (const float2 *)uv; A.conic = conic; A.opacity = opacity; A.feature = feature;
-    A.idx_sorted = idx_sorted; A.tile_range = (const int2 *)tile_range;
-    A.W = W; A.H = H; A.gx = (W + TILE - 1) / TILE;
-    A.final_T = const_cast<float *>(final_T); A.ncontrib = const_cast<int *>(ncontrib);
-    A.dL_dout = dL_dout;
-    A.slot_sorted = slot_sorted; A.pair_buf = pair_records;
-    A.pack = pack_scratch;
-    A.dbg_T_front = dbg_T_front;
-    A.cull_flags = const_cast<uint32_t *>(cull_flags);
-    const int T = A.gx * ((H + TILE - 1) / TILE);
-    A.F = F; A.T = T; A.cap = capacity; A.tile_only = 1;
-    A.pack_fs = (long long)P * (long long)Rec<SetsCfg::CH>::RS;
-    A.opacity_fs = opacity_frame_stride; A.feature_fs = feature_frame_stride;
-    A.c0 = 0; A.cn = C;
+    // the sets tile [0, C): every row channel has exactly one slot (every record component is written)
+    const RowCover cover = row_cover(C, 3, set_c0, set_cn, nullptr);
+    SPLAT_CHECK_ARG(cover != COVER_OUTSIDE, "set outside the row");
+    SPLAT_CHECK_ARG(cover != COVER_OVERLAP, "the sets overlap");
+    SPLAT_CHECK_ARG(cover != COVER_HOLE, "the sets do not cover the row's channels");
+    BlendArgs A = blend_args(F, P, C, W, H, capacity);
+    SPLAT_CHECK_ARG(tiles_fit(A), "too many tiles");
+    set_geometry(A, uv, conic, opacity, opacity_frame_stride, feature, feature_frame_stride);
+    set_lists(A, idx_sorted, tile_range);
+    set_tile_backward(A, final_T, ncontrib, dL_dout, slot_sorted, pair_records, dbg_T_front, cull_flags, 1);
+    set_pack(A, pack_scratch, (long long)P * (long long)Rec<SetsCfg::CH>::RS, 0);   // the sets' record, not a chunk's
+    A.c0 = 0; A.cn = C;   // (the backgrounds are the sets': s0bg .. s2bg)
     A.s0c0 = set_c0[0]; A.s0cn = set_cn[0]; A.s0bg = set_bg[0];
     A.s1c0 = set_c0[1]; A.s1cn = set_cn[1]; A.s1bg = set_bg[1];
     A.s2c0 = set_c0[2]; A.s2cn = set_cn[2]; A.s2bg = set_bg[2];
@@ -4564,39 +4531,40 @@ static int backward_batch_sets_impl(int F, int P, int C, const int32_t *set_c0, 
         A.l1_s0 = l1_scale[0]; A.l1_s1 = l1_scale[1]; A.l1_s2 = l1_scale[2];
     }
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)(T * F)), block(256);
-    // the renderer's own plan (rgb 0-2 | depth 3 | 19 attributes 4-22): channel gradients stored as whole float4
-    const bool std_plan = C == 23 && set_c0[0] == 0 && set_cn[0] == 3 && set_c0[1] == 3 && set_cn[1] == 1 && set_c0[2] == 4 &&
-                          set_cn[2] == 19 && sets_std_plan_enabled();
+    const dim3 grid((unsigned)(A.T * F)), block(256);
+    // the quarter-list kernel (the forward's quarter bits) as <ABS, STD, FWDREC, SMALL>
+    using yes = std::true_type;
+    using no = std::false_type;
+    auto quarter = [&](auto ABS, auto STD, auto FWDREC, auto SMALL) {
+        SPLAT_LAUNCH("blend_bwd", (blend_bwd_sets_quarter_kernel<decltype(ABS)::value, decltype(STD)::value, decltype(FWDREC)::value, decltype(SMALL)::value>),
+                     grid, block, 0, s, A);
+    };
     if (from_forward) {
         // the forward's packed records of this row (splat_alpha_blending_forward_batch_sets / _forward with C = 23: 32 floats per
         // Gaussian and frame) are staged directly: no packing launch
-        A.pack = const_cast<float *>(forward_pack);
-        A.pack_fs = (long long)P * 32;
-        if (want_abs) SPLAT_LAUNCH("blend_bwd", (blend_bwd_sets_quarter_kernel<true, true, true>), grid, block, 0, s, A);
-        else SPLAT_LAUNCH("blend_bwd", (blend_bwd_sets_quarter_kernel<false, true, true>), grid, block, 0, s, A);
+        set_pack(A, forward_pack, (long long)P * 32, 0);
+        dispatch_bools([&](auto ABS) { quarter(ABS, yes{}, yes{}, int_c<0>{}); }, want_abs != 0);
         SPLAT_POST_LAUNCH();
         return SPLAT_OK;
     }
     SPLAT_CHECK_ARG(pack_scratch, "pack_scratch is needed: the forward's records do not serve this plan / these kernels");
     SPLAT_LAUNCH("blend_pack", pack_sets_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)F), dim3(256), 0, s, A);
     SPLAT_POST_LAUNCH();
-    if (A.cull_flags && bwd_use_quarters()) {   // quarter lists (the forward's quarter bits)
-        // a detached set of at most four / eight channels leaves slots 12 .. / 16 .. 27 empty: the SMALL instantiations
+    if (A.cull_flags && bwd_use_quarters()) {
+        // the renderer's own plan stores the channel gradients as whole float4; of the others, a detached set of at most four /
+        // eight channels leaves slots 12 .. / 16 .. 27 empty: the SMALL instantiations
+        const bool std_plan = is_std_plan(C, set_c0, set_cn);
         const int small = std_plan ? 0 : set_cn[2] <= 4 ? 3 : set_cn[2] <= 8 ? 4 : 0;
-        if (want_abs) {
-            if (std_plan) SPLAT_LAUNCH("blend_bwd", (blend_bwd_sets_quarter_kernel<true, true>), grid, block, 0, s, A);
-            else if (small == 3) SPLAT_LAUNCH("blend_bwd", (blend_bwd_sets_quarter_kernel<true, false, false, 3>), grid, block, 0, s, A);
-            else if (small == 4) SPLAT_LAUNCH("blend_bwd", (blend_bwd_sets_quarter_kernel<true, false, false, 4>), grid, block, 0, s, A);
-            else SPLAT_LAUNCH("blend_bwd", (blend_bwd_sets_quarter_kernel<true, false>), grid, block, 0, s, A);
-        } else {
-            if (std_plan) SPLAT_LAUNCH("blend_bwd", (blend_bwd_sets_quarter_kernel<false, true>), grid, block, 0, s, A);
-            else if (small == 3) SPLAT_LAUNCH("blend_bwd", (blend_bwd_sets_quarter_kernel<false, false, false, 3>), grid, block, 0, s, A);
-            else if (small == 4) SPLAT_LAUNCH("blend_bwd", (blend_bwd_sets_quarter_kernel<false, false, false, 4>), grid, block, 0, s, A);
-            else SPLAT_LAUNCH("blend_bwd", (blend_bwd_sets_quarter_kernel<false, false>), grid, block, 0, s, A);
-        }
-    } else if (want_abs) SPLAT_LAUNCH("blend_bwd", blend_bwd_sets_kernel<true>, grid, block, 0, s, A);
-    else SPLAT_LAUNCH("blend_bwd", blend_bwd_sets_kernel<false>, grid, block, 0, s, A);
+        dispatch_bools([&](auto ABS) {
+            if (std_plan) quarter(ABS, yes{}, no{}, int_c<0>{});
+            else if (small == 3) quarter(ABS, no{}, no{}, int_c<3>{});
+            else if (small == 4) quarter(ABS, no{}, no{}, int_c<4>{});
+            else quarter(ABS, no{}, no{}, int_c<0>{});
+        }, want_abs != 0);
+    } else {
+        dispatch_bools([&](auto ABS) { SPLAT_LAUNCH("blend_bwd", blend_bwd_sets_kernel<decltype(ABS)::value>, grid, block, 0, s, A); },
+                       want_abs != 0);
+    }
     SPLAT_POST_LAUNCH();
     return SPLAT_OK;
 }
@@ -4643,12 +4611,6 @@ extern "C" int splat_alpha_blending_backward_batch_sets_packed(int F, int P, int
                                     cull_flags, dbg_T_front, forward_pack, stream);
 }
 
-// Per-Gaussian sums of pair records of ANY layout: out[i, :] = sum of the records in Gaussian i's slots [goff_incl[i-1],
-// goff_incl[i]) (stride `ncp` floats, a multiple of 4).  The SINGLE-FRAME use of splat_alpha_blending_backward_batch_sets
-// (F = 1: the per-frame operator gs.alpha_blending_shared, where the three blends are separate from the projection and the
-// gradients go back to autograd as d uv / d conic / d opacity / d feature): the caller slices the summed SETS record
-// [ux uy ca cb | cc o ax ay | tx ty 0 0 | row channels].  A thread per (Gaussian, 16-byte chunk): the threads of a record read
-// it contiguously.  out is fully written ([P, ncp]); deterministic (slot order).
 // splat_alpha_blending_backward_batch_sets_packed with the L1 image loss FUSED into the tile kernel's hoist of the image gradient:
 // set_target[g] = the set's target image [F, cn, H, W] (instead of a gradient image), pred_row = the forward's output row
 // [F, C, H, W], the gradient of a channel of set g is l1_scale_host[g] * sign(pred - target) and l1_sum[(f * tiles + t) * 3 + g]
@@ -4673,6 +4635,12 @@ extern "C" int splat_alpha_blending_backward_batch_sets_l1(int F, int P, int C, 
                                     forward_pack, stream, pred_row, l1_scale_host, l1_sum);
 }
 
+// Per-Gaussian sums of pair records of ANY layout: out[i, :] = sum of the records in Gaussian i's slots [goff_incl[i-1],
+// goff_incl[i]) (stride `ncp` floats, a multiple of 4).  The SINGLE-FRAME use of splat_alpha_blending_backward_batch_sets
+// (F = 1: the per-frame operator gs.alpha_blending_shared, where the three blends are separate from the projection and the
+// gradients go back to autograd as d uv / d conic / d opacity / d feature): the caller slices the summed SETS record
+// [ux uy ca cb | cc o ax ay | tx ty 0 0 | row channels].  A thread per (Gaussian, 16-byte chunk): the threads of a record read
+// it contiguously.  out is fully written ([P, ncp]); deterministic (slot order).
 namespace {
 __global__ void __launch_bounds__(256)
 records_segment_sum_kernel(int P, int nq, const float4 *__restrict__ rec, const int *__restrict__ goff, float4 *__restrict__ out) {

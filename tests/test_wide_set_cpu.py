@@ -90,6 +90,26 @@ def test_backward_chunk_validates_before_hip(L):
     assert _bwd(lib, W=1 << 16, H=1 << 16, F=1 << 10) == -1 and b"too many tiles" in lib.splat_last_error()
 
 
+def test_every_frame_batch_backward_refuses_too_many_tiles(L):
+    """F * tiles must fit an int in every frame-batch entry of csrc/blend.hip: the row's, the set's and the three-set backward
+    refuse the shape their forward refuses (the chunk's twin is checked above)"""
+    lib = L.lib()
+    F, W, H = 1 << 10, 1 << 16, 1 << 16
+
+    def i3(*v):
+        return (ctypes.c_int32 * 3)(*v)
+
+    assert lib.splat_alpha_blending_backward_batch(F, 10, 3, ONE, ONE, 100, 0.0, W, H, ONE, ONE, ONE, 0, ONE, ONE, ONE, ONE, None, None) == -1
+    assert lib.splat_last_error() == b"splat_alpha_blending_backward_batch: too many tiles"
+    assert lib.splat_alpha_blending_backward_batch_set(F, 10, 23, 4, 19, ONE, ONE, ONE, 0, ONE, 0, ONE, ONE, 100, 0.0, W, H, ONE, ONE, ONE,
+                                                       0, ONE, ONE, ONE, None, None) == -1
+    assert lib.splat_last_error() == b"splat_alpha_blending_backward_batch_set: too many tiles"
+    assert lib.splat_alpha_blending_backward_batch_sets(F, 10, 23, i3(0, 3, 4), i3(3, 1, 19), (F32 * 3)(0.2, 1.0, 0.0), ONE, ONE, ONE, 0,
+                                                        ONE, 0, None, None, ONE, ONE, 100, W, H, ONE, ONE, ONE, None, 0, ONE, ONE, ONE,
+                                                        ONE, None, None) == -1
+    assert lib.splat_last_error().endswith(b": too many tiles")
+
+
 def test_fold_validates_before_hip(L):
     lib = L.lib()
     assert _fold(lib, F=0) == -1 and b"sizes" in lib.splat_last_error() and FOLD.encode() in lib.splat_last_error()
