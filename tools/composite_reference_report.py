@@ -2,11 +2,13 @@
 
     python tools/composite_reference_report.py --backend float32 --out profiles/composite_reference_cpu_float32.json
     python tools/composite_reference_report.py --backend hip     --out profiles/composite_reference_gpu.json
+    python tools/composite_reference_report.py --backend hip-frames --out profiles/frames_composite_reference_gpu.json
 
 ``--backend float32`` is the numpy float32 restatement of the kernels' arithmetic on the CPU: its worst error / companion per
 output gives the K of every bar (smallest power of two at or above 4 x the ratio), which tests/test_composite_ref_cpu.py
 re-checks.  ``--backend hip`` runs every case of tests/test_gpu_composite_reference.py and records the worst error / bar per
 route and output, what the kernels write into the gradient rows of non-finite operands, and the library's build id.
+``--backend hip-frames`` does the same for the frame batch's entry points (tests/test_gpu_frames_composite_reference.py).
 """
 import argparse
 import json
@@ -20,7 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--backend", choices=["float32", "hip"], required=True)
+    ap.add_argument("--backend", choices=["float32", "hip", "hip-frames"], required=True)
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     import oracle
@@ -32,7 +34,10 @@ def main():
     else:
         import torch
         from splatter_a_video_amd import _lib as L
-        import test_gpu_composite_reference as t
+        if a.backend == "hip-frames":
+            import test_gpu_frames_composite_reference as t
+        else:
+            import test_gpu_composite_reference as t
         worst, nonfinite = t.measure()
         rnd = lambda d: {k: (rnd(v) if isinstance(v, dict) else float(f"{v:.4g}")) for k, v in sorted(d.items())}
         rec = dict(what="worst |error| / bar per route and output (1.0 = on the bar; bar = K x companion, K from "
