@@ -280,14 +280,20 @@ def forward(wk: Walk, feature, bg):
 GRADS = ("uv", "conic", "opacity", "feature", "bias", "abs_uv")
 
 
-def backward(wk: Walk, conic, opacity, feature, bg, dL_dout, companions=True):
+def backward(wk: Walk, conic, opacity, feature, bg, dL_dout, companions=True, dL_mag=None, mult=None, geom_mult=1):
     """The back-to-front recurrence, written out:  dL/dalpha_i = T_i f_i.g - S_after_i / (1 - alpha_i),
     S_after_i = sum_{j > i} w_j f_j.g + T_final bg.g;  dL/dpower = dL/dalpha o exp(power) (straight-through clamp).
-    Returns (grads, comps): dicts over GRADS; abs_uv sums |.| of the uv terms per chunk of 32 channels."""
+    Returns (grads, comps): dicts over GRADS; abs_uv sums |.| of the uv terms per chunk of 32 channels.
+    For a pixel gradient that is itself a sum of several terms (tests/points_ref.py: the corner terms of sparse queries):
+    dL_mag [C,H,W] = the sum of the terms' magnitudes, which the companions then use instead of |dL_dout|; mult [H,W] = the
+    terms per pixel, counted instead of 1 in the "n eps x magnitude" term; geom_mult = how often every term is added to the
+    geometry gradients (once per launch over a chunk of channels).  The defaults leave every result as it was, bit for bit."""
     f = _f64(feature)
     N, C = f.shape
     cn = _f64(conic).reshape(-1, 3)
     gim = _f64(dL_dout).reshape(C, wk.H, wk.W)
+    gmag = None if dL_mag is None else _f64(dL_mag).reshape(C, wk.H, wk.W)
+    pmult = None if mult is None else _f64(mult).reshape(wk.H, wk.W)
     bgv = _bg_vec(bg, C)
     shp = dict(uv=(N, 2), conic=(N, 3), opacity=(N,), feature=(N, C), bias=(N,), abs_uv=(N, 2))
     g = {k: np.zeros(s) for k, s in shp.items()}
@@ -328,6 +334,8 @@ def backward(wk: Walk, conic, opacity, feature, bg, dL_dout, companions=True):
             continue
         # ---- the same sums over magnitudes, each term weighted by the error accumulated at its entry
         ga, fa = np.abs(gp_), np.abs(ft)
+        if gmag is not None:
+            ga = gmag[:, t.y0:t.y0 + t.ny, t.x0:t.x0 + t.nx].reshape(C, -1)
         napp = app.sum(0)
         R = t.ETf + (napp + C + 8) * EPS                                       # [P]: transmittance (either direction), sums, dot
         r = np.where(app, R[None, :] + t.ea * (1.0 + t.alpha / one_m), 0.0)
@@ -356,13 +364,18 @@ def backward(wk: Walk, conic, opacity, feature, bg, dL_dout, companions=True):
         cm["bias"][ids] += magL.sum(1)
         ce["feature"][ids] += (w * (t.ET + t.ea + 2 * EPS)) @ ga.T
         cm["feature"][ids] += w @ ga.T
-        cnt[ids] += app.sum(1)
+        if pmult is None:
+            cnt[ids] += app.sum(1)
+        else:
+            cnt[ids] += (app * pmult[t.y0:t.y0 + t.ny, t.x0:t.x0 + t.nx].reshape(1, -1)).sum(1)
     if not companions:
         return g, None
     ce["abs_uv"], cm["abs_uv"] = ce["uv"], cm["uv"]
     comps = {}
     for k in GRADS:
         n = cnt.reshape((N,) + (1,) * (len(shp[k]) - 1))
+        if geom_mult != 1 and k not in ("feature",):
+            n = n * geom_mult
         comps[k] = ce[k] + (n + 4) * EPS * cm[k]
     return g, comps
 
