@@ -1,5 +1,5 @@
 """ctypes binding of libsplat_hip.so (C ABI: include/splat_hip.h and its extensions include/splat_hip_views.h,
-include/splat_hip_views_grad.h, include/splat_hip_camera_grad.h and include/splat_hip_layers_cam.h).
+include/splat_hip_views_grad.h, include/splat_hip_camera_grad.h, include/splat_hip_layers_cam.h and include/splat_hip_flow.h).
 
 The product path has NO fallback: if the HIP library is missing or a tensor is not a contiguous
 float32/int32 CUDA tensor the call raises.  (The CPU oracle lives in ``oracle/`` and is never
@@ -36,16 +36,17 @@ FeatureSource = HEADER.structs["splat_feature_source_t"]
 # structs and brings none of its own: the names its prototypes use are the core header's), the same library, a version of their
 # own.  One row per extension: (file name, version define, version function) -- the cameras per frame and the pinhole camera of a
 # dynamic batch; training under those cameras; the camera gradients of a dynamic batch; layered scenes (layer editing, feature
-# lifting) under those cameras
+# lifting) under those cameras; dense optical flow (the flow attribute of frame pairs, flow colours, flow error)
 EXTENSIONS = (("splat_hip_views.h", "SPLAT_VIEWS_ABI_VERSION", "splat_views_abi_version"),
               ("splat_hip_views_grad.h", "SPLAT_VIEWS_GRAD_ABI_VERSION", "splat_views_grad_abi_version"),
               ("splat_hip_camera_grad.h", "SPLAT_CAMERA_GRAD_ABI_VERSION", "splat_camera_grad_abi_version"),
-              ("splat_hip_layers_cam.h", "SPLAT_LAYERS_CAM_ABI_VERSION", "splat_layers_cam_abi_version"))
+              ("splat_hip_layers_cam.h", "SPLAT_LAYERS_CAM_ABI_VERSION", "splat_layers_cam_abi_version"),
+              ("splat_hip_flow.h", "SPLAT_FLOW_ABI_VERSION", "splat_flow_abi_version"))
 _EXT = tuple(_load(file, HEADER) for file, _, _ in EXTENSIONS)
-VIEWS_HEADER, VIEWS_GRAD_HEADER, CAMERA_GRAD_HEADER, LAYERS_CAM_HEADER = _EXT
-VIEWS_ABI_VERSION, VIEWS_GRAD_ABI_VERSION, CAMERA_GRAD_ABI_VERSION, LAYERS_CAM_ABI_VERSION = (
+VIEWS_HEADER, VIEWS_GRAD_HEADER, CAMERA_GRAD_HEADER, LAYERS_CAM_HEADER, FLOW_HEADER = _EXT
+VIEWS_ABI_VERSION, VIEWS_GRAD_ABI_VERSION, CAMERA_GRAD_ABI_VERSION, LAYERS_CAM_ABI_VERSION, FLOW_ABI_VERSION = (
     h.defines[define] for h, (_, define, _) in zip(_EXT, EXTENSIONS))
-VIEWS_SYMBOLS, VIEWS_GRAD_SYMBOLS, CAMERA_GRAD_SYMBOLS, LAYERS_CAM_SYMBOLS = (list(h.functions) for h in _EXT)
+VIEWS_SYMBOLS, VIEWS_GRAD_SYMBOLS, CAMERA_GRAD_SYMBOLS, LAYERS_CAM_SYMBOLS, FLOW_SYMBOLS = (list(h.functions) for h in _EXT)
 
 
 class SplatError(RuntimeError):

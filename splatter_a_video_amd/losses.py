@@ -399,3 +399,33 @@ def depth_loss_dpt(pred_depth: torch.Tensor, gt_depth: torch.Tensor, weight=None
     if pred_depth.shape != gt_depth.shape:
         raise ValueError(f"depth_loss_dpt: shapes differ: {tuple(pred_depth.shape)} vs {tuple(gt_depth.shape)}")
     return _DepthDPT.apply(_depth_frames(pred_depth, "pred_depth"), _depth_frames(gt_depth, "gt_depth"))
+
+
+class _FlowL1(torch.autograd.Function):
+    """mean over the maps of the weighted-mean L1; the forward's one call also writes the gradient (scale = 1 / T)"""
+
+    @staticmethod
+    def forward(ctx, pred, gt, weight):
+        from .flow import flow_error_sums
+        sums, grad = flow_error_sums(pred.detach(), gt, weight, scale=1.0 / pred.shape[0], want_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(grad)
+        return (sums[:, 0] / sums[:, 2].clamp_min(1e-30)).mean().to(torch.float32)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None
+
+
+def flow_l1(pred: torch.Tensor, gt: torch.Tensor, weight=None) -> torch.Tensor:
+    """the trainer's earlier flow term ``masked_l1_loss(pred_flow, gt_flow, weights)`` (src/trainer_fragGS.py:525-526) on flow
+    maps [T, 2, H, W]: per map ``sum w (|du| + |dv|) / sum w`` (``weight`` [T, H, W]; None: 1), then the mean over the maps; a
+    map whose weights are all zero contributes 0.  One call each way (csrc/flow.hip: float32 partials of 2048 pixels folded in
+    float64 in a fixed order, no float atomics: bit-reproducible).  Differentiable w.r.t. ``pred`` (once); ``gt`` and
+    ``weight`` are data."""
+    _check(pred, "pred")
+    _check(gt, "gt")
+    if gt.requires_grad or (isinstance(weight, torch.Tensor) and weight.requires_grad):
+        raise ValueError("flow_l1: gt and weight are data; detach them (no gradient with respect to them is computed)")
+    return _FlowL1.apply(pred, gt, weight)

@@ -192,7 +192,8 @@ class _Clip:
     """the model, the feature sets and the frame batch of one clip; ``batch`` renders ``F`` frames and never returns a batch
     whose tile-Gaussian pairs outgrew the pair capacity (the ``LayeredClip`` rule)"""
 
-    def __init__(self, model, clock, W, H, sets, frames_per_batch, K, nearest, extent, bg, shs, cubic_layout, capacity, wide):
+    def __init__(self, model, clock, W, H, sets, frames_per_batch, K, nearest, extent, bg, shs, cubic_layout, capacity, wide,
+                 differentiable: bool = False):
         from .frames import FrameBatch
         from .layers import _params
         if isinstance(frames_per_batch, bool) or int(frames_per_batch) != frames_per_batch or not (1 <= int(frames_per_batch) <= 65535):
@@ -220,14 +221,16 @@ class _Clip:
         self.F, self.W, self.H, self.K = int(frames_per_batch), int(W), int(H), int(K)
         self.nearest, self.extent = float(nearest), float(extent)
         self.fb = FrameBatch(self.F, int(pos.shape[0]), self.W, self.H, sum(self.widths), self.dev,
-                             capacity=None if capacity is None else int(capacity), records=False)      # forward only
+                             capacity=None if capacity is None else int(capacity), records=bool(differentiable))
+        self.differentiable = bool(differentiable)      # False: forward only (no pair-record buffer); flow.render_flow opts in
         self.regrows = 0            # batches rendered again after their pairs outgrew the capacity
 
     def batch(self, times, extr: Tensor, intr: Optional[Tensor]):
         fb = self.fb
         while True:
             res = fb.render_dynamic_sets(self.clock, times, extr, self.sets, cubic_layout=self.layout, K=self.K, nearest=self.nearest,
-                                         extent=self.extent, wide=self.wide, intr=intr, **self.geo)
+                                         extent=self.extent, wide=self.wide, intr=intr, **self.geo,
+                                         **(dict(differentiable=True) if self.differentiable else {}))
             try:
                 fb.check()          # the pair counts are on the device: one synchronisation per batch
                 return res
