@@ -1,6 +1,6 @@
 """Reader of the C ABI's headers (include/splat_hip.h and its extensions include/splat_hip_views.h,
-include/splat_hip_views_grad.h, include/splat_hip_camera_grad.h, include/splat_hip_layers_cam.h and include/splat_hip_flow.h): prototypes, structs and
-integer #defines as ctypes types.
+include/splat_hip_views_grad.h, include/splat_hip_camera_grad.h, include/splat_hip_layers_cam.h, include/splat_hip_flow.h and
+include/splat_hip_flow_occ.h): prototypes, structs and integer #defines as ctypes types.
 
 The header is the only place a prototype is written; ``_lib.lib()`` applies what ``parse`` yields to every function.
 Anything the reader does not understand raises ``HeaderError`` -- it never guesses a type.

@@ -1,5 +1,6 @@
 """ctypes binding of libsplat_hip.so (C ABI: include/splat_hip.h and its extensions include/splat_hip_views.h,
-include/splat_hip_views_grad.h, include/splat_hip_camera_grad.h, include/splat_hip_layers_cam.h and include/splat_hip_flow.h).
+include/splat_hip_views_grad.h, include/splat_hip_camera_grad.h, include/splat_hip_layers_cam.h, include/splat_hip_flow.h and
+include/splat_hip_flow_occ.h).
 
 The product path has NO fallback: if the HIP library is missing or a tensor is not a contiguous
 float32/int32 CUDA tensor the call raises.  (The CPU oracle lives in ``oracle/`` and is never
@@ -47,6 +48,13 @@ VIEWS_HEADER, VIEWS_GRAD_HEADER, CAMERA_GRAD_HEADER, LAYERS_CAM_HEADER, FLOW_HEA
 VIEWS_ABI_VERSION, VIEWS_GRAD_ABI_VERSION, CAMERA_GRAD_ABI_VERSION, LAYERS_CAM_ABI_VERSION, FLOW_ABI_VERSION = (
     h.defines[define] for h, (_, define, _) in zip(_EXT, EXTENSIONS))
 VIEWS_SYMBOLS, VIEWS_GRAD_SYMBOLS, CAMERA_GRAD_SYMBOLS, LAYERS_CAM_SYMBOLS, FLOW_SYMBOLS = (list(h.functions) for h in _EXT)
+# extension headers after those five (EXTENSIONS keeps its rows): where a dense flow is valid -- the flow attribute with the
+# depth, occlusion masks and warped frames
+LATER_EXTENSIONS = (("splat_hip_flow_occ.h", "SPLAT_FLOW_OCC_ABI_VERSION", "splat_flow_occ_abi_version"),)
+_LATER = tuple(_load(file, HEADER) for file, _, _ in LATER_EXTENSIONS)
+FLOW_OCC_HEADER, = _LATER
+FLOW_OCC_ABI_VERSION = FLOW_OCC_HEADER.defines[LATER_EXTENSIONS[0][1]]
+FLOW_OCC_SYMBOLS = list(FLOW_OCC_HEADER.functions)
 
 
 class SplatError(RuntimeError):
@@ -65,7 +73,7 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C splatter_a_video_amd/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
         L = ctypes.CDLL(LIB_PATH)
-        headers = ((CORE, HEADER),) + tuple(zip(EXTENSIONS, _EXT))
+        headers = ((CORE, HEADER),) + tuple(zip(EXTENSIONS, _EXT)) + tuple(zip(LATER_EXTENSIONS, _LATER))
         for (file, _, _), h in headers:
             for name, (restype, argtypes) in h.functions.items():
                 fn = getattr(L, name, None)

@@ -3,7 +3,9 @@
 // with util.flow_to_image (src/util.py:421-536).  Here:
 //   - the per-Gaussian flow attribute of a batch of frame pairs and its gradient (one launch each way),
 //   - the Middlebury colouring on the device (maximum radius: partials + fold; colouring),
-//   - the flow error sums against a reference flow with the gradient of the weighted-mean L1.
+//   - the flow error sums against a reference flow with the gradient of the weighted-mean L1,
+//   - (include/splat_hip_flow_occ.h) the attribute with the depth -- the same two kernels, templated on the channel count --
+//     and the fused per-pixel occlusion / warp kernel, whose decisions follow from the bits of a float32 restatement.
 // This file is compiled with -ffp-contract=off (Makefile): every product and sum below is rounded once, so that the two
 // projections of a pair are the same instructions whatever the compiler inlines where (a pair of equal times gives +0.0)
 // and the float32 steps of the colouring are the ones numpy takes.  The spline position alone carries one explicit
@@ -11,7 +13,7 @@
 #include "common.h"
 #include "dynamics_dev.h"
 #include "pointwise_dev.h"
-#include "../../include/splat_hip_flow.h"
+#include "../../include/splat_hip_flow_occ.h"
 
 namespace {
 
@@ -47,55 +49,67 @@ __device__ __forceinline__ void spline_position(const float *__restrict__ cubic,
 
 template <bool PERSP>
 __device__ __forceinline__ bool project_pt(const Cam &c, const float p[3], int W, int H, float nearest, float extent, float &u,
-                                           float &v) {
-    float d;
+                                           float &v, float &d) {
     return PERSP ? project_persp_pt(c, p[0], p[1], p[2], W, H, nearest, extent, u, v, d)
                  : project_ortho_pt(c, p[0], p[1], p[2], W, H, nearest, extent, u, v, d);
 }
 
+// the attribute's row: NCH = 2 (u2 - u1, v2 - v1), NCH = 4 (..., z2 - z1, z2), one store of 8 or 16 bytes
+template <int NCH> struct FlowRow;
+template <> struct FlowRow<2> { using type = float2; };
+template <> struct FlowRow<4> { using type = float4; };
+
 // One lane per Gaussian walks its slice of the pairs (grid.y slices them as dynamic_positions_fwd_kernel slices its frames):
-// base position read once, per pair the two 48-byte spline records, two projections, one 8-byte store.
-template <bool PERSP>
+// base position read once, per pair the two 48-byte spline records, two projections, one 8-byte (NCH = 4: 16-byte) store.
+template <bool PERSP, int NCH>
 __global__ __launch_bounds__(FLOW_BLOCK) void flow_attribute_kernel(int F, int P, int I, int layout,
                                                                     const DynTab *__restrict__ tab1,
                                                                     const DynTab *__restrict__ tab2,
                                                                     const float *__restrict__ position,
                                                                     const float *__restrict__ cubic, FlowCam fc1, FlowCam fc2,
                                                                     int W, int H, float nearest, float extent, int zero_culled,
-                                                                    float2 *__restrict__ flow) {
+                                                                    typename FlowRow<NCH>::type *__restrict__ flow) {
     const size_t n = (size_t)blockIdx.x * FLOW_BLOCK + threadIdx.x;
     if (n >= (size_t)P) return;
     const float base[3] = {position[n * 3], position[n * 3 + 1], position[n * 3 + 2]};
     const int per = (F + gridDim.y - 1) / gridDim.y;
     const int f0 = blockIdx.y * per, f1 = imin_(F, f0 + per);
     for (int f = f0; f < f1; ++f) {
-        float p1[3], p2[3], u1, v1, u2, v2;
+        float p1[3], p2[3], u1, v1, z1, u2, v2, z2;
         Cam c1, c2;
         spline_position(cubic, cubic_addr(layout, P, I, tab1[f].seg), n, tab1[f].d, base, p1);
         spline_position(cubic, cubic_addr(layout, P, I, tab2[f].seg), n, tab2[f].d, base, p2);
         load_flow_cam(fc1, f, c1);
         load_flow_cam(fc2, f, c2);
-        const bool cull1 = project_pt<PERSP>(c1, p1, W, H, nearest, extent, u1, v1);
-        const bool cull2 = project_pt<PERSP>(c2, p2, W, H, nearest, extent, u2, v2);
-        if (cull1) u1 = v1 = 0.f;
-        if (cull2) u2 = v2 = 0.f;
-        float2 o = make_float2(u2 - u1, v2 - v1);
-        if (zero_culled && (cull1 || cull2)) o = make_float2(0.f, 0.f);
-        flow[(size_t)f * P + n] = o;
+        const bool cull1 = project_pt<PERSP>(c1, p1, W, H, nearest, extent, u1, v1, z1);
+        const bool cull2 = project_pt<PERSP>(c2, p2, W, H, nearest, extent, u2, v2, z2);
+        if (cull1) u1 = v1 = z1 = 0.f;
+        if (cull2) u2 = v2 = z2 = 0.f;
+        const bool none = zero_culled && (cull1 || cull2);
+        if constexpr (NCH == 2) {
+            float2 o = make_float2(u2 - u1, v2 - v1);
+            if (none) o = make_float2(0.f, 0.f);
+            flow[(size_t)f * P + n] = o;
+        } else {
+            float4 o = make_float4(u2 - u1, v2 - v1, z2 - z1, z2);
+            if (none) o = make_float4(0.f, 0.f, 0.f, 0.f);
+            flow[(size_t)f * P + n] = o;
+        }
     }
 }
 
 // Backward: the lane owns its Gaussian's rows of d_position and d_cubic (no atomics).  It walks the pairs in tab1's walk
 // order (dynamic_positions_bwd_kernel's) and keeps, for each of the two times of a pair, the coefficient sums of the current
 // segment in registers; a side's sums are added to memory when that side's walk leaves the segment.
-template <bool PERSP>
+template <bool PERSP, int NCH>
 __global__ __launch_bounds__(FLOW_BLOCK) void flow_attribute_bwd_kernel(int F, int P, int I, int layout,
                                                                         const DynTab *__restrict__ tab1,
                                                                         const DynTab *__restrict__ tab2,
                                                                         const float *__restrict__ position,
                                                                         const float *__restrict__ cubic, FlowCam fc1,
                                                                         FlowCam fc2, int W, int H, float nearest, float extent,
-                                                                        int zero_culled, const float2 *__restrict__ g,
+                                                                        int zero_culled,
+                                                                        const typename FlowRow<NCH>::type *__restrict__ g,
                                                                         float *__restrict__ d_position,
                                                                         float *__restrict__ d_cubic) {
     const size_t n = (size_t)blockIdx.x * FLOW_BLOCK + threadIdx.x;
@@ -124,7 +138,7 @@ __global__ __launch_bounds__(FLOW_BLOCK) void flow_attribute_bwd_kernel(int F, i
         const int o = __float_as_int(tab1[i].pad[0]);
         const int f = (o >= 1 && o <= F) ? o - 1 : i;
         const DynTab *tabs[2] = {tab1 + f, tab2 + f};
-        float p[2][3], u, v;
+        float p[2][3], u, v, z;
         Cam c[2];
         bool cull[2];
         load_flow_cam(fc1, f, c[0]);
@@ -132,9 +146,9 @@ __global__ __launch_bounds__(FLOW_BLOCK) void flow_attribute_bwd_kernel(int F, i
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             spline_position(cubic, cubic_addr(layout, P, I, tabs[s]->seg), n, tabs[s]->d, base, p[s]);
-            cull[s] = project_pt<PERSP>(c[s], p[s], W, H, nearest, extent, u, v);
+            cull[s] = project_pt<PERSP>(c[s], p[s], W, H, nearest, extent, u, v, z);
         }
-        const float2 gf = g[(size_t)f * P + n];
+        const auto gf = g[(size_t)f * P + n];
         const bool none = zero_culled && (cull[0] || cull[1]);
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
@@ -146,9 +160,11 @@ __global__ __launch_bounds__(FLOW_BLOCK) void flow_attribute_bwd_kernel(int F, i
             }
             if (none || cull[s]) continue;
             const float sg = s == 0 ? -1.f : 1.f;   // flow = uv2 - uv1
+            float gd = 0.f;                          // NCH = 4: z2 - z1 and z2
+            if constexpr (NCH == 4) gd = s == 0 ? -gf.z : gf.z + gf.w;
             float gp[3];
-            if (PERSP) project_persp_grad_pt(c[s], p[s][0], p[s][1], p[s][2], sg * gf.x, sg * gf.y, 0.f, gp);
-            else project_ortho_grad_pt(c[s], W, H, sg * gf.x, sg * gf.y, 0.f, gp);
+            if (PERSP) project_persp_grad_pt(c[s], p[s][0], p[s][1], p[s][2], sg * gf.x, sg * gf.y, gd, gp);
+            else project_ortho_grad_pt(c[s], W, H, sg * gf.x, sg * gf.y, gd, gp);
             const float d = tabs[s]->d, d2 = d * d, d3 = d2 * d;
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
@@ -172,6 +188,15 @@ __global__ __launch_bounds__(FLOW_BLOCK) void flow_attribute_bwd_kernel(int F, i
             splat_set_error("%s: %s", who, msg);   \
             return SPLAT_E_ARG;                    \
         }                                          \
+    } while (0)
+
+#define FLOW_CHECK_HIP(who, expr)                                                 \
+    do {                                                                          \
+        hipError_t e_ = (expr);                                                   \
+        if (e_ != hipSuccess) {                                                   \
+            splat_set_error("%s: %s -> %s", who, #expr, hipGetErrorString(e_));   \
+            return SPLAT_E_LAUNCH;                                                \
+        }                                                                         \
     } while (0)
 
 int flow_camera(const char *who, const splat_camera_t *cam, FlowCam &fc) {
@@ -385,15 +410,20 @@ __global__ __launch_bounds__(FLOW_BLOCK) void flow_error_grad_kernel(int HW, con
 
 extern "C" int splat_flow_abi_version(void) { return SPLAT_FLOW_ABI_VERSION; }
 
-extern "C" int splat_flow_attribute_batch(int F, int P, int I, const void *tab1, const void *tab2, const float *position,
-                                          const float *cubic, int cubic_layout, const splat_camera_t *cam1,
-                                          const splat_camera_t *cam2, int W, int H, float nearest, float extent, int zero_culled,
-                                          float *flow, void *stream) {
+namespace {
+
+// both channel counts: the checks, the grid and the launch of the forward (`who`: the entry point's name)
+template <int NCH>
+int flow_attribute_launch(const char *who, int F, int P, int I, const void *tab1, const void *tab2, const float *position,
+                          const float *cubic, int cubic_layout, const splat_camera_t *cam1, const splat_camera_t *cam2, int W,
+                          int H, float nearest, float extent, int zero_culled, float *flow, void *stream) {
+    using Row = typename FlowRow<NCH>::type;
     FlowCam fc1, fc2;
     bool persp = false;
-    if (int rc = flow_args(__func__, F, P, I, tab1, tab2, position, cubic, cubic_layout, cam1, cam2, W, H, fc1, fc2, persp)) return rc;
+    if (int rc = flow_args(who, F, P, I, tab1, tab2, position, cubic, cubic_layout, cam1, cam2, W, H, fc1, fc2, persp)) return rc;
     if (F == 0 || P == 0) return SPLAT_OK;
-    SPLAT_CHECK_ARG(flow != nullptr && ((uintptr_t)flow & 7) == 0, "null / misaligned output (flow: 8-byte aligned)");
+    FLOW_CHECK(who, flow != nullptr && ((uintptr_t)flow & (sizeof(Row) - 1)) == 0,
+               NCH == 2 ? "null / misaligned output (flow: 8-byte aligned)" : "null / misaligned output (out: 16-byte aligned)");
     const unsigned blocks = (unsigned)(((size_t)P + FLOW_BLOCK - 1) / FLOW_BLOCK);
     unsigned slices = 1;   // enough workgroups to fill the chip: slice the pairs when the Gaussians alone do not
     while (blocks * slices < 2048u && slices < (unsigned)F) slices *= 2;
@@ -401,15 +431,57 @@ extern "C" int splat_flow_attribute_batch(int F, int P, int I, const void *tab1,
     const dim3 grid(blocks, slices);
     hipStream_t s = (hipStream_t)stream;
     if (persp)
-        SPLAT_LAUNCH("flow_attribute", flow_attribute_kernel<true>, grid, dim3(FLOW_BLOCK), 0, s, F, P, I, cubic_layout,
+        SPLAT_LAUNCH("flow_attribute", (flow_attribute_kernel<true, NCH>), grid, dim3(FLOW_BLOCK), 0, s, F, P, I, cubic_layout,
                      (const DynTab *)tab1, (const DynTab *)tab2, position, cubic, fc1, fc2, W, H, nearest, extent, zero_culled,
-                     (float2 *)flow);
+                     (Row *)flow);
     else
-        SPLAT_LAUNCH("flow_attribute", flow_attribute_kernel<false>, grid, dim3(FLOW_BLOCK), 0, s, F, P, I, cubic_layout,
+        SPLAT_LAUNCH("flow_attribute", (flow_attribute_kernel<false, NCH>), grid, dim3(FLOW_BLOCK), 0, s, F, P, I, cubic_layout,
                      (const DynTab *)tab1, (const DynTab *)tab2, position, cubic, fc1, fc2, W, H, nearest, extent, zero_culled,
-                     (float2 *)flow);
-    SPLAT_POST_LAUNCH();
+                     (Row *)flow);
+    FLOW_CHECK_HIP(who, hipGetLastError());
     return SPLAT_OK;
+}
+
+template <int NCH>
+int flow_attribute_bwd_launch(const char *who, int F, int P, int I, const void *tab1, const void *tab2, const float *position,
+                              const float *cubic, int cubic_layout, const splat_camera_t *cam1, const splat_camera_t *cam2,
+                              int W, int H, float nearest, float extent, int zero_culled, const float *g, int accumulate,
+                              float *d_position, float *d_cubic, void *stream) {
+    using Row = typename FlowRow<NCH>::type;
+    FlowCam fc1, fc2;
+    bool persp = false;
+    if (int rc = flow_args(who, F, P, I, tab1, tab2, position, cubic, cubic_layout, cam1, cam2, W, H, fc1, fc2, persp)) return rc;
+    if (P == 0 || (!d_position && !d_cubic)) return SPLAT_OK;
+    if (F > 0)   // in front of any HIP call
+        FLOW_CHECK(who, g != nullptr && ((uintptr_t)g & (sizeof(Row) - 1)) == 0,
+                   NCH == 2 ? "null / misaligned gradient (g: 8-byte aligned)" : "null / misaligned gradient (g: 16-byte aligned)");
+    hipStream_t s = (hipStream_t)stream;
+    if (!accumulate) {
+        if (d_position) FLOW_CHECK_HIP(who, hipMemsetAsync(d_position, 0, (size_t)P * 3 * sizeof(float), s));
+        if (d_cubic) FLOW_CHECK_HIP(who, hipMemsetAsync(d_cubic, 0, (size_t)P * 12 * (size_t)I * sizeof(float), s));
+    }
+    if (F == 0) return SPLAT_OK;
+    const dim3 grid((unsigned)(((size_t)P + FLOW_BLOCK - 1) / FLOW_BLOCK));
+    if (persp)
+        SPLAT_LAUNCH("flow_attribute_bwd", (flow_attribute_bwd_kernel<true, NCH>), grid, dim3(FLOW_BLOCK), 0, s, F, P, I,
+                     cubic_layout, (const DynTab *)tab1, (const DynTab *)tab2, position, cubic, fc1, fc2, W, H, nearest, extent,
+                     zero_culled, (const Row *)g, d_position, d_cubic);
+    else
+        SPLAT_LAUNCH("flow_attribute_bwd", (flow_attribute_bwd_kernel<false, NCH>), grid, dim3(FLOW_BLOCK), 0, s, F, P, I,
+                     cubic_layout, (const DynTab *)tab1, (const DynTab *)tab2, position, cubic, fc1, fc2, W, H, nearest, extent,
+                     zero_culled, (const Row *)g, d_position, d_cubic);
+    FLOW_CHECK_HIP(who, hipGetLastError());
+    return SPLAT_OK;
+}
+
+}  // namespace
+
+extern "C" int splat_flow_attribute_batch(int F, int P, int I, const void *tab1, const void *tab2, const float *position,
+                                          const float *cubic, int cubic_layout, const splat_camera_t *cam1,
+                                          const splat_camera_t *cam2, int W, int H, float nearest, float extent, int zero_culled,
+                                          float *flow, void *stream) {
+    return flow_attribute_launch<2>(__func__, F, P, I, tab1, tab2, position, cubic, cubic_layout, cam1, cam2, W, H, nearest, extent,
+                                    zero_culled, flow, stream);
 }
 
 extern "C" int splat_flow_attribute_batch_backward(int F, int P, int I, const void *tab1, const void *tab2, const float *position,
@@ -417,28 +489,8 @@ extern "C" int splat_flow_attribute_batch_backward(int F, int P, int I, const vo
                                                    const splat_camera_t *cam2, int W, int H, float nearest, float extent,
                                                    int zero_culled, const float *g, int accumulate, float *d_position,
                                                    float *d_cubic, void *stream) {
-    FlowCam fc1, fc2;
-    bool persp = false;
-    if (int rc = flow_args(__func__, F, P, I, tab1, tab2, position, cubic, cubic_layout, cam1, cam2, W, H, fc1, fc2, persp)) return rc;
-    if (P == 0 || (!d_position && !d_cubic)) return SPLAT_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (!accumulate) {
-        if (d_position) SPLAT_CHECK_HIP(hipMemsetAsync(d_position, 0, (size_t)P * 3 * sizeof(float), s));
-        if (d_cubic) SPLAT_CHECK_HIP(hipMemsetAsync(d_cubic, 0, (size_t)P * 12 * (size_t)I * sizeof(float), s));
-    }
-    if (F == 0) return SPLAT_OK;
-    SPLAT_CHECK_ARG(g != nullptr && ((uintptr_t)g & 7) == 0, "null / misaligned gradient (g: 8-byte aligned)");
-    const dim3 grid((unsigned)(((size_t)P + FLOW_BLOCK - 1) / FLOW_BLOCK));
-    if (persp)
-        SPLAT_LAUNCH("flow_attribute_bwd", flow_attribute_bwd_kernel<true>, grid, dim3(FLOW_BLOCK), 0, s, F, P, I, cubic_layout,
-                     (const DynTab *)tab1, (const DynTab *)tab2, position, cubic, fc1, fc2, W, H, nearest, extent, zero_culled,
-                     (const float2 *)g, d_position, d_cubic);
-    else
-        SPLAT_LAUNCH("flow_attribute_bwd", flow_attribute_bwd_kernel<false>, grid, dim3(FLOW_BLOCK), 0, s, F, P, I, cubic_layout,
-                     (const DynTab *)tab1, (const DynTab *)tab2, position, cubic, fc1, fc2, W, H, nearest, extent, zero_culled,
-                     (const float2 *)g, d_position, d_cubic);
-    SPLAT_POST_LAUNCH();
-    return SPLAT_OK;
+    return flow_attribute_bwd_launch<2>(__func__, F, P, I, tab1, tab2, position, cubic, cubic_layout, cam1, cam2, W, H, nearest,
+                                        extent, zero_culled, g, accumulate, d_position, d_cubic, stream);
 }
 
 extern "C" size_t splat_flow_scratch_bytes(int F, int H, int W) {
@@ -512,6 +564,215 @@ extern "C" int splat_flow_error(int F, int H, int W, const float *pred, const fl
     if (grad)
         SPLAT_LAUNCH("flow_error_grad", flow_error_grad_kernel, dim3((HW + FLOW_BLOCK - 1) / FLOW_BLOCK, F), dim3(FLOW_BLOCK), 0, s,
                      HW, pred, gt, weight, scale, sums, grad);
+    SPLAT_POST_LAUNCH();
+    return SPLAT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- occlusion
+// include/splat_hip_flow_occ.h.  The attribute with the depth is the NCH = 4 instantiation of the kernels above.
+extern "C" int splat_flow_occ_abi_version(void) { return SPLAT_FLOW_OCC_ABI_VERSION; }
+
+extern "C" int splat_flow_attribute_depth_batch(int F, int P, int I, const void *tab1, const void *tab2, const float *position,
+                                                const float *cubic, int cubic_layout, const splat_camera_t *cam1,
+                                                const splat_camera_t *cam2, int W, int H, float nearest, float extent,
+                                                int zero_culled, float *out, void *stream) {
+    return flow_attribute_launch<4>(__func__, F, P, I, tab1, tab2, position, cubic, cubic_layout, cam1, cam2, W, H, nearest, extent,
+                                    zero_culled, out, stream);
+}
+
+extern "C" int splat_flow_attribute_depth_batch_backward(int F, int P, int I, const void *tab1, const void *tab2,
+                                                         const float *position, const float *cubic, int cubic_layout,
+                                                         const splat_camera_t *cam1, const splat_camera_t *cam2, int W, int H,
+                                                         float nearest, float extent, int zero_culled, const float *g,
+                                                         int accumulate, float *d_position, float *d_cubic, void *stream) {
+    return flow_attribute_bwd_launch<4>(__func__, F, P, I, tab1, tab2, position, cubic, cubic_layout, cam1, cam2, W, H, nearest,
+                                        extent, zero_culled, g, accumulate, d_position, d_cubic, stream);
+}
+
+namespace {
+
+struct OccArgs {
+    const float *flow, *track_depth, *surface, *coverage, *flow_back, *src;
+    float bg_depth, depth_margin, min_coverage, fb_alpha, fb_beta;
+    unsigned char *mask;
+    float *depth_gap, *fb_sq, *warped;
+    int *partial;   // [F][blocks][4] or NULL
+};
+
+// V consecutive floats / bytes of a plane: one 16-byte (4-byte) access when V = 4 -- the host picks V = 4 only when every
+// plane of every map starts on a 16-byte boundary (H * W a multiple of 4, aligned base pointers)
+template <int V>
+__device__ __forceinline__ void load_run(const float *__restrict__ p, float o[V]) {
+    if constexpr (V == 4) {
+        const float4 t = *reinterpret_cast<const float4 *>(p);
+        o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
+    } else {
+        o[0] = p[0];
+    }
+}
+template <int V>
+__device__ __forceinline__ void store_run(float *__restrict__ p, const float o[V]) {
+    if constexpr (V == 4) *reinterpret_cast<float4 *>(p) = make_float4(o[0], o[1], o[2], o[3]);
+    else p[0] = o[0];
+}
+
+// the four corners and the two weights of q in an H x W plane; q is inside [0, W - 1] x [0, H - 1]
+struct Corners {
+    int o00, o01, o10, o11;
+    float fx, fy, gx, gy;   // gx = 1 - fx
+};
+__device__ __forceinline__ Corners corners(float qx, float qy, int W, int H) {
+    const float x0f = floorf(qx), y0f = floorf(qy);
+    const int x0 = (int)x0f, y0 = (int)y0f;
+    const int x1 = imin_(x0 + 1, W - 1), y1 = imin_(y0 + 1, H - 1);
+    Corners c;
+    c.o00 = y0 * W + x0; c.o01 = y0 * W + x1; c.o10 = y1 * W + x0; c.o11 = y1 * W + x1;
+    c.fx = qx - x0f; c.fy = qy - y0f;
+    c.gx = 1.f - c.fx; c.gy = 1.f - c.fy;
+    return c;
+}
+__device__ __forceinline__ float bilinear(const float *__restrict__ plane, const Corners &c) {
+    const float v00 = plane[c.o00], v01 = plane[c.o01], v10 = plane[c.o10], v11 = plane[c.o11];
+    return ((v00 * c.gx) + (v01 * c.fx)) * c.gy + ((v10 * c.gx) + (v11 * c.fx)) * c.fy;
+}
+
+// A thread takes PIX_ITEMS / V runs of V consecutive pixels (flow.hip's pixels-per-thread idiom; a wave's runs are contiguous):
+// the pixel's own planes (flow, track depth, coverage) are read once in runs, the outputs stored in runs; the four-corner
+// gathers of neighbouring pixels overlap (a flow field is smooth) and come from the cache.
+template <int V>
+__global__ __launch_bounds__(FLOW_BLOCK) void flow_occlusion_kernel(int H, int W, int C, OccArgs a) {
+    const int f = blockIdx.y, HW = H * W;
+    const size_t m = (size_t)f * HW;                  // offset of map f in a one-plane tensor
+    const float *fu = a.flow + 2 * m, *fv = fu + HW;
+    const float wmax = (float)(W - 1), hmax = (float)(H - 1);
+    int cnt[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < PIX_ITEMS / V; ++k) {
+        const int i0 = blockIdx.x * PIX_PER_BLOCK + (k * FLOW_BLOCK + (int)threadIdx.x) * V;
+        if (i0 >= HW) continue;                       // V = 4: HW is a multiple of 4, a run is inside or outside as a whole
+        float u[V], v[V], td[V], cov[V], gap[V], fb[V];
+        unsigned char bits[V];
+        Corners cs[V];
+        bool in[V];
+        load_run<V>(fu + i0, u);
+        load_run<V>(fv + i0, v);
+        if (a.track_depth) load_run<V>(a.track_depth + m + i0, td);
+        if (a.coverage) load_run<V>(a.coverage + m + i0, cov);
+        const int y = i0 / W;
+        int x = i0 - y * W, yy = y;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            if (x >= W) { x -= W; ++yy; }             // a run may cross the end of a row
+            const float qx = (float)x + u[j], qy = (float)yy + v[j];
+            const bool inside = qx >= 0.f && qx <= wmax && qy >= 0.f && qy <= hmax;      // false for a NaN
+            unsigned b = inside ? 0u : (unsigned)SPLAT_FLOW_OCC_OUTSIDE;
+            if (a.coverage && !(cov[j] >= a.min_coverage)) b |= SPLAT_FLOW_OCC_UNCOVERED;
+            const bool decide = b == 0u;
+            gap[j] = 0.f;
+            fb[j] = 0.f;
+            if (inside) {
+                const Corners c = corners(qx, qy, W, H);
+                if (a.surface) {
+                    const float s = bilinear(a.surface + m, c);
+                    float t = td[j];
+                    if (a.coverage) t = t + (1.f - cov[j]) * a.bg_depth;
+                    gap[j] = t - s;
+                    if (decide && gap[j] > a.depth_margin) b |= SPLAT_FLOW_OCC_IN_FRONT;
+                }
+                if (a.flow_back) {
+                    const float bu = bilinear(a.flow_back + 2 * m, c), bv = bilinear(a.flow_back + 2 * m + HW, c);
+                    const float ru = u[j] + bu, rv = v[j] + bv;
+                    fb[j] = ru * ru + rv * rv;
+                    const float lim = a.fb_alpha * ((u[j] * u[j] + v[j] * v[j]) + (bu * bu + bv * bv)) + a.fb_beta;
+                    if (decide && fb[j] > lim) b |= SPLAT_FLOW_OCC_INCONSISTENT;
+                }
+                cs[j] = c;
+            }
+            in[j] = inside;
+            bits[j] = (unsigned char)b;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) cnt[t] += (int)((b >> t) & 1u);
+            ++x;
+        }
+        if constexpr (V == 4) *reinterpret_cast<uchar4 *>(a.mask + m + i0) = make_uchar4(bits[0], bits[1], bits[2], bits[3]);
+        else a.mask[m + i0] = bits[0];
+        if (a.depth_gap) store_run<V>(a.depth_gap + m + i0, gap);
+        if (a.fb_sq) store_run<V>(a.fb_sq + m + i0, fb);
+        if (a.warped) {
+            for (int ch = 0; ch < C; ++ch) {
+                const size_t o = ((size_t)f * C + ch) * HW;
+                float w[V];
+#pragma unroll
+                for (int j = 0; j < V; ++j) w[j] = in[j] ? bilinear(a.src + o, cs[j]) : 0.f;
+                store_run<V>(a.warped + o + i0, w);
+            }
+        }
+    }
+    if (a.partial) {   // integer sums: any order gives the same counts
+        __shared__ int sm[4];
+        if (threadIdx.x < 4) sm[threadIdx.x] = 0;
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            if (cnt[t]) atomicAdd(&sm[t], cnt[t]);
+        __syncthreads();
+        if (threadIdx.x < 4) a.partial[((size_t)f * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = sm[threadIdx.x];
+    }
+}
+
+// counts[f][bit] = the partials of map f; thread = (map, bit)
+__global__ __launch_bounds__(64) void flow_occlusion_fold_kernel(int F, int nb, const int *__restrict__ partial,
+                                                                int *__restrict__ counts) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= F * 4) return;
+    const int f = t >> 2, c = t & 3;
+    int s = 0;
+    for (int b = 0; b < nb; ++b) s += partial[((size_t)f * nb + b) * 4 + c];
+    counts[t] = s;
+}
+
+}  // namespace
+
+extern "C" size_t splat_flow_occlusion_scratch_bytes(int F, int H, int W) {
+    if (F < 1 || H < 1 || W < 1) return 0;
+    return (size_t)F * (size_t)pix_blocks(H, W) * 4 * sizeof(int);
+}
+
+extern "C" int splat_flow_occlusion(int F, int H, int W, int C, const float *flow, const float *track_depth, const float *surface,
+                                    const float *coverage, const float *flow_back, const float *src, float bg_depth,
+                                    float depth_margin, float min_coverage, float fb_alpha, float fb_beta, uint8_t *mask,
+                                    float *depth_gap, float *fb_sq, float *warped, int *counts, void *scratch,
+                                    size_t scratch_bytes, void *stream) {
+    const char *why;
+    flow_maps(F, H, W, why);
+    SPLAT_CHECK_ARG(!why, why);
+    SPLAT_CHECK_ARG(!track_depth == !surface, "track_depth and surface are given both or neither");
+    SPLAT_CHECK_ARG(src ? (C >= 1 && C <= 8) : C == 0, "src needs 1 <= C <= 8 planes (C == 0 without src)");
+    SPLAT_CHECK_ARG(!depth_gap || surface, "depth_gap needs track_depth and surface");
+    SPLAT_CHECK_ARG(!fb_sq || flow_back, "fb_sq needs flow_back");
+    SPLAT_CHECK_ARG(!warped == !src, "warped and src are given both or neither");
+    SPLAT_CHECK_ARG(bg_depth == bg_depth && depth_margin == depth_margin && min_coverage == min_coverage && fb_alpha == fb_alpha &&
+                        fb_beta == fb_beta, "a NaN parameter");
+    if (F == 0) return SPLAT_OK;
+    SPLAT_CHECK_ARG(flow && mask, "null pointer (flow and mask are required)");
+    SPLAT_CHECK_ARG((((uintptr_t)flow | (uintptr_t)track_depth | (uintptr_t)surface | (uintptr_t)coverage | (uintptr_t)flow_back |
+                      (uintptr_t)src | (uintptr_t)depth_gap | (uintptr_t)fb_sq | (uintptr_t)warped | (uintptr_t)counts) & 3) == 0,
+                    "misaligned pointer (float / int: 4-byte aligned)");
+    const int HW = H * W, nb = pix_blocks(H, W);
+    SPLAT_CHECK_ARG(!counts || (scratch && ((uintptr_t)scratch & 3) == 0 &&
+                                scratch_bytes >= splat_flow_occlusion_scratch_bytes(F, H, W)),
+                    "scratch missing or too small (splat_flow_occlusion_scratch_bytes)");
+    OccArgs a{flow, track_depth, surface, coverage, flow_back, src, bg_depth, depth_margin, min_coverage, fb_alpha, fb_beta,
+              mask, depth_gap, fb_sq, warped, counts ? (int *)scratch : nullptr};
+    // runs of four pixels when every plane of every map starts on a 16-byte boundary (the mask: 4 bytes)
+    const bool wide = (HW & 3) == 0 && (((uintptr_t)flow | (uintptr_t)track_depth | (uintptr_t)coverage | (uintptr_t)depth_gap |
+                                         (uintptr_t)fb_sq | (uintptr_t)warped) & 15) == 0 && ((uintptr_t)mask & 3) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (wide) SPLAT_LAUNCH("flow_occlusion", flow_occlusion_kernel<4>, dim3(nb, F), dim3(FLOW_BLOCK), 0, s, H, W, C, a);
+    else SPLAT_LAUNCH("flow_occlusion", flow_occlusion_kernel<1>, dim3(nb, F), dim3(FLOW_BLOCK), 0, s, H, W, C, a);
+    if (counts)
+        SPLAT_LAUNCH("flow_occlusion_fold", flow_occlusion_fold_kernel, dim3((F * 4 + 63) / 64), dim3(64), 0, s, F, nb,
+                     (const int *)scratch, counts);
     SPLAT_POST_LAUNCH();
     return SPLAT_OK;
 }
